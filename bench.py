@@ -88,6 +88,10 @@ def parse_args(argv=None):
                     help="N = 1 values of the strong-scaling configurations (by layout, with the kernel sources' digest): what speedup_vs_n1 divides by")
     ap.add_argument("--ny", type=int, default=721)
     ap.add_argument("--nx", type=int, default=1440)
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed passes, write what the last timed pass delivered (the packed per-time-step records of the whole "
+                         "series, split into scalars [T, 16] and levels [T, 21, nl], fp64) as DIR/<name>.npy; a larger series is cut to a "
+                         "fixed seeded sample of time steps (time_index.npy) so that the files stay within 64 MB")
     return ap.parse_args(argv)
 
 
@@ -389,6 +393,34 @@ class RankContext:
             os.dup2(2, 1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirpath, records, nanflag=None):
+    """--dump-outputs: what the last timed pass delivered, as fp64 .npy files in `dirpath` -- scalars [T, 16] (constants.SCALAR_TERMS),
+    levels [T, 21, nl] (constants.LEVEL_TERMS), time_index [T] (the global time steps written) and, when the pass was one rank's,
+    nanflag [T].  `records`: the packed [T, 16 + 21 nl] records of the whole series (rank 0's gathered copy at N > 1).  A series
+    whose files would pass 64 MB keeps a fixed seeded sample of its time steps: the same steps in every run of one configuration."""
+    import torch
+    from lorenzcycletoolkit_amd._lib import LEC_NLEVTAB, LEC_NSCALAR
+    T, width = int(records.shape[0]), int(records.shape[1])
+    per_step = 8 * (width + 1 + (0 if nanflag is None else 1))
+    keep = np.arange(T)
+    if T * per_step > DUMP_LIMIT_BYTES:
+        keep = np.sort(np.random.default_rng(0).choice(T, size=DUMP_LIMIT_BYTES // per_step, replace=False))
+    idx = torch.as_tensor(keep, device=records.device)
+    rec = records.index_select(0, idx).to("cpu", torch.float64).numpy()
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "scalars.npy"), np.ascontiguousarray(rec[:, :LEC_NSCALAR]))
+    np.save(os.path.join(dirpath, "levels.npy"), np.ascontiguousarray(rec[:, LEC_NSCALAR:].reshape(len(keep), LEC_NLEVTAB, -1)))
+    np.save(os.path.join(dirpath, "time_index.npy"), keep.astype(np.float64))
+    nanflag_file = os.path.join(dirpath, "nanflag.npy")
+    if nanflag is not None:
+        np.save(nanflag_file, nanflag.index_select(0, idx).cpu().numpy().astype(np.float64))
+    elif os.path.exists(nanflag_file):        # not one from an earlier run of another configuration
+        os.remove(nanflag_file)
+
+
 def n1_key(args, T_global, packed):
     """Key of a strong-scaling configuration in --n1-file: the series' layout is part of it (a packed and a cube series are different work)."""
     kind = ("moving_" + ("packed" if packed else "cube")) if args.moving else "fixed"
@@ -644,6 +676,10 @@ def measure(args, ctx, cpu_kind="none"):
         mine = torch.tensor([elapsed_own], dtype=torch.float64, device=device)
         from lorenzcycletoolkit_amd.parallel import _all_gather_small
         per_rank = [float(x) / args.steps * 1e3 for x in _all_gather_small(mine).view(-1)]
+    # before the instrumented passes below, which write the same buffers again
+    if args.dump_outputs and rank == 0:
+        gathered = series is not None and gat.active
+        dump_outputs(args.dump_outputs, series if gathered else res.packed, nanflag=None if gathered else res.nanflag)
 
     # The PRODUCER of a packed series (the per-step slice and dT/dt, which the reference's clock spans: lorenzcycletoolkit.py:173-199,
     # box_data.py:297-310), per pass over this rank's shard, on HIP events of its own.  Streamed runs produce every chunk inside every
@@ -991,7 +1027,7 @@ def strong_legs(args, ctx):
     for name, T, moving in (("config4", t4, False), ("config5", t5, True)):
         la = copy.copy(args)
         la.timesteps_global, la.moving, la.steps, la.warmup, la.chunk = T, moving, args.leg_steps, 1, 0
-        la.write_digest = False
+        la.write_digest, la.dump_outputs = False, None
         tic = time.perf_counter()
         o, _ = measure(la, ctx, cpu_kind="none")
         gc.collect()
@@ -1042,6 +1078,8 @@ def main():
     args = parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if args.gpus > 1:

@@ -297,3 +297,26 @@ def test_bench_strong_scaling_chunked_equals_resident(extra):
     assert a["scaling"] == b["scaling"] == "strong" and a["config"]["timesteps_global"] == 8 and a["n_gpus"] == 1
     assert a["config"]["chunk"] == 3 and "chunk" not in b["config"] and a["config"]["results_finite"] and b["config"]["results_finite"]
     assert a["value"] > 0 and a["config"]["wall_ms_per_step_incl_generation"] >= a["ms_per_step"]
+
+
+def test_dump_outputs_writes_what_the_last_timed_pass_delivered(tmp_path):
+    """--dump-outputs DIR: the packed records of the last timed pass as fp64 .npy files.  The same arguments give the same seeded inputs
+    and so the same files, and a two-rank run dumps the gathered series, equal to the one-rank run's of the same global length."""
+    import numpy as np
+    runs = {"a": ["--timesteps", "6"], "b": ["--timesteps", "6"], "two": ["--gpus", "2", "--timesteps", "3", "--no-strong-legs"]}
+    got = {}
+    for name, extra in runs.items():
+        r, lines = _bench(extra + ["--cpu-baseline", "none", "--dump-outputs", str(tmp_path / name), "--ny", "61", "--nx", "128",
+                                   "--steps", "3", "--warmup", "1"], env={"LEC_DIST_BACKEND": "gloo"})
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["config"]["timesteps_global"] == 6
+        got[name] = {f[:-4]: np.load(tmp_path / name / f) for f in os.listdir(tmp_path / name)}
+    a, b, two = got["a"], got["b"], got["two"]
+    assert set(a) == {"scalars", "levels", "time_index", "nanflag"} and set(two) == {"scalars", "levels", "time_index"}
+    assert a["scalars"].shape == (6, 16) and a["levels"].shape == (6, 21, 37) and list(a["time_index"]) == list(range(6))
+    assert all(v.dtype == np.float64 for v in a.values()) and np.isfinite(a["scalars"]).all() and not a["nanflag"].any()
+    for k in a:
+        assert np.array_equal(a[k], b[k], equal_nan=True), k
+    for k in two:
+        assert np.array_equal(a[k], two[k], equal_nan=True), k
