@@ -76,8 +76,9 @@ enum lec_kernel {
     LEC_KERNEL_ROW_SWEEP = 2,  /* lec_rowsweep.hip: one wave per row, one sweep */
     LEC_KERNEL_ROW_BLOCK = 3,  /* lec_rowblock.hip: blocks of neighbouring rows exchange T through LDS (all terms, one fixed box, dT/dt from the cube) */
     LEC_KERNEL_BOX_TILE = 4,   /* lec_boxtile.hip: one wave per four box rows walks the levels; six values per point transposed through LDS */
-    LEC_KERNEL_BOX_PLANE = 5   /* lec_boxplane.hip (ABI 10): the same rows and sums with the planes brought into LDS by DMA -- a box-packed fp64 series with a
-                                  dT/dt cube on even longitudes, slabs of at most 64 columns (what LEC_KERNEL_AUTO picks there; bit-identical records) */
+    LEC_KERNEL_BOX_PLANE = 5   /* lec_boxplane.hip (ABI 10): the same rows and sums with the planes' rows loaded straight into the compute layout -- a
+                                  box-packed series on even longitudes, slabs of at most 64 columns: fp64 or fp32 storage with a dT/dt cube, or fp32
+                                  storage with T of the time neighbours as tm_d / tp_d (what LEC_KERNEL_AUTO picks there; bit-identical records) */
 };
 
 /* workgroup -> row order of the row kernels (speed only) */
@@ -91,10 +92,12 @@ enum lec_order {
 /* Kernel selection of lec_rowstats; all zero = library defaults. */
 typedef struct lec_tuning {
     int32_t kernel;        /* enum lec_kernel */
-    int32_t block_shape;   /* LEC_KERNEL_ROW_BLOCK: 100 bt + 10 bk + bj waves (time x level x latitude, each 1 or 2); 0 = 212 */
+    int32_t block_shape;   /* LEC_KERNEL_ROW_BLOCK: 100 bt + 10 bk + bj waves (time x level x latitude, each 1 or 2); 0 = 212.
+                              Box-tile / box-plane calls: 0 or 1 (one time step per workgroup) */
     int32_t order;         /* enum lec_order */
     int32_t tile_t, tile_j; /* tile extents of LEC_ORDER_XCD_TILED / of the row-block kernel (in blocks); box tiles: tile_t = time steps per
-                               workgroup group, tile_j = levels per wave (default: from the launch size; at most 21, more is LEC_ERR_ARG);
+                               workgroup group, tile_j = levels per wave (default: from the launch size; at most 21 for the box-tile kernel
+                               and 42 for the box-plane kernel, more is LEC_ERR_ARG);
                                0 = default; must be >= 0 */
     int32_t f32_vec;       /* fp32 storage, one wave per row: 0 = float4 trips when the cubes are 16-byte aligned, 2 = float2 trips */
     int32_t reserved[2];   /* must be 0 */

@@ -1,6 +1,5 @@
-// lec_boxplane.hip -- stage 1 for a BOX-PACKED series of the moving framework in fp64 storage (include/lec_hip.h: cubes
-// [nt][nl][ny][nx] whose step t holds box t alone, dT/dt as the series' own cube): the planes' rows go STRAIGHT into the layout the
-// sums are taken in.
+// lec_boxplane.hip -- stage 1 for a BOX-PACKED series of the moving framework (include/lec_hip.h: cubes [nt][nl][ny][nx] whose
+// step t holds box t alone): the planes' rows go STRAIGHT into the layout the sums are taken in.
 //
 // lec_boxtile.hip was built for row fragments of a track-extent crop: lanes along longitude, one 488-byte box row per wave
 // instruction, the diabatic-heating residual formed in that layout, six values per point transposed through LDS into the compute
@@ -49,13 +48,6 @@
 
 using namespace lec;
 
-#ifndef LEC_BP_ABLATE       // measurement builds only (tools/build_variant.sh), bit mask: 1 = no arithmetic on the points, 2 = no global loads
-#define LEC_BP_ABLATE 0
-#endif
-#ifndef LEC_BP_NT           // cache policy of the once-read planes (u, v, omega, Phi, dT/dt): 1 = nontemporal (measured: slower)
-#define LEC_BP_NT 0
-#endif
-
 namespace {
 
 constexpr int kWR = 4;                    // box rows per wave
@@ -77,31 +69,25 @@ __device__ __forceinline__ double lane_value(double v, int src) {
 // 16 bytes at (run start + byte_off), as two doubles.  The resource of the load is the run itself (base = its first byte, num_records =
 // its length) and the range check is per dword: what lies past the run reads as zero and is never touched.
 typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
-template <bool NT>
 __device__ __forceinline__ u32x4_t load16(__amdgpu_buffer_rsrc_t run, unsigned byte_off) {
-    return __builtin_amdgcn_raw_buffer_load_b128(run, (int)byte_off, 0, NT ? 2 : 0);
+    return __builtin_amdgcn_raw_buffer_load_b128(run, (int)byte_off, 0, 0);
 }
 // the lane's four consecutive elements of a plane: 32 bytes (two loads) in fp64 storage, 16 bytes (one load) in fp32
 template <typename TIN> struct Quad;
 template <> struct Quad<double> {
     u32x4_t h[2];
-    template <bool NT> __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t run, unsigned byte_off) { h[0] = load16<NT>(run, byte_off); h[1] = load16<NT>(run, byte_off + 16u); }
+    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t run, unsigned byte_off) { h[0] = load16(run, byte_off); h[1] = load16(run, byte_off + 16u); }
     __device__ __forceinline__ void get(double (&o)[4]) const {
         o[0] = __hiloint2double((int)h[0].y, (int)h[0].x); o[1] = __hiloint2double((int)h[0].w, (int)h[0].z);
         o[2] = __hiloint2double((int)h[1].y, (int)h[1].x); o[3] = __hiloint2double((int)h[1].w, (int)h[1].z);
     }
-    __device__ __forceinline__ void fill(double a, double b) {
-        h[0].x = h[1].x = (unsigned)__double2loint(a); h[0].y = h[1].y = (unsigned)__double2hiint(a);
-        h[0].z = h[1].z = (unsigned)__double2loint(b); h[0].w = h[1].w = (unsigned)__double2hiint(b);
-    }
 };
 template <> struct Quad<float> {
     u32x4_t h;
-    template <bool NT> __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t run, unsigned byte_off) { h = load16<NT>(run, byte_off); }
+    __device__ __forceinline__ void load(__amdgpu_buffer_rsrc_t run, unsigned byte_off) { h = load16(run, byte_off); }
     __device__ __forceinline__ void get(double (&o)[4]) const {
         o[0] = (double)__uint_as_float(h.x); o[1] = (double)__uint_as_float(h.y); o[2] = (double)__uint_as_float(h.z); o[3] = (double)__uint_as_float(h.w);
     }
-    __device__ __forceinline__ void fill(double a, double b) { h.x = h.z = __float_as_uint((float)a); h.y = h.w = __float_as_uint((float)b); }
 };
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t run_resource(const void* first, unsigned bytes) {
     // (wave-uniform, and said so: a resource the compiler cannot prove uniform costs a waterfall loop around every load)
@@ -135,22 +121,17 @@ __device__ __forceinline__ void finish_lane(const double (&tot)[kNA], double cT,
     o[21] = tot[19] - 2 * db * tot[12] + db * db * dd - 2 * dc * tot[13] + dc * dc * dd + cW * (sUU + sVV);
 }
 
-// G: waves per workgroup = neighbouring row blocks of one (time step, level chunk).  The waves share nothing and never wait for each other;
-// they run on ONE CU at about the same time, so the lines two neighbouring blocks both ask for -- a block's first and last row are its
-// neighbours' halo rows, and a run rarely ends on a line boundary -- are asked for once: the second request finds the line in that CU's L1,
-// or on its way there (the kernel is bound by the L1's outstanding misses: every merged request is a slot).
 // TIN: storage type.  MODE 2: dT/dt is a cube (p.DT);  MODE 1: dT/dt = ta T(t-1) + tb T(t) + tc T(t+1) per point, T of the two time
 // neighbours on this step's box in cubes of their own (p.TM, p.TP: a box-packed series).
-template <typename TIN, int MODE, int G>
-__global__ void __launch_bounds__(64 * G, 2) lec_boxplane_kernel(const RowParams p) {
+template <typename TIN, int MODE>
+__global__ void __launch_bounds__(64, 2) lec_boxplane_kernel(const RowParams p) {
     static_assert(MODE == 2 || (MODE == 1 && sizeof(TIN) == 4), "time neighbours as operands: fp32 storage (six 32-byte operands per set do not fit)");
     constexpr int kPiecesT = (kTileT * (int)sizeof(TIN) + 1023) / 1024;      // flat 1-KiB pieces of the T run: 3 (fp64) / 2 (fp32)
     constexpr int kTileStride = kPiecesT * 1024 / (int)sizeof(TIN);          // elements between the two tiles: whole pieces (a piece's lanes past the run write zeros)
     static_assert(2 * kTileStride * sizeof(TIN) <= 2 * kTileT * sizeof(double), "the two tiles must fit their LDS");
     constexpr int NX = MODE == 2 ? 1 : 2;                  // dT/dt operands per point
     constexpr unsigned ESZ = (unsigned)sizeof(TIN);
-    __shared__ __attribute__((aligned(16))) double sm_all[G * kLdsDoubles];
-    double* const sm = sm_all + (G > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0) * kLdsDoubles;
+    __shared__ __attribute__((aligned(16))) double sm[kLdsDoubles];
     TIN* const tiles = reinterpret_cast<TIN*>(sm);         // 2 x [6 rows][W]: T of this level and of the next, each as it lies in memory
     double* const part = sm + 2 * kTileT;                  // [kHalf][kPS]: the lanes' partial sums of a level, ten statistics at a time
     double* const stash = part + kHalf * kPS;              // [kLB levels][kWR rows][kNA]: row totals waiting for their finishing lane
@@ -162,7 +143,7 @@ __global__ void __launch_bounds__(64 * G, 2) lec_boxplane_kernel(const RowParams
     const int n_rb = p.jrows, kchunk = p.jgroup, n_kc = (p.nl + kchunk - 1) / kchunk;
     const int xcd = blockIdx.x & 7;
     int q0 = blockIdx.x >> 3;
-    const int rbi = (q0 % n_rb) * G + (G > 1 ? __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)) : 0); q0 /= n_rb;     // (n_rb: row-block GROUPS)
+    const int rbi = q0 % n_rb; q0 /= n_rb;
     const int ti = q0 % p.tgroup; q0 /= p.tgroup;
     const int kc = q0 % n_kc;
     const int tin = (q0 / n_kc) * p.tgroup + ti;
@@ -250,34 +231,25 @@ __global__ void __launch_bounds__(64 * G, 2) lec_boxplane_kernel(const RowParams
     u32x4_t tT[kPiecesT];
     Quad<TIN> fU[2], fV[2], fW[2], fP[2], fX[2][NX];
     auto issue_T = [&](int kT) {
-        if (LEC_BP_ABLATE & 2) return;
         const __amdgpu_buffer_rsrc_t rt = run_resource(gT + lev(kT), bytesT);
 #pragma unroll
-        for (int i = 0; i < kPiecesT; ++i) tT[i] = load16<false>(rt, 1024u * i + 16u * lane);      // (halo rows are the neighbouring wave's own rows: default policy)
+        for (int i = 0; i < kPiecesT; ++i) tT[i] = load16(rt, 1024u * i + 16u * lane);      // (halo rows are the neighbouring wave's own rows: default policy)
     };
     auto issue_F = [&](auto set_tag, int kF) {
         constexpr int SET = decltype(set_tag)::value;
-        if (LEC_BP_ABLATE & 2) return;
         const size_t lk = lev(kF);
-        fU[SET].template load<LEC_BP_NT != 0>(run_resource(gU + lk, bytesF), offF);
-        fV[SET].template load<LEC_BP_NT != 0>(run_resource(gV + lk, bytesF), offF);
-        fW[SET].template load<LEC_BP_NT != 0>(run_resource(gW + lk, bytesF), offF);
-        fP[SET].template load<LEC_BP_NT != 0>(run_resource(gP + lk, bytesF), offF);
-        fX[SET][0].template load<LEC_BP_NT != 0>(run_resource(gX0 + lk, bytesF), offF);
-        if (NX > 1) fX[SET][NX - 1].template load<LEC_BP_NT != 0>(run_resource(gX1 + lk, bytesF), offF);
+        fU[SET].load(run_resource(gU + lk, bytesF), offF);
+        fV[SET].load(run_resource(gV + lk, bytesF), offF);
+        fW[SET].load(run_resource(gW + lk, bytesF), offF);
+        fP[SET].load(run_resource(gP + lk, bytesF), offF);
+        fX[SET][0].load(run_resource(gX0 + lk, bytesF), offF);
+        if (NX > 1) fX[SET][NX - 1].load(run_resource(gX1 + lk, bytesF), offF);
     };
     auto tile_in = [&](TIN* tile, const u32x4_t (&xT)[kPiecesT]) {     // a T run into a tile, as it lies in memory (the tile's readers are done: one wave, LDS in order)
         u32x4_t* dst = reinterpret_cast<u32x4_t*>(tile);
 #pragma unroll
         for (int i = 0; i < kPiecesT; ++i) dst[64 * i + lane] = xT[i];
     };
-    if (LEC_BP_ABLATE & 2) {
-        Quad<TIN> z; z.fill(280.0 + lane, 281.0);
-#pragma unroll
-        for (int i = 0; i < kPiecesT; ++i) tT[i] = sizeof(TIN) == 8 ? reinterpret_cast<const Quad<double>&>(z).h[0] : reinterpret_cast<const Quad<float>&>(z).h;
-#pragma unroll
-        for (int w = 0; w < 2; ++w) { fU[w].fill(lane, 1.0); fV[w].fill(lane, 2.0); fW[w].fill(0.1, 0.2); fP[w].fill(lane, 3.0); fX[w][0].fill(0.1, 0.2); fX[w][NX - 1].fill(0.1, 0.2); }
-    }
 
     // ---- prologue: T(k0)'s tile, the lane's points of T(k0 - 1); the loads of level k0 and T(k0 + 1)'s run on their way
     double Tm[4];
@@ -285,7 +257,7 @@ __global__ void __launch_bounds__(64 * G, 2) lec_boxplane_kernel(const RowParams
         const __amdgpu_buffer_rsrc_t rt = run_resource(gT + lev(k0), bytesT);
         u32x4_t x[kPiecesT];
 #pragma unroll
-        for (int i = 0; i < kPiecesT; ++i) x[i] = load16<false>(rt, 1024u * i + 16u * lane);
+        for (int i = 0; i < kPiecesT; ++i) x[i] = load16(rt, 1024u * i + 16u * lane);
         const TIN* g = (const TIN*)p.T + (size_t)t * cube + lev(k0 - 1) + (size_t)(js + jbc) * W + iw;
 #pragma unroll
         for (int q = 0; q < 4; ++q) Tm[q] = (double)g[col[q]];
@@ -314,7 +286,7 @@ __global__ void __launch_bounds__(64 * G, 2) lec_boxplane_kernel(const RowParams
         // the shifts of the other four planes: the row's first box element, which the lane of group 0 holds -- through the side array
         if (first[0]) { sd[0] = (double)tileC[rT]; sd[1] = Uq[0]; sd[2] = Vq[0]; sd[3] = Wq[0]; sd[4] = Pq[0]; }
         row_sync<64>();
-        if (!(LEC_BP_ABLATE & 1)) {
+        {
 #pragma clang fp contract(off)
             auto levc = [&](int e) -> double { return e < 64 ? lane_value(levv, e) : lane_value(levw, e - 64); };      // (wave-uniform choice)
             const double al = levc(3 * kk), be = levc(3 * kk + 1), gm = levc(3 * kk + 2);
@@ -430,13 +402,11 @@ bool lec_boxplane_serves(const lec::RowParams& p, int dtype, bool uniform, int m
     return mode == 1 && dtype == LEC_F32 && p.TM && p.TP;                  // time neighbours as cubes of their own: a box-packed fp32 series
 }
 
-// p.tgroup: time steps per tile group, p.jgroup: levels per wave (< 1: chosen here; more than 21: LEC_ERR_ARG) -- as lec_launch_boxtile
+// p.tgroup: time steps per tile group, p.jgroup: levels per wave (< 1: chosen here; more than 42: LEC_ERR_ARG) -- as lec_launch_boxtile.
+// One wave per workgroup: 2 and 4 waves (neighbouring row blocks) per workgroup measured 0.76-0.78 ms per 512 steps against 0.757 for 1
+// (profiles/r06_notes.md)
 int lec_launch_boxplane(lec::RowParams p, int dtype, int mode, hipStream_t st) {
-#ifndef LEC_BP_GROUP      // measured (profiles/r06_notes.md): 2 and 4 waves per workgroup 0.76-0.78 ms per 512 steps against 0.757 for 1 -- no gain
-#define LEC_BP_GROUP 1
-#endif
-    constexpr int G = LEC_BP_GROUP;                       // waves (neighbouring row blocks) per workgroup
-    const long long n_rb = ((p.nyb_max + kWR - 1) / kWR + G - 1) / G;      // row-block groups
+    const long long n_rb = (p.nyb_max + kWR - 1) / kWR;
     p.jrows = (int)n_rb;
     p.jchunk = (int)((p.t_count + 7) / 8);                // time steps per XCD
     if (p.jgroup > kMaxLevels) return LEC_ERR_ARG;
@@ -446,7 +416,7 @@ int lec_launch_boxplane(lec::RowParams p, int dtype, int mode, hipStream_t st) {
         // more than kWalk levels unless asked (512 steps: 10 levels per wave 0.743 ms, 19: 0.750, 37: 0.754; 2048 steps: 2.77 / 2.78 /
         // 2.87 ms; profiles/r06_notes.md)
         constexpr long long kTargetWaves = 32768, kWalk = 10;
-        const long long per_chunk = 8LL * p.jchunk * n_rb * G;
+        const long long per_chunk = 8LL * p.jchunk * n_rb;
         const long long want = (kTargetWaves + per_chunk - 1) / per_chunk;
         const long long most = (p.nl + kMinLevels - 1) / kMinLevels, least = (p.nl + kWalk - 1) / kWalk;
         const long long n_kc0 = want < least ? least : (want > most ? most : want);
@@ -459,9 +429,9 @@ int lec_launch_boxplane(lec::RowParams p, int dtype, int mode, hipStream_t st) {
     const long long tgroups = (p.jchunk + p.tgroup - 1) / p.tgroup;
     const long long nblocks = 8LL * tgroups * p.tgroup * n_rb * n_kc;
     if (nblocks > 0x7fffffffLL) return LEC_ERR_UNSUPPORTED;
-    const dim3 grid((unsigned)nblocks), block(64 * G);
-    if (dtype == LEC_F64) hipLaunchKernelGGL((lec_boxplane_kernel<double, 2, G>), grid, block, 0, st, p);
-    else if (mode == 2) hipLaunchKernelGGL((lec_boxplane_kernel<float, 2, G>), grid, block, 0, st, p);
-    else hipLaunchKernelGGL((lec_boxplane_kernel<float, 1, G>), grid, block, 0, st, p);
+    const dim3 grid((unsigned)nblocks), block(64);
+    if (dtype == LEC_F64) hipLaunchKernelGGL((lec_boxplane_kernel<double, 2>), grid, block, 0, st, p);
+    else if (mode == 2) hipLaunchKernelGGL((lec_boxplane_kernel<float, 2>), grid, block, 0, st, p);
+    else hipLaunchKernelGGL((lec_boxplane_kernel<float, 1>), grid, block, 0, st, p);
     return LEC_OK;
 }

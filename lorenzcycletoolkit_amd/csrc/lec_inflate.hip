@@ -35,33 +35,12 @@
 #include "../../include/lec_hip.h"
 #include "lec_internal.h"
 
-// measurement knobs (defaults = what ships)
-#ifndef LEC_INFLATE_LITBITS
-#define LEC_INFLATE_LITBITS 10
-#endif
-#ifndef LEC_INFLATE_DISTBITS
-#define LEC_INFLATE_DISTBITS 9
-#endif
-#ifndef LEC_INFLATE_RING
-#define LEC_INFLATE_RING 8192
-#endif
-#ifndef LEC_INFLATE_TIMING
-#define LEC_INFLATE_TIMING 0          // debug builds (tools/probes/inflate_timing.py): 1..4 = time the round's window / decode / walk / write
-#endif                                // phase, 6..8 = within the write phase: offsets + literals / the matches / sync + flush; 9 = a census of far / all / overlapping matches
-#define LEC_TICK(k, var) if (LEC_INFLATE_TIMING == (k)) var = (uint32_t)__builtin_amdgcn_s_memtime()
-#ifndef LEC_INFLATE_C_WALK
-#define LEC_INFLATE_C_WALK 0
-#endif
-
 namespace {
 
-constexpr int kLitBits = LEC_INFLATE_LITBITS;        // lookup width of the literal / length code (codes up to 15 bits: the rest resolves on demand)
-constexpr int kDistBits = LEC_INFLATE_DISTBITS;
-constexpr int kRingDefault = LEC_INFLATE_RING;       // LDS history ring (bytes, power of two): what most matches refer to
-#ifndef LEC_INFLATE_RING_SHORT
-#define LEC_INFLATE_RING_SHORT 4096
-#endif
-constexpr int kRingShort = LEC_INFLATE_RING_SHORT;                     // ... for streams whose matches stay close (flags bit 1): 18 instead of 12 waves per CU
+constexpr int kLitBits = 10;         // lookup width of the literal / length code (codes up to 15 bits: the rest resolves on demand)
+constexpr int kDistBits = 9;
+constexpr int kRingDefault = 8192;   // LDS history ring (bytes, power of two): what most matches refer to
+constexpr int kRingShort = 4096;     // ... for streams whose matches stay close (flags bit 1): 18 instead of 12 waves per CU
 
 enum { T_LIT = 0, T_MATCH = 1, T_EOB = 2, T_SLOW = 3, T_BAD = 4 };
 
@@ -242,13 +221,8 @@ enum {
     ST_DISTANCE = 7, ST_INPUT_END = 8, ST_OUTPUT_FULL = 9, ST_SIZE = 10, ST_STALLED = 11, ST_CHECKSUM = 12, ST_ADLER = 13
 };
 
-#ifdef LEC_INFLATE_WAVES
-#define LEC_INFLATE_OCC __attribute__((amdgpu_waves_per_eu(LEC_INFLATE_WAVES)))
-#else
-#define LEC_INFLATE_OCC
-#endif
 template <int kRing>
-__global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const InflateParams P) {
+__global__ void __launch_bounds__(64) lec_inflate_kernel(const InflateParams P) {
     constexpr int kCap = kRing / 4;             // most output bytes one round of tokens may produce (up to its last match)
     constexpr int kFlushAt = kRing / 8;         // pending bytes that trigger a flush of the ring to HBM
     __shared__ InflateLds<kRing> L;
@@ -350,7 +324,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
         }
     };
 
-    uint32_t tsum = 0, trounds = 0, tmatches = 0;      // (timing builds)
     bool last = false;
     while (status == ST_OK && !last) {
         // ------------------------------------------------------------------ block header (wave-uniform)
@@ -444,8 +417,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
         bool eob = false;
         uint32_t rounds = 0;
         while (!eob) {
-            uint32_t tk0 = 0, tk1 = 0;
-            LEC_TICK(1, tk0);
             if (++rounds > src_bits + 8u) { status = ST_STALLED; break; }
             in.seek(bitpos);
             // 64 bits of the stream from bit (bitpos + lane)
@@ -460,8 +431,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 win = (((uint64_t)x1 << 32) | x0) >> sh;
                 if (sh) win |= (uint64_t)x2 << (64u - sh);
             }
-            LEC_TICK(1, tk1);
-            LEC_TICK(2, tk0);
             // the token that would start here -- straight-line code: every lane evaluates the literal AND the match reading (the second
             // table lookup included: its index is masked, so garbage bits are harmless) and selects; with 64 speculative positions some
             // lane takes every path anyway, and divergent branches cost scalar instructions on a unit the whole CU shares
@@ -486,8 +455,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 value = sym < 256u ? sym : length;
                 used = type == T_MATCH ? l2 + dextra : l0;
             }
-            LEC_TICK(2, tk1);
-            LEC_TICK(3, tk0);
             // Follow the true chain through the lanes.  One word per lane carries what the walk needs of a token: bits used (6) |
             // type (3) | output bytes (9); a literal -- the common case -- is recognised by one compare and costs one readlane.
             auto pack = [](uint32_t ty, uint32_t nbits, uint32_t val) {
@@ -501,16 +468,9 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 // a run of literals: the scalar unit is shared by the whole CU, so this inner loop is kept to a handful of
                 // scalar instructions and touches no vector register
                 uint32_t inf = 0;
-#if LEC_INFLATE_C_WALK
-                while (pos < 64u) {
-                    inf = rl(info, pos);
-                    if ((int)inf >= 0) break;                                     // not a literal
-                    chain |= 1ull << pos;
-                    pos += inf & 63u;
-                }
-#else
-                // written out: the compiler's version of the loop above is 14 scalar instructions per literal (three branches, a
-                // 64-bit shift + or for the chain bit); these are 8.  Matches are taken here too (label 3: their output bytes go to
+                // written out: the compiler's version of the plain loop (while pos < 64: inf = rl(info, pos), stop unless a literal,
+                // set the chain bit, pos += its bits) is 14 scalar instructions per literal (three branches, a 64-bit shift + or for
+                // the chain bit); these are 8.  Matches are taken here too (label 3: their output bytes go to
                 // extra_out) as long as the round stays well below its output cap -- a round of a real field holds about three, and
                 // each trip through the general path below costs as much as several literals.  Leaves with pos >= 64, or with `inf` =
                 // the token at pos that the general path has to look at (end of block, a long code, a bad one, a match near the cap).
@@ -555,7 +515,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                         : [info] "v"(info), [limit] "s"((uint32_t)(kCap - 65))
                         : "scc");
                 }
-#endif
                 if (pos >= 64u) break;
                 const uint32_t ty = (inf >> 6) & 7u;
                 if (ty == T_SLOW) {
@@ -594,16 +553,12 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 extra_out += n_out - 1u;
                 pos += inf & 63u;
             }
-            LEC_TICK(3, tk1);
-            LEC_TICK(4, tk0);
             if (status != ST_OK) break;
             if (bitpos + pos > src_bits) { status = ST_INPUT_END; break; }
             const uint32_t produced = (uint32_t)__popcll(chain) + extra_out;
             if (produced > out_len - opos) { status = ST_OUTPUT_FULL; break; }
             const bool mine = (chain >> lane) & 1ull;
             uint64_t mm = chain & __ballot(type == T_MATCH);
-            LEC_TICK(6, tk0);
-            if (LEC_INFLATE_TIMING) tmatches += (uint32_t)__popcll(mm);
             // where each token's output starts: the output bytes of the chain tokens below it (a prefix sum in the vector ALU)
             const uint32_t ooff = wave_exclusive_sum(mine ? (type == T_MATCH ? value : type == T_LIT ? 1u : 0u) : 0u);
             const uint32_t mdesc = value | (dist << 9);                        // a match in one word (length <= 258, distance <= 32768)
@@ -612,8 +567,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
             // matches, in stream order, 64 bytes at a time
             const int safe_lo = (int)opos + kCap + 64 - kRing;                 // positions from here on are in the ring for the whole round (a round
                                                                                 // writes at most kCap bytes up to its last match, then < 64 literals)
-            LEC_TICK(6, tk1);
-            LEC_TICK(7, tk0);
             uint32_t nx_md = 0, nx_off = 0;
             if (mm) { const uint32_t i = (uint32_t)__builtin_ctzll(mm); nx_md = rl(mdesc, i); nx_off = rl(ooff, i); }
             while (mm) {
@@ -625,7 +578,6 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 }
                 if (d > p) { status = ST_DISTANCE; break; }
                 const int from = (int)(p - d);
-                if (LEC_INFLATE_TIMING == 9) { tsum += (from < safe_lo); trounds += (d < len); }     // (a census: far / overlapping matches)
                 if (from < safe_lo && (uint32_t)from + (len < d ? len : d) > fenced) {
                     // the source was flushed by this wave's own earlier stores: make them visible to its loads
                     __threadfence();
@@ -660,16 +612,11 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
                 }
                 wave_sync();
             }
-            LEC_TICK(7, tk1);
-            LEC_TICK(8, tk0);
             if (status != ST_OK) break;
             wave_sync();
             opos += produced;
             bitpos += pos;
             if (opos - flushed >= (uint32_t)kFlushAt) flush(false);
-            LEC_TICK(4, tk1);
-            LEC_TICK(8, tk1);
-            if (LEC_INFLATE_TIMING && LEC_INFLATE_TIMING != 9) { tsum += tk1 - tk0; ++trounds; }
         }
     }
     if (status == ST_OK) {
@@ -690,10 +637,7 @@ __global__ void __launch_bounds__(64) LEC_INFLATE_OCC lec_inflate_kernel(const I
             if (stored != ((s2 << 16) | s1)) status = ST_ADLER;
         }
     }
-    if (lane == 0) {
-        P.status[4 * s + 0] = status; P.status[4 * s + 1] = block; P.status[4 * s + 2] = (int)opos; P.status[4 * s + 3] = (int)bitpos;
-        if (LEC_INFLATE_TIMING) { P.status[4 * s + 1] = (int)tsum; P.status[4 * s + 2] = (int)tmatches; P.status[4 * s + 3] = (int)trounds; }
-    }
+    if (lane == 0) { P.status[4 * s + 0] = status; P.status[4 * s + 1] = block; P.status[4 * s + 2] = (int)opos; P.status[4 * s + 3] = (int)bitpos; }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------

@@ -11,14 +11,8 @@
 
 // vectors per lane of the largest row kernel (rows up to 256 * LEC_MAX_ITERS vectors)
 #define LEC_MAX_ITERS 8
-// > 0 overrides the per-configuration waves-per-SIMD request of the row kernel (experiments)
-#ifndef LEC_MINW
-#define LEC_MINW 0
-#endif
 // waves per SIMD requested for the single-sweep row kernel
-#ifndef LEC_MINW_SINGLE
-#define LEC_MINW_SINGLE 4
-#endif
+constexpr int kMinWavesSingle = 4;
 
 // records an error message (thread-local) and returns `code`
 int lec_set_error(int code, const char* msg);

@@ -304,13 +304,10 @@ struct LaneSums {
 };
 
 // grid (nl * t_count), block 64; requires nyb_max <= 64
-#ifndef LEC_SMALL_WAVES
-// (rounds 2-5: 193 VGPRs, two waves per SIMD -- the hand-over's fully unrolled loop had sixty LDS values in flight at once.  Round 6:
-// four waves per SIMD, and the SAME 85 us per 512 x 37 levels: the kernel is not bound by its occupancy; nor by its record loads --
-// staged through LDS as coalesced 16-byte loads: 86 us.  profiles/r06_stage2_pmc.txt)
-#define LEC_SMALL_WAVES 4
-#endif
-__global__ void __launch_bounds__(64, LEC_SMALL_WAVES) lec_level_small_kernel(const RedParams p) {
+// four waves per SIMD (rounds 2-5: 193 VGPRs, two waves per SIMD -- the hand-over's fully unrolled loop had sixty LDS values in flight
+// at once.  Round 6: four waves per SIMD, and the SAME 85 us per 512 x 37 levels: the kernel is not bound by its occupancy; nor by its
+// record loads -- staged through LDS as coalesced 16-byte loads: 86 us.  profiles/r06_stage2_pmc.txt)
+__global__ void __launch_bounds__(64, 4) lec_level_small_kernel(const RedParams p) {
     __shared__ double part[kSmallRound * kPartStride];
     const int tl = blockIdx.x / p.nl, k = blockIdx.x - tl * p.nl, lane = threadIdx.x;
     const int nl = p.nl, nyb_max = p.nyb_max;

@@ -34,11 +34,7 @@ using namespace lec;
 // the fp64 all-terms kernel is fastest unconstrained (170 VGPRs, 2 waves; forcing 128 spills).
 template <typename TIN, int NTHR, int ITERS, int MODE>
 constexpr int lec_min_waves() {
-#if LEC_MINW > 0
-    return LEC_MINW;
-#else
     return (ITERS > 3) ? 1 : (sizeof(TIN) == 4 ? 3 : (MODE == 0 ? 4 : 1));
-#endif
 }
 
 template <typename TIN, int VEC, int NTHR, int ITERS, bool UNIFORM, int MODE>
@@ -303,7 +299,7 @@ int launch_vec(const RowParams& p, bool uniform, int mode, int nblocks, hipStrea
 
 int lec_launch_rowsweep(const lec::RowParams& p, int dtype, bool aligned, bool aligned8, bool uniform, int mode, int f32_vec, hipStream_t st);
 int lec_launch_rowblock(lec::RowParams p, int dtype, bool aligned, bool aligned8, bool uniform, int bt, int bk, int bj, hipStream_t st);
-int lec_launch_boxtile(const lec::RowParams& p, int dtype, bool uniform, int mode, int tg, hipStream_t st);
+int lec_launch_boxtile(const lec::RowParams& p, int dtype, bool uniform, int mode, hipStream_t st);
 int lec_launch_qtime(const lec::RowParams& p, hipStream_t st);
 bool lec_boxplane_serves(const lec::RowParams& p, int dtype, bool uniform, int mode);
 int lec_launch_boxplane(lec::RowParams p, int dtype, int mode, hipStream_t st);
@@ -348,9 +344,9 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
     if (tu.reserved[0] || tu.reserved[1]) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: tuning.reserved must be 0");
     int bt = 2, bk = 1, bj = 2;
     const bool tile_call = tu.kernel == LEC_KERNEL_BOX_TILE || tu.kernel == LEC_KERNEL_BOX_PLANE || (tu.kernel == LEC_KERNEL_AUTO && a->box_per_step);
-    if (tile_call) {         // the box-tile kernel reads block_shape as the time steps per workgroup (0 = default)
-        if (tu.block_shape != 0 && tu.block_shape != 1 && tu.block_shape != 2 && tu.block_shape != 4)
-            return lec_set_error(LEC_ERR_ARG, "lec_rowstats: tuning.block_shape of a box-tile call (time steps per workgroup) must be 0, 1, 2 or 4");
+    if (tile_call) {         // the box-tile / box-plane kernels run one time step per workgroup
+        if (tu.block_shape != 0 && tu.block_shape != 1)
+            return lec_set_error(LEC_ERR_ARG, "lec_rowstats: tuning.block_shape of a box-tile / box-plane call must be 0 or 1");
     } else if (tu.block_shape) {
         bt = tu.block_shape / 100; bk = (tu.block_shape / 10) % 10; bj = tu.block_shape % 10;
         if (tu.block_shape < 0 || bt < 1 || bt > 2 || bk < 1 || bk > 2 || bj < 1 || bj > 2 || bt * bk * bj < 2)
@@ -358,8 +354,8 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
     }
     const size_t esz = a->dtype == LEC_F32 ? 4 : 8;
     const int vecw = (int)(16 / esz);
-    if (packed && (!tile_call || tu.block_shape > 1))
-        return lec_set_error(LEC_ERR_ARG, "lec_rowstats: a box-packed series runs on the box-tile / box-plane kernels, one time step per workgroup");
+    if (packed && !tile_call)
+        return lec_set_error(LEC_ERR_ARG, "lec_rowstats: a box-packed series runs on the box-tile / box-plane kernels");
     const void* cubes[8] = {a->tair_d, a->u_d, a->v_d, a->omega_d, a->geopt_d, a->dTdt_d, a->tm_d, a->tp_d};
     bool aligned = (a->nx % vecw) == 0, aligned8 = (a->nx % 2) == 0;
     for (const void* c : cubes) {
@@ -432,15 +428,16 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
         RowParams pt = p;
         pt.tgroup = tu.tile_t;                              // time steps per tile group; 0 = the kernel's default (8)
         pt.jgroup = tu.tile_j;                              // levels per wave; 0 = chosen from the launch size
-        // a box-packed fp64 series with its dT/dt cube (what every -t path of the product hands over for fp64 data): the planes come into
-        // LDS by DMA (lec_boxplane.hip).  Decided by the kind of call and the slabs' shape, so every shard and chunk of a series agrees;
-        // the records are bit-identical to the box-tile kernel's anyway (tested)
-        const bool plane_ok = a->box_per_step && tu.block_shape <= 1 && lec_boxplane_serves(pt, a->dtype, uni, wq);
+        // a box-packed series with its dT/dt cube (fp64 storage) or with T of its time neighbours (fp32 storage): what every -t path
+        // of the product hands over.  The planes' rows go straight into the compute layout by buffer loads (lec_boxplane.hip).
+        // Decided by the kind of call and the slabs' shape, so every shard and chunk of a series agrees; the records are
+        // bit-identical to the box-tile kernel's anyway (tested)
+        const bool plane_ok = a->box_per_step && lec_boxplane_serves(pt, a->dtype, uni, wq);
         if (kernel == LEC_KERNEL_BOX_PLANE && !plane_ok)
             return lec_set_error(LEC_ERR_ARG, "lec_rowstats: LEC_KERNEL_BOX_PLANE serves per-step boxes with geopotential on even longitudes, cubes at most 64 columns wide, "
                                               "dT/dt as a cube or (fp32 storage, box-packed) T of the two time neighbours as tm_d / tp_d");
         if (plane_ok && (kernel == LEC_KERNEL_BOX_PLANE || tu.kernel == LEC_KERNEL_AUTO)) rc = lec_launch_boxplane(pt, a->dtype, wq, st);
-        else rc = lec_launch_boxtile(pt, a->dtype, uni, wq, tu.block_shape, st);
+        else rc = lec_launch_boxtile(pt, a->dtype, uni, wq, st);
     } else {
         // Single-sweep row kernels.  All terms with dT/dt from the cube on one fixed box (the headline configuration, mode 3): a
         // row reads T(t+1) only and the time-derivative parts of [Q], [Q'T'] are completed from the records afterwards

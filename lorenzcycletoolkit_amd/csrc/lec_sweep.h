@@ -17,11 +17,7 @@ constexpr int kRowShift = 3;  // log2 of the lanes that cooperate on one statist
 
 template <typename TIN, int VEC, int MODE>
 constexpr int sweep_min_waves() {
-#if LEC_MINW > 0
-    return LEC_MINW;
-#else
-    return (sizeof(TIN) == 4 && MODE != 0 && VEC == 4) ? LEC_MINW_SINGLE - 1 : LEC_MINW_SINGLE;   // float4 all-terms: 149 VGPRs, 3 waves (a 128 cap spills: 13.4 vs 10.7 ms)
-#endif
+    return (sizeof(TIN) == 4 && MODE != 0 && VEC == 4) ? kMinWavesSingle - 1 : kMinWavesSingle;   // float4 all-terms: 149 VGPRs, 3 waves (a 128 cap spills: 13.4 vs 10.7 ms)
 }
 
 // value of the neighbouring lane of the wave (DPP wave shift: VALU only, no LDS, no memory); lanes at
@@ -159,8 +155,8 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
 //                 and with uniform longitudes the weight is the constant 1 (the row epilogue multiplies by h).
 //   EDGE = true : the first / last trips: half weights at the row ends, lanes outside the row contribute 0; lanes whose whole
 //                 vector lies past the row (the tail of the last trip) sit the element loop out instead of adding exact zeros
-//                 (same bits, and 20 fewer VGPRs in the fp32 all-terms instantiation).  Measured and NOT kept (LEC_EDGE_BALLOT,
-//                 profiles/r03_notes.md): per element, a wave-uniform test "is any lane's element a row end or outside" choosing
+//                 (same bits, and 20 fewer VGPRs in the fp32 all-terms instantiation).  Measured and NOT kept
+//                 (profiles/r03_notes.md): per element, a wave-uniform test "is any lane's element a row end or outside" choosing
 //                 between the plain and the general form -- the same bits with 190 fewer instructions per 1440-point fp32 row, but
 //                 both forms side by side cost 9-30 VGPRs, the capped instantiations spill, and every configuration got slower.
 //   QMODE: 0 no Q;
@@ -182,17 +178,7 @@ __device__ __forceinline__ void sweep_elems(double (&acc)[kNA], double (&xacc)[k
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
         if (EDGE) {
-            const int e = e0 + q;
-            const bool special = (unsigned)(e - 1) >= (unsigned)(r.nxb - 2);        // e <= 0 or e >= nxb - 1: a row end, or outside the row
-#if defined(LEC_EDGE_BALLOT) && LEC_EDGE_BALLOT
-            if (__builtin_amdgcn_ballot_w64(special) != 0)
-                sweep_one<VEC, UNIFORM, true, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
-            else
-                sweep_one<VEC, UNIFORM, false, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
-#else
-            (void)special;
             sweep_one<VEC, UNIFORM, true, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
-#endif
         } else {
             sweep_one<VEC, UNIFORM, false, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
         }

@@ -90,11 +90,6 @@ def one_case(rng, case, with_oracle):
         err = rows_close(r, auto)
         if not err <= 2e-11:
             fails.append(f"{what}: {fam} differs from the default family by {err:.3e}")
-    if moving:      # time groups of the box-tile kernel (waves of consecutive steps share T through LDS on the union of their boxes): no bit may move
-        for tg in (2, 4):
-            r = eng.compute(*f, boxes, tuning={"kernel": "box_tile", "block_shape": tg}, **kw)
-            if not (same_bits(r.rows[..., :28], auto.rows[..., :28]) and same_bits(r.scalars, auto.scalars)):
-                fails.append(f"{what}: box_tile with time groups of {tg} is not bit-identical to the default")
     if moving:      # the box-packed form of the series (each step's box alone, dT/dt as the series' own data; include/lec_hip.h): no bit may move
         tc = eng.time_coefs_device(dom.time_s)
         pb = eng.prepare_boxes(boxes, nyb_min=auto.rows.shape[2], packed=True)
@@ -132,8 +127,8 @@ def one_case(rng, case, with_oracle):
 
 def config5_case(rng, case, T=512):
     """BASELINE config 5 at size: a track of 15-degree (61 x 61 point) boxes over a 37 x 162 x 243 crop, T steps (one rank's share of
-    T = 4096 on 8 GPUs), the track's speed and phase random: the shipped box-tile kernel, its time groups of 2 and 4, the box-packed
-    series and a shard in the middle must give the same bits; the one-wave-per-row kernel the same records to rounding."""
+    T = 4096 on 8 GPUs), the track's speed and phase random: the shipped box-tile kernel, the box-packed series and a shard in the
+    middle must give the same bits; the one-wave-per-row kernel the same records to rounding."""
     from lorenzcycletoolkit_amd.synthetic import era5_like_levels, synthetic_cube
     lat, lon = np.arange(-57.75, -17.5 + 1e-9, 0.25), np.arange(-80.25, -19.75 + 1e-9, 0.25)
     level = era5_like_levels()
@@ -151,10 +146,6 @@ def config5_case(rng, case, T=512):
     fails = []
     plain = eng.prepare_boxes(boxes)
     base = eng.rowstats(*cubes, plain, tcoef=tc, t_begin=0, t_count=T, per_step_boxes=True)
-    for g in (2, 4):
-        r = eng.rowstats(*cubes, plain, tcoef=tc, t_begin=0, t_count=T, per_step_boxes=True, tuning={"kernel": "box_tile", "block_shape": g})
-        if not same_bits(r[..., :28], base[..., :28]):
-            fails.append(f"{what}: time groups of {g} are not bit-identical")
     sw = eng.rowstats(*cubes, plain, tcoef=tc, t_begin=0, t_count=T, per_step_boxes=True, tuning={"kernel": "row_sweep"})
     den = base[..., :28].abs().amax(dim=(0, 1, 2)).clamp_min(1e-300)
     err = float(((sw[..., :28] - base[..., :28]).abs().amax(dim=(0, 1, 2)) / den).max())

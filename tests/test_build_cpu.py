@@ -30,3 +30,21 @@ def test_inflate_kernels_use_no_flat_memory_instructions(tmp_path):
         flat = re.findall(r"^\s*(flat_(?:load|store|atomic)\w*)", body, re.M)
         assert not flat, f"{k}: {sorted(set(flat))}"
         assert "ds_read" in body and "global_load" in body and "global_store" in body
+
+
+def test_no_compile_time_knobs_in_the_kernel_sources():
+    """The shipped kernels are the only kernels: no `-D` switch may select another variant of them.  So the only preprocessor
+    conditionals on LEC_ names in csrc/ are the include guards and the part selectors of lec_level_row.inc."""
+    allowed = {"LEC_INTERNAL_H", "LEC_ROWCOMMON_H", "LEC_SWEEP_H", "LEC_ROW_COMMON", "LEC_ROW_PART_A", "LEC_ROW_PART_B"}
+    csrc = os.path.join(ROOT, "lorenzcycletoolkit_amd", "csrc")
+    cond = re.compile(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$")
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h", ".inc")):
+            continue
+        with open(os.path.join(csrc, name)) as fh:
+            for n, line in enumerate(fh, 1):
+                m = cond.match(line)
+                if m:
+                    found += [f"{name}:{n}: {w}" for w in re.findall(r"\bLEC_\w+", m.group(1)) if w not in allowed]
+    assert not found, found

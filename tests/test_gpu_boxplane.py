@@ -1,8 +1,9 @@
-"""lec_boxplane.hip (LEC_KERNEL_BOX_PLANE): stage 1 of a box-packed fp64 series with the planes brought into LDS by DMA.
+"""lec_boxplane.hip (LEC_KERNEL_BOX_PLANE): stage 1 of a box-packed series (fp64 or fp32 storage) with the planes' rows loaded
+straight into the compute layout.
 
-It replaces lec_boxtile.hip for that kind of call (what every -t path of the product hands stage 1 for fp64 data) and must give that
-kernel's row records BIT for bit: the same products, rounding points, summation groups and order -- only where the operands come
-from differs (global_load_lds pieces of contiguous plane rows, T's vertical neighbours one level back / ahead in registers).  The
+It replaces lec_boxtile.hip for that kind of call (what every -t path of the product hands stage 1) and must give that kernel's row
+records BIT for bit: the same products, rounding points, summation groups and order -- only where the operands come from differs
+(16-byte buffer loads of contiguous plane rows, T through two LDS tiles, T's vertical neighbours one level back in registers).  The
 box-tile kernel itself is held to the independent one-wave-per-row kernel and to the oracle elsewhere (test_gpu_parity.py,
 test_gpu_packed.py); here: every record equal, across geometries, level chunks, slab paddings, NaNs and shards -- and against the
 oracle once more (the reference's moving framework: lec_moving_framework.py:639-745, box_data.py:297-310)."""

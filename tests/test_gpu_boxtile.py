@@ -1,9 +1,7 @@
-"""Time groups of the box-tile kernel (lec_boxtile.hip, template parameter TG): a workgroup of TG waves owns the same four rows of TG
-consecutive time steps and hands T(t - 1) / T(t + 1) from wave to wave through LDS instead of loading them.  The waves of a group
-load on the rows and columns of the UNION of their boxes, while everything that shapes a sum stays box-relative -- so the row records
-must not depend on TG, on whether a group's boxes fit one union (64 columns, the launch's row blocks), on how a series is cut into
-groups, shards or chunks, or on what lies just outside a box: bit for bit against TG = 1, and to rounding against the independent
-one-wave-per-row kernel."""
+"""The box-tile kernel (lec_boxtile.hip: one wave per four box rows of one time step walks a chunk of levels; the stage-1 kernel
+of per-step boxes on a crop): its row records against the independent one-wave-per-row kernel on boxes of many shapes, for fp64
+and fp32 storage, uniform and stretched longitudes; bit for bit the same whether a series runs whole or as a shard; untouched by
+what lies just outside a box; and the terms of BASELINE config 5's shape against the oracle."""
 import numpy as np
 import pytest
 
@@ -22,10 +20,10 @@ def _same(a, b):
     return bool(((a == b) | (torch.isnan(a) & torch.isnan(b))).all())
 
 
-def _rows(eng, f, boxes, time_s, tg, t_begin=0, t_count=None, nyb=None):
-    """Row records + terms of steps [t_begin, t_begin + t_count) with time groups of `tg` (0: the one-wave-per-row kernel).  The record
-    buffer is handed over full of NaN: a row the kernel fails to write -- a padding row of a lower box, say -- shows."""
-    tuning = {"kernel": "box_tile", "block_shape": tg} if tg else {"kernel": "row_sweep"}
+def _rows(eng, f, boxes, time_s, kernel="box_tile", t_begin=0, t_count=None, nyb=None):
+    """Row records + terms of steps [t_begin, t_begin + t_count) on `kernel`.  The record buffer is handed over full of NaN: a row the
+    kernel fails to write -- a padding row of a lower box, say -- shows."""
+    tuning = {"kernel": kernel}
     t_count = len(boxes) if t_count is None else t_count
     nyb = max(b[3] - b[2] + 1 for b in boxes) if nyb is None else nyb
     prep = eng.prepare_boxes(boxes, nyb_min=nyb)
@@ -50,42 +48,36 @@ def _track(nt, nx, ny, w, h, rng, jumps=()):
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("nonuniform", [False, True])
-def test_records_do_not_depend_on_the_time_group(dtype, nonuniform):
+def test_records_match_the_row_sweep_and_do_not_depend_on_the_shard(dtype, nonuniform):
     rng = np.random.default_rng(11)
     nt, nl, ny, nx = 23, 9, 80, 100
     dom = synthetic_domain(nt, nl, ny, nx, seed=3, dtype=dtype, lat0=-60, lat1=19, lon0=-100, lon1=-1, nonuniform_lon=nonuniform)
     eng = LECEngine(dom.lat, dom.lon, dom.level, device=DEV)
     cases = {
-        "61x61 drifting (unions of 64 fit, some do not)": _track(nt, nx, ny, 61, 61, rng),
-        "50x45 drifting with jumps (groups that cannot share)": _track(nt, nx, ny, 50, 45, rng, jumps=(6, 7, 15)),
+        "61x61 drifting": _track(nt, nx, ny, 61, 61, rng),
+        "50x45 drifting with jumps": _track(nt, nx, ny, 50, 45, rng, jumps=(6, 7, 15)),
         "one box for every step": [(10, 70, 8, 68)] * nt,
         "two-row, three-column boxes": _track(nt, nx, ny, 3, 2, rng),
         "boxes of changing size": [(4 + t % 3, 40 + 2 * (t % 11), 3 + t % 2, 30 + 3 * (t % 7)) for t in range(nt)],
         "64 columns wide, 64 rows high": [(20 + (t % 2), 83 + (t % 2), 10, 73) for t in range(nt)],
-        # (found by the soak: a LOW box that starts far below the top of its group's union -- its padding rows, which stage 2 reads
-        # as zeros, must still lie inside the launch's row blocks, else the group may not share)
-        "a low box far down the union": [(7, 13, 41, 53) if t % 2 == 0 else (3, 9, 45, 46) for t in range(nt)],
+        # (a low box beside a tall one: its padding rows, which stage 2 reads as zeros, must be written)
+        "a low box beside a tall one": [(7, 13, 41, 53) if t % 2 == 0 else (3, 9, 45, 46) for t in range(nt)],
         "boxes of very different heights": [[(13, 30, 8, 42), (0, 30, 6, 56), (16, 30, 6, 23), (4, 17, 23, 40)][t % 4] for t in range(nt)],
     }
     for what, boxes in cases.items():
         f = [torch.as_tensor(np.ascontiguousarray(x)).to(DEV) for x in (dom.tair, dom.u, dom.v, dom.omega, dom.geopt)]
-        one = _rows(eng, f, boxes, dom.time_s, 1)
-        ind = _rows(eng, f, boxes, dom.time_s, 0)                                 # the one-wave-per-row kernel: an independent formulation
+        one = _rows(eng, f, boxes, dom.time_s)
+        ind = _rows(eng, f, boxes, dom.time_s, "row_sweep")                      # the one-wave-per-row kernel: an independent formulation
         den = ind.rows[..., :28].abs().amax(dim=(0, 1, 2)).clamp_min(1e-300)
         assert float(((one.rows[..., :28] - ind.rows[..., :28]).abs().amax(dim=(0, 1, 2)) / den).max()) < 1e-10, what
-        for tg in (2, 4):
-            got = _rows(eng, f, boxes, dom.time_s, tg)
-            assert _same(got.rows, one.rows), (what, tg)
-            assert torch.equal(got.scalars, one.scalars) and torch.equal(got.levels, one.levels), (what, tg)
-            # a shard that cuts the groups elsewhere (steps 3..13 of the series, its own one-step halo)
-            part = _rows(eng, f, boxes[3:14], dom.time_s, tg, t_begin=3, t_count=11, nyb=int(one.rows.shape[2]))
-            assert _same(part.rows, one.rows[3:14]), (what, tg, "shard")
+        # a shard of the series (steps 3..13, its own one-step halo)
+        part = _rows(eng, f, boxes[3:14], dom.time_s, t_begin=3, t_count=11, nyb=int(one.rows.shape[2]))
+        assert _same(part.rows, one.rows[3:14]), (what, "shard")
 
 
 def test_what_lies_outside_a_box_does_not_reach_its_records():
     """NaN just outside every box -- the rows above and below it and the columns either side, at the step's own time and at its
-    time neighbours' -- where a sharing group loads the union's rows: the one-sided stencils give those points the coefficient 0,
-    and 0 x NaN must not be formed."""
+    time neighbours': the one-sided stencils give those points the coefficient 0, and 0 x NaN must not be formed."""
     rng = np.random.default_rng(5)
     nt, nl, ny, nx = 14, 6, 70, 90
     dom = synthetic_domain(nt, nl, ny, nx, seed=8, dtype=np.float64, lat0=-60, lat1=9, lon0=-100, lon1=-11)
@@ -105,16 +97,14 @@ def test_what_lies_outside_a_box_does_not_reach_its_records():
     eng = LECEngine(dom.lat, dom.lon, dom.level, device=DEV)
     clean = [torch.as_tensor(np.ascontiguousarray(x)).to(DEV) for x in (dom.tair, dom.u, dom.v, dom.omega, dom.geopt)]
     dirty = [torch.as_tensor(np.ascontiguousarray(T)).to(DEV)] + clean[1:]
-    ref = _rows(eng, clean, boxes, dom.time_s, 1)
+    ref = _rows(eng, clean, boxes, dom.time_s)
     assert bool(torch.isfinite(ref.rows[..., :28]).all())
-    for tg in (1, 2, 4):
-        got = _rows(eng, dirty, boxes, dom.time_s, tg)
-        assert _same(got.rows, ref.rows), tg
+    got = _rows(eng, dirty, boxes, dom.time_s)
+    assert _same(got.rows, ref.rows)
 
 
-def test_config5_shape_in_time_groups():
-    """BASELINE config 5's shape (37 levels, 61 x 61 boxes on a 0.25-degree crop, the bench's track) on 37 steps: TG = 2 and 4 against
-    TG = 1, the terms against the oracle."""
+def test_config5_shape():
+    """BASELINE config 5's shape (37 levels, 61 x 61 boxes on a 0.25-degree crop): the terms of six steps against the oracle."""
     from lorenzcycletoolkit_amd.synthetic import era5_like_levels, synthetic_cube
     from oracle import lec_oracle as o
     from tests.helpers import scale_err
@@ -124,32 +114,25 @@ def test_config5_shape_in_time_groups():
     nt = 37
     f = synthetic_cube(nt, level, lat, lon, device=DEV, dtype=torch.float64, seed=77)
     eng = LECEngine(lat, lon, level, device=DEV)
-    tg_ = np.arange(nt) * 9                                                        # nine bench steps apart: boxes up to 7 columns apart
-    clat = -37.5 + 12.0 * np.sin(2 * np.pi * tg_ / 400.0)
-    clon = -50.0 + 22.0 * np.cos(2 * np.pi * tg_ / 700.0)
     slow = [eng.box_from_limits(-50.0 + 0.2 * t - 7.5, -50.0 + 0.2 * t + 7.5, -37.5 - 7.5, -37.5 + 7.5) for t in range(nt)]
-    fast = [eng.box_from_limits(lo - 7.5, lo + 7.5, la - 7.5, la + 7.5) for la, lo in zip(clat, clon)]
     time_s = np.arange(nt) * 3600.0
     cubes = [f["tair"], f["u"], f["v"], f["omega"], f["geopt"]]
-    for boxes in (slow, fast):
-        one = _rows(eng, cubes, boxes, time_s, 1)
-        for tg in (2, 4):
-            got = _rows(eng, cubes, boxes, time_s, tg)
-            assert _same(got.rows, one.rows) and torch.equal(got.scalars, one.scalars), tg
     host = {k: v[:6].cpu().numpy() for k, v in f.items()}
     dom = o.Domain(host["tair"], host["u"], host["v"], host["omega"], host["geopt"], lat, lon, level, time_s[:6])
     limits = [(lon[b[0]], lon[b[1]], lat[b[2]], lat[b[3]]) for b in slow[:6]]
     sc, _ = o.lec_moving(dom, limits)
-    got = eng.compute(*[c[:6] for c in cubes], slow[:6], time_s=time_s[:6], per_step_boxes=True, tuning={"kernel": "box_tile", "block_shape": 4})
+    got = eng.compute(*[c[:6] for c in cubes], slow[:6], time_s=time_s[:6], per_step_boxes=True, tuning={"kernel": "box_tile"})
     names = ("Az", "Ae", "Kz", "Ke", "Cz", "Ca", "Ck", "Ce", "BAz", "BAe", "BKz", "BKe", "BΦZ", "BΦE", "Gz", "Ge")
     gs = got.scalars_dict()
     for n in names:
         assert scale_err(gs[n], np.asarray(sc[n])) < 1e-9, n
 
 
-def test_bad_time_group_is_refused():
+def test_block_shape_above_one_is_refused():
+    """A box-tile call runs one time step per workgroup: block_shape is 0 or 1."""
     dom = synthetic_domain(4, 3, 20, 30, seed=1)
     eng = LECEngine(dom.lat, dom.lon, dom.level, device=DEV)
     f = [torch.as_tensor(np.ascontiguousarray(x)).to(DEV) for x in (dom.tair, dom.u, dom.v, dom.omega, dom.geopt)]
-    with pytest.raises(ValueError, match="block_shape"):
-        eng.compute(*f, [(2, 20, 2, 15)] * 4, time_s=dom.time_s, per_step_boxes=True, tuning={"kernel": "box_tile", "block_shape": 3})
+    for block_shape in (2, 3, 4):
+        with pytest.raises(ValueError, match="block_shape"):
+            eng.compute(*f, [(2, 20, 2, 15)] * 4, time_s=dom.time_s, per_step_boxes=True, tuning={"kernel": "box_tile", "block_shape": block_shape})

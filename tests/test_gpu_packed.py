@@ -152,6 +152,6 @@ def test_packed_arguments_are_checked():
     with pytest.raises(ValueError, match="box-tile"):
         eng.rowstats(*pk, pb, tm=tm, tp=tp, tuning={"kernel": "row_sweep"}, **kw)    # another kernel family would read the wrong neighbours
     with pytest.raises(ValueError, match="box-tile"):
-        eng.rowstats(*pk, pb, tm=tm, tp=tp, tuning={"kernel": "box_tile", "block_shape": 2}, **kw)      # time groups share grid rows: not packed
+        eng.rowstats(*pk, pb, tm=tm, tp=tp, tuning={"kernel": "box_tile", "block_shape": 2}, **kw)      # box-tile calls: block_shape 0 or 1 only
     with pytest.raises(ValueError, match="tallest"):
         eng.rowstats(*[c[:, :, :5] .contiguous() for c in pk], pb, tm=tm[:, :, :5].contiguous(), tp=tp[:, :, :5].contiguous(), **kw)

@@ -16,9 +16,10 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def test_soak_slice_resident_kernels_oracle_and_shards():
+def test_soak_slice_kernel_families_oracle_and_shards():
     """50 random grids / boxes / dtypes / time axes / NaN patches: every kernel family that can run a case agrees record by record,
-    the terms agree with the oracle (every other case), a shard of the series reproduces the whole bit for bit."""
+    the box-packed form of a track series gives the same bits, the terms agree with the oracle (every other case), a shard of the
+    series reproduces the whole bit for bit."""
     from tests import soak_gpu as soak
     rng = np.random.default_rng(20260401)
     fails = []

@@ -1,5 +1,5 @@
 mkdir -p gpurun_out/r06
-python -m pytest tests/test_gpu_packed.py tests/test_gpu_timegroups.py tests/test_gpu_parity.py tests/test_gpu_boxplane.py -x -q -m gpu 2>&1 | tail -5 || exit 1
+python -m pytest tests/test_gpu_packed.py tests/test_gpu_boxtile.py tests/test_gpu_parity.py tests/test_gpu_boxplane.py -x -q -m gpu 2>&1 | tail -5 || exit 1
 for r in 1 2 3; do
  for L in tools/probes/liblec_old.so ""; do
   for A in "--moving --timesteps 512 --moving-layout cube" "--moving --timesteps 2048 --moving-layout cube"; do
