@@ -46,8 +46,10 @@ extern "C" {
 
 /* ABI 8 (round 4): lec_reduce_args.stage (the two halves of stage 2 run apart; no 65535-step limit), lec_inflate_args.dst_bytes and
  * lec_chunk_scatter_args.src_bytes (the destination / payload ranges of every descriptor are bounds-checked on the device). */
-#define LEC_ABI_VERSION 10
-/* ABI 10 (round 6): lec_ingest_args.nt_src (was reserved0) / jmap_len / imap_len: a per-step gather table (step_d) is bounds-checked --
+#define LEC_ABI_VERSION 11
+/* ABI 11: lec_rowstats_steps -- stage 1 over the boxes of several tracks on ONE cube, each box naming its cube step and that step's time
+ * neighbours in a device table (lec_rowstats_args unchanged).
+ * ABI 10 (round 6): lec_ingest_args.nt_src (was reserved0) / jmap_len / imap_len: a per-step gather table (step_d) is bounds-checked --
  * lec_ingest refuses one without them, its kernel writes NaN rows for an entry that points outside the source or the maps instead of
  * reading there, and lec_check_maps scans the table and names the first bad entry.
  * ABI 9 (round 5): lec_format_csv_rows (host): a per-level table as the text pandas writes for it, one call per table;
@@ -308,6 +310,22 @@ const char* lec_last_error(void);
 int lec_max_row(int dtype, int aligned, int kernel);
 
 int lec_rowstats(const lec_rowstats_args* args);
+
+/*
+ * Stage 1 over the boxes of MANY tracks on one cube (ABI 11).  The reference runs one process per track (its documented batch is a
+ * shell loop, docs/source/examples_and_tutorials.rst); here K tracks over one file share one cube -- the union of their time steps on
+ * the union of their crops -- and one launch.  Box b reads cube step step_d[b][0] and forms dT/dt per point as
+ *   tc[b][0] T[step_d[b][1]] + tc[b][1] T[step_d[b][0]] + tc[b][2] T[step_d[b][2]],   tc = tcoef_d indexed BY BOX ([t_count][3])
+ * -- the track's own previous / next time, which need not be the cube's neighbouring step (a 6-hourly track over 3-hourly data) and may
+ * be shared with other tracks' boxes.  At a track's first / last time the neighbour is the step itself and its coefficient 0, as in
+ * lec_rowstats.  The records (and so lec_reduce) are those of lec_rowstats on the track's own cube, bit for bit.
+ *   step_d   device memory, int32 [t_count][3] = {t, t_prev, t_next}, absolute cube steps.  An entry outside [0, nt) never reads: that
+ *            box's records are written as NaN (the table lives where argument validation cannot see it; the Python host checks it first).
+ *   args     as for lec_rowstats, with box_per_step = 1, n_box = t_count, t_begin = 0 (t_count may exceed nt), with_q = 1 and tcoef_d;
+ *            dTdt_d, tm_d and tp_d NULL (the cube layout only).  tuning.kernel other than LEC_KERNEL_AUTO / LEC_KERNEL_BOX_TILE:
+ *            LEC_ERR_UNSUPPORTED (the box-tile kernel serves every call).
+ */
+int lec_rowstats_steps(const lec_rowstats_args* args, const int32_t* step_d);
 int lec_ingest(const lec_ingest_args* args);
 int lec_reduce(const lec_reduce_args* args);
 

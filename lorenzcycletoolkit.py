@@ -22,7 +22,7 @@ import pandas as pd
 
 from lorenzcycletoolkit_amd import phases
 from lorenzcycletoolkit_amd.dataset import prepare_data
-from lorenzcycletoolkit_amd.frameworks import lec_fixed, lec_moving
+from lorenzcycletoolkit_amd.frameworks import lec_fixed, lec_moving, lec_moving_batch
 
 phases.mark("imports")          # interpreter start -> here: Python, pandas, torch and the package
 
@@ -46,6 +46,9 @@ def create_arg_parser():
     parser.add_argument("--cdsapi", action="store_true", help="download ERA5 through the CDS API first (needs network access: not available in this build)")
     parser.add_argument("--time-resolution", type=int, default=3, help="hours between downloaded analyses with --cdsapi (default: 3)")
     parser.add_argument("--trackfile", type=str, default="inputs/track", help="track file for -t (default: inputs/track)")
+    parser.add_argument("--trackfiles", nargs="+", metavar="PATH", help="with -t: many track files over the same data file in ONE pass "
+                        "(a directory stands for every regular file in it, sorted by name).  Each track writes LEC_Results/<infile>_<track>_track/ "
+                        "with the files a --trackfile run of it writes; the log and batch.csv go to LEC_Results/<infile>_track_batch/")
     parser.add_argument("--box_limits", type=str, default="inputs/box_limits", help="box-limits file for -f (default: inputs/box_limits)")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
@@ -139,6 +142,8 @@ def main(argv=None):
     args = create_arg_parser().parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.trackfiles is not None:
+        return main_batch(args, argv)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # this process only starts the ranks (before anything touches a GPU) and waits for them
@@ -230,6 +235,59 @@ def main(argv=None):
             import torch.distributed as dist
             if dist.is_initialized():
                 dist.destroy_process_group()
+
+
+def refuse_batch_options(args):
+    """What a --trackfiles run does not do, said before any GPU work."""
+    if not args.track:
+        raise SystemExit("--trackfiles goes with -t/--track")
+    if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--trackfiles runs on one GPU: --gpus > 1 is not supported for a batch of tracks")
+    if args.ingest == "device" or args.device_ingest:
+        raise SystemExit("--trackfiles prepares the data on the host: --ingest device / --device-ingest is not supported for a batch of tracks")
+
+
+def main_batch(args, argv):
+    """-t --trackfiles: every track's tree as its own -t --trackfile run writes it, one pass over the data (lorenzcycletoolkit_amd/batch.py)."""
+    from lorenzcycletoolkit_amd import batch
+    refuse_batch_options(args)
+    args.shard = None
+    stem = "".join(args.infile.split("/")[-1].split(".nc"))
+    batch_dir = os.path.join("./LEC_Results/", stem + "_track_batch")
+    created = [] if os.path.isdir(batch_dir) else [batch_dir]
+    os.makedirs(batch_dir, exist_ok=True)
+    app_logger = initialize_logging(batch_dir, args)
+    app_logger.info("Starting LEC analysis (batch of tracks)")
+    app_logger.info(f"Command line arguments: {args}")
+    try:
+        start_time = time.time()
+        trackfiles = batch.expand_trackfiles(args.trackfiles)
+        variable_list_df = pd.read_csv("inputs/namelist", sep=";", index_col=0, header=0)
+        data, plan = batch.prepare_union(args, trackfiles, "inputs/namelist", app_logger)
+        phases.mark("open_decode_and_prepare")
+        directories = []
+        for tr in plan.tracks:
+            tree = os.path.join("./LEC_Results/", f"{stem}_{tr.stem}_track")
+            if not os.path.isdir(tree):
+                created.append(tree)
+            vl, fig = os.path.join(tree, "results_vertical_levels"), os.path.join(tree, "Figures")
+            for d in (fig, tree, vl):
+                os.makedirs(d, exist_ok=True)
+            directories.append((tree, fig, vl))
+        lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
+        pd.DataFrame({"trackfile": [tr.path for tr in plan.tracks], "results_directory": [d[0] for d in directories],
+                      "steps": [tr.n for tr in plan.tracks]}).to_csv(os.path.join(batch_dir, "batch.csv"), index=False)
+        app_logger.info("Analysis complete! Moving framework ran %d tracks in %.2f seconds" % (len(plan.tracks), time.time() - start_time))
+    except Exception:
+        app_logger.exception("LEC analysis failed")
+        for tree in created:
+            _leave_only_the_log(tree)
+            if tree != batch_dir and not os.listdir(tree):
+                os.rmdir(tree)
+        raise
+    finally:
+        phases.mark("end")
+        phases.dump({"argv": argv})
 
 
 if __name__ == "__main__":

@@ -10,7 +10,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # LEC_LIB: alternative build of the same ABI (kernel experiments only)
 LIB_PATH = os.environ.get("LEC_LIB") or os.path.join(_HERE, "liblec_hip.so")
 
-LEC_ABI_VERSION = 10
+LEC_ABI_VERSION = 11
 LEC_NSTAT = 32
 LEC_NLEVRAW = 40
 LEC_NSCALAR = 16
@@ -42,7 +42,7 @@ def source_digest() -> str:
 
 EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_reduce", "lec_dropmask", "lec_ingest", "lec_track_diag",
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
-           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt"]
+           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps"]
 
 
 class Tuning(C.Structure):
@@ -161,6 +161,8 @@ def load():
     lib.lec_max_row.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.lec_rowstats.restype = C.c_int
     lib.lec_rowstats.argtypes = [C.POINTER(RowstatsArgs)]
+    lib.lec_rowstats_steps.restype = C.c_int
+    lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int
     lib.lec_reduce.argtypes = [C.POINTER(ReduceArgs)]
     lib.lec_dropmask.restype = C.c_int

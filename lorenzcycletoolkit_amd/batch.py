@@ -1,0 +1,233 @@
+"""Many tracks over one data set in ONE moving-framework pass (``lorenzcycletoolkit.py -t --trackfiles``).
+
+The reference runs one process per track (its documented batch is a shell loop, docs/source/examples_and_tutorials.rst); every run
+opens, decodes and crops the same file again.  Here the tracks are planned together on the host:
+
+* every track is validated exactly as a single ``-t --trackfile`` run validates it, before any GPU work; a failure refuses the whole
+  batch and names the track file;
+* the data are prepared ONCE on the union of the tracks' time steps and the bounding rectangle of their crops (each track's own
+  ``domain_slices`` window);
+* every track's boxes are found on its OWN window's coordinates (so they are the grid points of its single run) and shifted into the
+  union crop; a slice table {step, previous step, next step} in union steps and the track's own d/dt coefficients go with them
+  (``LECEngine.rowstats(steps=...)``, ``lec_rowstats_steps``);
+* tracks are grouped by what a single run of the track decides from its own data -- the record extents (tallest / widest box) and
+  the longitude formulation of its own crop (``TrackPlan.group_key``): one engine call per group, so no track's bits depend on which
+  other tracks share the batch.
+
+This module is host-only (NumPy / pandas); ``frameworks.lec_moving_batch`` runs the plan on the GPU.
+"""
+from __future__ import annotations
+
+import os
+from dataclasses import dataclass, field
+from types import SimpleNamespace
+from typing import Dict, List, Sequence, Tuple
+
+import numpy as np
+import pandas as pd
+
+from . import dataset as ds
+from . import tables
+
+
+class BatchRefusal(ValueError):
+    """A batch that cannot run as given (a track that a single run would refuse, duplicate track names)."""
+
+
+@dataclass
+class TrackPlan:
+    path: str                    # the track file
+    stem: str                    # its name without the extension: the results directory's suffix
+    track: pd.DataFrame
+    time: np.ndarray             # datetime64[ns]: the track's times (= the time axis of its single run)
+    ustep: np.ndarray            # int [n]: the union step of each of the track's times
+    js: slice                    # the track's own crop (single run) in the sorted grid
+    is_: slice
+    joff: int                    # offset of that crop inside the union crop
+    ioff: int
+    limits: List[dict]           # get_limits per time step (the single run's)
+    boxes: List[Tuple[int, int, int, int]]       # inclusive (iw, ie, js, jn) in UNION crop indices
+    steps: np.ndarray            # int32 [n, 3]: {union step, previous, next} of the track's own time axis
+    tcoef: np.ndarray            # [n, 3]: tables.time_coefs of the track's own time axis
+    lon_uniform: bool = True     # the kernels' longitude formulation, decided on the track's OWN crop as its single run decides it
+
+    @property
+    def n(self) -> int:
+        return len(self.time)
+
+    @property
+    def time_s(self) -> np.ndarray:
+        return (self.time - self.time.min()) / np.timedelta64(1, "s")
+
+    @property
+    def extents(self) -> Tuple[int, int]:
+        """(nyb_max, nxb_max) of the track's single run: its record buffer's rows and the widest box."""
+        return (int(max(b[3] - b[2] + 1 for b in self.boxes)), int(max(b[1] - b[0] + 1 for b in self.boxes)))
+
+    @property
+    def group_key(self) -> Tuple[int, int, bool]:
+        """What a single run of the track decides from its own data and a batch must keep: the record extents and the longitude
+        formulation (tables.build_box_tables: on a partly stretched grid a track's crop can be evenly spaced while the union's is not,
+        and the two formulations differ in the last bits)."""
+        return self.extents + (self.lon_uniform,)
+
+    def window(self, lat: np.ndarray, lon: np.ndarray):
+        """(lat, lon) of the track's own crop, from the union crop's coordinates."""
+        ny, nx = self.js.stop - self.js.start, self.is_.stop - self.is_.start
+        return lat[self.joff: self.joff + ny], lon[self.ioff: self.ioff + nx]
+
+
+@dataclass
+class BatchPlan:
+    tracks: List[TrackPlan]
+    px: ds.ProcessIndex          # the file's sorted axes over ALL its time steps
+    tpos: np.ndarray             # sorted file time steps of the union
+    js: slice                    # union crop in the sorted grid
+    is_: slice
+    groups: Dict[Tuple[int, int, bool], List[int]] = field(default_factory=dict)   # TrackPlan.group_key -> track indices, in batch order
+
+    @property
+    def lat(self) -> np.ndarray:
+        return self.px.lat[self.js]
+
+    @property
+    def lon(self) -> np.ndarray:
+        return self.px.lon[self.is_]
+
+    @property
+    def time(self) -> np.ndarray:
+        return self.px.time[self.tpos]
+
+
+def expand_trackfiles(paths: Sequence[str]) -> List[str]:
+    """The ``--trackfiles`` arguments as a list of files: a directory stands for every regular file in it, sorted by name.  Two
+    files with the same stem would write one results directory: refused."""
+    out = []
+    for p in paths:
+        if os.path.isdir(p):
+            out += [os.path.join(p, f) for f in sorted(os.listdir(p)) if os.path.isfile(os.path.join(p, f))]
+        else:
+            out.append(p)
+    if not out:
+        raise BatchRefusal("--trackfiles: no track files given")
+    seen = {}
+    for p in out:
+        stem = track_stem(p)
+        if stem in seen:
+            raise BatchRefusal(f"track files {seen[stem]} and {p} have the same name '{stem}': their results directories would collide")
+        seen[stem] = p
+    return out
+
+
+def track_stem(path: str) -> str:
+    return os.path.splitext(os.path.basename(path))[0]
+
+
+def _refuse(path: str, e: BaseException):
+    msg = e.args[0] if (isinstance(e, KeyError) and e.args) else str(e)
+    raise BatchRefusal(f"track file {path}: {msg}") from e
+
+
+def plan_batch(lat, lon, lev, time, level_units, names, trackfiles: Sequence[str], app_logger=None) -> BatchPlan:
+    """The batch on the FILE's coordinates (as ``process_index`` takes them): per track the checks of a single run, its time steps,
+    its crop, its boxes, slice table and d/dt coefficients; then the union and the groups.  No data are read."""
+    from .frameworks import get_limits
+    px = ds.process_index(lat, lon, lev, time, level_units, names, SimpleNamespace(track=False), app_logger)
+    raw = []
+    for path in trackfiles:
+        try:
+            track = ds.read_track(path, app_logger)
+            if len(track) < 2:
+                raise ValueError(f"a track needs at least 2 time steps, this one has {len(track)}")
+            tpos = ds.select_track_times(px.time, track)
+            js, is_ = ds.domain_slices(px.lat, px.lon, None, track=track)
+            wlat, wlon = px.lat[js], px.lon[is_]
+            # the checks lec_moving makes on its (cropped) data set (lec_moving_framework.py:112-154)
+            t = px.time[tpos]
+            if track.index[0] < t.min() or track.index[-1] > t.max():
+                raise ValueError("Track time limits do not match with data time limits.")
+            for name, coord in (("Lon", wlon), ("Lat", wlat)):
+                word = "longitude" if name == "Lon" else "latitude"
+                if track[name].max() > coord.max():
+                    raise ValueError(f"Track file {word} max limit ({track[name].max():.2f}) exceeds data max {word} limit ({float(coord.max()):.2f}).")
+                if track[name].min() < coord.min():
+                    raise ValueError(f"Track file {word} min limit ({track[name].min():.2f}) is below data min {word} limit ({float(coord.min()):.2f}).")
+            if 85000.0 not in px.level:
+                raise KeyError("no 85000 Pa level in the data (the 850-hPa track diagnostics select it)")
+            limits = [get_limits(track, tt) for tt in pd.DatetimeIndex(t)]
+            wboxes = [tables.box_indices(wlat, wlon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in limits]
+        except BatchRefusal:
+            raise
+        except (ValueError, KeyError, IndexError, FileNotFoundError) as e:
+            _refuse(path, e)
+        raw.append((path, track, np.asarray(tpos), t, js, is_, limits, wboxes))
+
+    tpos_u = np.unique(np.concatenate([r[2] for r in raw]))
+    j0, j1 = min(r[4].start for r in raw), max(r[4].stop for r in raw)
+    i0, i1 = min(r[5].start for r in raw), max(r[5].stop for r in raw)
+    plans = []
+    for path, track, tpos, t, js, is_, limits, wboxes in raw:
+        joff, ioff = js.start - j0, is_.start - i0
+        boxes = [(int(iw + ioff), int(ie + ioff), int(jsb + joff), int(jn + joff)) for iw, ie, jsb, jn in wboxes]
+        u = np.searchsorted(tpos_u, tpos)
+        n = u.size
+        steps = np.stack([u, u[np.maximum(np.arange(n) - 1, 0)], u[np.minimum(np.arange(n) + 1, n - 1)]], axis=1).astype(np.int32)
+        tr = TrackPlan(path=path, stem=track_stem(path), track=track, time=t, ustep=u, js=js, is_=is_, joff=joff, ioff=ioff,
+                       limits=limits, boxes=boxes, steps=steps, tcoef=None, lon_uniform=tables.is_uniform(px.lon[is_]))
+        tr.tcoef = tables.time_coefs(tr.time_s)
+        plans.append(tr)
+    plan = BatchPlan(plans, px, tpos_u, slice(j0, j1), slice(i0, i1))
+    for k, tr in enumerate(plans):
+        plan.groups.setdefault(tr.group_key, []).append(k)
+    return plan
+
+
+def union_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> int:
+    """Device bytes of the union cubes (``n_fields`` cubes of ``itemsize``-byte elements)."""
+    return n_fields * itemsize * len(plan.tpos) * len(plan.px.level) * len(plan.lat) * len(plan.lon)
+
+
+def device_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> dict:
+    """Device memory of a batch run (``frameworks.lec_moving_batch``): the union cubes (held throughout), the row records of the
+    largest group (one group's stage-1 output at a time: fp64 [boxes, nl, nyb_max, 32]) with stage 2's workspaces, and the packed
+    per-step results of all tracks (kept until the files are written)."""
+    from . import _lib
+    nl = len(plan.px.level)
+    cubes = union_bytes(plan, n_fields, itemsize)
+    rows = 0
+    for key, members in plan.groups.items():
+        n = sum(plan.tracks[k].n for k in members)
+        rows = max(rows, 8 * n * nl * (key[0] * _lib.LEC_NSTAT + 8 + _lib.LEC_NLEVRAW))
+    results = 8 * sum(tr.n for tr in plan.tracks) * (_lib.LEC_NSCALAR + _lib.LEC_NLEVTAB * nl + 1)
+    return {"cubes": cubes, "records": rows, "results": results, "total": cubes + rows + results}
+
+
+def prepare_union(args, trackfiles: Sequence[str], varlist: str = "inputs/namelist", app_logger=None):
+    """``prepare_data`` for a batch: the plan, and the data set of the union (its time steps, its crop), decoded once.
+    Returns (LECDataset, BatchPlan)."""
+    variable_list_df = ds.read_namelist(varlist, app_logger)
+    mpas = bool(getattr(args, "mpas", False))
+    try:
+        raw = ds.open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
+    except ValueError as e:
+        if "order" not in str(e) and "device ingest reads" not in str(e):
+            raise
+        data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)
+        plan = plan_batch(data.lat, data.lon, data.level, data.time, data.level_units, data.names, trackfiles, app_logger)
+        data = ds.process_data(data, SimpleNamespace(track=False), variable_list_df, app_logger)
+        return data.isel(t=plan.tpos, j=plan.js, i=plan.is_), plan
+    try:
+        plan = plan_batch(raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, trackfiles, app_logger)
+        px = plan.px
+        i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+        ip = ds.IngestPlan(plan.tpos, i32(px.ik), i32(px.ij[plan.js]), i32(px.io[plan.is_]), plan.lat, plan.lon, px.level, plan.time)
+        variables = {name: ds.gather_on_host(var, ip) for name, var in raw.variables.items()}
+        return ds.LECDataset(variables, ip.lat, ip.lon, ip.level, ip.time, dict(raw.names), "Pa"), plan
+    finally:
+        raw.close()
+
+
+def track_view(data: ds.LECDataset, tr: TrackPlan) -> ds.LECDataset:
+    """The union data set restricted to one track's times and its own crop: the data set of the track's single run."""
+    ny, nx = tr.js.stop - tr.js.start, tr.is_.stop - tr.is_.start
+    return data.isel(t=tr.ustep, j=slice(tr.joff, tr.joff + ny), i=slice(tr.ioff, tr.ioff + nx))

@@ -95,8 +95,12 @@ __device__ __forceinline__ void finish_lane(const double (&tot)[kNA], double cT,
 // MODE 0: T, u, v, omega (Phi if present), no Q;  1: dT/dt = ta T(t-1) + tb T(t) + tc T(t+1) per point;  2: dT/dt cube.
 // WINDOW: rows fit one column chunk, so a wave walks its level chunk with T(k-1), T(k), T(k+1) sliding through registers;
 // otherwise every pass loads its own T neighbours (wide boxes; same arithmetic, same bits).
-template <typename TIN, bool UNIFORM, int MODE, bool WINDOW>
+// STEPS (MODE 1 only, lec_rowstats_steps): box tl reads cube step p.steps[tl][0] and takes its T neighbours from p.steps[tl][1] /
+// p.steps[tl][2] (the boxes of several tracks over one cube: steps repeat, neighbours need not be adjacent); p.tcoef is indexed by box.
+// An entry outside [0, nt) never reads: the box's records are written as NaN.
+template <typename TIN, bool UNIFORM, int MODE, bool WINDOW, bool STEPS = false>
 __global__ void __launch_bounds__(64, 2) lec_boxtile_kernel(const RowParams p) {
+    static_assert(!STEPS || MODE == 1, "a step table serves dT/dt from the cube's time neighbours");
     constexpr bool WITH_Q = MODE != 0;
     constexpr int NT = n_tiles<UNIFORM, MODE>();
     __shared__ double sm[lds_doubles<UNIFORM, MODE>()];
@@ -127,6 +131,18 @@ __global__ void __launch_bounds__(64, 2) lec_boxtile_kernel(const RowParams p) {
     const int nxb = ie - iw + 1, nyb = jn - js + 1;
     const int k0 = kc * kchunk, k1 = min(k0 + kchunk, p.nl);
     const int jb0 = rbi * kWR;                       // box-relative row of the wave's first row
+    int tst = p.t_begin + tl, tsm = 0, tsp = 0;      // STEPS: the box's cube step and its two time neighbours
+    if (STEPS) {
+        tst = p.steps[3 * tl]; tsm = p.steps[3 * tl + 1]; tsp = p.steps[3 * tl + 2];
+        if ((unsigned)tst >= (unsigned)p.nt || (unsigned)tsm >= (unsigned)p.nt || (unsigned)tsp >= (unsigned)p.nt) {
+            const int nrow = min(jb0 + kWR, p.nyb_max) - jb0;
+            for (int k = k0; k < k1; ++k) {
+                double* rec = p.rows + ((size_t)(tl * p.nl + k) * p.nyb_max + jb0) * LEC_NSTAT;
+                for (int e = lane; e < nrow * LEC_NSTAT; e += 64) rec[e] = __builtin_nan("");
+            }
+            return;
+        }
+    }
     if (jb0 >= nyb) {                                // a row block that holds only padding rows of a box lower than nyb_max
         const int nrow = min(jb0 + kWR, p.nyb_max) - jb0;
         for (int k = k0; k < k1; ++k) {
@@ -136,7 +152,7 @@ __global__ void __launch_bounds__(64, 2) lec_boxtile_kernel(const RowParams p) {
         return;
     }
 
-    const int t = p.t_begin + tl;
+    const int t = tst;
     const size_t plane = (size_t)p.ny * p.nx;
     const size_t cube = plane * p.nl;
     const size_t t0off = (size_t)t * cube + (size_t)iw;
@@ -149,10 +165,12 @@ __global__ void __launch_bounds__(64, 2) lec_boxtile_kernel(const RowParams p) {
     // neighbours in time: the own time step where there is none (the coefficient is 0 there); MODE 2: the dT/dt cube
     // (a box-packed series: the cube's neighbouring steps hold other boxes; T(t-1), T(t+1) on THIS step's box come in cubes of their own)
     const bool packed = MODE == 1 && p.TM != nullptr;
-    const TIN* __restrict__ gD0 = (MODE == 2) ? (const TIN*)p.DT + t0off : (packed ? (const TIN*)p.TM + t0off : ((t > 0) ? gT - cube : gT));
-    const TIN* __restrict__ gD1 = packed ? (const TIN*)p.TP + t0off : ((t < p.nt - 1) ? gT + cube : gT);
+    const TIN* __restrict__ gD0 = STEPS ? (const TIN*)p.T + ((size_t)tsm * cube + (size_t)iw)
+                                        : ((MODE == 2) ? (const TIN*)p.DT + t0off : (packed ? (const TIN*)p.TM + t0off : ((t > 0) ? gT - cube : gT)));
+    const TIN* __restrict__ gD1 = STEPS ? (const TIN*)p.T + ((size_t)tsp * cube + (size_t)iw)
+                                        : (packed ? (const TIN*)p.TP + t0off : ((t < p.nt - 1) ? gT + cube : gT));
     double ta = 0, tb = 0, tc = 0;
-    if (MODE == 1) { const double* tcf = p.tcoef + (size_t)t * 3; ta = tcf[0]; tb = tcf[1]; tc = tcf[2]; }
+    if (MODE == 1) { const double* tcf = p.tcoef + (size_t)(STEPS ? tl : t) * 3; ta = tcf[0]; tb = tcf[1]; tc = tcf[2]; }
     // Row / level coefficients are wave-uniform, but inside the pass loop (which stores row records) the compiler would fetch them
     // with VECTOR loads followed by s_waitcnt vmcnt(0) -- draining the prefetched rows every time.  So they are loaded once, here,
     // spread over the lanes, and picked with v_readlane:
@@ -477,8 +495,13 @@ int launch_tiles(RowParams p, bool uniform, int mode, hipStream_t st) {
     dim3 grid((unsigned)nblocks), block(64);
 #define LEC_TILE(U, M, W) hipLaunchKernelGGL((lec_boxtile_kernel<TIN, U, M, W>), grid, block, 0, st, p)
 #define LEC_TILE_W(U, M) do { if (window) LEC_TILE(U, M, true); else LEC_TILE(U, M, false); } while (0)
-    if (uniform) { if (mode == 0) LEC_TILE(true, 0, false); else if (mode == 1) LEC_TILE_W(true, 1); else LEC_TILE_W(true, 2); }
+#define LEC_TILE_S(U, W) hipLaunchKernelGGL((lec_boxtile_kernel<TIN, U, 1, W, true>), grid, block, 0, st, p)
+    if (p.steps) {          // a per-box step table (lec_rowstats_steps): MODE 1 only, checked by the caller
+        if (uniform) { if (window) LEC_TILE_S(true, true); else LEC_TILE_S(true, false); }
+        else { if (window) LEC_TILE_S(false, true); else LEC_TILE_S(false, false); }
+    } else if (uniform) { if (mode == 0) LEC_TILE(true, 0, false); else if (mode == 1) LEC_TILE_W(true, 1); else LEC_TILE_W(true, 2); }
     else { if (mode == 0) LEC_TILE(false, 0, false); else if (mode == 1) LEC_TILE_W(false, 1); else LEC_TILE_W(false, 2); }
+#undef LEC_TILE_S
 #undef LEC_TILE_W
 #undef LEC_TILE
     return LEC_OK;

@@ -159,6 +159,7 @@ struct RowParams {
     int jgroup;  // order 7: latitudes per tile
     int jrows;   // sweep kernel: latitudes per workgroup
     int cpx;     // sweep kernel: latitude chunks per XCD
+    const int* steps = nullptr;   // box-tile kernel, MODE 1 (lec_rowstats_steps): [t_count][3] absolute cube steps {t, t - 1, t + 1} per box
 };
 
 

@@ -312,13 +312,23 @@ extern "C" int lec_max_row(int dtype, int aligned, int kernel) {
     return 1 << 24;
 }
 
-extern "C" int lec_rowstats(const lec_rowstats_args* a) {
+// lec_rowstats and lec_rowstats_steps (step_d != NULL: a per-box source-step table, box-tile kernel only)
+static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d) {
     if (!a) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: null args");
+    if (step_d) {       // boxes of several tracks over one cube: every box names its cube step and the step's time neighbours
+        if (a->box_per_step != 1 || a->n_box != a->t_count || a->t_begin != 0 || a->t_count < 1)
+            return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: needs box_per_step = 1, n_box = t_count >= 1 and t_begin = 0");
+        if (a->dTdt_d || a->tm_d || a->tp_d)
+            return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: dTdt_d, tm_d and tp_d must be NULL (dT/dt from the cube's steps named by the table)");
+        if (!a->with_q || !a->tcoef_d) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: needs with_q and tcoef_d ([t_count][3], by box)");
+        if (a->tuning.kernel != LEC_KERNEL_AUTO && a->tuning.kernel != LEC_KERNEL_BOX_TILE)
+            return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_rowstats_steps: only LEC_KERNEL_AUTO and LEC_KERNEL_BOX_TILE read a step table");
+    }
     if (!a->tair_d || !a->u_d || !a->v_d || !a->omega_d || !a->rows_d || !a->box_d || !a->boxtab_d)
         return lec_set_error(LEC_ERR_ARG, "lec_rowstats: null field / output / box pointer");
     if (a->dtype != LEC_F64 && a->dtype != LEC_F32) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: dtype must be LEC_F64 or LEC_F32");
     if (a->nt < 1 || a->nl < 2 || a->ny < 2 || a->nx < 2) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: cube needs nt>=1, nl>=2, ny>=2, nx>=2");
-    if (a->t_begin < 0 || a->t_count < 1 || a->t_begin + a->t_count > a->nt) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: [t_begin, t_begin+t_count) outside the cube");
+    if (!step_d && (a->t_begin < 0 || a->t_count < 1 || a->t_begin + a->t_count > a->nt)) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: [t_begin, t_begin+t_count) outside the cube");
     if (a->box_per_step != 0 && a->box_per_step != 1) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: box_per_step must be 0 or 1");
     if (a->n_box != (a->box_per_step ? a->t_count : 1)) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: n_box must be 1 (fixed box) or t_count (box_per_step)");
     if (a->reserved0) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: reserved0 must be 0");
@@ -379,6 +389,7 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
     p.lattab = a->lattab_d; p.levtab = a->levtab_d; p.tcoef = a->tcoef_d;
     p.rows = a->rows_d;
     p.ntrips = 0; p.jrows = 0; p.cpx = 0;
+    p.steps = step_d;
     hipStream_t st = (hipStream_t)a->stream;
     const bool uni = a->lon_uniform != 0;
     const int wq = !a->with_q ? 0 : (a->dTdt_d ? 2 : 1);      // Q: none / dT/dt from the cube's time axis / dT/dt cube
@@ -432,7 +443,7 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
         // of the product hands over.  The planes' rows go straight into the compute layout by buffer loads (lec_boxplane.hip).
         // Decided by the kind of call and the slabs' shape, so every shard and chunk of a series agrees; the records are
         // bit-identical to the box-tile kernel's anyway (tested)
-        const bool plane_ok = a->box_per_step && lec_boxplane_serves(pt, a->dtype, uni, wq);
+        const bool plane_ok = !step_d && a->box_per_step && lec_boxplane_serves(pt, a->dtype, uni, wq);
         if (kernel == LEC_KERNEL_BOX_PLANE && !plane_ok)
             return lec_set_error(LEC_ERR_ARG, "lec_rowstats: LEC_KERNEL_BOX_PLANE serves per-step boxes with geopotential on even longitudes, cubes at most 64 columns wide, "
                                               "dT/dt as a cube or (fp32 storage, box-packed) T of the two time neighbours as tm_d / tp_d");
@@ -457,4 +468,11 @@ extern "C" int lec_rowstats(const lec_rowstats_args* a) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
     return LEC_OK;
+}
+
+extern "C" int lec_rowstats(const lec_rowstats_args* a) { return rowstats_impl(a, nullptr); }
+
+extern "C" int lec_rowstats_steps(const lec_rowstats_args* a, const int32_t* step_d) {
+    if (!step_d) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: null step_d");
+    return rowstats_impl(a, step_d);
 }

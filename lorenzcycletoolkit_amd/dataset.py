@@ -399,23 +399,33 @@ def process_index(lat, lon, lev, time, level_units, names, args, app_logger=None
     longitudes, level -> Pa, sort lon / level / lat ascending, drop levels above 10 hPa."""
     tpos = None
     if getattr(args, "track", False):
-        track = read_track(args.trackfile, app_logger)
-        data_dt = int((time[1] - time[0]) / np.timedelta64(1, "h"))
-        track_dt = int((track.index[1] - track.index[0]) / np.timedelta64(1, "h"))
-        if data_dt > track_dt:
-            raise ValueError(f"Data time step ({data_dt}h) is higher than track time step ({track_dt}h). "
-                             "Cannot select track timesteps that don't exist in data. "
-                             "Please resample the track or re-download data with higher temporal resolution.")
-        if track.index[0] < time[0]:
-            raise ValueError(f"Track initial timestamp ({track.index[0]}) is earlier than data initial timestamp "
-                             f"({time[0]}). Please adjust the track file.")
-        if track.index[-1] > time[-1]:
-            raise ValueError(f"Track final timestamp ({track.index[-1]}) is later than data final timestamp "
-                             f"({time[-1]}). Please adjust the track file or re-download the data.")
-        tpos = pd.Index(time).get_indexer(track.index.values)
-        if np.any(tpos < 0):
-            raise KeyError(f"track times not found in the data: {list(track.index[tpos < 0])}")
+        tpos = select_track_times(time, read_track(args.trackfile, app_logger))
         time = time[tpos]
+    return _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger)
+
+
+def select_track_times(time: np.ndarray, track: pd.DataFrame) -> np.ndarray:
+    """The track-time selection of process_data (preprocessing.py:171-200) with its checks: the positions of the track's times in
+    the data's time axis."""
+    data_dt = int((time[1] - time[0]) / np.timedelta64(1, "h"))
+    track_dt = int((track.index[1] - track.index[0]) / np.timedelta64(1, "h"))
+    if data_dt > track_dt:
+        raise ValueError(f"Data time step ({data_dt}h) is higher than track time step ({track_dt}h). "
+                         "Cannot select track timesteps that don't exist in data. "
+                         "Please resample the track or re-download data with higher temporal resolution.")
+    if track.index[0] < time[0]:
+        raise ValueError(f"Track initial timestamp ({track.index[0]}) is earlier than data initial timestamp "
+                         f"({time[0]}). Please adjust the track file.")
+    if track.index[-1] > time[-1]:
+        raise ValueError(f"Track final timestamp ({track.index[-1]}) is later than data final timestamp "
+                         f"({time[-1]}). Please adjust the track file or re-download the data.")
+    tpos = pd.Index(time).get_indexer(track.index.values)
+    if np.any(tpos < 0):
+        raise KeyError(f"track times not found in the data: {list(track.index[tpos < 0])}")
+    return tpos
+
+
+def _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger=None) -> ProcessIndex:
     if lon.min() < -180 or lon.max() > 180:
         lon = (lon + 180) % 360 - 180                                   # tools.py:76-92
     key = (level_units or "hPa").strip().lower()
@@ -439,19 +449,20 @@ def process_data(data: LECDataset, args, variable_list_df: pd.DataFrame, app_log
     return LECDataset(v, px.lat, px.lon, px.level, px.time, dict(data.names), "Pa")
 
 
-def domain_slices(lat: np.ndarray, lon: np.ndarray, args):
+def domain_slices(lat: np.ndarray, lon: np.ndarray, args, track: Optional[pd.DataFrame] = None):
     """slice_domain (select_area.py:254-338) on sorted coordinates: (lat slice, lon slice).  Fixed -> nearest-point
     crop from the hard-coded inputs/box_limits; track -> label slice of the track extent +- (half the largest
-    box + one grid step)."""
+    box + one grid step).  ``track``: a track already read (one of a batch, batch.py) instead of ``args.trackfile``."""
     from .tables import nearest_index
     if getattr(args, "fixed", False):
         w, e, s, n = read_box_limits("inputs/box_limits")
         iw, ie = nearest_index(lon, w), nearest_index(lon, e)
         js, jn = nearest_index(lat, s), nearest_index(lat, n)
         return slice(js, jn + 1), slice(iw, ie + 1)
-    if getattr(args, "track", False):
+    if getattr(args, "track", False) or track is not None:
         dx, dy = lon[1] - lon[0], lat[1] - lat[0]
-        track = read_track(args.trackfile or "inputs/track")
+        if track is None:
+            track = read_track(args.trackfile or "inputs/track")
         if "width" in track.columns:
             mw, ml = track["width"].max(), track["length"].max()
         else:

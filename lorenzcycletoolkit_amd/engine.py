@@ -125,13 +125,14 @@ class LECEngine:
         """Nearest-grid-point inclusive box, as BoxData._set_domain_limits (box_data.py:115-131)."""
         return tables.box_indices(self.lat, self.lon, west, east, south, north)
 
-    def prepare_boxes(self, boxes, nyb_min: int = 0, packed: bool = False) -> PreparedBoxes:
+    def prepare_boxes(self, boxes, nyb_min: int = 0, packed: bool = False, lon_uniform: Optional[bool] = None) -> PreparedBoxes:
         """Index quadruples (iw, ie, js, jn) -> PreparedBoxes for ``rowstats`` / ``reduce`` / ``compute``.  ``nyb_min``: the row
         count of the record buffer the boxes will be used with (chunks of a series share the tallest box's).  ``packed``: the boxes
         of a BOX-PACKED series (``pack_boxes``; include/lec_hip.h): stage 1 then addresses every step's box at the origin of its
-        slab, while every table is built from the true grid boxes as always."""
+        slab, while every table is built from the true grid boxes as always.  ``lon_uniform``: see ``tables.build_box_tables`` (a track
+        of a batch keeps its own crop's formulation)."""
         boxes = [tuple(int(x) for x in b) for b in boxes]
-        bt, dev = self._box_tables(boxes, nyb_min)
+        bt, dev = self._box_tables(boxes, nyb_min, lon_uniform)
         if packed:
             dev = dict(dev, box_data=self._up(np.array([(0, b[1] - b[0], 0, b[3] - b[2]) for b in boxes], dtype=np.int32), torch.int32))
         return PreparedBoxes(boxes, bt, dev)
@@ -258,12 +259,12 @@ class LECEngine:
         bt, dev = self._box_tables(boxes, nyb_min)
         return boxes, bt, dev
 
-    def _box_tables(self, boxes, nyb_min: int = 0):
-        key = (int(nyb_min),) + tuple(int(v) for b in boxes for v in b)
+    def _box_tables(self, boxes, nyb_min: int = 0, lon_uniform: Optional[bool] = None):
+        key = (int(nyb_min), lon_uniform) + tuple(int(v) for b in boxes for v in b)
         hit = self._box_cache.get(key)
         if hit is not None:
             return hit
-        bt = tables.build_box_tables(self.lat, self.lon, boxes, nyb_min=nyb_min)
+        bt = tables.build_box_tables(self.lat, self.lon, boxes, nyb_min=nyb_min, lon_uniform=lon_uniform)
         dev = {
             "box": self._up(bt.box, torch.int32), "boxtab": self._up(bt.boxtab), "wlon": self._up(bt.wlon),
             "glon": self._up(bt.glon), "lattab": self._up(bt.lattab), "boxtab2": self._up(bt.boxtab2),
@@ -290,9 +291,10 @@ class LECEngine:
                 merge_dropmask: Optional[Callable[[torch.Tensor], None]] = None,
                 tuning: Optional[dict] = None, per_step_boxes: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
-                tcoef: Optional[torch.Tensor] = None) -> LECResult:
+                tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
-        (``tm`` / ``tp`` / ``tcoef``: a box-packed series, see ``rowstats``.)
+        (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
+        ``rowstats``.)
 
         ``boxes``: one (iw, ie, js, jn) quadruple (fixed framework) or one per processed time step
         (moving framework).  ``per_step_boxes``: True = the moving framework's semantics (default when more than one
@@ -307,7 +309,10 @@ class LECEngine:
         stream around the stage-1 kernel (bench.py's roofline figure).
         """
         rows = self.rowstats(tair, u, v, omega, geopt, boxes, time_s=time_s, dTdt=dTdt, t_begin=t_begin, t_count=t_count,
-                             with_q=with_q, timing=timing, tuning=tuning, per_step_boxes=per_step_boxes, tm=tm, tp=tp, tcoef=tcoef)
+                             with_q=with_q, timing=timing, tuning=tuning, per_step_boxes=per_step_boxes, tm=tm, tp=tp, tcoef=tcoef,
+                             steps=steps)
+        if steps is not None:
+            per_step_boxes = True
         if drop_any_time is None and per_step_boxes:
             drop_any_time = False
         return self.reduce(rows, boxes, phi_scale=phi_scale, drop_any_time=drop_any_time, merge_dropmask=merge_dropmask,
@@ -319,17 +324,26 @@ class LECEngine:
                  t_count: Optional[int] = None, with_q: bool = True, timing: Optional[list] = None,
                  rows_out: Optional[torch.Tensor] = None, tuning: Optional[dict] = None,
                  per_step_boxes: Optional[bool] = None, tcoef: Optional[torch.Tensor] = None,
-                 tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None) -> torch.Tensor:
+                 tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
+                 steps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stage 1 (``lec_rowstats``): row records [t_count, nl, nyb_max, 32] of time steps [t_begin, t_begin + t_count).
         ``tm`` / ``tp``: a BOX-PACKED series (``pack_boxes``; ``boxes`` prepared with ``packed=True``): the cubes hold every step's
         box at the origin of its slab, ``tm`` / ``tp`` T of the previous / next step on that box.  Same records, bit for bit.
         ``tuning``: see ``make_tuning`` (kernel family / order / tile shape; default = the library's choice).
         ``tcoef``: the d/dt coefficients of the cube's time steps already on the device (fp64 [nt, 3], e.g. rows [h0, h1) of
         ``time_coefs_device`` of the whole series) instead of ``time_s`` -- a chunk loop then uploads nothing per call (an upload from
-        pageable memory makes the host wait for the stream, which serialises a copy / compute pipeline)."""
+        pageable memory makes the host wait for the stream, which serialises a copy / compute pipeline).
+        ``steps``: the boxes of SEVERAL tracks over one cube (``lec_rowstats_steps``): int32 [S, 3] on the device, one row per box =
+        {cube step, previous step, next step} of the box's own track (the step itself at the track's ends), with ``tcoef`` fp64 [S, 3]
+        by box and S boxes; the records of every box are those of its track's own cube, bit for bit.  The table is checked on the host
+        (entries in [0, nt)) before anything is launched."""
         if tair.dim() != 4:
             raise ValueError("fields must be [time, level, lat, lon]")
         nt, nl, ny, nx = tair.shape
+        if steps is not None:
+            return self._rowstats_steps(tair, u, v, omega, geopt, boxes, steps, tcoef, dTdt=dTdt, t_begin=t_begin, t_count=t_count,
+                                        with_q=with_q, timing=timing, rows_out=rows_out, tuning=tuning, per_step_boxes=per_step_boxes,
+                                        tm=tm, tp=tp)
         packed = tm is not None or tp is not None or (isinstance(boxes, PreparedBoxes) and "box_data" in boxes.dev)
         if packed:
             if not isinstance(boxes, PreparedBoxes) or "box_data" not in boxes.dev or (with_q and (dTdt is None) == (tm is None or tp is None)):
@@ -409,6 +423,72 @@ class LECEngine:
             if timing is not None:
                 ev1.record()
                 timing.append((ev0, ev1))
+        return rows
+
+    def check_steps(self, steps: torch.Tensor, tcoef: Optional[torch.Tensor], nt: int, device) -> int:
+        """Host validation of a step table (``rowstats(steps=...)``) before any launch: int32 [S, 3] contiguous on ``device``, entries in
+        [0, nt); ``tcoef`` fp64 [S, 3] contiguous on ``device``.  Returns S; raises ValueError."""
+        if not isinstance(steps, torch.Tensor) or steps.dtype != torch.int32 or steps.dim() != 2 or steps.shape[1] != 3 or steps.shape[0] < 1:
+            raise ValueError("steps must be an int32 [S, 3] tensor (S >= 1): {cube step, previous step, next step} per box")
+        if steps.device != torch.device(device) or not steps.is_contiguous():
+            raise ValueError("steps must be contiguous and on the fields' device")
+        s = int(steps.shape[0])
+        if (tcoef is None or not isinstance(tcoef, torch.Tensor) or tuple(tcoef.shape) != (s, 3) or tcoef.dtype != torch.float64
+                or tcoef.device != torch.device(device) or not tcoef.is_contiguous()):
+            raise ValueError(f"steps needs tcoef: a contiguous fp64 [{s}, 3] tensor (by box) on the fields' device")
+        host = steps.cpu().numpy()
+        bad = np.flatnonzero(np.any((host < 0) | (host >= nt), axis=1))
+        if bad.size:
+            raise ValueError(f"steps: box {int(bad[0])} names cube steps {host[bad[0]].tolist()} outside [0, {nt})")
+        return s
+
+    def _rowstats_steps(self, tair, u, v, omega, geopt, boxes, steps, tcoef, *, dTdt, t_begin, t_count, with_q, timing, rows_out, tuning,
+                        per_step_boxes, tm, tp) -> torch.Tensor:
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        if dTdt is not None or tm is not None or tp is not None or not with_q or t_begin != 0 or per_step_boxes is False:
+            raise ValueError("steps: dT/dt from the cube's own steps (no dTdt / tm / tp), with_q, t_begin = 0, per-step boxes")
+        if (nl, ny, nx) != (self.level.size, self.lat.size, self.lon.size):
+            raise ValueError(f"field shape {tuple(tair.shape)} does not match the engine grid "
+                             f"({self.level.size} levels, {self.lat.size} lats, {self.lon.size} lons)")
+        if tair.dtype not in (torch.float64, torch.float32):
+            raise ValueError("fields must be float64 or float32")
+        for c in [tair, u, v, omega] + ([geopt] if geopt is not None else []):
+            if c.shape != tair.shape or c.dtype != tair.dtype or c.device != tair.device or not c.is_contiguous():
+                raise ValueError("all field cubes must share shape, dtype, device and be contiguous")
+        if tair.device.type != "cuda":
+            raise _lib.LecLibraryError("fields must live on the GPU: there is no CPU path")
+        n = self.check_steps(steps, tcoef, nt, tair.device)
+        if t_count is not None and t_count != n:
+            raise ValueError("steps: t_count must equal the number of table rows")
+        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=0 if rows_out is None else int(rows_out.shape[2]))
+        if len(boxes) != n:
+            raise ValueError("steps: one box per table row")
+        f64 = dict(dtype=torch.float64, device=tair.device)
+        rows = rows_out if rows_out is not None else torch.empty((n, nl, bt.nyb_max, _lib.LEC_NSTAT), **f64)
+        if rows.shape != (n, nl, bt.nyb_max, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or not rows.is_contiguous():
+            raise ValueError("rows_out must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
+        whole = PreparedBoxes(boxes, bt, dev)
+        stream = C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream)
+        # cut like the series of ``rowstats``: every launch takes at most MAX_STEPS_PER_LAUNCH boxes, its slice of the table and tcoef
+        for a in range(0, n, self.MAX_STEPS_PER_LAUNCH):
+            b = min(a + self.MAX_STEPS_PER_LAUNCH, n)
+            part = whole.part(a, b) if (a, b) != (0, n) else whole
+            ra = _lib.RowstatsArgs(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), geopt_d=_ptr(geopt), dTdt_d=None,
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, with_q=1,
+                nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0, t_count=b - a,
+                n_box=b - a, nxb_max=bt.nxb_max, nyb_max=bt.nyb_max, lon_uniform=int(bt.lon_uniform),
+                box_per_step=1, reserved0=0, box_d=_ptr(part.dev["box"]), boxtab_d=_ptr(part.dev["boxtab"]), wlon_d=_ptr(part.dev["wlon"]),
+                glon_d=_ptr(part.dev["glon"]), lattab_d=_ptr(part.dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef[a:b]),
+                rows_d=_ptr(rows[a:b]), stream=stream, tuning=make_tuning(tuning), tm_d=None, tp_d=None)
+            with torch.cuda.device(tair.device):
+                if timing is not None:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                _lib.check(self.lib.lec_rowstats_steps(C.byref(ra), _ptr(steps[a:b])), "lec_rowstats_steps")
+                if timing is not None:
+                    ev1.record()
+                    timing.append((ev0, ev1))
         return rows
 
     @staticmethod

@@ -142,21 +142,7 @@ class BoxData:
             held = (h0, h1)
         if tuple(held) != (h0, h1):
             raise ValueError(f"data set holds time steps {held}, this rank needs {(h0, h1)}")
-        geo_role = "Geopotential" if "Geopotential" in variable_list_df.index else "Geopotential Height"
-        roles = ["Air Temperature", "Eastward Wind Component", "Northward Wind Component", "Omega Velocity", geo_role]
-        arrays = []
-        for role in roles:
-            a = data.variables[str(variable_list_df.loc[role]["Variable"])]
-            if a.dtype.kind != "f":                     # an unpacked integer variable: xarray would compute with it as it is
-                a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
-            scale = ds.field_scale(variable_list_df, role)
-            if role != geo_role and scale != 1.0:
-                a = a * a.dtype.type(scale)
-            arrays.append(a)
-        # a file may mix dtypes (float32 T, u, v with an int16-packed z that decodes to float64): the engine wants one storage
-        # dtype, the widest of them -- widening is exact, and all arithmetic is fp64 anyway (xarray would promote pairwise)
-        common = np.result_type(*[a.dtype for a in arrays])
-        phi_scale = ds.field_scale(variable_list_df, geo_role)
+        arrays, common, phi_scale = host_fields(data, variable_list_df)
         if self.per_step_boxes and dTdt is None:
             return self._compute_resident_packed(arrays, common, data, dev, phi_scale, merge, out)
         cubes = [torch.as_tensor(np.ascontiguousarray(a, dtype=common)).to(dev) for a in arrays]
@@ -201,6 +187,26 @@ class BoxData:
         kw = dict(dTdt=self.engine.time_stencil(tm, f[0], tp, tcoef)) if common == np.float64 else dict(tm=tm, tp=tp, tcoef=tcoef)
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
                                    drop_any_time=False, merge_dropmask=merge, out=out, **kw)
+
+
+def host_fields(data: ds.LECDataset, variable_list_df: pd.DataFrame):
+    """The five field arrays of a host-prepared data set in SI units (geopotential as stored), their common storage dtype and
+    the geopotential's factor to m^2/s^2."""
+    geo_role = "Geopotential" if "Geopotential" in variable_list_df.index else "Geopotential Height"
+    roles = ["Air Temperature", "Eastward Wind Component", "Northward Wind Component", "Omega Velocity", geo_role]
+    arrays = []
+    for role in roles:
+        a = data.variables[str(variable_list_df.loc[role]["Variable"])]
+        if a.dtype.kind != "f":                     # an unpacked integer variable: xarray would compute with it as it is
+            a = a.astype(np.float32 if a.dtype.itemsize <= 2 else np.float64)
+        scale = ds.field_scale(variable_list_df, role)
+        if role != geo_role and scale != 1.0:
+            a = a * a.dtype.type(scale)
+        arrays.append(a)
+    # a file may mix dtypes (float32 T, u, v with an int16-packed z that decodes to float64): the engine wants one storage
+    # dtype, the widest of them -- widening is exact, and all arithmetic is fp64 anyway (xarray would promote pairwise)
+    common = np.result_type(*[a.dtype for a in arrays])
+    return arrays, common, ds.field_scale(variable_list_df, geo_role)
 
 
 def time_labels(times, method: str):
@@ -442,9 +448,15 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     phases.mark("track_diagnostics")
     if box_obj.result is None:              # time-sharded run: rank 0 holds the gathered series and writes every file
         return None
+    return _write_moving_results(box_obj, times, data.time_s, limits, positions, results_subdirectory, form, app_logger, args)
+
+
+def _write_moving_results(box_obj, times, time_s, limits, positions, results_subdirectory, form, app_logger, args):
+    """The files of one track (after its numbers exist): terms -> DataFrame -> budgets -> results CSV -> trackfile.  ``box_obj``:
+    a BoxData or anything with its series and per-level plumbing (``_TrackResult``)."""
     terms = _compute_all(box_obj, "moving", app_logger)
     df = pd.DataFrame({c: terms[c] for c in MOVING_COLUMNS}, index=times, dtype=float)
-    full = budgets_and_residuals({c: df[c].values for c in df.columns}, data.time_s,
+    full = budgets_and_residuals({c: df[c].values for c in df.columns}, time_s,
                                  residuals=bool(getattr(args, "residuals", False)))
     for col in full:
         if col not in df.columns:
@@ -464,3 +476,77 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     out_track.to_csv(os.path.join(results_subdirectory, f"{infile_name}_{method}_trackfile"), index=False, sep=";")
     phases.mark("csv_writes")
     return results_file, df
+
+
+class _TrackResult:
+    """One track's share of a batch (``lec_moving_batch``), shaped like the BoxData the per-level writers read."""
+
+    def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, result: LECResult, results_subdirectory: str,
+                 results_subdirectory_vertical_levels: str):
+        self.results_subdirectory = results_subdirectory
+        self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
+        self.VerticalCoordIndexer = variable_list_df.loc["Vertical Level"]["Variable"]
+        self.PressureData = data.level
+        self.time = data.time
+        self._row_labels = {}
+        self.result = result
+        self.scalars = result.scalars_dict()
+        self.levels = result.levels_dict()
+        self.nanflag = result.nanflag.cpu().numpy()
+
+    row_labels = BoxData.row_labels
+
+
+def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, directories, app_logger, args):
+    """Many tracks over one data set (``batch.prepare_union``): ONE upload of the union cubes, one stage-1 + stage-2 call per group of
+    tracks with equal record extents (``LECEngine.compute(steps=...)``), then every track's files written by the code ``lec_moving``
+    writes them with.  ``directories``: per track (results, figures, vertical levels).  The files of every track are byte for byte
+    those of its own ``-t --trackfile`` run.  Returns [(results file, DataFrame)] in batch order."""
+    from . import batch as bt
+    from .diagnostics import track_diagnostics
+    dev = _device(args)
+    time_name = variable_list_df.loc["Time"]["Variable"]
+    vert_name = variable_list_df.loc["Vertical Level"]["Variable"]
+    arrays, common, phi_scale = host_fields(data, variable_list_df)
+    mem = bt.device_bytes(plan, len(arrays), np.dtype(common).itemsize)
+    need = mem["total"]
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > free // 2:
+        raise MemoryError(f"the batch needs {need / 1e9:.2f} GB of device memory (union cubes {mem['cubes'] / 1e9:.2f} GB, row records of the "
+                          f"largest group {mem['records'] / 1e9:.2f} GB, results {mem['results'] / 1e9:.2f} GB), more than half of the "
+                          f"{free / 1e9:.2f} GB free: run the tracks in smaller batches")
+    engine = LECEngine(data.lat, data.lon, data.level, device=dev)
+    cubes = [torch.as_tensor(np.ascontiguousarray(a, dtype=common)).to(dev) for a in arrays]
+    app_logger.info(f"Batch of {len(plan.tracks)} tracks: union of {len(plan.tpos)} time steps on a {len(plan.lat)} x {len(plan.lon)} crop "
+                    f"({need / 1e9:.2f} GB on the device), {len(plan.groups)} group(s) of equal box extents and longitude formulation")
+    results = [None] * len(plan.tracks)
+    for (nyb, nxb, uniform), members in plan.groups.items():
+        trs = [plan.tracks[k] for k in members]
+        boxes = [b for tr in trs for b in tr.boxes]
+        steps = torch.as_tensor(np.concatenate([tr.steps for tr in trs])).to(dev)
+        tcoef = torch.as_tensor(np.concatenate([tr.tcoef for tr in trs])).to(dev)
+        pb = engine.prepare_boxes(boxes, nyb_min=nyb, lon_uniform=uniform)      # (the formulation of the tracks' own crops)
+        res = engine.compute(cubes[0], cubes[1], cubes[2], cubes[3], cubes[4], pb, phi_scale=phi_scale, per_step_boxes=True,
+                             drop_any_time=False, steps=steps, tcoef=tcoef)
+        a = 0
+        for k, tr in zip(members, trs):
+            b = a + tr.n
+            results[k] = LECResult(scalars=res.scalars[a:b], levels=res.levels[a:b], nanflag=res.nanflag[a:b], packed=res.packed[a:b])
+            a = b
+    torch.cuda.synchronize(dev)
+    phases.mark("ingest_compute_gather")
+    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
+    written = []
+    for tr, res, (results_subdirectory, figures_directory, vl_directory) in zip(plan.tracks, results, directories):
+        view = bt.track_view(data, tr)
+        _create_level_csvs(vl_directory, time_name, vert_name, view.level)
+        holder = _TrackResult(view, variable_list_df, res, results_subdirectory, vl_directory)
+        if int(holder.nanflag.sum()):
+            app_logger.warning(f"{tr.path}: NaN level values were interpolated/dropped per time step (_handle_nans semantics)")
+        # the 850-hPa diagnostics on the track's own crop: the stencil's end coefficients depend on the crop's edges
+        positions = track_diagnostics(view, variable_list_df, tr.limits, tr.track, use_track_zeta=bool(getattr(args, "zeta", False)),
+                                      device=dev, formulation=form)
+        app_logger.info(f"Track {tr.path}: {tr.n} time steps -> {results_subdirectory}")
+        written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, positions, results_subdirectory,
+                                             form, app_logger, args))
+    return written

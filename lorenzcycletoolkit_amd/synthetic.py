@@ -83,3 +83,37 @@ def synthetic_cube(nt: int, level_pa, lat_deg, lon_deg, device, dtype=torch.floa
         if dev.type == "cuda":                # no deep backlog of launches (the buffers are reused; and see the note above)
             torch.cuda.synchronize(dev)
     return out
+
+
+def write_classic_nc(path, dtype, nt: int = 12, seed: int = 0, lon=None) -> None:
+    """A small seeded classic NetCDF file with the ERA5 preset's names (inputs/namelist_ERA5: T, U, V, W, Z): 3-hourly, 1 degree
+    (``lon``: other longitudes, e.g. a partly stretched axis), lat N -> S, 7 levels in hPa, ``dtype`` float32 or float64 storage.
+    For the command-line tests and tools/bench_batch.py."""
+    from scipy.io import netcdf_file
+    rng = np.random.default_rng(seed)
+    lat = np.arange(-10.0, -60.5, -1.0)
+    lon = np.arange(-80.0, -19.5, 1.0) if lon is None else np.asarray(lon, dtype=np.float64)
+    lev = np.array([1000, 925, 850, 700, 500, 300, 200], dtype=np.int32)
+    nl, ny, nx = lev.size, lat.size, lon.size
+    f = netcdf_file(path, "w", version=2)
+    for n, s in (("time", nt), ("level", nl), ("latitude", ny), ("longitude", nx)):
+        f.createDimension(n, s)
+    tv = f.createVariable("time", "i", ("time",)); tv[:] = 3 * np.arange(nt); tv.units = "hours since 2020-01-01 00:00:00"
+    lv = f.createVariable("level", "i", ("level",)); lv[:] = lev; lv.units = "millibars"
+    la = f.createVariable("latitude", "f", ("latitude",)); la[:] = lat
+    lo = f.createVariable("longitude", "f", ("longitude",)); lo[:] = lon
+    p = (lev[None, :, None, None] * 100.0) / 1e5
+    shp = (nt, nl, ny, nx)
+    phi = np.deg2rad(lat)[None, None, :, None]
+    fields = {
+        "T": 288.0 * p ** 0.19 + 8.0 * np.cos(2 * phi) * p + rng.standard_normal(shp),
+        "U": 20.0 * np.cos(phi) * (1 - p / 1.2) + 5 * rng.standard_normal(shp),
+        "V": 3.0 * rng.standard_normal(shp),
+        "W": 0.1 * rng.standard_normal(shp),
+        "Z": 9.80665 * 7000.0 * np.log(1.0 / p) + 100.0 * rng.standard_normal(shp),
+    }
+    code = "d" if dtype == np.float64 else "f"
+    for name, a in fields.items():
+        v = f.createVariable(name, code, ("time", "level", "latitude", "longitude"))
+        v[:] = a.astype(dtype)
+    f.close()

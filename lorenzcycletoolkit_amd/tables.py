@@ -8,7 +8,7 @@ happens only in the kernels.
 from __future__ import annotations
 
 from dataclasses import dataclass
-from typing import Sequence
+from typing import Optional, Sequence
 
 import numpy as np
 
@@ -80,10 +80,14 @@ class BoxTables:
     lon_uniform: bool
 
 
-def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[Sequence[int]], nyb_min: int = 0) -> BoxTables:
+def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[Sequence[int]], nyb_min: int = 0,
+                     lon_uniform: Optional[bool] = None) -> BoxTables:
     """Per-box tables for both stages.  ``boxes`` = inclusive index quadruples (iw, ie, js, jn).
     ``nyb_min``: pad the latitude extent of the tables (and of the row records) to at least this many rows -- chunks of one
-    series of moving boxes share one record buffer, whose row count is the tallest box of the whole series."""
+    series of moving boxes share one record buffer, whose row count is the tallest box of the whole series.
+    ``lon_uniform``: the formulation's flag as decided on ANOTHER longitude axis than ``lon_deg`` -- a track of a batch (batch.py) keeps
+    the flag of its own crop while its boxes are addressed in the union crop; None = decided on ``lon_deg`` (the default everywhere
+    else).  True needs every box's longitudes evenly spaced."""
     lat = np.asarray(lat_deg, dtype=np.float64)
     lon = np.asarray(lon_deg, dtype=np.float64)
     box = np.asarray(boxes, dtype=np.int32).reshape(-1, 4)
@@ -99,7 +103,9 @@ def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[S
         raise ValueError("nyb_min exceeds the grid")
     t = BoxTables(box=box, boxtab=np.zeros((nb, 4)), wlon=np.zeros((nb, nxm)), glon=np.zeros((nb, nxm, 3)),
                   lattab=np.zeros((nb, nym, 4)), boxtab2=np.zeros((nb, 4)), lattab2=np.zeros((nb, nym, 8)),
-                  nxb_max=nxm, nyb_max=nym, lon_uniform=is_uniform(lon))
+                  nxb_max=nxm, nyb_max=nym, lon_uniform=is_uniform(lon) if lon_uniform is None else bool(lon_uniform))
+    if lon_uniform and not all(is_uniform(lon[int(b[0]): int(b[1]) + 1]) for b in box):
+        raise ValueError("lon_uniform: a box's longitudes are not evenly spaced")
     # (lon_uniform selects the kernels' fast path and is decided on the grid's whole longitude axis, not on the boxes at hand: a
     # chunk or shard of a moving series may hold only boxes that happen to lie in an evenly spaced part of a stretched grid -- any
     # two-point-wide box does -- and must still use the formulation the whole series uses, or it differs from it by an ulp;

@@ -1,0 +1,236 @@
+#!/usr/bin/env python3
+"""Many tracks over one data set: one batch pass (``LECEngine.compute(steps=...)``, ``lec_rowstats_steps``) against the loop of
+single-track computations the moving framework runs today, on a seeded synthetic data set at ERA5 spacing (37 levels, 0.25 degrees,
+a regional union crop, K tracks of ~40 six-hourly steps with 15 x 15 degree boxes).  Prints ONE JSON line:
+
+  batch        one upload of the union cubes, then stage 1 + stage 2 per group of tracks (device events, after a synchronize)
+  loop         K single-track resident computations in-process, as frameworks.BoxData does them (host slice of every box, upload of
+               the box-packed series, lec_dtdt / stage 1 / stage 2); its terms must equal the batch's bit for bit (checked)
+  one_track    lec_rowstats on the cube with t +- 1 addressing against lec_rowstats_steps with the identity table: same records
+               (checked), kernel times of both
+
+``--cli``: the command line instead -- K single ``-r -t --trackfile`` processes one after another against ONE ``-r -t --trackfiles``
+process over the same seeded file (synthetic.write_classic_nc: float32, 7 levels, 1 degree, 40 three-hourly steps; K tracks of 16
+steps, default 15 x 15 degree boxes), both wall clocks and whether every track's results CSV and trackfile are the same bytes.  Works
+in a temporary directory.
+
+Reads nothing outside the tree.  Usage: python tools/bench_batch.py [--tracks K] [--steps 40] [--reps 5] | --cli [--tracks K]
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from lorenzcycletoolkit_amd import tables                                     # noqa: E402
+from lorenzcycletoolkit_amd.engine import LECEngine                          # noqa: E402
+from lorenzcycletoolkit_amd.synthetic import era5_like_levels, synthetic_cube  # noqa: E402
+
+HBM_PEAK_GBS = 8000.0          # as bench.py
+
+
+def _tracks(k, n, nt, lat, lon, rng):
+    """K tracks of n six-hourly steps (the data are 6-hourly): start step, centre drifting east / south-east, 15 x 15 degree boxes."""
+    out = []
+    for _ in range(k):
+        t0 = int(rng.integers(0, nt - n + 1))
+        la0, lo0 = rng.uniform(lat[0] + 10, lat[-1] - 15), rng.uniform(lon[0] + 10, lon[-1] - 25)
+        steps = np.arange(t0, t0 + n)
+        cen = [(la0 - 0.05 * i, lo0 + 0.3 * i) for i in range(n)]
+        out.append((steps, [tables.box_indices(lat, lon, c[1] - 7.5, c[1] + 7.5, c[0] - 7.5, c[0] + 7.5) for c in cen]))
+    return out
+
+
+def _events():
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    return a, b
+
+
+def cli_wall_clock(k: int, seed: int) -> dict:
+    """K single-track CLI processes against one --trackfiles process on the same file (see the module docstring)."""
+    import filecmp
+    import shutil
+    import subprocess
+    import tempfile
+
+    import pandas as pd
+    from lorenzcycletoolkit_amd.synthetic import write_classic_nc
+    cli = os.path.join(ROOT, "lorenzcycletoolkit.py")
+    rng = np.random.default_rng(seed)
+    with tempfile.TemporaryDirectory() as work:
+        os.makedirs(os.path.join(work, "inputs"))
+        shutil.copy(os.path.join(ROOT, "tests", "golden", "inputs", "namelist_ERA5"), os.path.join(work, "inputs", "namelist"))
+        infile = os.path.join(work, "synth.nc")
+        write_classic_nc(infile, np.float32, nt=40, seed=seed)
+        tracks = []
+        for i in range(k):
+            t0, n = int(rng.integers(0, 20)), 16
+            rows = [f"{(pd.Timestamp('2020-01-01') + pd.Timedelta(hours=3 * (t0 + s))).strftime('%Y-%m-%d-%H%M')};"
+                    f"{-35 + rng.uniform(-5, 5) - 0.2 * s:.2f};{-55 + rng.uniform(-8, 8) + 0.4 * s:.2f}" for s in range(n)]
+            p = os.path.join(work, f"trk{i:02d}")
+            with open(p, "w") as f:
+                f.write("time;Lat;Lon\n" + "\n".join(rows) + "\n")
+            tracks.append(p)
+        t0 = time.perf_counter()
+        for p in tracks:
+            subprocess.run([sys.executable, cli, infile, "-r", "-t", "--trackfile", p], cwd=work, check=True, capture_output=True, timeout=300)
+            shutil.move(os.path.join(work, "LEC_Results", "synth_track"), os.path.join(work, "single_" + os.path.basename(p)))
+        single_s = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        subprocess.run([sys.executable, cli, infile, "-r", "-t", "--trackfiles", *tracks], cwd=work, check=True, capture_output=True, timeout=600)
+        batch_s = time.perf_counter() - t0
+        same = all(filecmp.cmp(os.path.join(work, "single_" + os.path.basename(p), f),
+                               os.path.join(work, "LEC_Results", f"synth_{os.path.basename(p)}_track", f), shallow=False)
+                   for p in tracks for f in ("synth_track_results.csv", "synth_track_trackfile"))
+    return {"tracks": k, "steps_per_track": 16, "file": "synthetic.write_classic_nc: float32 classic NetCDF, 7 levels, 1 degree, 40 three-hourly steps",
+            "what": f"{k} single `-r -t --trackfile` processes one after another vs one `-r -t --trackfiles` process, same file",
+            "single_runs_s": single_s, "batch_run_s": batch_s, "speedup": single_s / batch_s, "results_and_trackfiles_identical": bool(same)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--tracks", type=int, default=16)
+    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--nt", type=int, default=64, help="6-hourly steps of the data set")
+    ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
+    ap.add_argument("--seed", type=int, default=2024)
+    ap.add_argument("--only-steps-kernel", action="store_true", help="run the batch's stage-1 launches alone (profiler runs)")
+    ap.add_argument("--cli", action="store_true", help="the command line: K single-track processes against one --trackfiles process")
+    a = ap.parse_args()
+    if a.cli:
+        print(json.dumps(cli_wall_clock(a.tracks, a.seed)))
+        return
+    dev = "cuda:0"
+    dt = torch.float32 if a.dtype == "float32" else torch.float64
+    level = era5_like_levels()
+    lat = np.arange(-57.75, -17.5 + 1e-9, 0.25)
+    lon = np.arange(-80.25, -19.75 + 1e-9, 0.25)
+    rng = np.random.default_rng(a.seed)
+    f = synthetic_cube(a.nt, level, lat, lon, device=dev, dtype=dt, seed=a.seed)
+    host = [f[k].cpu().numpy() for k in ("tair", "u", "v", "omega", "geopt")]
+    del f
+    torch.cuda.empty_cache()
+    time_s = np.arange(a.nt) * 21600.0
+    tracks = _tracks(a.tracks, a.steps, a.nt, lat, lon, rng)
+    eng = LECEngine(lat, lon, level, device=dev)
+    esz = np.dtype(a.dtype).itemsize
+    nl = level.size
+
+    # ---- (a) batch: one upload, one stage-1 + stage-2 call per group
+    groups = {}
+    for k, (u, bx) in enumerate(tracks):
+        groups.setdefault((max(b[3] - b[2] + 1 for b in bx), max(b[1] - b[0] + 1 for b in bx)), []).append(k)
+    prepared = []
+    for (nyb, _), members in groups.items():
+        boxes = [b for k in members for b in tracks[k][1]]
+        st = np.concatenate([np.stack([tracks[k][0], np.r_[tracks[k][0][0], tracks[k][0][:-1]], np.r_[tracks[k][0][1:], tracks[k][0][-1]]], 1)
+                             for k in members]).astype(np.int32)
+        tc = np.concatenate([tables.time_coefs(time_s[tracks[k][0]] - time_s[tracks[k][0][0]]) for k in members])
+        prepared.append((members, eng.prepare_boxes(boxes, nyb_min=nyb), torch.as_tensor(st).to(dev), torch.as_tensor(tc).to(dev)))
+
+    def batch_pass(timing=None):
+        cubes = [torch.as_tensor(h).to(dev) for h in host]
+        outs = {}
+        for members, pb, st, tc in prepared:
+            if a.only_steps_kernel:
+                eng.rowstats(*cubes, pb, steps=st, tcoef=tc, timing=timing)
+                continue
+            res = eng.compute(*cubes, pb, steps=st, tcoef=tc, per_step_boxes=True, drop_any_time=False, timing=timing)
+            o = 0
+            for k in members:
+                outs[k] = res.packed[o: o + len(tracks[k][0])]
+                o += len(tracks[k][0])
+        return outs
+
+    # ---- (b) loop: one single-track resident computation per track (frameworks.BoxData._compute_resident_packed)
+    def loop_pass():
+        outs = {}
+        for k, (u, bx) in enumerate(tracks):
+            nyb, nxb = max(b[3] - b[2] + 1 for b in bx), max(b[1] - b[0] + 1 for b in bx)
+
+            def pack(arr, shift=0):
+                p = np.zeros((len(u), nl, nyb, nxb), dtype=arr.dtype)
+                for i, (iw, ie, js, jn) in enumerate(bx):
+                    ts = u[min(max(i + shift, 0), len(u) - 1)]
+                    p[i, :, : jn - js + 1, : ie - iw + 1] = arr[ts, :, js: jn + 1, iw: ie + 1]
+                return torch.as_tensor(p).to(dev)
+            fl = [pack(h) for h in host]
+            tm, tp = pack(host[0], -1), pack(host[0], +1)
+            tcoef = eng.time_coefs_device(time_s[u] - time_s[u[0]])
+            pb = eng.prepare_boxes(bx, nyb_min=nyb, packed=True)
+            kw = dict(dTdt=eng.time_stencil(tm, fl[0], tp, tcoef)) if dt == torch.float64 else dict(tm=tm, tp=tp, tcoef=tcoef)
+            outs[k] = eng.compute(*fl, pb, per_step_boxes=True, drop_any_time=False, **kw).packed
+        return outs
+
+    def wall(fn, *args):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn(*args)
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    out = {"workload": f"synthetic {a.dtype} {nl} levels x {lat.size} x {lon.size} 0.25-degree union crop, {a.nt} six-hourly steps, "
+                       f"{a.tracks} tracks of {a.steps} steps, 15 x 15 degree boxes", "groups": len(groups),
+           "boxes": int(sum(len(t[0]) for t in tracks))}
+    if a.only_steps_kernel:
+        for _ in range(a.reps):
+            batch_pass()
+        torch.cuda.synchronize()
+        out["only_steps_kernel"] = True
+        print(json.dumps(out))
+        return
+    batch_pass(); loop_pass()            # warm-up (library load, allocator, box tables)
+    bw, lw, kms = [], [], []
+    for _ in range(a.reps):
+        tm_ = []
+        ms, ob = wall(batch_pass, tm_)
+        bw.append(ms)
+        kms.append(sum(x.elapsed_time(y) for x, y in tm_))
+        ms, ol = wall(loop_pass)
+        lw.append(ms)
+    same_ab = all(torch.equal(torch.nan_to_num(ob[k], nan=7.0), torch.nan_to_num(ol[k], nan=7.0)) for k in range(a.tracks))
+    out["batch_ms"] = {"median": float(np.median(bw)), "min": float(np.min(bw)), "all": [round(x, 2) for x in bw],
+                       "what": "wall clock: upload of the union cubes + stage 1 + stage 2 per group, synchronized"}
+    out["loop_ms"] = {"median": float(np.median(lw)), "min": float(np.min(lw)), "all": [round(x, 2) for x in lw],
+                      "what": "wall clock: per track host slice of every box + upload of the box-packed series + dT/dt + stage 1 + stage 2"}
+    out["speedup_median"] = out["loop_ms"]["median"] / out["batch_ms"]["median"]
+    out["bits_equal_batch_vs_loop"] = bool(same_ab)
+    # share of the roofline of the step-table stage-1 launches, counted as bench.py counts the cube layout (the box is read: 5 fields)
+    kbytes = 5 * nl * 61 * 61 * esz * out["boxes"]
+    out["steps_kernel_ms_median"] = float(np.median(kms))
+    out["steps_kernel_roofline_frac"] = kbytes / (np.median(kms) * 1e-3) / 1e9 / HBM_PEAK_GBS
+
+    # ---- (c) one track: t +- 1 addressing against the identity table, same records
+    u, bx = tracks[0]
+    n = len(u)
+    cubes = [torch.as_tensor(np.ascontiguousarray(h[u[0]: u[0] + n])).to(dev) for h in host]
+    ts = time_s[u] - time_s[u[0]]
+    ident = torch.as_tensor(np.stack([np.arange(n), np.r_[0, np.arange(n - 1)], np.r_[np.arange(1, n), n - 1]], 1).astype(np.int32)).to(dev)
+    tc = eng.time_coefs_device(ts)
+    r_pm = eng.rowstats(*cubes, bx, time_s=ts, per_step_boxes=True, tuning={"kernel": "box_tile"})
+    r_st = eng.rowstats(*cubes, bx, steps=ident, tcoef=tc)
+    torch.cuda.synchronize()
+    same_c = bool(((r_pm[..., :28] == r_st[..., :28]) | (torch.isnan(r_pm[..., :28]) & torch.isnan(r_st[..., :28]))).all())
+    t_pm, t_st = [], []
+    for _ in range(max(a.reps, 5) * 4):            # interleaved, so that drift hits both alike
+        e = []
+        eng.rowstats(*cubes, bx, time_s=ts, per_step_boxes=True, tuning={"kernel": "box_tile"}, timing=e)
+        eng.rowstats(*cubes, bx, steps=ident, tcoef=tc, timing=e)
+        torch.cuda.synchronize()
+        t_pm.append(e[0][0].elapsed_time(e[0][1]))
+        t_st.append(e[1][0].elapsed_time(e[1][1]))
+    out["one_track"] = {"steps": n, "bits_equal": same_c, "tpm1_kernel_ms_median": float(np.median(t_pm)), "steps_kernel_ms_median": float(np.median(t_st)),
+                        "tpm1_kernel_ms_iqr": [float(np.percentile(t_pm, 25)), float(np.percentile(t_pm, 75))],
+                        "steps_kernel_ms_iqr": [float(np.percentile(t_st, 25)), float(np.percentile(t_st, 75))]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
