@@ -67,6 +67,16 @@ def make_tuning(tuning: Optional[dict]) -> "_lib.Tuning":
     return t
 
 
+def pack_host(a: np.ndarray, boxes, src, nyb: int, nxb: int, dtype=None) -> np.ndarray:
+    """The box-packed form of the host array ``a`` [steps, level, lat, lon]: step i of the result holds box i (iw, ie, js, jn) of
+    ``a[src[i]]`` at the origin of an ``nyb`` x ``nxb`` slab, zeros beside it (``dtype``: default ``a``'s) -- the reference's per-step
+    slice (box_data.py:297-310) done on the host before the upload (``LECEngine.pack_boxes`` gathers on the device)."""
+    p = np.zeros((len(boxes), a.shape[1], nyb, nxb), dtype=a.dtype if dtype is None else dtype)
+    for i, ((iw, ie, js, jn), ts) in enumerate(zip(boxes, src)):
+        p[i, :, : jn - js + 1, : ie - iw + 1] = a[ts, :, js: jn + 1, iw: ie + 1]
+    return p
+
+
 class PreparedBoxes:
     """Boxes whose host tables are built and uploaded (``LECEngine.prepare_boxes``): a series of thousands of per-time-step boxes
     is normalised, keyed and looked up once instead of at every call."""
@@ -114,6 +124,7 @@ class LECEngine:
         self._levtab = self._up(levtab)
         self._levtab2 = self._up(levtab2)
         self._box_cache = {}
+        self._pack_maps = {}   # pack_boxes' index maps of the last grid / slab shape
         self._work = {}        # stage-2 workspaces by shape: am, levraw, dropmask (true scratch: never handed out)
         self._tcoef = None     # (time axis, its d/dt coefficients on the device) of the last call
 
@@ -137,26 +148,37 @@ class LECEngine:
             dev = dict(dev, box_data=self._up(np.array([(0, b[1] - b[0], 0, b[3] - b[2]) for b in boxes], dtype=np.int32), torch.int32))
         return PreparedBoxes(boxes, bt, dev)
 
+    @staticmethod
+    def _pack_geometry(cube: torch.Tensor, boxes, ny: Optional[int], nx: Optional[int]):
+        """(boxes as int64 [nt, 4], box rows, box columns, slab rows, slab columns) of a ``pack_boxes`` call: one box per step of the
+        cube, each inside its grid; the slab defaults to the tallest / widest box."""
+        b = np.array([tuple(int(x) for x in q) for q in (boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes)], dtype=np.int64)
+        nt, _, ny_in, nx_in = (int(x) for x in cube.shape)
+        if len(b) != nt:
+            raise ValueError("pack_boxes: one box per time step of the cube")
+        bad = np.flatnonzero((b[:, 0] < 0) | (b[:, 2] < 0) | (b[:, 1] >= nx_in) | (b[:, 3] >= ny_in))
+        if bad.size:
+            raise ValueError(f"pack_boxes: box {int(bad[0])} (iw, ie, js, jn) = {tuple(b[bad[0]].tolist())} lies outside the {ny_in} x {nx_in} grid")
+        nxb, nyb = b[:, 1] - b[:, 0] + 1, b[:, 3] - b[:, 2] + 1
+        return b, nyb, nxb, int(ny or nyb.max()), int(nx or nxb.max())
+
     def pack_boxes(self, cube: torch.Tensor, boxes, shift: int = 0, ny: Optional[int] = None, nx: Optional[int] = None) -> torch.Tensor:
         """[nt, nl, ny_grid, nx_grid] -> the box-packed layout [len(boxes), nl, ny, nx] (default: the tallest / widest box): step t
         holds box t of ``cube[t + shift]`` (clamped to the cube: the step itself where a time neighbour does not exist) at its
-        origin.  ONE launch of ``lec_ingest`` -- the gather the streamed moving framework packs its series with (``ingest.lec_streamed``:
-        there the source is the file's raw bytes, here a cube in HBM; ``lec_ingest_args.step_d`` = per step {source step, where the box
-        starts}) -- for tests, ``bench.py --moving`` and cubes a caller already holds.  What a slab holds beside a box lower / narrower
-        than the slab is whatever the lengthened index maps point at (the grid's last row / column): stage 1 never reads it."""
-        b = np.array([tuple(int(x) for x in q) for q in (boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes)], dtype=np.int64)
+        origin.  ONE launch of ``lec_ingest`` per 8192 steps -- the gather the streamed moving framework packs its series with
+        (``ingest.lec_streamed``: there the source is the file's raw bytes, here a cube in HBM; ``lec_ingest_args.step_d`` = per step
+        {source step, where the box starts}) -- for tests, ``bench.py --moving`` and cubes a caller already holds.  Every box must lie
+        inside the grid (ValueError naming the first that does not).  What a slab holds beside a box lower / narrower than the slab is
+        whatever the lengthened index maps point at (the grid's last row / column): stage 1 never reads it."""
+        b, nyb, nxb, ny, nx = self._pack_geometry(cube, boxes, ny, nx)
         nt, nl, ny_in, nx_in = (int(x) for x in cube.shape)
-        if len(b) != nt:
-            raise ValueError("pack_boxes: one box per time step of the cube")
         if cube.dtype not in (torch.float64, torch.float32) or not cube.is_contiguous() or cube.device.type != "cuda":
             raise ValueError("pack_boxes: a contiguous float64 / float32 cube on the GPU")
-        nxb, nyb = b[:, 1] - b[:, 0] + 1, b[:, 3] - b[:, 2] + 1
-        ny, nx = int(ny or nyb.max()), int(nx or nxb.max())
         if ny < nyb.max() or nx < nxb.max() or ny > ny_in or nx > nx_in:
             raise ValueError("pack_boxes: slabs must hold the tallest / widest box and fit the grid")
         dev = cube.device
         key = (nl, ny_in, nx_in, ny, nx, str(dev))
-        maps = self._pack_maps.get(key) if hasattr(self, "_pack_maps") else None
+        maps = self._pack_maps.get(key)
         if maps is None:            # identity maps, lengthened by a slab (their last entry repeated): a box at the grid's edge is gathered with the slab's extents
             up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32).to(dev)
             maps = (up(np.arange(nl)), up(np.minimum(np.arange(ny_in + ny), ny_in - 1)), up(np.minimum(np.arange(nx_in + nx), nx_in - 1)))
@@ -179,12 +201,8 @@ class LECEngine:
     def pack_boxes_by_indexing(self, cube: torch.Tensor, boxes, shift: int = 0, ny: Optional[int] = None, nx: Optional[int] = None) -> torch.Tensor:
         """``pack_boxes`` as one torch advanced-indexing gather, zeros beside the boxes: the independent form the tests hold the
         ``lec_ingest`` gather to (inside the boxes: the same values)."""
-        b = np.array([tuple(int(x) for x in q) for q in (boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes)], dtype=np.int64)
+        b, nyb, nxb, ny, nx = self._pack_geometry(cube, boxes, ny, nx)
         nt = cube.shape[0]
-        if len(b) != nt:
-            raise ValueError("pack_boxes: one box per time step of the cube")
-        nxb, nyb = b[:, 1] - b[:, 0] + 1, b[:, 3] - b[:, 2] + 1
-        ny, nx = int(ny or nyb.max()), int(nx or nxb.max())
         dev = cube.device
         tt = torch.as_tensor(np.clip(np.arange(nt) + shift, 0, nt - 1), device=dev)[:, None, None, None]
         kk = torch.arange(cube.shape[1], device=dev)[None, :, None, None]
@@ -217,15 +235,22 @@ class LECEngine:
                 _lib.check(self.lib.lec_dtdt(C.byref(args)), "lec_dtdt")
         return out
 
+    def packed_dtdt(self, tm: torch.Tensor, t: torch.Tensor, tp: torch.Tensor, tcoef: torch.Tensor, out: Optional[torch.Tensor] = None) -> dict:
+        """The dT/dt arguments of ``rowstats`` for a box-packed series whose T is ``t`` and whose time neighbours on every step's box are
+        ``tm`` / ``tp`` (``tcoef``: the rows of the cubes' steps): for fp64 storage {"dTdt"}, an fp64 cube made by ``time_stencil``
+        (one operand fewer per point; written into ``out`` when given); for fp32 storage {"tm", "tp", "tcoef"} (the same bytes as a
+        cube would be, and no rounding of dT/dt to the storage dtype).  The one place that picks the form."""
+        if t.dtype == torch.float64:
+            return {"dTdt": self.time_stencil(tm, t, tp, tcoef, out=out)}
+        return {"tm": tm, "tp": tp, "tcoef": tcoef}
+
     def pack_series(self, tair, u, v, omega, geopt, boxes, tcoef: torch.Tensor, ny: Optional[int] = None, nx: Optional[int] = None,
                     timing: Optional[dict] = None) -> dict:
-        """The box-packed form of a moving series held as whole cubes (tests, ``bench.py --moving``, host-prepared tracks): the keyword
-        arguments of ``rowstats`` -- the five fields packed per step (``pack_boxes``) and dT/dt as the series' own data: an fp64 cube
-        for fp64 storage (``time_stencil``: one operand fewer per point), T of the two time neighbours on the step's box for fp32
-        storage (the same bytes as a cube would be, and no rounding of dT/dt to the storage dtype).  ``tcoef``: rows of the cubes' steps.
-        ``timing``: a dict that receives HIP events recorded on the current stream -- "pack" = (start, end) around the gathers (the
-        per-step slice, box_data.py:297-310), "dtdt" = (start, end) around ``lec_dtdt`` (fp64 storage only): what the PRODUCER of a
-        packed series spends, which ``bench.py --moving`` reports beside the consumer's rate."""
+        """The box-packed form of a moving series held as whole cubes (tests, ``bench.py --moving``): the five fields packed per step
+        (``pack_boxes``) and dT/dt in the form of ``packed_dtdt`` -- "dTdt", or "tm" / "tp" (the caller adds ``tcoef``).  ``tcoef``:
+        rows of the cubes' steps.  ``timing``: a dict that receives HIP events recorded on the current stream -- "pack" = (start, end)
+        around the gathers (the per-step slice, box_data.py:297-310), "dtdt" = (start, end) around ``lec_dtdt`` (fp64 storage only):
+        what the PRODUCER of a packed series spends, which ``bench.py --moving`` reports beside the consumer's rate."""
         def ev():
             if timing is None:
                 return None
@@ -238,11 +263,10 @@ class LECEngine:
             pk = {k: self.pack_boxes(c, boxes, ny=ny, nx=nx) for k, c in (("tair", tair), ("u", u), ("v", v), ("omega", omega), ("geopt", geopt)) if c is not None}
             tm, tp = self.pack_boxes(tair, boxes, shift=-1, ny=ny, nx=nx), self.pack_boxes(tair, boxes, shift=+1, ny=ny, nx=nx)
             e1 = ev()
-            if tair.dtype == torch.float64:
-                pk["dTdt"] = self.time_stencil(tm, pk["tair"], tp, tcoef)
-            else:
-                pk["tm"], pk["tp"] = tm, tp
+            dt = self.packed_dtdt(tm, pk["tair"], tp, tcoef)
             e2 = ev()
+        dt.pop("tcoef", None)
+        pk.update(dt)
         if timing is not None:
             timing["pack"] = (e0, e1)
             if "dTdt" in pk:
@@ -306,7 +330,7 @@ class LECEngine:
         True for one fixed box, False for per-time-step boxes (the moving framework builds one BoxData per step).
         ``merge_dropmask``: see ``reduce`` (time-sharded runs).
         ``timing``: a list that receives one (start, end) pair of HIP events recorded on the launch
-        stream around the stage-1 kernel (bench.py's roofline figure).
+        stream around every stage-1 launch (bench.py's roofline figure).
         """
         rows = self.rowstats(tair, u, v, omega, geopt, boxes, time_s=time_s, dTdt=dTdt, t_begin=t_begin, t_count=t_count,
                              with_q=with_q, timing=timing, tuning=tuning, per_step_boxes=per_step_boxes, tm=tm, tp=tp, tcoef=tcoef,
@@ -326,104 +350,118 @@ class LECEngine:
                  per_step_boxes: Optional[bool] = None, tcoef: Optional[torch.Tensor] = None,
                  tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                  steps: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Stage 1 (``lec_rowstats``): row records [t_count, nl, nyb_max, 32] of time steps [t_begin, t_begin + t_count).
-        ``tm`` / ``tp``: a BOX-PACKED series (``pack_boxes``; ``boxes`` prepared with ``packed=True``): the cubes hold every step's
-        box at the origin of its slab, ``tm`` / ``tp`` T of the previous / next step on that box.  Same records, bit for bit.
+        """Stage 1: row records [t_count, nl, nyb_max, 32] of time steps [t_begin, t_begin + t_count) of the cubes.  Three kinds of call
+        share one path:
+
+        * whole cubes on the engine's grid (``lec_rowstats``), dT/dt from ``time_s`` / ``tcoef`` or a ``dTdt`` cube;
+        * a BOX-PACKED series (``pack_boxes``; ``boxes`` prepared with ``packed=True``): the cubes hold every step's box at the origin
+          of its slab, with dT/dt as ``packed_dtdt`` hands it over -- a ``dTdt`` cube, or ``tm`` / ``tp`` (T of the previous / next
+          step on that box) with ``tcoef``.  The records of the whole cubes, bit for bit;
+        * ``steps``: the boxes of SEVERAL tracks over one cube on the engine's grid (``lec_rowstats_steps``): int32 [S, 3] on the
+          device, one row per box = {cube step, previous step, next step} of the box's own track (the step itself at the track's
+          ends), with ``tcoef`` fp64 [S, 3] by box and S boxes; ``t_begin`` 0, no ``dTdt`` / ``tm`` / ``tp``.  The records of every box
+          are those of its track's own cube, bit for bit.  The table is checked on the host (``check_steps``) before anything is
+          launched.
+
         ``tuning``: see ``make_tuning`` (kernel family / order / tile shape; default = the library's choice).
-        ``tcoef``: the d/dt coefficients of the cube's time steps already on the device (fp64 [nt, 3], e.g. rows [h0, h1) of
-        ``time_coefs_device`` of the whole series) instead of ``time_s`` -- a chunk loop then uploads nothing per call (an upload from
-        pageable memory makes the host wait for the stream, which serialises a copy / compute pipeline).
-        ``steps``: the boxes of SEVERAL tracks over one cube (``lec_rowstats_steps``): int32 [S, 3] on the device, one row per box =
-        {cube step, previous step, next step} of the box's own track (the step itself at the track's ends), with ``tcoef`` fp64 [S, 3]
-        by box and S boxes; the records of every box are those of its track's own cube, bit for bit.  The table is checked on the host
-        (entries in [0, nt)) before anything is launched."""
+        ``tcoef`` (cubes, packed series): the d/dt coefficients of the cube's time steps already on the device (fp64 [nt, 3], e.g. rows
+        [h0, h1) of ``time_coefs_device`` of the whole series) instead of ``time_s`` -- a chunk loop then uploads nothing per call (an
+        upload from pageable memory makes the host wait for the stream, which serialises a copy / compute pipeline).
+        ``rows_out``: a caller-owned record buffer (e.g. a slice of a longer series' one; its row count may exceed this call's boxes).
+        A call is cut into launches of at most ``MAX_STEPS_PER_LAUNCH`` steps (boxes of a step table): some kernel families address
+        their time steps with 16-bit grid coordinates.  Same kernels, same bits: results do not depend on how a series is cut.
+        ``timing``: a list that receives one (start, end) pair of HIP events per launch, recorded on the launch stream."""
+        if steps is not None and (dTdt is not None or tm is not None or tp is not None or not with_q or t_begin != 0 or per_step_boxes is False):
+            raise ValueError("steps: dT/dt from the cube's own steps (no dTdt / tm / tp), with_q, t_begin = 0, per-step boxes")
+        packed = steps is None and (tm is not None or tp is not None or (isinstance(boxes, PreparedBoxes) and "box_data" in boxes.dev))
+        if packed and (not isinstance(boxes, PreparedBoxes) or "box_data" not in boxes.dev or (with_q and (dTdt is None) == (tm is None or tp is None))):
+            raise ValueError("a box-packed series: boxes from prepare_boxes(..., packed=True) and, with_q, either tm and tp or a dTdt cube")
+        self._check_fields([tair, u, v, omega] + [c for c in (geopt, dTdt, tm, tp) if c is not None], boxes if packed else None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+
+        if steps is not None:
+            n = self.check_steps(steps, tcoef, nt, tair.device)
+            if t_count is not None and t_count != n:
+                raise ValueError("steps: t_count must equal the number of table rows")
+            t_count, per_step_boxes = n, True
+        else:
+            if t_count is None:
+                t_count = nt - t_begin
+            if tcoef is not None:
+                if tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
+                    raise ValueError("tcoef must be a contiguous fp64 [nt, 3] tensor on the fields' device")
+                if nt < 2 and tm is None:           # (a box-packed series brings its time neighbours along: one step is a series)
+                    raise ValueError("dT/dt by finite differences needs at least 2 time steps")
+            elif with_q and dTdt is None:
+                if time_s is None:
+                    raise ValueError("with_q needs time_s (seconds) or a dTdt cube")
+                time_s = np.asarray(time_s, dtype=np.float64)
+                if time_s.size != nt:
+                    raise ValueError("time_s must have one entry per time step of the cube")
+                if nt < 2:
+                    raise ValueError("dT/dt by finite differences needs at least 2 time steps")
+                # cached: an upload from pageable memory makes the host wait for the stream at every call
+                if self._tcoef is None or self._tcoef[0].shape != time_s.shape or not np.array_equal(self._tcoef[0], time_s):
+                    self._tcoef = (time_s.copy(), self._up(tables.time_coefs(time_s)))
+                tcoef = self._tcoef[1]
+        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=0 if rows_out is None else int(rows_out.shape[2]))
+        if per_step_boxes is None:
+            per_step_boxes = len(boxes) != 1
+        if len(boxes) != (t_count if per_step_boxes else 1):
+            raise ValueError("boxes: give one box, or one per processed time step" if steps is None else "steps: one box per table row")
+        shape = (t_count, nl, bt.nyb_max, _lib.LEC_NSTAT)
+        rows = torch.empty(shape, dtype=torch.float64, device=tair.device) if rows_out is None else rows_out
+        if rows.shape != shape or rows.dtype != torch.float64 or not rows.is_contiguous():
+            raise ValueError("rows_out must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
+
+        whole = PreparedBoxes(boxes, bt, dev)
+        stream = C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream)
+        for a in range(0, max(t_count, 1), self.MAX_STEPS_PER_LAUNCH):      # (t_count 0: one launch, which the library refuses)
+            b = min(a + self.MAX_STEPS_PER_LAUNCH, t_count)
+            part = whole.part(a, b) if per_step_boxes and (a, b) != (0, t_count) else whole
+            ra = _lib.RowstatsArgs(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), geopt_d=_ptr(geopt), dTdt_d=_ptr(dTdt),
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, with_q=int(bool(with_q)),
+                nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin + a if steps is None else 0, t_count=b - a,
+                n_box=len(part), nxb_max=bt.nxb_max, nyb_max=bt.nyb_max, lon_uniform=int(bt.lon_uniform),
+                box_per_step=int(bool(per_step_boxes)), reserved0=0, box_d=_ptr(part.dev["box_data" if packed else "box"]),
+                boxtab_d=_ptr(part.dev["boxtab"]), wlon_d=_ptr(part.dev["wlon"]), glon_d=_ptr(part.dev["glon"]), lattab_d=_ptr(part.dev["lattab"]),
+                levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef if steps is None else tcoef[a:b]),
+                rows_d=_ptr(rows[a:b]), stream=stream, tuning=make_tuning(tuning), tm_d=_ptr(tm), tp_d=_ptr(tp))
+            with torch.cuda.device(tair.device):
+                if timing is not None:
+                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    ev0.record()
+                if steps is None:
+                    _lib.check(self.lib.lec_rowstats(C.byref(ra)), "lec_rowstats")
+                else:
+                    _lib.check(self.lib.lec_rowstats_steps(C.byref(ra), _ptr(steps[a:b])), "lec_rowstats_steps")
+                if timing is not None:
+                    ev1.record()
+                    timing.append((ev0, ev1))
+        return rows
+
+    def _check_fields(self, cubes: Sequence[torch.Tensor], packed: Optional[PreparedBoxes]) -> None:
+        """The field cubes of a stage-1 call (T first): [time, level, lat, lon], fp64 or fp32, one shape, dtype and GPU device,
+        contiguous; on the engine's grid -- or, for a box-packed series (``packed``: its boxes), on slabs that hold the tallest /
+        widest box."""
+        tair = cubes[0]
         if tair.dim() != 4:
             raise ValueError("fields must be [time, level, lat, lon]")
-        nt, nl, ny, nx = tair.shape
-        if steps is not None:
-            return self._rowstats_steps(tair, u, v, omega, geopt, boxes, steps, tcoef, dTdt=dTdt, t_begin=t_begin, t_count=t_count,
-                                        with_q=with_q, timing=timing, rows_out=rows_out, tuning=tuning, per_step_boxes=per_step_boxes,
-                                        tm=tm, tp=tp)
-        packed = tm is not None or tp is not None or (isinstance(boxes, PreparedBoxes) and "box_data" in boxes.dev)
-        if packed:
-            if not isinstance(boxes, PreparedBoxes) or "box_data" not in boxes.dev or (with_q and (dTdt is None) == (tm is None or tp is None)):
-                raise ValueError("a box-packed series: boxes from prepare_boxes(..., packed=True) and, with_q, either tm and tp or a dTdt cube")
-            if nl != self.level.size or ny < boxes.bt.nyb_max or nx < boxes.bt.nxb_max or ny > self.lat.size or nx > self.lon.size:
+        nl, ny, nx = tair.shape[1:]
+        if packed is not None:
+            if nl != self.level.size or ny < packed.bt.nyb_max or nx < packed.bt.nxb_max or ny > self.lat.size or nx > self.lon.size:
                 raise ValueError(f"packed cubes {tuple(tair.shape)}: need {self.level.size} levels and slabs that hold the tallest / widest box")
         elif (nl, ny, nx) != (self.level.size, self.lat.size, self.lon.size):
             raise ValueError(f"field shape {tuple(tair.shape)} does not match the engine grid "
                              f"({self.level.size} levels, {self.lat.size} lats, {self.lon.size} lons)")
         if tair.dtype not in (torch.float64, torch.float32):
             raise ValueError("fields must be float64 or float32")
-        cubes = [tair, u, v, omega] + ([geopt] if geopt is not None else []) + ([dTdt] if dTdt is not None else []) + ([tm, tp] if tm is not None else [])
         for c in cubes:
             if c.shape != tair.shape or c.dtype != tair.dtype or c.device != tair.device or not c.is_contiguous():
                 raise ValueError("all field cubes must share shape, dtype, device and be contiguous")
         if tair.device.type != "cuda":
             raise _lib.LecLibraryError("fields must live on the GPU: there is no CPU path")
-        if t_count is None:
-            t_count = nt - t_begin
-        # rows_out: a slice of a longer series' record buffer (chunked processing): its row count is the tallest box of the whole series
-        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=0 if rows_out is None else int(rows_out.shape[2]))
-        if per_step_boxes is None:
-            per_step_boxes = len(boxes) != 1
-        if len(boxes) != (t_count if per_step_boxes else 1):
-            raise ValueError("boxes: give one box, or one per processed time step")
-
-        if tcoef is not None:
-            if tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
-                raise ValueError("tcoef must be a contiguous fp64 [nt, 3] tensor on the fields' device")
-            if nt < 2 and tm is None:           # (a box-packed series brings its time neighbours along: one step is a series)
-                raise ValueError("dT/dt by finite differences needs at least 2 time steps")
-        elif with_q and dTdt is None:
-            if time_s is None:
-                raise ValueError("with_q needs time_s (seconds) or a dTdt cube")
-            time_s = np.asarray(time_s, dtype=np.float64)
-            if time_s.size != nt:
-                raise ValueError("time_s must have one entry per time step of the cube")
-            if nt < 2:
-                raise ValueError("dT/dt by finite differences needs at least 2 time steps")
-            # cached: an upload from pageable memory makes the host wait for the stream at every call
-            if self._tcoef is None or self._tcoef[0].shape != time_s.shape or not np.array_equal(self._tcoef[0], time_s):
-                self._tcoef = (time_s.copy(), self._up(tables.time_coefs(time_s)))
-            tcoef = self._tcoef[1]
-
-        f64 = dict(dtype=torch.float64, device=tair.device)
-        if t_count > self.MAX_STEPS_PER_LAUNCH:
-            # a stage-1 launch addresses its time steps with 16-bit grid coordinates in some kernel families: longer series go out in
-            # parts (same kernels, same bits: results do not depend on how a series is cut)
-            rows = rows_out if rows_out is not None else torch.empty((t_count, nl, bt.nyb_max, _lib.LEC_NSTAT), **f64)
-            whole = PreparedBoxes(boxes, bt, dev)
-            for a in range(0, t_count, self.MAX_STEPS_PER_LAUNCH):
-                b = min(a + self.MAX_STEPS_PER_LAUNCH, t_count)
-                self.rowstats(tair, u, v, omega, geopt, whole.part(a, b) if per_step_boxes else whole, dTdt=dTdt, t_begin=t_begin + a,
-                              t_count=b - a, with_q=with_q, timing=timing, rows_out=rows[a:b], tuning=tuning, per_step_boxes=per_step_boxes,
-                              tcoef=tcoef, tm=tm, tp=tp)
-            return rows
-        if rows_out is None:
-            rows = torch.empty((t_count, nl, bt.nyb_max, _lib.LEC_NSTAT), **f64)
-        else:       # a slice of a longer series' record buffer (chunked ingest): stage 2 runs once over all of it
-            rows = rows_out
-            if rows.shape != (t_count, nl, bt.nyb_max, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or not rows.is_contiguous():
-                raise ValueError("rows_out must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
-        stream = C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream)
-        ra = _lib.RowstatsArgs(
-            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), geopt_d=_ptr(geopt), dTdt_d=_ptr(dTdt),
-            dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, with_q=int(bool(with_q)),
-            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count,
-            n_box=len(boxes), nxb_max=bt.nxb_max, nyb_max=bt.nyb_max, lon_uniform=int(bt.lon_uniform),
-            box_per_step=int(bool(per_step_boxes)), reserved0=0, box_d=_ptr(dev["box_data"] if packed else dev["box"]), boxtab_d=_ptr(dev["boxtab"]), wlon_d=_ptr(dev["wlon"]), glon_d=_ptr(dev["glon"]),
-            lattab_d=_ptr(dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef),
-            rows_d=_ptr(rows), stream=stream, tuning=make_tuning(tuning), tm_d=_ptr(tm), tp_d=_ptr(tp))
-        with torch.cuda.device(tair.device):
-            if timing is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            _lib.check(self.lib.lec_rowstats(C.byref(ra)), "lec_rowstats")
-            if timing is not None:
-                ev1.record()
-                timing.append((ev0, ev1))
-        return rows
 
     def check_steps(self, steps: torch.Tensor, tcoef: Optional[torch.Tensor], nt: int, device) -> int:
         """Host validation of a step table (``rowstats(steps=...)``) before any launch: int32 [S, 3] contiguous on ``device``, entries in
@@ -441,55 +479,6 @@ class LECEngine:
         if bad.size:
             raise ValueError(f"steps: box {int(bad[0])} names cube steps {host[bad[0]].tolist()} outside [0, {nt})")
         return s
-
-    def _rowstats_steps(self, tair, u, v, omega, geopt, boxes, steps, tcoef, *, dTdt, t_begin, t_count, with_q, timing, rows_out, tuning,
-                        per_step_boxes, tm, tp) -> torch.Tensor:
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        if dTdt is not None or tm is not None or tp is not None or not with_q or t_begin != 0 or per_step_boxes is False:
-            raise ValueError("steps: dT/dt from the cube's own steps (no dTdt / tm / tp), with_q, t_begin = 0, per-step boxes")
-        if (nl, ny, nx) != (self.level.size, self.lat.size, self.lon.size):
-            raise ValueError(f"field shape {tuple(tair.shape)} does not match the engine grid "
-                             f"({self.level.size} levels, {self.lat.size} lats, {self.lon.size} lons)")
-        if tair.dtype not in (torch.float64, torch.float32):
-            raise ValueError("fields must be float64 or float32")
-        for c in [tair, u, v, omega] + ([geopt] if geopt is not None else []):
-            if c.shape != tair.shape or c.dtype != tair.dtype or c.device != tair.device or not c.is_contiguous():
-                raise ValueError("all field cubes must share shape, dtype, device and be contiguous")
-        if tair.device.type != "cuda":
-            raise _lib.LecLibraryError("fields must live on the GPU: there is no CPU path")
-        n = self.check_steps(steps, tcoef, nt, tair.device)
-        if t_count is not None and t_count != n:
-            raise ValueError("steps: t_count must equal the number of table rows")
-        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=0 if rows_out is None else int(rows_out.shape[2]))
-        if len(boxes) != n:
-            raise ValueError("steps: one box per table row")
-        f64 = dict(dtype=torch.float64, device=tair.device)
-        rows = rows_out if rows_out is not None else torch.empty((n, nl, bt.nyb_max, _lib.LEC_NSTAT), **f64)
-        if rows.shape != (n, nl, bt.nyb_max, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or not rows.is_contiguous():
-            raise ValueError("rows_out must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
-        whole = PreparedBoxes(boxes, bt, dev)
-        stream = C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream)
-        # cut like the series of ``rowstats``: every launch takes at most MAX_STEPS_PER_LAUNCH boxes, its slice of the table and tcoef
-        for a in range(0, n, self.MAX_STEPS_PER_LAUNCH):
-            b = min(a + self.MAX_STEPS_PER_LAUNCH, n)
-            part = whole.part(a, b) if (a, b) != (0, n) else whole
-            ra = _lib.RowstatsArgs(
-                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), geopt_d=_ptr(geopt), dTdt_d=None,
-                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, with_q=1,
-                nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0, t_count=b - a,
-                n_box=b - a, nxb_max=bt.nxb_max, nyb_max=bt.nyb_max, lon_uniform=int(bt.lon_uniform),
-                box_per_step=1, reserved0=0, box_d=_ptr(part.dev["box"]), boxtab_d=_ptr(part.dev["boxtab"]), wlon_d=_ptr(part.dev["wlon"]),
-                glon_d=_ptr(part.dev["glon"]), lattab_d=_ptr(part.dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef[a:b]),
-                rows_d=_ptr(rows[a:b]), stream=stream, tuning=make_tuning(tuning), tm_d=None, tp_d=None)
-            with torch.cuda.device(tair.device):
-                if timing is not None:
-                    ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    ev0.record()
-                _lib.check(self.lib.lec_rowstats_steps(C.byref(ra), _ptr(steps[a:b])), "lec_rowstats_steps")
-                if timing is not None:
-                    ev1.record()
-                    timing.append((ev0, ev1))
-        return rows
 
     @staticmethod
     def packed_width(nl: int) -> int:
@@ -511,11 +500,7 @@ class LECEngine:
         max, e.g. an all_reduce); the merged mask then applies to every shard, as xarray's dropna(dim=level) on the
         whole [time, level] array does in the reference (energy_contents.py:203-207)."""
         t_count, nl = int(rows.shape[0]), int(rows.shape[1])
-        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=int(rows.shape[2]))
-        if len(boxes) not in (1, t_count):
-            raise ValueError("boxes: give one box, or one per processed time step")
-        if rows.shape != (t_count, self.level.size, bt.nyb_max, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or not rows.is_contiguous():
-            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
+        boxes, bt, dev = self._stage2_input(rows, boxes)
         am, levraw, dropmask_ws = self._workspace(t_count, nl, rows.device)
         res = self._stage2(_lib.STAGE_BOTH, rows, levraw, am, dropmask_ws, boxes, bt, dev, phi_scale, drop_any_time, merge_dropmask, out, nanflag_out)
         res.rows = rows if keep_rows else None
@@ -527,11 +512,7 @@ class LECEngine:
         latitude half of stage 2 for a chunk of a series.  6.8 MB of row records per 37 x 721 time step become 12 KB, so a streamed
         series keeps ONE levraw buffer for all its steps and recycles the chunk's row records."""
         t_count, nl = int(rows.shape[0]), int(rows.shape[1])
-        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=int(rows.shape[2]))
-        if len(boxes) not in (1, t_count):
-            raise ValueError("boxes: give one box, or one per processed time step")
-        if rows.shape != (t_count, self.level.size, bt.nyb_max, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or not rows.is_contiguous():
-            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
+        boxes, bt, dev = self._stage2_input(rows, boxes)
         if (levraw_out.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw_out.dtype != torch.float64 or levraw_out.device != rows.device
                 or not levraw_out.is_contiguous()):
             raise ValueError("levraw_out must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
@@ -545,13 +526,22 @@ class LECEngine:
         _handle_nans with the any-time mask over ALL the steps (``drop_any_time`` / ``merge_dropmask`` as in ``reduce``), the pressure
         integrals and the boundary assembly.  ``boxes``: the series' box(es), for the per-box constants."""
         t_count, nl = int(levraw.shape[0]), int(levraw.shape[1])
-        boxes, bt, dev = self._resolve_boxes(boxes)
-        if len(boxes) not in (1, t_count):
-            raise ValueError("boxes: give one box, or one per processed time step")
-        if levraw.shape != (t_count, self.level.size, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or not levraw.is_contiguous():
-            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor")
+        boxes, bt, dev = self._stage2_input(levraw, boxes, levraw=True)
         dropmask_ws = torch.empty((_lib.LEC_NLEVFUN, nl), dtype=torch.int32, device=levraw.device)
         return self._stage2(_lib.STAGE_VERTICAL, None, levraw, None, dropmask_ws, boxes, bt, dev, 1.0, drop_any_time, merge_dropmask, out, nanflag_out)
+
+    def _stage2_input(self, rec: torch.Tensor, boxes, levraw: bool = False):
+        """(boxes, tables, device tables) of a stage-2 call on its input records: row records [t_count, nl, nyb_max, 32], or
+        ``levraw`` [t_count, nl, 40] -- contiguous fp64 on the engine's levels, with one box or one per step."""
+        t_count = int(rec.shape[0])
+        boxes, bt, dev = self._resolve_boxes(boxes, nyb_min=0 if levraw else int(rec.shape[2]))
+        if len(boxes) not in (1, t_count):
+            raise ValueError("boxes: give one box, or one per processed time step")
+        tail = (_lib.LEC_NLEVRAW,) if levraw else (bt.nyb_max, _lib.LEC_NSTAT)
+        if rec.shape != (t_count, self.level.size) + tail or rec.dtype != torch.float64 or not rec.is_contiguous():
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor" if levraw else
+                             "rows must be a contiguous fp64 [t_count, nl, nyb_max, 32] tensor")
+        return boxes, bt, dev
 
     def _workspace(self, t_count: int, nl: int, device, am_only: bool = False):
         # the workspaces are scratch of one call only (stream-ordered: the next call on the stream may reuse them); keyed by the

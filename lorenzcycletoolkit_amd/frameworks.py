@@ -23,7 +23,7 @@ import torch
 from . import dataset as ds
 from . import phases
 from .constants import LEVEL_TERMS
-from .engine import LECEngine, LECResult
+from .engine import LECEngine, LECResult, pack_host
 from .tables import budgets_and_residuals
 
 FIXED_COLUMNS = ["Az", "Ae", "Kz", "Ke", "Cz", "Ca", "Ck", "Ce", "BAz", "BAe", "BKz", "BKe", "Gz", "Ge"]
@@ -171,20 +171,16 @@ class BoxData:
         boxes = self.boxes[t0:t1]
         nyb = max(b[3] - b[2] + 1 for b in self.boxes)       # (the records of every rank have the row count of the tallest box of the WHOLE series)
         nxb = max(b[1] - b[0] + 1 for b in self.boxes)
-        nl = arrays[0].shape[1]
 
         def pack(a, shift=0):
-            p = np.zeros((t1 - t0, nl, nyb, nxb), dtype=common)
-            for i, (iw, ie, js, jn) in enumerate(boxes):
-                ts = min(max(t0 + i + shift, h0), h1 - 1) - h0       # the step itself where the series has no neighbour (coefficient 0)
-                p[i, :, : jn - js + 1, : ie - iw + 1] = a[ts, :, js: jn + 1, iw: ie + 1]
-            return torch.as_tensor(p).to(dev)
+            src = np.clip(np.arange(t0, t1) + shift, h0, h1 - 1) - h0       # the step itself where the series has no neighbour (coefficient 0)
+            return torch.as_tensor(pack_host(a, boxes, src, nyb, nxb, dtype=common)).to(dev)
 
         f = [pack(a) for a in arrays]
         tm, tp = pack(arrays[0], -1), pack(arrays[0], +1)
         tcoef = self.engine.time_coefs_device(data.time_s[h0:h1])[t0 - h0: t1 - h0].contiguous()
         pb = self.engine.prepare_boxes(boxes, nyb_min=nyb, packed=True)
-        kw = dict(dTdt=self.engine.time_stencil(tm, f[0], tp, tcoef)) if common == np.float64 else dict(tm=tm, tp=tp, tcoef=tcoef)
+        kw = self.engine.packed_dtdt(tm, f[0], tp, tcoef)
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
                                    drop_any_time=False, merge_dropmask=merge, out=out, **kw)
 

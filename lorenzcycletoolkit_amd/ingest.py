@@ -816,6 +816,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         nyp, nxp = bt.nyb_max, bt.nxb_max
         dec_steps = min(chunk_steps, max(4, (1 << 30) // (nl * nyp * nxp * esize)))
         cubes = {k: torch.empty((dec_steps, nl, nyp, nxp), dtype=out_dtype, device=dev) for k in list(keys.values()) + ["tm", "tp"]}
+        # (the `out` of engine.packed_dtdt, which writes a dT/dt cube for fp64 storage only)
         dtdt = torch.empty((dec_steps, nl, nyp, nxp), dtype=torch.float64, device=dev) if common == np.float64 else None
         maps = (up(kmap_rel), up(np.concatenate([jmap_rel, np.repeat(jmap_rel[-1:], nyp)])), up(np.concatenate([imap_rel, np.repeat(imap_rel[-1:], nxp)])))
         # per output step {source step, where its box starts in the latitude / longitude maps}: for the fields, and for T of the two
@@ -900,53 +901,44 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                         moved += (b - a) * stagers[r].step_elems * stagers[r].itemsize
                 copied[slot][n].record(up)
             compute.wait_event(copied[slot][n])
-        # decode + row pass, sub-chunk by sub-chunk: T with the one-step halo of the SUB-chunk (rows of the raw slot count from h0)
-        for s0 in (() if packed else range(c0, c1, dec_steps)):
+        # decode + row pass, sub-chunk by sub-chunk, in the layout of the call: the box-packed series (every output step holds that
+        # step's box alone: lec_ingest enters the maps at the box's south-west corner, step by step -- `step_tab` --, T also from the
+        # two neighbouring steps' raw slices), or the cubes with T's one-step halo of the SUB-chunk (rows of the raw slot count from h0)
+        for s0 in range(c0, c1, dec_steps):
             s1 = min(s0 + dec_steps, c1)
-            g0, g1 = (max(s0 - 1, 0), min(s1 + 1, nt)) if with_q else (s0, s1)
-            with torch.cuda.device(dev):
-                for r in roles:
-                    a, b = (g0 - h0, g1 - h0) if r == "Air Temperature" else (s0 - h0, s1 - h0)
-                    unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
-                    _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][a].data_ptr(), b - a, (nl_in, ny_in, nx_in, nl, ny, nx), maps, unit,
-                                 decode[r], common, cubes[keys[r]][a - (g0 - h0)].data_ptr(), compute)
-            f = {k: t[: g1 - g0] for k, t in cubes.items()}
-            if keep is not None:                # (u, v, geopotential start at their own first step: rows [s0 - g0, s1 - g0) of the cubes)
-                for k in keep:
-                    keep[k][s0 - t0: s1 - t0].copy_(cubes[k][s0 - g0: s1 - g0, k_keep])
-            part = own_boxes.part(s0 - t0, s1 - t0) if per_step_boxes else fixed_box
-            engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part,
-                            tcoef=tcoef_all[g0:g1] if with_q else None, t_begin=s0 - g0, t_count=s1 - s0, with_q=with_q,
-                            rows_out=rows[: s1 - s0], per_step_boxes=per_step_boxes)
-            engine.level_stage(rows[: s1 - s0], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
-        for s0 in (range(c0, c1, dec_steps) if packed else ()):
-            # the box-packed series: every output step holds that step's box alone (lec_ingest enters the maps at the box's south-west
-            # corner, step by step: `step_tab`), T also from the two neighbouring steps' raw slices
-            s1 = min(s0 + dec_steps, c1)
-            geom = (nl_in, ny_in, nx_in, nl, nyp, nxp)
             n = s1 - s0
             with torch.cuda.device(dev):
-                for r in roles:                 # ONE gather per plane and sub-chunk: every output step's box through lec_ingest's per-step origins
-                    unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
-                    for key, shift in [(keys[r], 0)] + ([("tm", -1), ("tp", 1)] if r == "Air Temperature" else []):
-                        _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, geom, maps, unit, decode[r], common,
-                                     cubes[key][0].data_ptr(), compute, step=step_tab[shift][s0:s1], step_base=h0,
-                                     nt_src=int(stagers[r].raw_dev[slot].shape[0]))
-                if keep is not None:            # the diagnostics' level of u, v, Phi over the whole crop: one gather of that level per field
-                    kmap1 = maps[0][k_keep: k_keep + 1]
-                    for r, k in (("Eastward Wind Component", "u"), ("Northward Wind Component", "v"), (geo_role, "geopt")):
+                if packed:
+                    geom = (nl_in, ny_in, nx_in, nl, nyp, nxp)
+                    for r in roles:             # ONE gather per plane and sub-chunk: every output step's box through lec_ingest's per-step origins
                         unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
-                        _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][s0 - h0].data_ptr(), n, (nl_in, ny_in, nx_in, 1, ny, nx),
-                                     (kmap1, maps[1], maps[2]), unit, decode[r], common, keep[k][s0 - t0].data_ptr(), compute)
-            f = {k: t[:n] for k, t in cubes.items()}
-            part = own_boxes.part(s0 - t0, s1 - t0)
-            if dtdt is not None:
-                engine.time_stencil(f["tm"], f["tair"], f["tp"], tcoef_all[s0:s1], out=dtdt[:n])
-                tkw = dict(dTdt=dtdt[:n])
-            else:
-                tkw = dict(tm=f["tm"], tp=f["tp"], tcoef=tcoef_all[s0:s1])
-            engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_begin=0, t_count=n, with_q=True,
-                            rows_out=rows[:n], per_step_boxes=True, **tkw)
+                        for key, shift in [(keys[r], 0)] + ([("tm", -1), ("tp", 1)] if r == "Air Temperature" else []):
+                            _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, geom, maps, unit, decode[r], common,
+                                         cubes[key][0].data_ptr(), compute, step=step_tab[shift][s0:s1], step_base=h0,
+                                         nt_src=int(stagers[r].raw_dev[slot].shape[0]))
+                    if keep is not None:        # the diagnostics' level of u, v, Phi over the whole crop: one gather of that level per field
+                        kmap1 = maps[0][k_keep: k_keep + 1]
+                        for r, k in (("Eastward Wind Component", "u"), ("Northward Wind Component", "v"), (geo_role, "geopt")):
+                            unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
+                            _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][s0 - h0].data_ptr(), n, (nl_in, ny_in, nx_in, 1, ny, nx),
+                                         (kmap1, maps[1], maps[2]), unit, decode[r], common, keep[k][s0 - t0].data_ptr(), compute)
+                    f = {k: t[:n] for k, t in cubes.items()}
+                    kw = dict(t_begin=0, **engine.packed_dtdt(f["tm"], f["tair"], f["tp"], tcoef_all[s0:s1], out=None if dtdt is None else dtdt[:n]))
+                else:
+                    g0, g1 = (max(s0 - 1, 0), min(s1 + 1, nt)) if with_q else (s0, s1)
+                    for r in roles:
+                        a, b = (g0 - h0, g1 - h0) if r == "Air Temperature" else (s0 - h0, s1 - h0)
+                        unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
+                        _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][a].data_ptr(), b - a, (nl_in, ny_in, nx_in, nl, ny, nx), maps, unit,
+                                     decode[r], common, cubes[keys[r]][a - (g0 - h0)].data_ptr(), compute)
+                    f = {k: t[: g1 - g0] for k, t in cubes.items()}
+                    if keep is not None:        # (u, v, geopotential start at their own first step: rows [s0 - g0, s1 - g0) of the cubes)
+                        for k in keep:
+                            keep[k][s0 - t0: s1 - t0].copy_(cubes[k][s0 - g0: s1 - g0, k_keep])
+                    kw = dict(t_begin=s0 - g0, tcoef=tcoef_all[g0:g1] if with_q else None)
+            part = own_boxes.part(s0 - t0, s1 - t0) if per_step_boxes else fixed_box
+            engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_count=n, with_q=with_q, rows_out=rows[:n],
+                            per_step_boxes=per_step_boxes, **kw)
             engine.level_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
         consumed[slot].record(compute)
         used[slot] = True

@@ -139,6 +139,38 @@ def test_stage_halves_and_launch_splitting_change_no_bit():
             assert same(got.scalars, ref.scalars) and same(got.levels, ref.levels) and torch.equal(got.nanflag, ref.nanflag), (dtype, moving)
 
 
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_packed_series_cut_into_launches_changes_no_bit(dtype):
+    """A box-packed series -- fp64 storage with its dT/dt cube, fp32 with T of the two time neighbours, as ``pack_series`` hands them
+    over -- cut into launches of 5 steps: one timing pair per launch, and the records and terms of the uncut call bit for bit."""
+    from tests.helpers import synthetic_domain
+    dom = synthetic_domain(23, 6, 40, 64, seed=7, dtype=dtype, lat0=-50, lat1=28, lon0=-120, lon1=6)
+    eng = LECEngine(dom.lat, dom.lon, dom.level, device="cuda:0")
+    f = [torch.as_tensor(np.ascontiguousarray(x)).to("cuda:0") for x in (dom.tair, dom.u, dom.v, dom.omega, dom.geopt)]
+    boxes = [(3 + t % 4, 50 + t % 5, 2 + t % 3, 30 + t % 6) for t in range(23)]
+    tc = eng.time_coefs_device(dom.time_s)
+    ps = eng.pack_series(*f, boxes, tc)
+    kw = {k: ps[k] for k in ("dTdt", "tm", "tp") if k in ps}
+    if "tm" in kw:
+        kw["tcoef"] = tc
+    assert ("dTdt" in kw) == (dtype == np.float64)
+    pb = eng.prepare_boxes(boxes, packed=True)
+    fields = [ps[k] for k in ("tair", "u", "v", "omega", "geopt")]
+    whole, cut = [], []
+    ref = eng.compute(*fields, pb, per_step_boxes=True, keep_rows=True, timing=whole, **kw)
+    eng.MAX_STEPS_PER_LAUNCH = 5
+    try:
+        got = eng.compute(*fields, pb, per_step_boxes=True, keep_rows=True, timing=cut, **kw)
+    finally:
+        del eng.MAX_STEPS_PER_LAUNCH
+    torch.cuda.synchronize()
+    assert len(whole) == 1 and len(cut) == 5                      # 23 steps: 5 + 5 + 5 + 5 + 3
+    same = lambda x, y: bool(((x == y) | (torch.isnan(x) & torch.isnan(y))).all())
+    # (the 28 statistics: the four spare slots of a record are scratch of the cross-time covariance form)
+    assert same(got.rows[..., :28], ref.rows[..., :28]) and bool(torch.isfinite(ref.rows[..., :28]).all())
+    assert same(got.scalars, ref.scalars) and same(got.levels, ref.levels) and torch.equal(got.nanflag, ref.nanflag)
+
+
 def test_deflated_and_plain_variables_mixed_in_one_streamed_run():
     """a file whose variables take DIFFERENT roads to the GPU -- T (the first role) and w in deflated HDF5 chunks, inflated on
     the device on their own streams; u, v, z plain arrays, staged to pinned memory and copied on the shared copy stream -- through many

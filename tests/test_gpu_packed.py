@@ -87,6 +87,21 @@ def test_pack_boxes_is_the_products_gather():
         eng.pack_boxes(cube, boxes, ny=10)
 
 
+def test_pack_boxes_refuses_boxes_outside_the_grid():
+    """A box with a negative origin or one that ends past the grid's last row / column is refused by name, before any gather (it
+    would otherwise become NaN rows); the torch gather the tests hold it to refuses it alike."""
+    dom = synthetic_domain(3, 4, 23, 31, seed=12)
+    eng = _engine(dom)
+    cube = _dev(dom.tair)
+    good = [(0, 9, 0, 5), (21, 30, 17, 22), (3, 30, 0, 22)]
+    for k, bad in ((1, (-1, 9, 0, 5)), (2, (3, 30, -2, 22)), (1, (21, 31, 17, 22)), (2, (3, 30, 0, 23))):
+        boxes = list(good)
+        boxes[k] = bad
+        for gather in (eng.pack_boxes, eng.pack_boxes_by_indexing):
+            with pytest.raises(ValueError, match=f"box {k} .*outside"):
+                gather(cube, boxes)
+
+
 def test_packed_series_random_geometries():
     """Boxes of any size anywhere in the grid (also at its edges, also wider than one 64-column pass), slabs larger than the boxes,
     1..6 steps, fp32 / fp64, uniform or stretched longitudes: records equal bit for bit, padding rows of the lower boxes zero."""

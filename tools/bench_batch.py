@@ -29,7 +29,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from lorenzcycletoolkit_amd import tables                                     # noqa: E402
-from lorenzcycletoolkit_amd.engine import LECEngine                          # noqa: E402
+from lorenzcycletoolkit_amd.engine import LECEngine, pack_host               # noqa: E402
 from lorenzcycletoolkit_amd.synthetic import era5_like_levels, synthetic_cube  # noqa: E402
 
 HBM_PEAK_GBS = 8000.0          # as bench.py
@@ -154,18 +154,13 @@ def main():
         outs = {}
         for k, (u, bx) in enumerate(tracks):
             nyb, nxb = max(b[3] - b[2] + 1 for b in bx), max(b[1] - b[0] + 1 for b in bx)
-
-            def pack(arr, shift=0):
-                p = np.zeros((len(u), nl, nyb, nxb), dtype=arr.dtype)
-                for i, (iw, ie, js, jn) in enumerate(bx):
-                    ts = u[min(max(i + shift, 0), len(u) - 1)]
-                    p[i, :, : jn - js + 1, : ie - iw + 1] = arr[ts, :, js: jn + 1, iw: ie + 1]
-                return torch.as_tensor(p).to(dev)
+            src = lambda shift: u[np.clip(np.arange(len(u)) + shift, 0, len(u) - 1)]       # (the step itself at the track's ends)
+            pack = lambda arr, shift=0: torch.as_tensor(pack_host(arr, bx, src(shift), nyb, nxb)).to(dev)
             fl = [pack(h) for h in host]
             tm, tp = pack(host[0], -1), pack(host[0], +1)
             tcoef = eng.time_coefs_device(time_s[u] - time_s[u[0]])
             pb = eng.prepare_boxes(bx, nyb_min=nyb, packed=True)
-            kw = dict(dTdt=eng.time_stencil(tm, fl[0], tp, tcoef)) if dt == torch.float64 else dict(tm=tm, tp=tp, tcoef=tcoef)
+            kw = eng.packed_dtdt(tm, fl[0], tp, tcoef)
             outs[k] = eng.compute(*fl, pb, per_step_boxes=True, drop_any_time=False, **kw).packed
         return outs
 
