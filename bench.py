@@ -23,9 +23,14 @@ Scaling modes.
 Either way the data path has no collective: one all_reduce of the [28, L] NaN-level mask and one
 gather of the per-time-step results per pass.  Prints ONE JSON line on rank 0.
 
-The default N > 1 run (``--gpus N`` and nothing else: what the driver passes) also carries BASELINE configs 4 and 5: after the
-weak-scaling headline and before the CPU leg the same process group runs two short strong-scaling legs -- the fixed box at
-T = 2048 (chunked) and the moving box at T = 4096 -- and attaches them as ``config.strong_scaling`` (``--no-strong-legs`` for A/B runs).
+A plain run does only what its headline needs: set-up, the warm-up and timed passes, --dump-outputs, the line (with the
+roofline figure the timed passes' own HIP events give, and whether the last pass's terms are finite).  ``--full`` adds
+everything else the benchmark measures or checks, each after the timed passes: the CPU baseline and its parity check against
+the oracle, the instrumented passes (``segments_ms``), the conversion-terms launches, the producer of a packed series, the
+moving kernel cross-check, the gather's checks, the series digest and the stored N = 1 values.  A ``--full`` N > 1 run of the
+default configuration (``--gpus N --full``) also carries BASELINE configs 4 and 5: after the weak-scaling headline and before
+the CPU leg the same process group runs two short strong-scaling legs -- the fixed box at T = 2048 (chunked) and the moving box
+at T = 4096 -- and attaches them as ``config.strong_scaling`` (``--no-strong-legs`` for A/B runs).
 
 What a ``--moving`` line times.  The reference clocks its whole call, dT/dt and the per-step slice included
 (lorenzcycletoolkit.py:173-199, box_data.py:297-310).  With ``--moving-layout packed`` (the layout every ``-t`` path of the
@@ -62,8 +67,12 @@ def parse_args(argv=None):
                     "shard if it fits in HBM, else as many steps as half of the free HBM holds")
     ap.add_argument("--storage", choices=["f64", "f32"], default="f64", help="storage dtype of the field cubes")
     ap.add_argument("--no-q", action="store_true", help="conversion-terms configuration: T,u,v,omega only (no Q, no Phi)")
+    ap.add_argument("--full", action="store_true", help="also measure and check everything beside the headline (CPU baseline and parity, "
+                    "instrumented passes, conversion terms, producer, cross-checks, digests, N = 1 values, strong-scaling legs), after the "
+                    "timed passes; a plain run leaves them out")
     ap.add_argument("--cpu-baseline", choices=["full", "quick", "none"], default="full",
-                    help="full: the bounded sample described in DESIGN.md section 6 (~1 min of host time); quick: a tiny one (tests)")
+                    help="the CPU leg of a --full run -- full: the bounded sample described in DESIGN.md section 6 (~1 min of host time); "
+                         "quick: a tiny one (tests)")
     ap.add_argument("--no-cpu-baseline", action="store_true", help="same as --cpu-baseline none")
     ap.add_argument("--moving", action="store_true", help="semi-Lagrangian configuration: one 15x15 degree box per time step "
                     "on a track-extent crop of the 0.25 degree grid (BASELINE config 5)")
@@ -76,10 +85,10 @@ def parse_args(argv=None):
                     "(the N > 1 code path -- RCCL init, barrier, mask all_reduce, gather -- on a one-GPU box)")
     ap.add_argument("--digest-file", type=str, default=os.path.join(ROOT, "profiles", "series_digests.json"),
                     help="per-step checksums of the packed series of one-GPU runs: what config.series_equals_n1 compares an N-GPU run with")
-    ap.add_argument("--write-digest", action="store_true", help="N = 1 only: add this run's series digest to --digest-file")
+    ap.add_argument("--write-digest", action="store_true", help="N = 1 and --full only: add this run's series digest to --digest-file")
     ap.add_argument("--nonuniform-lon", action="store_true", help="stretched longitudes (a Gaussian / regridded-MPAS style axis): the kernels "
                     "then carry per-column trapezoid weights and d/dlon coefficient tables instead of the even-spacing fast path")
-    ap.add_argument("--no-strong-legs", action="store_true", help="N > 1 default run: leave out the two strong-scaling legs (BASELINE configs 4 / 5) "
+    ap.add_argument("--no-strong-legs", action="store_true", help="N > 1 default --full run: leave out the two strong-scaling legs (BASELINE configs 4 / 5) "
                     "that otherwise ride in config.strong_scaling")
     ap.add_argument("--leg-timesteps", type=str, default="2048,4096", help="global series lengths of the two strong-scaling legs (fixed box, "
                     "moving box); BASELINE configs 4 / 5 are 2048 / 4096 (rehearsals on one GPU use shorter ones)")
@@ -428,10 +437,10 @@ def n1_key(args, T_global, packed):
 
 
 def measure(args, ctx, cpu_kind="none"):
-    """One bench configuration on the job's process group: generation, warm-up, the timed passes, the instrumented passes and the
-    self-checks.  Returns (out, cpu_leg): rank 0's JSON object (None elsewhere) and -- rank 0, cpu_kind != "none" -- a callable
+    """One bench configuration on the job's process group: generation, warm-up, the timed passes and -- args.full -- the instrumented
+    passes and the self-checks.  Returns (out, cpu_leg): rank 0's JSON object (None elsewhere) and -- rank 0, cpu_kind != "none" -- a callable
     that runs the CPU leg and fills out["cpu_baseline"] / out["parity"]; it holds only the few time steps it needs, so the caller
-    may run other configurations in between (the strong-scaling legs of the default N > 1 line)."""
+    may run other configurations in between (the strong-scaling legs of the default N > 1 --full line)."""
     import torch
     import torch.distributed as dist
 
@@ -670,9 +679,9 @@ def measure(args, ctx, cpu_kind="none"):
     res = last["res"]
     series = last.get("series")
     # every rank's block of the gathered series against the checksums of what that rank sent (not only rank 0's own block)
-    peers = verify_gather(series, res.packed, T_global) if use_dist else None
+    peers = verify_gather(series, res.packed, T_global) if (use_dist and args.full) else None
     per_rank = None
-    if use_dist:      # each rank's own clock for the timed region (the line's ms_per_step is their maximum)
+    if use_dist and args.full:      # each rank's own clock for the timed region (the line's ms_per_step is their maximum)
         mine = torch.tensor([elapsed_own], dtype=torch.float64, device=device)
         from lorenzcycletoolkit_amd.parallel import _all_gather_small
         per_rank = [float(x) / args.steps * 1e3 for x in _all_gather_small(mine).view(-1)]
@@ -685,7 +694,7 @@ def measure(args, ctx, cpu_kind="none"):
     # box_data.py:297-310), per pass over this rank's shard, on HIP events of its own.  Streamed runs produce every chunk inside every
     # pass (generate(): the events were taken there); a resident run re-produces its series from the crop it kept, three times.
     producer = None
-    if packed:
+    if packed and args.full:
         repack_same = None
         if resident and not crop:          # the crop was not kept (ranks share a GPU): what producing the series took, once, before the timed passes
             per_pass = [float(produced_once["pack"][-1]), float(produced_once["dtdt"][-1])]
@@ -717,7 +726,7 @@ def measure(args, ctx, cpu_kind="none"):
     # Where a pass's time goes: three instrumented passes (every segment closed by a device synchronisation, the gather completed
     # inside its pass), median per segment.  Reported beside the timed figure, never inside it.
     seg_runs = []
-    if resident:
+    if resident and args.full:
         for _ in range(3):
             sync()
             sg = {}
@@ -747,7 +756,7 @@ def measure(args, ctx, cpu_kind="none"):
 
     # the BASELINE target configuration (conversion terms: T, u, v, omega) on the same resident fields, rank 0
     conv = None
-    if rank == 0 and resident and with_q and not args.moving:
+    if args.full and rank == 0 and resident and with_q and not args.moving:
         h0, h1, f = held[:3]
         ev = []
         for i in range(2 + 5):
@@ -765,7 +774,7 @@ def measure(args, ctx, cpu_kind="none"):
     # moving boxes: the shipped kernel family (box tiles) against the independent one-wave-per-row formulation on the first steps of the
     # resident shard -- record by record and term by term (finite is not a check: wrong coefficients give finite numbers too)
     moving_check = None
-    if rank == 0 and resident and args.moving:
+    if args.full and rank == 0 and resident and args.moving:
         # (a box-packed series: the check runs on the CROP the series was produced from, so it also says that packing changed no
         # value: the timed pass read the packed series, `a` reads the crop)
         h0, f = (crop_head["h0"], crop_head["f"]) if packed else held[:3:2]
@@ -791,7 +800,7 @@ def measure(args, ctx, cpu_kind="none"):
         from lorenzcycletoolkit_amd._lib import source_digest
         finite = bool(torch.isfinite(res.scalars).all().item())
         gathered_ok = None
-        if series is not None and gat.active:       # rank 0's block of the gathered series is what its own stage 2 wrote
+        if args.full and series is not None and gat.active:       # rank 0's block of the gathered series is what its own stage 2 wrote
             gathered_ok = bool(torch.equal(series[t0:t1], res.packed)) and tuple(series.shape) == (T_global, LECEngine.packed_width(nl))
         bytes_per_step_t = nfields * nl * lat.size * lon.size * esz        # algorithmic bytes per time step
         if args.moving:
@@ -828,7 +837,7 @@ def measure(args, ctx, cpu_kind="none"):
             workload = (f"synthetic 0.25-degree {nl} lev x {lat.size} x {lon.size} track-extent crop, moving 15x15-degree box "
                         f"(61 x 61 points) per time step, storage {args.storage}, terms = {terms}"
                         + ("; the series lies in HBM BOX-PACKED (every step's box gathered out of the crop and dT/dt formed by the PRODUCER, outside the "
-                           "timed region -- config.producer_ms --, as the streamed moving framework's ingest writes it: 5 field slabs + "
+                           "timed region -- config.producer_ms of a --full line --, as the streamed moving framework's ingest writes it: 5 field slabs + "
                            + ("dT/dt as an fp64 cube" if args.storage == "f64" else "T of the two time neighbours")
                            + " per step; --moving-layout cube = the whole crop, rounds 1-4)" if packed else "; the series lies in HBM as the whole crop"))
         else:
@@ -857,8 +866,8 @@ def measure(args, ctx, cpu_kind="none"):
             timed_region = "lec_rowstats per chunk + lec_reduce + collectives (synchronised segments); synthetic generation excluded"
         if packed:
             timed_region += ("; the series is resident BOX-PACKED: the per-step slice (box_data.py:297-310) and dT/dt (lorenzcycletoolkit.py:184-186) -- both "
-                             "inside the reference's own clock -- are the producer's work and OUTSIDE this region: config.producer_ms times them, "
-                             "config.value_incl_producer is the rate with them inside")
+                             "inside the reference's own clock -- are the producer's work and OUTSIDE this region: with --full, config.producer_ms "
+                             "times them and config.value_incl_producer is the rate with them inside")
         elif args.moving:
             timed_region += "; the kernel slices every step's box by index and forms dT/dt per point: both inside this region"
         out = {
@@ -922,11 +931,11 @@ def measure(args, ctx, cpu_kind="none"):
         if conv is not None:
             out["roofline"]["conversion_terms"] = conv
         # the synthetic fields are seeded per GLOBAL time step and the kernels are bitwise reproducible under sharding and chunking,
-        # so the series does not depend on N: compare it with the digest a one-GPU run stored (profiles/series_digests.json)
+        # so the series does not depend on N: --full compares it with the digest a one-GPU run stored (profiles/series_digests.json)
         dkey = (f"{'moving' if args.moving else 'fixed'}_{args.storage}_{'noq' if args.no_q else 'all'}_{nl}x{lat.size}x{lon.size}_T{T_global}"
                 + ("_stretched" if args.nonuniform_lon else ""))
         full = series if (series is not None and gat.active) else res.packed
-        sums = record_checksums(full).cpu().numpy() if full.shape[0] == T_global else None
+        sums = record_checksums(full).cpu().numpy() if (args.full and full.shape[0] == T_global) else None
         if sums is not None:
             import hashlib
             digest = {"sha256": hashlib.sha256(sums.tobytes()).hexdigest(), "steps": int(T_global),
@@ -951,7 +960,7 @@ def measure(args, ctx, cpu_kind="none"):
                 book[dkey] = digest
                 os.makedirs(os.path.dirname(os.path.abspath(args.digest_file)), exist_ok=True)
                 json.dump(book, open(args.digest_file, "w"), indent=1)
-        if strong:
+        if strong and args.full:
             # the N = 1 value of this configuration (profiles/strong_scaling_n1.json, keyed by the series' layout, stamped with the kernel
             # sources it was measured on; tools/update_n1.py writes it from one-GPU lines).  A one-GPU run IS the N = 1 value.
             nkey = n1_key(args, T_global, packed)
@@ -1016,7 +1025,7 @@ def measure(args, ctx, cpu_kind="none"):
 
 
 def strong_legs(args, ctx):
-    """BASELINE configs 4 and 5 inside the default N > 1 run (the driver passes --gpus N and nothing else): the fixed box at T = 2048
+    """BASELINE configs 4 and 5 inside a --full N > 1 run of the default configuration (--gpus N --full): the fixed box at T = 2048
     (sharded, streamed through HBM in chunks) and the moving box at T = 4096, one warm-up pass and --leg-steps timed passes each, on
     the job's own process group.  Returns rank 0's summary for config.strong_scaling (None elsewhere)."""
     import copy
@@ -1052,11 +1061,11 @@ def run_rank(args):
     import torch
     import torch.distributed as dist
     ctx = RankContext(args)
-    kind = "none" if args.no_cpu_baseline else args.cpu_baseline
+    kind = "none" if (args.no_cpu_baseline or not args.full) else args.cpu_baseline
     out, cpu_leg = measure(args, ctx, cpu_kind=kind)
-    # the default N > 1 line: BASELINE configs 4 and 5 as two short strong-scaling legs, after the headline and before the CPU leg
+    # the default N > 1 --full line: BASELINE configs 4 and 5 as two short strong-scaling legs, after the headline and before the CPU leg
     default_line = not (args.moving or args.timesteps_global > 0 or args.no_q or args.storage != "f64" or args.nonuniform_lon or args.tuning)
-    if ctx.world > 1 and default_line and not args.no_strong_legs:
+    if args.full and ctx.world > 1 and default_line and not args.no_strong_legs:
         gc.collect()
         torch.cuda.empty_cache()                # the headline's resident cube makes room for the legs' chunks
         legs = strong_legs(args, ctx)
@@ -1080,6 +1089,8 @@ def main():
         raise SystemExit("bench.py: --gpus must be >= 1")
     if args.steps < 1 or args.warmup < 0:
         raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
+    if args.write_digest and not args.full:
+        raise SystemExit("bench.py: --write-digest needs --full (the series digest is one of its checks)")
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None:
         if args.gpus > 1:

@@ -1,5 +1,5 @@
-"""bench.py prints ONE JSON line with the keys the driver contract names (plus `roofline` and `cpu_baseline`), launches its own
-ranks for --gpus N, and refuses a --gpus it cannot honour."""
+"""bench.py prints ONE JSON line with the keys its contract names (plus `roofline`; `--full` adds `cpu_baseline` and the other
+figures and checks beside the headline), launches its own ranks for --gpus N, and refuses a --gpus it cannot honour."""
 import json
 import os
 import subprocess
@@ -24,7 +24,7 @@ def _bench(extra, env=None, timeout=600):
 
 
 def test_bench_json_contract():
-    r, lines = _bench(["--timesteps", "3", "--cpu-baseline", "quick"] + SMALL)
+    r, lines = _bench(["--full", "--timesteps", "3", "--cpu-baseline", "quick"] + SMALL)
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
@@ -53,10 +53,27 @@ def test_bench_json_contract():
         assert k in sg and sg[k] >= 0 or k == "fixed_cost_per_pass", k
 
 
+@pytest.mark.parametrize("extra", [["--timesteps", "3"] + SMALL, ["--moving", "--timesteps", "12", "--steps", "2", "--warmup", "1"]])
+def test_a_plain_line_carries_the_headline_and_nothing_that_needs_runs_of_its_own(extra):
+    """Without --full a run does only what its headline needs: the contract's keys and the roofline its timed passes' own events give,
+    but no CPU leg, no instrumented passes, no conversion-terms launches, no producer, no cross-check and no digest."""
+    r, lines = _bench(extra)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert [ln for ln in r.stdout.splitlines() if ln.strip()] == lines and len(lines) == 1
+    d = json.loads(lines[0])
+    c = d["config"]
+    assert d["unit"] == "timesteps/s" and d["dtype"] == "f64" and d["higher_is_better"] is True and d["steps"] == 2 and d["warmup"] == 1
+    assert d["value"] > 0 and abs(d["value"] - c["timesteps_global"] / (d["ms_per_step"] * 1e-3)) <= 1e-6 * d["value"]
+    assert c["results_finite"] is True and d["roofline"]["achieved"] > 0 and "conversion_terms" not in d["roofline"]
+    assert "cpu_baseline" not in d and "parity" not in d
+    for k in ("segments_ms", "producer_ms", "value_incl_producer", "moving_check", "series_sha256", "series_equals_n1", "n1_key", "strong_scaling"):
+        assert k not in c, k
+
+
 def test_bench_starts_its_own_ranks_and_counts_them():
     """`python bench.py --gpus 2` with no launcher environment: the parent starts two rank processes (gloo rendezvous, both on
     this box's one GPU -- RCCL itself needs a GPU per rank) and rank 0 reports n_gpus = 2, twice the global series."""
-    r, lines = _bench(["--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs"] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs"] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1, r.stdout
     d = json.loads(lines[0])
@@ -79,7 +96,7 @@ def test_bench_starts_its_own_ranks_and_counts_them():
 def test_bench_under_the_drivers_launch_line(tmp_path):
     """The driver's own N > 1 launch: `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N --steps K --warmup W` -- the launcher's environment names the ranks, bench.py starts nobody, rank 0
-    prints the one line with both strong-scaling legs in it (gloo here: both ranks share this box's one GPU)."""
+    prints the one line, with --full both strong-scaling legs in it (gloo here: both ranks share one GPU)."""
     import socket
     with socket.socket() as so:
         so.bind(("127.0.0.1", 0))
@@ -91,7 +108,7 @@ def test_bench_under_the_drivers_launch_line(tmp_path):
     e["LEC_DIST_BACKEND"] = "gloo"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--timesteps", "3", "--ny", "61", "--nx", "128",
-           "--cpu-baseline", "quick", "--leg-timesteps", "12,16", "--n1-file", n1]
+           "--full", "--cpu-baseline", "quick", "--leg-timesteps", "12,16", "--n1-file", n1]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=e)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip().startswith("{")]
@@ -109,7 +126,7 @@ def test_bench_under_the_drivers_launch_line(tmp_path):
 def test_a_two_rank_line_carries_the_cpu_leg_and_the_parity_of_rank_0():
     """north_star: the N-GPU throughput "next to the reference CPU path timed on the node's own host cores in the same run".  Rank 0 runs
     the oracle after the timed region while rank 1 waits in the closing barrier; `parity` is rank 0's shard against the oracle."""
-    r, lines = _bench(["--gpus", "2", "--timesteps", "3", "--cpu-baseline", "full", "--no-strong-legs"] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--timesteps", "3", "--cpu-baseline", "full", "--no-strong-legs"] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert [ln for ln in r.stdout.splitlines() if ln.strip()] == lines and len(lines) == 1
     d = json.loads(lines[0])
@@ -123,7 +140,7 @@ def test_a_two_rank_line_carries_the_cpu_leg_and_the_parity_of_rank_0():
 def test_bench_runs_the_rccl_code_path_with_one_rank():
     """--force-dist: process group over backend "nccl" (= RCCL), barrier, the mask all_reduce and the gather run with world size 1 --
     the N > 1 code path of the product on the one GPU this box has (more RCCL ranks need more GPUs)."""
-    r, lines = _bench(["--force-dist", "--timesteps", "3", "--cpu-baseline", "quick"] + SMALL)
+    r, lines = _bench(["--full", "--force-dist", "--timesteps", "3", "--cpu-baseline", "quick"] + SMALL)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     assert d["cpu_baseline"]["value"] > 0 and d["parity"]["ok"] is True          # the CPU leg runs on the distributed code path too
@@ -140,12 +157,12 @@ def test_series_digest_of_a_two_rank_run_equals_the_one_gpu_digest(tmp_path):
     an N-rank run is the series of the one-GPU run: `--write-digest` stores the N = 1 per-step checksums, and a run finds
     `series_equals_n1` true -- or says which steps differ."""
     book = str(tmp_path / "digests.json")
-    r, lines = _bench(["--timesteps-global", "6", "--cpu-baseline", "none", "--digest-file", book, "--write-digest"] + SMALL)
+    r, lines = _bench(["--full", "--timesteps-global", "6", "--cpu-baseline", "none", "--digest-file", book, "--write-digest"] + SMALL)
     assert r.returncode == 0, r.stderr[-2000:]
     one = json.loads(lines[0])["config"]
     stored = json.load(open(book))["fixed_f64_all_37x61x128_T6"]
     assert stored["sha256"] == one["series_sha256"] and stored["steps"] == 6 and len(stored["per_step"]) == 96
-    r, lines = _bench(["--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs", "--digest-file", book] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs", "--digest-file", book] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     two = json.loads(lines[0])["config"]
     assert two["series_digest_key"] == "fixed_f64_all_37x61x128_T6" and two["series_sha256"] == one["series_sha256"]
@@ -155,13 +172,13 @@ def test_series_digest_of_a_two_rank_run_equals_the_one_gpu_digest(tmp_path):
     ps = bk["fixed_f64_all_37x61x128_T6"]["per_step"]
     bk["fixed_f64_all_37x61x128_T6"].update(sha256="0" * 64, per_step=ps[:16] + "f" * 16 + ps[32:80] + "0" * 16)
     json.dump(bk, open(book, "w"))
-    r, lines = _bench(["--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs", "--digest-file", book] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--timesteps", "3", "--cpu-baseline", "none", "--no-strong-legs", "--digest-file", book] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
     bad = json.loads(lines[0])["config"]
     assert bad["series_equals_n1"] is False and bad["series_steps_differing_from_n1"] == {"count": 2, "first": [1, 5]}
 
 
 def test_bench_moving_checks_its_kernel_against_the_independent_one():
-    r, lines = _bench(["--moving", "--timesteps", "12", "--cpu-baseline", "none", "--steps", "2", "--warmup", "1"])
+    r, lines = _bench(["--full", "--moving", "--timesteps", "12", "--cpu-baseline", "none", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     mc = json.loads(lines[0])["config"]["moving_check"]
     assert mc["ok"] is True and mc["steps"] == 8 and mc["timed_pass_bit_identical"] is True and mc["terms_max_rel_diff_vs_row_sweep"] <= 1e-9
@@ -185,13 +202,13 @@ def _moving_line_is_whole(d, steps, n_cpu, held):
 
 
 def test_a_moving_line_times_its_producer_and_carries_the_cpu_leg():
-    r, lines = _bench(["--moving", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
+    r, lines = _bench(["--full", "--moving", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     _moving_line_is_whole(d, 2, 3, 4)
     assert d["config"]["producer_ms"]["reproduced_series_is_the_timed_one"] is True and "re-produced 3 times" in d["config"]["producer_ms"]["how"]
     # the cube layout slices and differentiates inside the kernel: no producer, and the line says so
-    r, lines = _bench(["--moving", "--moving-layout", "cube", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
+    r, lines = _bench(["--full", "--moving", "--moving-layout", "cube", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     assert "producer_ms" not in d["config"] and "both inside this region" in d["config"]["timed_region"]
@@ -199,7 +216,7 @@ def test_a_moving_line_times_its_producer_and_carries_the_cpu_leg():
 
 
 def test_a_two_rank_moving_line_is_whole_too():
-    r, lines = _bench(["--gpus", "2", "--moving", "--timesteps", "6", "--cpu-baseline", "full", "--steps", "2", "--warmup", "1"], env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--moving", "--timesteps", "6", "--cpu-baseline", "full", "--steps", "2", "--warmup", "1"], env={"LEC_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["timesteps_global"] == 12 and "strong_scaling" not in d["config"]
@@ -208,7 +225,7 @@ def test_a_two_rank_moving_line_is_whole_too():
 
 
 def test_a_forced_rccl_moving_line_is_whole_too():
-    r, lines = _bench(["--force-dist", "--moving", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
+    r, lines = _bench(["--full", "--force-dist", "--moving", "--timesteps", "12", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1"])
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
     assert d["config"]["backend"] == "nccl"
@@ -220,7 +237,7 @@ def test_strong_scaling_lines_carry_the_cpu_leg_and_an_honest_n1(tmp_path):
     strong line IS the N = 1 value (speedup 1.0); an entry of --n1-file is keyed by the series' layout and stamped with the kernel
     sources' digest, and a line says when that stamp is stale."""
     n1 = str(tmp_path / "n1.json")
-    small = ["--ny", "61", "--nx", "128", "--steps", "2", "--warmup", "1", "--n1-file", n1]
+    small = ["--full", "--ny", "61", "--nx", "128", "--steps", "2", "--warmup", "1", "--n1-file", n1]
     r, lines = _bench(["--timesteps-global", "8", "--chunk", "3", "--cpu-baseline", "quick"] + small)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads(lines[0])
@@ -241,7 +258,7 @@ def test_strong_scaling_lines_carry_the_cpu_leg_and_an_honest_n1(tmp_path):
     c3 = json.loads(lines[0])["config"]
     assert c3["n1_stale"] is True and c3["speedup_vs_n1"] == 1.0           # (a one-GPU run is its own N = 1 value whatever is stored)
     # the moving configuration keys its entry by layout
-    r, lines = _bench(["--moving", "--timesteps-global", "10", "--chunk", "4", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1", "--n1-file", n1])
+    r, lines = _bench(["--full", "--moving", "--timesteps-global", "10", "--chunk", "4", "--cpu-baseline", "quick", "--steps", "2", "--warmup", "1", "--n1-file", n1])
     assert r.returncode == 0, r.stderr[-2000:]
     dm = json.loads(lines[0])
     assert dm["config"]["n1_key"] == "moving_packed_f64_all_T10" and dm["config"]["speedup_vs_n1"] == 1.0
@@ -250,12 +267,12 @@ def test_strong_scaling_lines_carry_the_cpu_leg_and_an_honest_n1(tmp_path):
 
 
 def test_the_default_two_rank_line_carries_the_strong_scaling_legs(tmp_path):
-    """`--gpus N` and nothing else is what the driver passes: the line then holds BASELINE configs 4 and 5 as config.strong_scaling
+    """`--gpus N --full` of the default configuration: the line then holds BASELINE configs 4 and 5 as config.strong_scaling
     (here with short series: --leg-timesteps), each with its value, its speed-up over the stored one-GPU value and its self-checks."""
     n1 = str(tmp_path / "n1.json")
     json.dump({"fixed_f64_all_T12": {"value": 100.0, "csrc_sha": "0" * 16, "source": "test"},
                "moving_packed_f64_all_T16": {"value": 1000.0, "value_incl_producer": 500.0, "csrc_sha": "0" * 16, "source": "test"}}, open(n1, "w"))
-    r, lines = _bench(["--gpus", "2", "--timesteps", "3", "--cpu-baseline", "quick", "--leg-timesteps", "12,16", "--n1-file", n1] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
+    r, lines = _bench(["--full", "--gpus", "2", "--timesteps", "3", "--cpu-baseline", "quick", "--leg-timesteps", "12,16", "--n1-file", n1] + SMALL, env={"LEC_DIST_BACKEND": "gloo"})
     assert r.returncode == 0, r.stderr[-2000:]
     assert len(lines) == 1
     d = json.loads(lines[0])

@@ -4,7 +4,7 @@ ROUNDS=$1; shift
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 for round in $(seq 1 $ROUNDS); do
 for A in "$@"; do
-  python3 $R/bench.py --cpu-baseline none --steps 10 --warmup 3 $A 2>/dev/null | python3 -c "
+  python3 $R/bench.py --full --cpu-baseline none --steps 10 --warmup 3 $A 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 c=d['config']

@@ -21,18 +21,18 @@ PY
 }
 if [ "$SET" = n1 ] || [ "$SET" = all ]; then
   # the N = 1 values of the strong-scaling configurations (tools/update_n1.py writes them into profiles/strong_scaling_n1.json)
-  LEC_DIST_BACKEND=nccl run n1m4096 400 python3 $R/bench.py --force-dist --moving --timesteps-global 4096 --steps 10 --warmup 2 &&
-  LEC_DIST_BACKEND=nccl run n1m4096cube 400 python3 $R/bench.py --force-dist --moving --moving-layout cube --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
-  LEC_DIST_BACKEND=nccl run n1m512 300 python3 $R/bench.py --force-dist --moving --timesteps-global 512 --cpu-baseline quick --steps 20 --warmup 3 &&
-  run n1f2048 500 python3 $R/bench.py --timesteps-global 2048 --cpu-baseline quick --steps 3 --warmup 1
+  LEC_DIST_BACKEND=nccl run n1m4096 400 python3 $R/bench.py --full --force-dist --moving --timesteps-global 4096 --steps 10 --warmup 2 &&
+  LEC_DIST_BACKEND=nccl run n1m4096cube 400 python3 $R/bench.py --full --force-dist --moving --moving-layout cube --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
+  LEC_DIST_BACKEND=nccl run n1m512 300 python3 $R/bench.py --full --force-dist --moving --timesteps-global 512 --cpu-baseline quick --steps 20 --warmup 3 &&
+  run n1f2048 500 python3 $R/bench.py --full --timesteps-global 2048 --cpu-baseline quick --steps 3 --warmup 1
 fi
 if [ "$SET" = gloo ] || [ "$SET" = all ]; then
   export LEC_DIST_BACKEND=gloo
   # the default N > 1 line with its two strong-scaling legs (short series: two and four ranks share one GPU here), as the driver runs it
-  run g2default 580 python3 $R/bench.py --gpus 2 --timesteps 8 --steps 5 --warmup 2 --leg-timesteps 64,1024 &&
-  run g4default 580 python3 $R/bench.py --gpus 4 --timesteps 8 --cpu-baseline quick --steps 5 --warmup 2 --leg-timesteps 64,1024 &&
-  run g2m4096 400 python3 $R/bench.py --gpus 2 --moving --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
-  run g4m4096 400 python3 $R/bench.py --gpus 4 --moving --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
-  run g2chunk 300 python3 $R/bench.py --gpus 2 --timesteps-global 12 --chunk 3 --ny 61 --nx 128 --cpu-baseline quick --steps 2 --warmup 1 &&
-  run g3mchunk 300 python3 $R/bench.py --gpus 3 --moving --timesteps-global 50 --chunk 7 --cpu-baseline quick --steps 2 --warmup 1
+  run g2default 580 python3 $R/bench.py --full --gpus 2 --timesteps 8 --steps 5 --warmup 2 --leg-timesteps 64,1024 &&
+  run g4default 580 python3 $R/bench.py --full --gpus 4 --timesteps 8 --cpu-baseline quick --steps 5 --warmup 2 --leg-timesteps 64,1024 &&
+  run g2m4096 400 python3 $R/bench.py --full --gpus 2 --moving --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
+  run g4m4096 400 python3 $R/bench.py --full --gpus 4 --moving --timesteps-global 4096 --cpu-baseline quick --steps 10 --warmup 2 &&
+  run g2chunk 300 python3 $R/bench.py --full --gpus 2 --timesteps-global 12 --chunk 3 --ny 61 --nx 128 --cpu-baseline quick --steps 2 --warmup 1 &&
+  run g3mchunk 300 python3 $R/bench.py --full --gpus 3 --moving --timesteps-global 50 --chunk 7 --cpu-baseline quick --steps 2 --warmup 1
 fi

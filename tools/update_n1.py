@@ -3,7 +3,7 @@
 
 Usage: tools/update_n1.py <file with a one-GPU strong-scaling bench line> ...
 
-Each input is the stdout of `python bench.py --timesteps-global T [--moving] ...` on ONE GPU (n_gpus == 1, scaling "strong").
+Each input is the stdout of `python bench.py --full --timesteps-global T [--moving] ...` on ONE GPU (n_gpus == 1, scaling "strong").
 An entry is keyed by configuration AND series layout (config.n1_key) and carries the digest of the kernel sources it was measured
 on (config.csrc_sha): bench.py prints `n1_stale` when the sources have changed since, as it does for the stored counter pass."""
 import json
