@@ -26,6 +26,9 @@
  *   lec_track_diag  replaces MetPy's wind_speed / vorticity on the 850-hPa slice and get_position /
  *                 find_extremum_coordinates of the moving framework
  *                 (src/frameworks/lec_moving_framework.py:269-417,650-663; src/utils/tools.py:95-128).
+ *   lec_follow    replaces the click loop of the interactive chooser (-c/--choose: src/utils/select_area.py:201-251, with the
+ *                 circle on the box's vorticity minimum, select_area.py:106-155) and get_limits' choose branch
+ *                 (lec_moving_framework.py:227-245): the box of every time step is centred on the system by the device.
  *
  * Conventions
  *   - All pointers named *_d are DEVICE pointers owned by the caller; the library allocates nothing.
@@ -302,6 +305,49 @@ typedef struct lec_diag_args {
     void* stream;
 } lec_diag_args;
 
+/*
+ * -c/--choose without a display: one box per time step that FOLLOWS the 850-hPa system.  Replaces the click loop of
+ *   select_area.py:201-251      draw_box_map: the user drags a box over the step's vorticity / height / wind map
+ *   select_area.py:106-155      plot_min_zeta: the circle on the minimum vorticity of the box that guides the next click
+ *   lec_moving_framework.py:227-245  get_limits, choose branch: the clicked box becomes the step's limits
+ * by a chain the device closes itself (additive call: no struct of ABI 11 changes).  Per time step t:
+ *   F_t(j, i)  field = LEC_FOLLOW_ZETA: the zeta of lec_track_diag (same tables, same expression);  LEC_FOLLOW_HGT: hgt_d
+ *   S_t(j, i)  the arithmetic mean of the finite F_t(j', i') with |j' - j| <= smooth_r, |i' - i| <= smooth_r inside the slice, summed in
+ *              row-major order; NaN when none is finite.  smooth_r = 0: F_t itself.
+ *   window     admissible centres [jlo, jhi] x [ilo, ihi] (grid points whose box lies inside the slice: the host's business) cut to
+ *              [jc - sj, jc + sj] x [ic - si, ic + si] around the centre (jc, ic) of step t - 1; step 0: around (j_start, i_start), or
+ *              all admissible centres when both are -1
+ *   centre     the position of the minimum (LEC_FOLLOW_MIN) / maximum (LEC_FOLLOW_MAX) finite S_t of the window; among equal values the
+ *              first in row-major order of the window (numpy's argmin / argmax); a window without a finite value keeps the previous
+ *              centre (step 0 without a start: jlo, ilo) and sets status 1
+ * The chain is sequential in time: ONE workgroup of 256 threads walks the steps and keeps the window's field in an LDS tile of
+ * min(2 sj + 1 + 2 smooth_r, ny) x min(2 si + 1 + 2 smooth_r, nx) doubles; a tile beyond the 160 KiB one workgroup may declare is
+ * LEC_ERR_UNSUPPORTED (the message gives both figures).  Scalars are validated before any HIP call, refused and never clamped
+ * (LEC_ERR_ARG names the field).
+ */
+enum lec_follow_field { LEC_FOLLOW_ZETA = 0, LEC_FOLLOW_HGT = 1 };
+enum lec_follow_sense { LEC_FOLLOW_MIN = 0, LEC_FOLLOW_MAX = 1 };
+
+typedef struct lec_follow_args {
+    const double* u_d;          /* [nt][ny][nx] eastward wind at 850 hPa (m/s) on the search domain (lat S->N, lon W->E) */
+    const double* v_d;          /* [nt][ny][nx] northward wind */
+    const double* hgt_d;        /* [nt][ny][nx] geopotential height (gpm); may be NULL unless field = LEC_FOLLOW_HGT */
+    int32_t nt, ny, nx;
+    int32_t field;              /* enum lec_follow_field */
+    const double* xcoef_d;      /* [ny][nx][3], [ny][3], [ny]: the vorticity tables of lec_diag_args */
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t sense;              /* enum lec_follow_sense */
+    int32_t smooth_r;           /* >= 0 grid points */
+    int32_t sj, si;             /* >= 1: the largest move per step, in grid points */
+    int32_t jlo, jhi, ilo, ihi; /* inclusive bounds of the admissible centres: 0 <= jlo <= jhi < ny, 0 <= ilo <= ihi < nx */
+    int32_t j_start, i_start;   /* an admissible centre, or both -1 */
+    int32_t* pos_d;             /* [nt][2]  (j, i) of every step's centre */
+    double* val_d;              /* [nt]     S_t at the centre it found; NaN where status is 1 */
+    int32_t* status_d;          /* [nt]     0, or 1: the window held no finite value and the centre was kept */
+    void* stream;
+} lec_follow_args;
+
 int lec_version(void);
 const char* lec_last_error(void);
 
@@ -336,6 +382,7 @@ int lec_reduce(const lec_reduce_args* args);
 int lec_dropmask(const lec_reduce_args* args);
 
 int lec_track_diag(const lec_diag_args* args);
+int lec_follow(const lec_follow_args* args);
 
 /*
  * What the library cannot see at launch: indices that live in DEVICE memory.  lec_rowstats validates every scalar argument, but a

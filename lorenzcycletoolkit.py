@@ -5,7 +5,12 @@ daniloceano/LorenzCycleToolkit (reference lorenzcycletoolkit.py:50-265).
 Same flags, same ``inputs/namelist`` / ``inputs/box_limits`` / track files, same
 ``./LEC_Results/<infile>_<method>/`` tree and CSV schema; the numerics run as HIP kernels on the GPU
 (``lorenzcycletoolkit_amd``).  Out of scope: plots (-p), the interactive
-domain chooser (-c), CDS-API downloads (--cdsapi).
+map of the domain chooser, CDS-API downloads (--cdsapi).
+
+-c/--choose runs without a display: instead of waiting for clicks on a map, the GPU follows the 850-hPa system from time step to
+time step (``lec_follow``; --choose-start, --choose-box, --choose-search, --choose-smooth, --choose-field, --choose-hemisphere,
+--choose-domain), writes the boxes' centres as a track file to ``LEC_Results/<infile>_choose/<infile>_choose_track`` and then
+runs the moving framework on that track -- the very run ``-t --trackfile <that file>`` does, under the chooser's file names.
 
 Several GPUs of one node: ``python lorenzcycletoolkit.py <file> -r -f --gpus N`` (this process starts N rank processes, one per
 GPU) or ``python -m torch.distributed.run --nproc-per-node N lorenzcycletoolkit.py <file> -r -f``.  The time steps are sharded
@@ -38,7 +43,9 @@ def create_arg_parser():
     group = parser.add_mutually_exclusive_group(required=True)
     group.add_argument("-f", "--fixed", action="store_true", help="Eulerian framework: one box for the whole series, read from the box-limits file")
     group.add_argument("-t", "--track", action="store_true", help="semi-Lagrangian framework: one box per time step, centred on the track file's positions")
-    group.add_argument("-c", "--choose", action="store_true", help="pick each time step's box on a map (needs a GUI: not available in this build)")
+    group.add_argument("-c", "--choose", action="store_true", help="semi-Lagrangian framework without a track file: the GPU picks each time step's box by "
+                       "following the 850-hPa vorticity (or height) extremum from step to step (the reference's interactive map needs a display; "
+                       "see the --choose-* options), writes the track it found and analyses it as -t would")
     parser.add_argument("-z", "--zeta", action="store_true", help="with -t: report the 850-hPa vorticity at the track position rather than the box extremum")
     parser.add_argument("-m", "--mpas", action="store_true", help="input comes from MPAS-A post-processed with MPAS-BR")
     parser.add_argument("-p", "--plots", action="store_true", help="accepted for compatibility; figures are made by the reference's plot scripts from the CSVs")
@@ -61,6 +68,16 @@ def create_arg_parser():
                         "the (deflated) chunks are inflated -- on the GPU (lec_inflate; the default wherever the variables allow it) or on the host's threads")
     parser.add_argument("--vorticity-form", choices=["metpy_no_crs", "spherical"], default="metpy_no_crs", help="with -t: formulation of the 850-hPa "
                         "relative vorticity in the trackfile (default: what MetPy 1.6.2 evaluates for data without a CRS, as the reference passes them)")
+    parser.add_argument("--choose-domain", metavar="FILE", help="with -c: box-limits file of the domain the system is searched in (default: the file's whole domain)")
+    parser.add_argument("--choose-start", nargs=2, type=float, metavar=("LAT", "LON"), help="with -c: where the system is at the first time step "
+                        "(default: the extremum of the whole search domain)")
+    parser.add_argument("--choose-box", nargs=2, type=float, metavar=("LENGTH", "WIDTH"), help="with -c: the box's size in degrees of latitude / longitude (default: 15 15)")
+    parser.add_argument("--choose-search", type=float, metavar="DEG", help="with -c: the largest move of the box's centre per time step, in degrees (default: 5)")
+    parser.add_argument("--choose-smooth", type=int, metavar="N", help="with -c: follow the mean over (2N + 1) x (2N + 1) grid points instead of the point values (default: 0)")
+    parser.add_argument("--choose-field", choices=["zeta", "hgt"], help="with -c: follow the 850-hPa relative vorticity (default; formulation of "
+                        "--vorticity-form) or the geopotential height minimum")
+    parser.add_argument("--choose-hemisphere", choices=["south", "north"], help="with -c and the vorticity: follow the minimum (south) or the maximum "
+                        "(north); default: south when the search domain's southern edge lies south of the equator")
     parser.add_argument("--gpus", type=int, default=1, help="shard the time steps over this many GPUs of the node (one process per GPU, "
                         "results gathered over RCCL; same output files).  Under torch.distributed.run the launcher's WORLD_SIZE counts")
     parser.add_argument("-o", "--outname", type=str, help="name of the results CSV (fixed framework)")
@@ -137,11 +154,36 @@ def run_lec_analysis(data, args, results_subdirectory, figures_directory, result
         app_logger.info("Analysis complete! Moving framework ran in %.2f seconds" % (time.time() - start_time))
 
 
+CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere")
+
+
+def refuse_choose_options(args):
+    """What goes with -c only, and what a -c run does not do, said before anything is created."""
+    given = ["--" + o.replace("_", "-") for o in CHOOSE_OPTIONS if getattr(args, o) is not None]
+    if given and not args.choose:
+        raise SystemExit(f"{', '.join(given)} go{'es' if len(given) == 1 else ''} with -c/--choose")
+    if not args.choose:
+        return
+    if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        stem = "".join(args.infile.split("/")[-1].split(".nc"))
+        raise SystemExit("-c/--choose follows the system on one GPU (a chain over the time steps): run -c once, then "
+                         f"-t --trackfile LEC_Results/{stem}_choose/{stem}_choose_track --gpus N for the sharded analysis of the track it wrote")
+    if args.choose_box is not None and min(args.choose_box) <= 0:
+        raise SystemExit("--choose-box LENGTH WIDTH must be positive")
+    if args.choose_search is not None and not args.choose_search > 0:
+        raise SystemExit("--choose-search must be > 0 degrees")
+    if args.choose_smooth is not None and args.choose_smooth < 0:
+        raise SystemExit("--choose-smooth must be >= 0 grid points")
+    if args.choose_domain is not None and not os.path.exists(args.choose_domain):
+        raise SystemExit(f"--choose-domain: {args.choose_domain} not found")
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
     args = create_arg_parser().parse_args(argv)
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    refuse_choose_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
     env_world = os.environ.get("WORLD_SIZE")
@@ -174,6 +216,14 @@ def main(argv=None):
     if args.shard is not None:
         app_logger.info(f"Time-sharded run: {args.shard.world} ranks (backend {args.shard.backend}), one GPU each; rank 0 writes the results")
     try:
+        if args.choose:
+            # phase A: the 850-hPa slices -> lec_follow -> the track file; from here on the run IS -t on that track
+            import copy
+            from lorenzcycletoolkit_amd.follow import write_choose_track
+            written = write_choose_track(args, results_subdirectory, app_logger, device=os.environ.get("LEC_DEVICE", "cuda:0"))
+            phases.mark("choose_track")
+            args = copy.copy(args)
+            args.track, args.choose, args.trackfile, args.choose_track = True, False, written, written
         opened, auto_chose = None, False
         if args.ingest == "device":
             args.device_ingest = True

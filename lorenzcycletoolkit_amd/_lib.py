@@ -42,7 +42,7 @@ def source_digest() -> str:
 
 EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_reduce", "lec_dropmask", "lec_ingest", "lec_track_diag",
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
-           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps"]
+           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow"]
 
 
 class Tuning(C.Structure):
@@ -112,6 +112,21 @@ class DiagArgs(C.Structure):
                 ("val_d", C.c_void_p), ("pos_d", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class FollowArgs(C.Structure):
+    """struct lec_follow_args (include/lec_hip.h)."""
+    _fields_ = [("u_d", C.c_void_p), ("v_d", C.c_void_p), ("hgt_d", C.c_void_p),
+                ("nt", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32), ("field", C.c_int32),
+                ("xcoef_d", C.c_void_p), ("ycoef_d", C.c_void_p), ("curv_d", C.c_void_p),
+                ("sense", C.c_int32), ("smooth_r", C.c_int32), ("sj", C.c_int32), ("si", C.c_int32),
+                ("jlo", C.c_int32), ("jhi", C.c_int32), ("ilo", C.c_int32), ("ihi", C.c_int32),
+                ("j_start", C.c_int32), ("i_start", C.c_int32),
+                ("pos_d", C.c_void_p), ("val_d", C.c_void_p), ("status_d", C.c_void_p), ("stream", C.c_void_p)]
+
+
+FOLLOW_ZETA, FOLLOW_HGT = 0, 1          # enum lec_follow_field
+FOLLOW_MIN, FOLLOW_MAX = 0, 1           # enum lec_follow_sense
+
+
 class DtdtArgs(C.Structure):
     """struct lec_dtdt_args (include/lec_hip.h)."""
     _fields_ = [("tm_d", C.c_void_p), ("t_d", C.c_void_p), ("tp_d", C.c_void_p), ("dtype", C.c_int32), ("n_steps", C.c_int32),
@@ -171,6 +186,8 @@ def load():
     lib.lec_ingest.argtypes = [C.POINTER(IngestArgs)]
     lib.lec_track_diag.restype = C.c_int
     lib.lec_track_diag.argtypes = [C.POINTER(DiagArgs)]
+    lib.lec_follow.restype = C.c_int
+    lib.lec_follow.argtypes = [C.POINTER(FollowArgs)]
     lib.lec_check_boxes.restype = C.c_int
     lib.lec_check_boxes.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_check_maps.restype = C.c_int

@@ -452,17 +452,19 @@ def process_data(data: LECDataset, args, variable_list_df: pd.DataFrame, app_log
 def domain_slices(lat: np.ndarray, lon: np.ndarray, args, track: Optional[pd.DataFrame] = None):
     """slice_domain (select_area.py:254-338) on sorted coordinates: (lat slice, lon slice).  Fixed -> nearest-point
     crop from the hard-coded inputs/box_limits; track -> label slice of the track extent +- (half the largest
-    box + one grid step).  ``track``: a track already read (one of a batch, batch.py) instead of ``args.trackfile``."""
+    box + one grid step).  ``track``: a track already read (one of a batch, batch.py) instead of ``args.trackfile``.
+    Choose -> the track branch on the track the GPU wrote (``args.choose_track``, follow.write_choose_track)."""
     from .tables import nearest_index
     if getattr(args, "fixed", False):
         w, e, s, n = read_box_limits("inputs/box_limits")
         iw, ie = nearest_index(lon, w), nearest_index(lon, e)
         js, jn = nearest_index(lat, s), nearest_index(lat, n)
         return slice(js, jn + 1), slice(iw, ie + 1)
-    if getattr(args, "track", False) or track is not None:
+    chosen = getattr(args, "choose_track", None) if getattr(args, "choose", False) else None
+    if getattr(args, "track", False) or track is not None or chosen:
         dx, dy = lon[1] - lon[0], lat[1] - lat[0]
         if track is None:
-            track = read_track(args.trackfile or "inputs/track")
+            track = read_track(chosen or args.trackfile or "inputs/track")
         if "width" in track.columns:
             mw, ml = track["width"].max(), track["length"].max()
         else:
@@ -474,7 +476,8 @@ def domain_slices(lat: np.ndarray, lon: np.ndarray, args, track: Optional[pd.Dat
         if ii.size < 2 or jj.size < 2:
             raise ValueError("track extent selects fewer than 2 grid points of the data")
         return slice(jj[0], jj[-1] + 1), slice(ii[0], ii[-1] + 1)
-    raise NotImplementedError("the interactive -c/--choose domain selection needs a GUI and is out of scope")
+    raise ValueError("-c/--choose crops by the track the GPU writes first (follow.write_choose_track sets args.choose_track); "
+                     "the interactive map of the reference needs a GUI and is out of scope")
 
 
 def slice_domain(data: LECDataset, args, variable_list_df: pd.DataFrame) -> LECDataset:

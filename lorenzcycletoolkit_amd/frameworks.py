@@ -409,8 +409,10 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     differentiates T over the dataset's (track-selected) time axis on the device, which is what
     run_lec_analysis computes (lorenzcycletoolkit.py:184-186)."""
     app_logger.info("Computing energetics using moving framework (MI355X HIP engine)...")
-    if not getattr(args, "track", False):
-        raise NotImplementedError("only -t/--track is supported; -c/--choose needs an interactive map")
+    # -c/--choose is -t on the track the GPU wrote (follow.write_choose_track: args.choose_track names it)
+    trackfile = getattr(args, "choose_track", None) or (args.trackfile if getattr(args, "track", False) else None)
+    if not trackfile:
+        raise ValueError("the moving framework needs a track: -t --trackfile FILE, or -c, whose track follow.write_choose_track writes first")
     time_name = variable_list_df.loc["Time"]["Variable"]
     vert_name = variable_list_df.loc["Vertical Level"]["Variable"]
     shard = getattr(args, "shard", None)
@@ -418,7 +420,7 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     times = pd.DatetimeIndex(data.time)
-    track = ds.read_track(args.trackfile, app_logger)
+    track = ds.read_track(trackfile, app_logger)
     # handle_track_file (lec_moving_framework.py:58-160)
     if track.index[0] < times.min() or track.index[-1] > times.max():
         raise ValueError("Track time limits do not match with data time limits.")
@@ -457,7 +459,7 @@ def _write_moving_results(box_obj, times, time_s, limits, positions, results_sub
     for col in full:
         if col not in df.columns:
             df[col] = full[col]
-    method = "track"
+    method = "choose" if getattr(args, "choose_track", None) else "track"       # (-c: the same files under the chooser's names)
     infile_name = os.path.basename(args.infile).split(".nc")[0]
     results_file = os.path.join(results_subdirectory, f"{infile_name}_{method}_results.csv")
     df.to_csv(results_file)
