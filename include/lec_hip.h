@@ -348,6 +348,81 @@ typedef struct lec_follow_args {
     void* stream;
 } lec_follow_args;
 
+/*
+ * -c/--choose for SEVERAL systems in one run (additive calls: no struct of ABI 11 changes).
+ *
+ * lec_follow_seeds: the systems of the FIRST time step.  The rule:
+ *   S         lec_follow's S on that slice: the mean of the finite field values within smooth_r, summed in row-major order, NaN where
+ *             none is finite.  S is defined on the WHOLE slice, not only on the admissible centres.
+ *   better    smaller for LEC_FOLLOW_MIN, larger for LEC_FOLLOW_MAX.
+ *   candidate a grid point (j, i) for which all four hold:
+ *               - it is an admissible centre (jlo..jhi x ilo..ihi);
+ *               - S(j, i) is finite;
+ *               - S(j, i) is at least as good as `threshold` (a NaN threshold: no threshold);
+ *               - among the finite S(j', i') with |j' - j| <= ej, |i' - i| <= ei inside the slice none is better than S(j, i), and none
+ *                 that comes before (j, i) in the slice's row-major order is equal to it.
+ *             The last condition makes a plateau or a tie yield exactly one candidate, its first point.  The neighbourhood reaches
+ *             over inadmissible points on purpose: a system whose centre lies outside the admissible centres is not seeded by its flank.
+ *   seeds     the candidates ordered by value, best first, equal values by row-major index; the first k_max of them are taken, and
+ *             n_found may be smaller than k_max.  Seed 0 is usually what lec_follow picks at step 0 without a start; the rule does not
+ *             promise it (lec_follow's extremum need not be a candidate: a better value may lie outside the admissible centres).
+ * Three phases on the caller's stream: (a) S of the whole slice into work_d, one thread per point, lanes along longitude, through the
+ * function lec_follow's first step uses; (b) the candidate test, one thread per admissible centre, the neighbourhood read from work_d;
+ * (c) ONE workgroup takes the best remaining candidate k_max times (the wave64 shuffles and LDS partials of lec_follow's extremum; key:
+ * the value, then the row-major index).  The library owns no device memory: work_d is the caller's, and its contents after the call
+ * are unspecified.  Every scalar is validated before any HIP call, refused and never clamped (LEC_ERR_ARG names the field).
+ *
+ * lec_follow_many: n_chains chains of lec_follow in ONE launch, workgroup c walking chain c from start_d[c] through the very device
+ * function lec_follow's kernel runs: chain c IS lec_follow with that start -- the same positions, the same status, the same val bit
+ * for bit -- and no workgroup communicates with another, so a chain's bits do not depend on its company.  start_d lives in DEVICE
+ * memory (the output of lec_follow_seeds plugs straight in), where argument validation cannot see it, so the kernel checks its entry
+ * first: (-1, -1) keeps lec_follow's meaning (step 0 scans every admissible centre); any other entry outside the admissible centres,
+ * (-2, -2) included, makes the chain read nothing: status LEC_FOLLOW_BAD_START, pos -1 and val NaN at every step.  The LDS tile, its
+ * 160 KiB refusal and the validation of the scalars are lec_follow's.
+ */
+#define LEC_FOLLOW_BAD_START 2  /* status of a chain of lec_follow_many whose start_d entry is no admissible centre */
+
+typedef struct lec_follow_seeds_args {
+    const double* u_d;          /* [ny][nx] ONE slice: eastward wind at 850 hPa on the search domain */
+    const double* v_d;          /* [ny][nx] northward wind */
+    const double* hgt_d;        /* [ny][nx] geopotential height (gpm); may be NULL unless field = LEC_FOLLOW_HGT */
+    int32_t ny, nx;
+    int32_t field, sense;       /* enum lec_follow_field, enum lec_follow_sense */
+    const double* xcoef_d;      /* the vorticity tables of lec_diag_args */
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t smooth_r;           /* >= 0 */
+    int32_t ej, ei;             /* >= 1: half-extent of the neighbourhood (the least separation of two seeds), in grid points */
+    int32_t k_max;              /* 1..256 */
+    int32_t jlo, jhi, ilo, ihi; /* inclusive bounds of the admissible centres */
+    double threshold;           /* the field's own value and sign; NaN: none */
+    double* work_d;             /* [ny][nx] caller-owned scratch */
+    int32_t* seed_pos_d;        /* [k_max][2] (j, i), best first; unused entries (-2, -2) */
+    double* seed_val_d;         /* [k_max]    S at the seed; NaN where unused */
+    int32_t* n_found_d;         /* [1]        seeds found, 0..k_max */
+    void* stream;
+} lec_follow_seeds_args;
+
+typedef struct lec_follow_many_args {
+    const double* u_d;          /* [nt][ny][nx], as lec_follow_args */
+    const double* v_d;
+    const double* hgt_d;
+    int32_t nt, ny, nx;
+    int32_t field;
+    const double* xcoef_d;
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t sense, smooth_r, sj, si;
+    int32_t jlo, jhi, ilo, ihi;
+    int32_t n_chains;           /* >= 1 */
+    int32_t reserved0;
+    const int32_t* start_d;     /* [n_chains][2] DEVICE memory: (j, i) an admissible centre, or (-1, -1) */
+    int32_t* pos_d;             /* [n_chains][nt][2] */
+    double* val_d;              /* [n_chains][nt] */
+    int32_t* status_d;          /* [n_chains][nt]  0, 1 as lec_follow, or LEC_FOLLOW_BAD_START */
+    void* stream;
+} lec_follow_many_args;
+
 int lec_version(void);
 const char* lec_last_error(void);
 
@@ -383,6 +458,8 @@ int lec_dropmask(const lec_reduce_args* args);
 
 int lec_track_diag(const lec_diag_args* args);
 int lec_follow(const lec_follow_args* args);
+int lec_follow_seeds(const lec_follow_seeds_args* args);
+int lec_follow_many(const lec_follow_many_args* args);
 
 /*
  * What the library cannot see at launch: indices that live in DEVICE memory.  lec_rowstats validates every scalar argument, but a

@@ -11,6 +11,9 @@ map of the domain chooser, CDS-API downloads (--cdsapi).
 time step (``lec_follow``; --choose-start, --choose-box, --choose-search, --choose-smooth, --choose-field, --choose-hemisphere,
 --choose-domain), writes the boxes' centres as a track file to ``LEC_Results/<infile>_choose/<infile>_choose_track`` and then
 runs the moving framework on that track -- the very run ``-t --trackfile <that file>`` does, under the chooser's file names.
+With --choose-systems K (or --choose-starts FILE) it finds the K strongest systems of the first time step (``lec_follow_seeds``),
+follows them all in one launch (``lec_follow_many``), writes ``LEC_Results/<infile>_choose_batch/choose_s01``, ``choose_s02``, ... and
+is from there on ``-t --trackfiles <those files>``: one tree ``LEC_Results/<infile>_choose_sNN_track/`` per system.
 
 Several GPUs of one node: ``python lorenzcycletoolkit.py <file> -r -f --gpus N`` (this process starts N rank processes, one per
 GPU) or ``python -m torch.distributed.run --nproc-per-node N lorenzcycletoolkit.py <file> -r -f``.  The time steps are sharded
@@ -78,6 +81,15 @@ def create_arg_parser():
                         "--vorticity-form) or the geopotential height minimum")
     parser.add_argument("--choose-hemisphere", choices=["south", "north"], help="with -c and the vorticity: follow the minimum (south) or the maximum "
                         "(north); default: south when the search domain's southern edge lies south of the equator")
+    parser.add_argument("--choose-systems", type=int, metavar="K", help="with -c: find the (at most) K strongest systems of the first time step, follow "
+                        "them all at once and analyse every one as -t --trackfiles would: the tracks choose_s01, choose_s02, ..., systems.csv, the log "
+                        "and batch.csv go to LEC_Results/<infile>_choose_batch/, each system's results to LEC_Results/<infile>_choose_sNN_track/")
+    parser.add_argument("--choose-threshold", type=float, metavar="X", help="with --choose-systems: only systems at least as strong as X, in the field's "
+                        "own unit AND sign (1/s for zeta, gpm for hgt): the southern-hemisphere vorticity minimum wants a negative number, e.g. -5e-5")
+    parser.add_argument("--choose-separation", nargs=2, type=float, metavar=("LAT_DEG", "LON_DEG"), help="with --choose-systems: a system is the "
+                        "best value within this many degrees of latitude / longitude around it (default: half the box)")
+    parser.add_argument("--choose-starts", metavar="FILE", help="with -c: follow the systems that are, at the first time step, at the positions "
+                        "of this Lat;Lon file (one row per system) instead of finding them; otherwise as --choose-systems")
     parser.add_argument("--gpus", type=int, default=1, help="shard the time steps over this many GPUs of the node (one process per GPU, "
                         "results gathered over RCCL; same output files).  Under torch.distributed.run the launcher's WORLD_SIZE counts")
     parser.add_argument("-o", "--outname", type=str, help="name of the results CSV (fixed framework)")
@@ -154,7 +166,8 @@ def run_lec_analysis(data, args, results_subdirectory, figures_directory, result
         app_logger.info("Analysis complete! Moving framework ran in %.2f seconds" % (time.time() - start_time))
 
 
-CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere")
+CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere",
+                  "choose_systems", "choose_threshold", "choose_separation", "choose_starts")
 
 
 def refuse_choose_options(args):
@@ -164,6 +177,28 @@ def refuse_choose_options(args):
         raise SystemExit(f"{', '.join(given)} go{'es' if len(given) == 1 else ''} with -c/--choose")
     if not args.choose:
         return
+    many = args.choose_systems is not None or args.choose_starts is not None
+    if args.choose_systems is not None and args.choose_starts is not None:
+        raise SystemExit("--choose-systems finds the systems, --choose-starts names them: give one of the two")
+    if many and args.choose_start is not None:
+        raise SystemExit("--choose-start is the one system of a plain -c run: with --choose-systems / --choose-starts leave it out "
+                         "(--choose-starts FILE takes any number of starts)")
+    for o in ("choose_threshold", "choose_separation"):
+        if getattr(args, o) is not None and args.choose_systems is None:
+            raise SystemExit(f"--{o.replace('_', '-')} goes with --choose-systems")
+    if many and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        stem = "".join(args.infile.split("/")[-1].split(".nc"))
+        raise SystemExit("-c/--choose follows the systems on one GPU (chains over the time steps): run -c once, then "
+                         f"-t --trackfile LEC_Results/{stem}_choose_batch/choose_sNN --gpus N for the sharded analysis of a track it wrote")
+    if many and (args.ingest == "device" or args.device_ingest):
+        raise SystemExit("-c --choose-systems / --choose-starts prepares the data on the host: --ingest device / --device-ingest is not supported "
+                         "for a batch of tracks")
+    if args.choose_systems is not None and not 1 <= args.choose_systems <= 256:
+        raise SystemExit("--choose-systems must be 1..256")
+    if args.choose_separation is not None and min(args.choose_separation) <= 0:
+        raise SystemExit("--choose-separation LAT_DEG LON_DEG must be positive")
+    if args.choose_starts is not None and not os.path.exists(args.choose_starts):
+        raise SystemExit(f"--choose-starts: {args.choose_starts} not found")
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         stem = "".join(args.infile.split("/")[-1].split(".nc"))
         raise SystemExit("-c/--choose follows the system on one GPU (a chain over the time steps): run -c once, then "
@@ -178,14 +213,29 @@ def refuse_choose_options(args):
         raise SystemExit(f"--choose-domain: {args.choose_domain} not found")
 
 
+def _join_threshold(argv):
+    """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5``: argparse takes a negative number in exponent form for an option."""
+    out = list(argv)
+    for n in range(len(out) - 1):
+        if out[n] == "--choose-threshold":
+            try:
+                float(out[n + 1])
+            except ValueError:
+                continue
+            out[n: n + 2] = [f"--choose-threshold={out[n + 1]}", None]
+    return [x for x in out if x is not None]
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else list(argv)
-    args = create_arg_parser().parse_args(argv)
+    args = create_arg_parser().parse_args(_join_threshold(argv))
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     refuse_choose_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
+    if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
+        return main_choose_batch(args, argv)
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
         # this process only starts the ranks (before anything touches a GPU) and waits for them
@@ -301,17 +351,41 @@ def main_batch(args, argv):
     """-t --trackfiles: every track's tree as its own -t --trackfile run writes it, one pass over the data (lorenzcycletoolkit_amd/batch.py)."""
     from lorenzcycletoolkit_amd import batch
     refuse_batch_options(args)
+    return run_batch(args, argv, "_track_batch", "batch of tracks", lambda batch_dir, app_logger: batch.expand_trackfiles(args.trackfiles))
+
+
+def main_choose_batch(args, argv):
+    """-c --choose-systems K / --choose-starts FILE: the GPU finds (or is told) the systems of the first time step and follows them all in
+    one launch (follow.write_choose_tracks); from the written tracks on the run IS -t --trackfiles on them."""
+    import copy
+    from lorenzcycletoolkit_amd import batch
+
+    def tracks(batch_dir, app_logger):
+        from lorenzcycletoolkit_amd.follow import write_choose_tracks
+        written = write_choose_tracks(args, batch_dir, app_logger, device=os.environ.get("LEC_DEVICE", "cuda:0"))
+        phases.mark("choose_track")
+        return batch.expand_trackfiles(written)
+
+    args = copy.copy(args)
+    args.track, args.choose = True, False
+    return run_batch(args, argv, "_choose_batch", "several systems of -c", tracks)
+
+
+def run_batch(args, argv, suffix, what, trackfiles_of):
+    """The body of a run over many tracks: the log and batch.csv in LEC_Results/<stem><suffix>/, one tree per track.
+    ``trackfiles_of(batch_dir, app_logger)`` gives the track files once the log is open (it may write them first)."""
+    from lorenzcycletoolkit_amd import batch
     args.shard = None
     stem = "".join(args.infile.split("/")[-1].split(".nc"))
-    batch_dir = os.path.join("./LEC_Results/", stem + "_track_batch")
+    batch_dir = os.path.join("./LEC_Results/", stem + suffix)
     created = [] if os.path.isdir(batch_dir) else [batch_dir]
     os.makedirs(batch_dir, exist_ok=True)
     app_logger = initialize_logging(batch_dir, args)
-    app_logger.info("Starting LEC analysis (batch of tracks)")
+    app_logger.info(f"Starting LEC analysis ({what})")
     app_logger.info(f"Command line arguments: {args}")
     try:
         start_time = time.time()
-        trackfiles = batch.expand_trackfiles(args.trackfiles)
+        trackfiles = trackfiles_of(batch_dir, app_logger)
         variable_list_df = pd.read_csv("inputs/namelist", sep=";", index_col=0, header=0)
         data, plan = batch.prepare_union(args, trackfiles, "inputs/namelist", app_logger)
         phases.mark("open_decode_and_prepare")

@@ -42,7 +42,8 @@ def source_digest() -> str:
 
 EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_reduce", "lec_dropmask", "lec_ingest", "lec_track_diag",
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
-           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow"]
+           "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
+           "lec_follow_seeds", "lec_follow_many"]
 
 
 class Tuning(C.Structure):
@@ -125,6 +126,29 @@ class FollowArgs(C.Structure):
 
 FOLLOW_ZETA, FOLLOW_HGT = 0, 1          # enum lec_follow_field
 FOLLOW_MIN, FOLLOW_MAX = 0, 1           # enum lec_follow_sense
+FOLLOW_BAD_START = 2                    # LEC_FOLLOW_BAD_START: status of a chain of lec_follow_many whose start is no admissible centre
+
+
+class FollowSeedsArgs(C.Structure):
+    """struct lec_follow_seeds_args (include/lec_hip.h)."""
+    _fields_ = [("u_d", C.c_void_p), ("v_d", C.c_void_p), ("hgt_d", C.c_void_p),
+                ("ny", C.c_int32), ("nx", C.c_int32), ("field", C.c_int32), ("sense", C.c_int32),
+                ("xcoef_d", C.c_void_p), ("ycoef_d", C.c_void_p), ("curv_d", C.c_void_p),
+                ("smooth_r", C.c_int32), ("ej", C.c_int32), ("ei", C.c_int32), ("k_max", C.c_int32),
+                ("jlo", C.c_int32), ("jhi", C.c_int32), ("ilo", C.c_int32), ("ihi", C.c_int32),
+                ("threshold", C.c_double), ("work_d", C.c_void_p),
+                ("seed_pos_d", C.c_void_p), ("seed_val_d", C.c_void_p), ("n_found_d", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class FollowManyArgs(C.Structure):
+    """struct lec_follow_many_args (include/lec_hip.h)."""
+    _fields_ = [("u_d", C.c_void_p), ("v_d", C.c_void_p), ("hgt_d", C.c_void_p),
+                ("nt", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32), ("field", C.c_int32),
+                ("xcoef_d", C.c_void_p), ("ycoef_d", C.c_void_p), ("curv_d", C.c_void_p),
+                ("sense", C.c_int32), ("smooth_r", C.c_int32), ("sj", C.c_int32), ("si", C.c_int32),
+                ("jlo", C.c_int32), ("jhi", C.c_int32), ("ilo", C.c_int32), ("ihi", C.c_int32),
+                ("n_chains", C.c_int32), ("reserved0", C.c_int32), ("start_d", C.c_void_p),
+                ("pos_d", C.c_void_p), ("val_d", C.c_void_p), ("status_d", C.c_void_p), ("stream", C.c_void_p)]
 
 
 class DtdtArgs(C.Structure):
@@ -188,6 +212,10 @@ def load():
     lib.lec_track_diag.argtypes = [C.POINTER(DiagArgs)]
     lib.lec_follow.restype = C.c_int
     lib.lec_follow.argtypes = [C.POINTER(FollowArgs)]
+    lib.lec_follow_seeds.restype = C.c_int
+    lib.lec_follow_seeds.argtypes = [C.POINTER(FollowSeedsArgs)]
+    lib.lec_follow_many.restype = C.c_int
+    lib.lec_follow_many.argtypes = [C.POINTER(FollowManyArgs)]
     lib.lec_check_boxes.restype = C.c_int
     lib.lec_check_boxes.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_check_maps.restype = C.c_int

@@ -59,9 +59,24 @@ __device__ __forceinline__ Best reduce_best(Best b, bool want_max, double* sv, i
     return r;
 }
 
-// grid 1, block kThreads, dynamic LDS kLdsFixed + the tile
-__global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams p) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
+// S at one point straight from global memory: the mean of the finite field values within r, summed in row-major order.  False (and s
+// untouched) where none is finite.  ONE function for lec_follow's first step without a start and for lec_follow_seeds: the same doubles.
+__device__ __forceinline__ bool smooth_global(const FollowParams& p, const double* u, const double* v, const double* h, int j, int i, double& s) {
+    const int r = p.r;
+    double sum = 0.0; int cnt = 0;
+    for (int jj = max(j - r, 0); jj <= min(j + r, p.ny - 1); ++jj)
+        for (int ii = max(i - r, 0); ii <= min(i + r, p.nx - 1); ++ii) {
+            const double f = field_at(p, u, v, h, jj, ii);
+            if (finite(f)) { sum += f; ++cnt; }
+        }
+    if (cnt) s = sum / cnt;
+    return cnt != 0;
+}
+
+// One chain, walked by one workgroup of kThreads: lec_follow_kernel's only one, lec_follow_many_kernel's chain blockIdx.x.  Nothing in
+// here knows which: the same start gives the same positions, status and val bits in either kernel, whatever the other workgroups do.
+// pos [nt][2], val [nt], status [nt]: this chain's; smem: kLdsFixed + the tile.
+__device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int ic, int* pos, double* val, int* status, char* smem) {
     double* sv = (double*)smem;                     // [kWaves]
     int* sn = (int*)(smem + 8 * kWaves);            // [kWaves]
     double* tile = (double*)(smem + kLdsFixed);
@@ -70,7 +85,7 @@ __global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams
     const size_t plane = (size_t)p.ny * p.nx;
     const double inf = __builtin_huge_val();
     const int none = 0x7fffffff;
-    int jc = p.j_start, ic = p.i_start;             // the centre: the same in every thread, from the partials in LDS
+    // (jc, ic) the centre: the same in every thread, from the partials in LDS
     for (int t = 0; t < p.nt; ++t) {
         const double* u = p.u + t * plane;
         const double* v = p.v + t * plane;
@@ -83,14 +98,8 @@ __global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams
         if (whole) {
             // strided over all of A, the field straight from global memory (it happens once)
             for (int n = tid; n < npt; n += kThreads) {
-                const int j = j0 + n / nxw, i = i0 + n % nxw;
-                double sum = 0.0; int cnt = 0;
-                for (int jj = max(j - r, 0); jj <= min(j + r, p.ny - 1); ++jj)
-                    for (int ii = max(i - r, 0); ii <= min(i + r, p.nx - 1); ++ii) {
-                        const double f = field_at(p, u, v, h, jj, ii);
-                        if (finite(f)) { sum += f; ++cnt; }
-                    }
-                if (cnt) { const double s = sum / cnt; if (want_max) b.take_max(s, n); else b.take_min(s, n); }
+                double s;
+                if (smooth_global(p, u, v, h, j0 + n / nxw, i0 + n % nxw, s)) { if (want_max) b.take_max(s, n); else b.take_min(s, n); }
             }
         } else {
             // (a) the field on the window grown by r (clipped to the slice), coalesced along longitude
@@ -118,61 +127,267 @@ __global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams
         if (found) { jc = j0 + b.n / nxw; ic = i0 + b.n % nxw; }
         else if (whole) { jc = p.jlo; ic = p.ilo; }
         if (tid == 0) {
-            p.pos[2 * (size_t)t] = jc; p.pos[2 * (size_t)t + 1] = ic;
-            p.val[t] = found ? b.v : nan("");
-            p.status[t] = found ? 0 : 1;
+            pos[2 * (size_t)t] = jc; pos[2 * (size_t)t + 1] = ic;
+            val[t] = found ? b.v : nan("");
+            status[t] = found ? 0 : 1;
         }
     }
+}
+
+// grid 1, block kThreads, dynamic LDS kLdsFixed + the tile
+__global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams p) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    follow_chain(p, p.j_start, p.i_start, p.pos, p.val, p.status, smem);
+}
+
+// grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks chain c from start[c].  The table lives in device
+// memory, so the kernel checks its entry before it reads anything else: (-1, -1) is lec_follow's "no start", anything else outside
+// the admissible centres makes the chain LEC_FOLLOW_BAD_START at every step.  (p.j_start, p.i_start are not used.)
+__global__ void __launch_bounds__(kThreads) lec_follow_many_kernel(const FollowParams p, const int* __restrict__ start) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t c = blockIdx.x;
+    const int js = start[2 * c], is = start[2 * c + 1];
+    int* pos = p.pos + 2 * c * (size_t)p.nt;
+    double* val = p.val + c * (size_t)p.nt;
+    int* status = p.status + c * (size_t)p.nt;
+    const bool no_start = js == -1 && is == -1;
+    if (!no_start && (js < p.jlo || js > p.jhi || is < p.ilo || is > p.ihi)) {
+        for (int t = threadIdx.x; t < p.nt; t += kThreads) {
+            pos[2 * (size_t)t] = -1; pos[2 * (size_t)t + 1] = -1;
+            val[t] = nan("");
+            status[t] = LEC_FOLLOW_BAD_START;
+        }
+        return;
+    }
+    follow_chain(p, js, is, pos, val, status, smem);
+}
+
+// ---- lec_follow_seeds: the systems of ONE slice (the rule: include/lec_hip.h) ----------------------------------------------------
+struct SeedParams {
+    FollowParams f;             // one slice: nt = 1; the field, the tables, r, the admissible bounds
+    int ej, ei, k_max;
+    double threshold;           // NaN: none
+    double* work;               // [ny][nx]
+    int* seed_pos; double* seed_val; int* n_found;
+};
+
+// (a) S of the whole slice -> work; NaN where S is not finite.  One thread per point, row-major: the lanes run along longitude.
+__global__ void __launch_bounds__(kThreads) lec_seeds_smooth_kernel(const SeedParams q) {
+    const FollowParams& p = q.f;
+    const unsigned n = blockIdx.x * kThreads + threadIdx.x;          // (ny * nx < 2^31: no wrap)
+    if (n >= (unsigned)(p.ny * p.nx)) return;
+    double s;
+    const bool any = smooth_global(p, p.u, p.v, p.h, n / p.nx, n % p.nx, s);
+    q.work[n] = any && finite(s) ? s : nan("");
+}
+
+// (b) the candidate test, one thread per admissible centre, the neighbourhood from work.  A CANDIDATE overwrites its own S with the
+// sentinel "better than any finite value" (-inf for the minimum, +inf for the maximum); nothing else is written.  Other workgroups may
+// read that point before or after: it does not change their answer.  A point R that has the candidate P in its neighbourhood lies in
+// P's (the neighbourhood is symmetric), so S(R) is worse than S(P), or equal and later in row-major order: R fails its test on P's true
+// value and on the sentinel alike.  (Marking NON-candidates in place would not be safe: a point could lose the very neighbour that
+// disqualifies it.)  Every thread reads its own S before it may write it.  8-byte relaxed atomics: a reader sees the old or the new double.
+__global__ void __launch_bounds__(kThreads) lec_seeds_candidate_kernel(const SeedParams q) {
+    const FollowParams& p = q.f;
+    const int nxa = p.ihi - p.ilo + 1, na = nxa * (p.jhi - p.jlo + 1);
+    const unsigned n = blockIdx.x * kThreads + threadIdx.x;
+    if (n >= (unsigned)na) return;
+    const int j = p.jlo + n / nxa, i = p.ilo + n % nxa;
+    const bool want_max = p.sense == LEC_FOLLOW_MAX;
+    const double inf = __builtin_huge_val();
+    const double s = __hip_atomic_load(q.work + (size_t)j * p.nx + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (!finite(s)) return;
+    if (q.threshold == q.threshold && (want_max ? s < q.threshold : s > q.threshold)) return;
+    for (int jj = max(j - q.ej, 0); jj <= min(j + q.ej, p.ny - 1); ++jj) {
+        const double* row = q.work + (size_t)jj * p.nx;
+        for (int ii = max(i - q.ei, 0); ii <= min(i + q.ei, p.nx - 1); ++ii) {
+            const double o = __hip_atomic_load(row + ii, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (o != o || (jj == j && ii == i)) continue;
+            const bool before = jj < j || (jj == j && ii < i);
+            if (want_max ? (o > s || (o == s && before)) : (o < s || (o == s && before))) return;
+        }
+    }
+    __hip_atomic_store(q.work + (size_t)j * p.nx + i, want_max ? inf : -inf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// (c) ONE workgroup.  First the admissible centres of work become what the selection reads: a candidate gets its S back (smooth_global
+// again: the double of phase (a)), everything else NaN.  Then k_max times: the best remaining candidate -- key: the value, then the
+// slice's row-major index, through reduce_best -- is written out and struck by the thread that scans it.
+__global__ void __launch_bounds__(kThreads) lec_seeds_select_kernel(const SeedParams q) {
+    __shared__ double sv[kWaves];
+    __shared__ int sn[kWaves];
+    const FollowParams& p = q.f;
+    const int tid = threadIdx.x;
+    const int nxa = p.ihi - p.ilo + 1, na = nxa * (p.jhi - p.jlo + 1);
+    const bool want_max = p.sense == LEC_FOLLOW_MAX;
+    const double inf = __builtin_huge_val();
+    const int none = 0x7fffffff;
+    for (int n = tid; n < na; n += kThreads) {
+        const int j = p.jlo + n / nxa, i = p.ilo + n % nxa;
+        double* w = q.work + (size_t)j * p.nx + i;
+        double s = nan("");
+        if (*w == (want_max ? inf : -inf)) smooth_global(p, p.u, p.v, p.h, j, i, s);
+        *w = s;
+    }
+    int found = 0;
+    for (int k = 0; k < q.k_max; ++k) {
+        Best b{want_max ? -inf : inf, none};
+        for (int n = tid; n < na; n += kThreads) {          // (each thread re-reads the points it wrote itself: no fence needed)
+            const int m = (p.jlo + n / nxa) * p.nx + p.ilo + n % nxa;
+            const double s = q.work[m];
+            if (s == s) { if (want_max) b.take_max(s, m); else b.take_min(s, m); }
+        }
+        b = reduce_best(b, want_max, sv, sn);
+        __syncthreads();                                    // the partials are read: the next round may overwrite them
+        if (b.n == none) break;                             // (the same in every thread)
+        const int j = b.n / p.nx, i = b.n % p.nx;
+        if (((j - p.jlo) * nxa + (i - p.ilo)) % kThreads == tid) q.work[b.n] = nan("");
+        if (tid == 0) { q.seed_pos[2 * k] = j; q.seed_pos[2 * k + 1] = i; q.seed_val[k] = b.v; }
+        ++found;
+    }
+    for (int k = found + tid; k < q.k_max; k += kThreads) { q.seed_pos[2 * k] = -2; q.seed_pos[2 * k + 1] = -2; q.seed_val[k] = nan(""); }
+    if (tid == 0) *q.n_found = found;
+}
+
+}  // namespace
+
+namespace {
+
+int refuse(int code, const char* who, const char* what) {
+    char msg[240];
+    snprintf(msg, sizeof msg, "%s: %s", who, what);
+    return lec_set_error(code, msg);
+}
+
+struct NamedPtr { const void* p; const char* name; };
+
+template <size_t N>
+int check_pointers(const char* who, const NamedPtr (&ptrs)[N]) {
+    for (const auto& q : ptrs)
+        if (!q.p) {
+            char msg[80];
+            snprintf(msg, sizeof msg, "null pointer argument %s", q.name);
+            return refuse(LEC_ERR_ARG, who, msg);
+        }
+    return LEC_OK;
+}
+
+// what the three calls share: the slice, the field and its sense, the smoothing radius, the admissible centres (nt = 1 for one slice)
+template <class A>
+int check_slice(const char* who, const A* a, int nt) {
+    if (nt < 1 || a->ny < 3 || a->nx < 3) return refuse(LEC_ERR_ARG, who, "needs nt >= 1 and at least 3 x 3 grid points (nt, ny, nx)");
+    if ((unsigned long long)a->ny * (unsigned long long)a->nx > 0x7fffffffULL) return refuse(LEC_ERR_UNSUPPORTED, who, "slice too large (ny * nx)");
+    if (a->field != LEC_FOLLOW_ZETA && a->field != LEC_FOLLOW_HGT) return refuse(LEC_ERR_ARG, who, "field must be LEC_FOLLOW_ZETA or LEC_FOLLOW_HGT");
+    if (a->sense != LEC_FOLLOW_MIN && a->sense != LEC_FOLLOW_MAX) return refuse(LEC_ERR_ARG, who, "sense must be LEC_FOLLOW_MIN or LEC_FOLLOW_MAX");
+    if (a->field == LEC_FOLLOW_HGT && !a->hgt_d) return refuse(LEC_ERR_ARG, who, "field LEC_FOLLOW_HGT needs hgt_d");
+    if (a->smooth_r < 0) return refuse(LEC_ERR_ARG, who, "smooth_r must be >= 0");
+    if (a->jlo < 0 || a->jlo > a->jhi || a->jhi >= a->ny) return refuse(LEC_ERR_ARG, who, "needs 0 <= jlo <= jhi < ny");
+    if (a->ilo < 0 || a->ilo > a->ihi || a->ihi >= a->nx) return refuse(LEC_ERR_ARG, who, "needs 0 <= ilo <= ihi < nx");
+    return LEC_OK;
+}
+
+// the chain's window: sj, si and the dynamic LDS of its tile (-> lds), refused beyond what one workgroup may declare
+template <class A>
+int check_window(const char* who, const A* a, long long* lds) {
+    if (a->sj < 1 || a->si < 1) return refuse(LEC_ERR_ARG, who, "sj and si must be >= 1");
+    // the tile never outgrows the slice: a search radius beyond the domain is a window of the whole of A
+    const long long th = (long long)a->ny < 2LL * a->sj + 1 + 2LL * a->smooth_r ? a->ny : 2LL * a->sj + 1 + 2LL * a->smooth_r;
+    const long long tw = (long long)a->nx < 2LL * a->si + 1 + 2LL * a->smooth_r ? a->nx : 2LL * a->si + 1 + 2LL * a->smooth_r;
+    *lds = kLdsFixed + 8 * th * tw;
+    if (*lds > kLdsLimit) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "the LDS tile of sj, si, smooth_r is %lld x %lld doubles = %lld bytes, the limit is %lld bytes",
+                 th, tw, 8 * th * tw, kLdsLimit - kLdsFixed);
+        return refuse(LEC_ERR_UNSUPPORTED, who, msg);
+    }
+    return LEC_OK;
+}
+
+template <class A>
+FollowParams slice_params(const A* a, int nt) {
+    FollowParams p{};
+    p.u = a->u_d; p.v = a->v_d; p.h = a->hgt_d; p.nt = nt; p.ny = a->ny; p.nx = a->nx;
+    p.xcoef = a->xcoef_d; p.ycoef = a->ycoef_d; p.curv = a->curv_d;
+    p.field = a->field; p.sense = a->sense; p.r = a->smooth_r;
+    p.jlo = a->jlo; p.jhi = a->jhi; p.ilo = a->ilo; p.ihi = a->ihi; p.j_start = -1; p.i_start = -1;
+    return p;
+}
+
+int launched(const char* who) {
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
+    return LEC_OK;
 }
 
 }  // namespace
 
 extern "C" int lec_follow(const lec_follow_args* a) {
-    if (!a) return lec_set_error(LEC_ERR_ARG, "lec_follow: null args");
-    const struct { const void* p; const char* name; } ptrs[] = {
-        {a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
-        {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}};
-    for (const auto& q : ptrs)
-        if (!q.p) {
-            char msg[80];
-            snprintf(msg, sizeof msg, "lec_follow: null pointer argument %s", q.name);
-            return lec_set_error(LEC_ERR_ARG, msg);
-        }
-    if (a->nt < 1 || a->ny < 3 || a->nx < 3) return lec_set_error(LEC_ERR_ARG, "lec_follow: needs nt >= 1 and at least 3 x 3 grid points (nt, ny, nx)");
-    if ((unsigned long long)a->ny * (unsigned long long)a->nx > 0x7fffffffULL) return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_follow: slice too large (ny * nx)");
-    if (a->field != LEC_FOLLOW_ZETA && a->field != LEC_FOLLOW_HGT) return lec_set_error(LEC_ERR_ARG, "lec_follow: field must be LEC_FOLLOW_ZETA or LEC_FOLLOW_HGT");
-    if (a->sense != LEC_FOLLOW_MIN && a->sense != LEC_FOLLOW_MAX) return lec_set_error(LEC_ERR_ARG, "lec_follow: sense must be LEC_FOLLOW_MIN or LEC_FOLLOW_MAX");
-    if (a->field == LEC_FOLLOW_HGT && !a->hgt_d) return lec_set_error(LEC_ERR_ARG, "lec_follow: field LEC_FOLLOW_HGT needs hgt_d");
-    if (a->smooth_r < 0) return lec_set_error(LEC_ERR_ARG, "lec_follow: smooth_r must be >= 0");
-    if (a->sj < 1 || a->si < 1) return lec_set_error(LEC_ERR_ARG, "lec_follow: sj and si must be >= 1");
-    if (a->jlo < 0 || a->jlo > a->jhi || a->jhi >= a->ny) return lec_set_error(LEC_ERR_ARG, "lec_follow: needs 0 <= jlo <= jhi < ny");
-    if (a->ilo < 0 || a->ilo > a->ihi || a->ihi >= a->nx) return lec_set_error(LEC_ERR_ARG, "lec_follow: needs 0 <= ilo <= ihi < nx");
+    const char* who = "lec_follow";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
+                             {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}};
+    if (int rc = check_pointers(who, ptrs)) return rc;
+    if (int rc = check_slice(who, a, a->nt)) return rc;
+    if (a->sj < 1 || a->si < 1) return refuse(LEC_ERR_ARG, who, "sj and si must be >= 1");
     const bool no_start = a->j_start == -1 && a->i_start == -1;
     if (!no_start && (a->j_start < a->jlo || a->j_start > a->jhi || a->i_start < a->ilo || a->i_start > a->ihi))
-        return lec_set_error(LEC_ERR_ARG, "lec_follow: j_start, i_start must be an admissible centre (jlo..jhi, ilo..ihi) or both -1");
-    // the tile never outgrows the slice: a search radius beyond the domain is a window of the whole of A
-    const long long th = (long long)a->ny < 2LL * a->sj + 1 + 2LL * a->smooth_r ? a->ny : 2LL * a->sj + 1 + 2LL * a->smooth_r;
-    const long long tw = (long long)a->nx < 2LL * a->si + 1 + 2LL * a->smooth_r ? a->nx : 2LL * a->si + 1 + 2LL * a->smooth_r;
-    const long long lds = kLdsFixed + 8 * th * tw;
-    if (lds > kLdsLimit) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "lec_follow: the LDS tile of sj, si, smooth_r is %lld x %lld doubles = %lld bytes, the limit is %lld bytes",
-                 th, tw, 8 * th * tw, kLdsLimit - kLdsFixed);
-        return lec_set_error(LEC_ERR_UNSUPPORTED, msg);
-    }
-    FollowParams p;
-    p.u = a->u_d; p.v = a->v_d; p.h = a->hgt_d; p.nt = a->nt; p.ny = a->ny; p.nx = a->nx;
-    p.xcoef = a->xcoef_d; p.ycoef = a->ycoef_d; p.curv = a->curv_d;
-    p.field = a->field; p.sense = a->sense; p.r = a->smooth_r; p.sj = a->sj; p.si = a->si;
-    p.jlo = a->jlo; p.jhi = a->jhi; p.ilo = a->ilo; p.ihi = a->ihi; p.j_start = a->j_start; p.i_start = a->i_start;
+        return refuse(LEC_ERR_ARG, who, "j_start, i_start must be an admissible centre (jlo..jhi, ilo..ihi) or both -1");
+    long long lds;
+    if (int rc = check_window(who, a, &lds)) return rc;
+    FollowParams p = slice_params(a, a->nt);
+    p.sj = a->sj; p.si = a->si; p.j_start = a->j_start; p.i_start = a->i_start;
     p.pos = a->pos_d; p.val = a->val_d; p.status = a->status_d;
     hipStream_t st = (hipStream_t)a->stream;
     if (lds > 48 * 1024) {
         const hipError_t e = hipFuncSetAttribute((const void*)lec_follow_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
+        if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
     }
     hipLaunchKernelGGL(lec_follow_kernel, dim3(1), dim3(kThreads), (size_t)lds, st, p);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
-    return LEC_OK;
+    return launched(who);
+}
+
+extern "C" int lec_follow_many(const lec_follow_many_args* a) {
+    const char* who = "lec_follow_many";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
+                             {a->start_d, "start_d"}, {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}};
+    if (int rc = check_pointers(who, ptrs)) return rc;
+    if (int rc = check_slice(who, a, a->nt)) return rc;
+    if (a->n_chains < 1) return refuse(LEC_ERR_ARG, who, "n_chains must be >= 1");
+    long long lds;
+    if (int rc = check_window(who, a, &lds)) return rc;
+    FollowParams p = slice_params(a, a->nt);
+    p.sj = a->sj; p.si = a->si;
+    p.pos = a->pos_d; p.val = a->val_d; p.status = a->status_d;
+    hipStream_t st = (hipStream_t)a->stream;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)lec_follow_many_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(lec_follow_many_kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d);
+    return launched(who);
+}
+
+extern "C" int lec_follow_seeds(const lec_follow_seeds_args* a) {
+    const char* who = "lec_follow_seeds";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
+                             {a->work_d, "work_d"}, {a->seed_pos_d, "seed_pos_d"}, {a->seed_val_d, "seed_val_d"}, {a->n_found_d, "n_found_d"}};
+    if (int rc = check_pointers(who, ptrs)) return rc;
+    if (int rc = check_slice(who, a, 1)) return rc;
+    if (a->ej < 1 || a->ei < 1) return refuse(LEC_ERR_ARG, who, "ej and ei must be >= 1");
+    if (a->k_max < 1 || a->k_max > 256) return refuse(LEC_ERR_ARG, who, "k_max must be 1..256");
+    SeedParams q{};
+    q.f = slice_params(a, 1);
+    // a neighbourhood that reaches beyond the slice is the slice: the same points, and j + ej cannot overflow
+    q.ej = a->ej < a->ny ? a->ej : a->ny; q.ei = a->ei < a->nx ? a->ei : a->nx; q.k_max = a->k_max;
+    if (q.f.r > (a->ny > a->nx ? a->ny : a->nx)) q.f.r = a->ny > a->nx ? a->ny : a->nx;      // likewise the smoothing radius
+    q.threshold = a->threshold;
+    q.work = a->work_d; q.seed_pos = a->seed_pos_d; q.seed_val = a->seed_val_d; q.n_found = a->n_found_d;
+    hipStream_t st = (hipStream_t)a->stream;
+    const long long n_all = (long long)a->ny * a->nx, n_adm = (long long)(a->jhi - a->jlo + 1) * (a->ihi - a->ilo + 1);
+    hipLaunchKernelGGL(lec_seeds_smooth_kernel, dim3((unsigned)((n_all + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
+    hipLaunchKernelGGL(lec_seeds_candidate_kernel, dim3((unsigned)((n_adm + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
+    hipLaunchKernelGGL(lec_seeds_select_kernel, dim3(1), dim3(kThreads), 0, st, q);
+    return launched(who);
 }

@@ -84,42 +84,20 @@ def follow_system(u850, v850, hgt850, lat, lon, *, length=DEFAULT_BOX[0], width=
     the window held no finite value and the centre was kept) as NumPy arrays.  Raises ValueError when the box does not fit into
     the domain (before any GPU work) and when the first step finds nothing."""
     import torch
-    lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
-    if smooth != int(smooth) or int(smooth) < 0:
-        raise ValueError(f"smooth must be a whole number of grid points >= 0, not {smooth!r}")
     if not search > 0:
         raise ValueError(f"search must be > 0 degrees, not {search!r}")
-    hemisphere, sense = sense_of(field, hemisphere, lat)
-    bounds = admissible(lat, lon, length, width)
-    sj, si = window_steps(lat, lon, search)
-    js, is_ = (-1, -1) if start is None else start_index(lat, lon, start, bounds)
-    if field == "hgt" and hgt850 is None:
-        raise ValueError("field 'hgt' needs the geopotential height slices")
-    xcoef, ycoef, curv = vorticity_tables(lat, lon, formulation)
-    lib = _lib.load()
-    dev = torch.device(device)
-    if dev.type != "cuda":
-        raise _lib.LecLibraryError("the system is followed on the GPU: there is no CPU path")
-    up = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))).to(device=dev, dtype=torch.float64).contiguous()
-    u, v = up(u850), up(v850)
-    h = None if hgt850 is None else up(hgt850)
-    if u.dim() != 3 or v.shape != u.shape or (h is not None and h.shape != u.shape):
-        raise ValueError("u, v and height must be [time, lat, lon] slices of one shape")
-    nt, ny, nx = (int(x) for x in u.shape)
-    if (ny, nx) != (lat.size, lon.size):
-        raise ValueError("slices and coordinates do not match")
-    xc_d, yc_d, cv_d = torch.as_tensor(xcoef).to(dev), torch.as_tensor(ycoef).to(dev), torch.as_tensor(curv).to(dev)
-    pos = torch.empty((nt, 2), dtype=torch.int32, device=dev)
-    val = torch.empty((nt,), dtype=torch.float64, device=dev)
-    status = torch.empty((nt,), dtype=torch.int32, device=dev)
+    s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    sj, si = window_steps(s.lat, s.lon, search)
+    js, is_ = (-1, -1) if start is None else start_index(s.lat, s.lon, start, s.bounds)
+    nt = int(s.u.shape[0])
+    pos = torch.empty((nt, 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((nt,), dtype=torch.float64, device=s.dev)
+    status = torch.empty((nt,), dtype=torch.int32, device=s.dev)
     ptr = lambda t: C.c_void_p(t.data_ptr())
-    args = _lib.FollowArgs(u_d=ptr(u), v_d=ptr(v), hgt_d=None if h is None else ptr(h), nt=nt, ny=ny, nx=nx,
-                           field=_lib.FOLLOW_HGT if field == "hgt" else _lib.FOLLOW_ZETA, xcoef_d=ptr(xc_d), ycoef_d=ptr(yc_d), curv_d=ptr(cv_d),
-                           sense=sense, smooth_r=int(smooth), sj=sj, si=si, jlo=bounds[0], jhi=bounds[1], ilo=bounds[2], ihi=bounds[3],
-                           j_start=js, i_start=is_, pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status),
-                           stream=C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        _lib.check(lib.lec_follow(C.byref(args)), "lec_follow")
+    args = _lib.FollowArgs(nt=nt, sj=sj, si=si, j_start=js, i_start=is_, pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status), **s.common())
+    with torch.cuda.device(s.dev):
+        _lib.check(s.lib.lec_follow(C.byref(args)), "lec_follow")
     pos, val, status = pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy()
     if status[0]:
         raise ValueError("the first time step's search window holds no finite value of the field: nothing to follow "
@@ -225,3 +203,216 @@ def write_choose_track(args, results_subdirectory, app_logger, varlist="inputs/n
                            "degrees beside the grid's coordinates; the analysis uses them as read, as a -t run on this file does")
     app_logger.info(f"-c/--choose: track written to {path} (a track file: -t --trackfile {path} repeats this run, --gpus N included)")
     return path
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# several systems in one run: lec_follow_seeds finds them at the first time step, lec_follow_many follows them in one launch
+# ---------------------------------------------------------------------------------------------------------------------------
+def separation_steps(lat, lon, sep_lat, sep_lon) -> tuple:
+    """(ej, ei): the half-extent of a seed's neighbourhood in grid points, max(1, floor(sep / median |spacing|)) per axis (as
+    ``window_steps``, with a separation of its own per axis)."""
+    return window_steps(lat, lon, sep_lat)[0], window_steps(lat, lon, sep_lon)[1]
+
+
+def read_starts(path) -> np.ndarray:
+    """[n][2] (lat, lon) from a ``Lat;Lon`` file (other columns are ignored), read with the track reader's parser (pandas' default,
+    ``dataset.read_track``): what ``write_track`` wrote comes back as a track's centres do."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"Starts file not found: {path}")
+    with open(path) as f:
+        first = f.readline().strip()
+    delim = ";" if ";" in first else ","
+    cols = [c.strip() for c in first.split(delim)]
+    missing = [c for c in ("Lat", "Lon") if c not in cols]
+    if missing:
+        raise ValueError(f"Starts file missing required columns: {missing}\nExpected: ['Lat', 'Lon']\nFound: {cols}")
+    table = pd.read_csv(path, delimiter=delim)
+    out = np.c_[table["Lat"].values.astype(np.float64), table["Lon"].values.astype(np.float64)]
+    if out.shape[0] < 1 or not np.all(np.isfinite(out)):
+        raise ValueError(f"Starts file {path}: needs at least one row, finite numbers only")
+    return out
+
+
+class _Slices:
+    """What lec_follow, lec_follow_seeds and lec_follow_many share: the checked options, the slices and the vorticity tables on the device."""
+
+    def __init__(self, u, v, h, lat, lon, ndim, *, length, width, smooth, field, hemisphere, formulation, device):
+        import torch
+        self.lat, self.lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
+        if smooth != int(smooth) or int(smooth) < 0:
+            raise ValueError(f"smooth must be a whole number of grid points >= 0, not {smooth!r}")
+        self.smooth, self.field = int(smooth), field
+        self.hemisphere, self.sense = sense_of(field, hemisphere, self.lat)
+        self.bounds = admissible(self.lat, self.lon, length, width)
+        if field == "hgt" and h is None:
+            raise ValueError("field 'hgt' needs the geopotential height slices")
+        tables = vorticity_tables(self.lat, self.lon, formulation)
+        self.lib = _lib.load()
+        self.dev = torch.device(device)
+        if self.dev.type != "cuda":
+            raise _lib.LecLibraryError("the system is followed on the GPU: there is no CPU path")
+        up = lambda a: (a if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))).to(device=self.dev, dtype=torch.float64).contiguous()
+        self.u, self.v = up(u), up(v)
+        self.h = None if h is None else up(h)
+        if self.u.dim() != ndim or self.v.shape != self.u.shape or (self.h is not None and self.h.shape != self.u.shape):
+            raise ValueError("u, v and height must be " + ("[time, lat, lon] slices" if ndim == 3 else "[lat, lon] slices") + " of one shape")
+        if tuple(self.u.shape[-2:]) != (self.lat.size, self.lon.size):
+            raise ValueError("slices and coordinates do not match")
+        self.tables = [torch.as_tensor(t).to(self.dev) for t in tables]
+
+    def common(self):
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        import torch
+        return dict(u_d=ptr(self.u), v_d=ptr(self.v), hgt_d=None if self.h is None else ptr(self.h), ny=self.lat.size, nx=self.lon.size,
+                    field=_lib.FOLLOW_HGT if self.field == "hgt" else _lib.FOLLOW_ZETA, xcoef_d=ptr(self.tables[0]), ycoef_d=ptr(self.tables[1]),
+                    curv_d=ptr(self.tables[2]), sense=self.sense, smooth_r=self.smooth, jlo=self.bounds[0], jhi=self.bounds[1],
+                    ilo=self.bounds[2], ihi=self.bounds[3], stream=C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream))
+
+
+def find_systems(u0, v0, h0, lat, lon, *, k, threshold=None, separation=None, length=DEFAULT_BOX[0], width=DEFAULT_BOX[1], smooth=0,
+                 field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0"):
+    """``lec_follow_seeds`` on ONE [lat, lon] slice (the first time step): (pos [n][2] grid indices, val [n]) of the at most ``k``
+    systems the rule of include/lec_hip.h finds, best first (n may be 0).  ``threshold``: in the field's own unit and sign, None: none.
+    ``separation``: (degrees of latitude, degrees of longitude) within which a system tolerates no better one; default: half the box."""
+    import torch
+    if k != int(k) or not 1 <= int(k) <= 256:
+        raise ValueError(f"k must be a whole number of systems, 1..256, not {k!r}")
+    sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
+    if len(sep) != 2 or not min(sep) > 0:
+        raise ValueError(f"separation must be two positive numbers of degrees (latitude, longitude), not {separation!r}")
+    s = _Slices(u0, v0, h0, lat, lon, 2, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    ej, ei = separation_steps(s.lat, s.lon, *sep)
+    work = torch.empty((s.lat.size, s.lon.size), dtype=torch.float64, device=s.dev)
+    pos = torch.empty((int(k), 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((int(k),), dtype=torch.float64, device=s.dev)
+    n = torch.empty((1,), dtype=torch.int32, device=s.dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    args = _lib.FollowSeedsArgs(ej=ej, ei=ei, k_max=int(k), threshold=float("nan") if threshold is None else float(threshold),
+                                work_d=ptr(work), seed_pos_d=ptr(pos), seed_val_d=ptr(val), n_found_d=ptr(n), **s.common())
+    with torch.cuda.device(s.dev):
+        _lib.check(s.lib.lec_follow_seeds(C.byref(args)), "lec_follow_seeds")
+    n = int(n.cpu().numpy()[0])
+    pos, val = pos.cpu().numpy(), val.cpu().numpy()
+    if not (np.all(pos[n:] == -2) and np.all(np.isnan(val[n:]))):
+        raise _lib.LecLibraryError("lec_follow_seeds: the unused entries are not marked")
+    return pos[:n], val[:n]
+
+
+def follow_systems(u850, v850, hgt850, lat, lon, *, starts=None, seeds=None, length=DEFAULT_BOX[0], width=DEFAULT_BOX[1],
+                   search=DEFAULT_SEARCH, smooth=0, field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0"):
+    """``lec_follow_many``: K chains over [time, lat, lon] slices in one launch -> (pos [K][nt][2], val [K][nt], status [K][nt]).
+    Exactly one of ``starts`` -- K entries, each (lat, lon) (through ``start_index``) or None (the extremum of the whole domain) --
+    and ``seeds`` -- [K][2] grid indices as ``find_systems`` returns them (a host array or a device tensor), handed to the kernel as
+    they are: an entry that is no admissible centre gives status ``FOLLOW_BAD_START`` at every step.  Chain c is ``follow_system``
+    from that start, bit for bit; unlike it, nothing is raised for a chain whose first step finds nothing (status[c, 0] = 1)."""
+    import torch
+    if (starts is None) == (seeds is None):
+        raise ValueError("follow_systems needs either starts or seeds")
+    if not search > 0:
+        raise ValueError(f"search must be > 0 degrees, not {search!r}")
+    s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    sj, si = window_steps(s.lat, s.lon, search)
+    if starts is not None:
+        seeds = np.array([(-1, -1) if st is None else start_index(s.lat, s.lon, st, s.bounds) for st in starts], dtype=np.int32).reshape(-1, 2)
+    start_d = (seeds if isinstance(seeds, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(seeds, dtype=np.int32))).to(device=s.dev, dtype=torch.int32).contiguous()
+    if start_d.dim() != 2 or start_d.shape[1] != 2 or start_d.shape[0] < 1:
+        raise ValueError("starts / seeds: needs at least one (j, i) pair")
+    K, nt = int(start_d.shape[0]), int(s.u.shape[0])
+    pos = torch.empty((K, nt, 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((K, nt), dtype=torch.float64, device=s.dev)
+    status = torch.empty((K, nt), dtype=torch.int32, device=s.dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    args = _lib.FollowManyArgs(nt=nt, sj=sj, si=si, n_chains=K, reserved0=0, start_d=ptr(start_d), pos_d=ptr(pos), val_d=ptr(val),
+                               status_d=ptr(status), **s.common())
+    with torch.cuda.device(s.dev):
+        _lib.check(s.lib.lec_follow_many(C.byref(args)), "lec_follow_many")
+    return pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy()
+
+
+def first_shared_centre(pos) -> list:
+    """For every chain of pos [K][nt][2]: None, or (the lowest-numbered earlier chain it ever shares a centre with, the first time step at
+    which it does).  Chains may converge on one system; that is reported, never resolved."""
+    out = []
+    for c in range(len(pos)):
+        hit = None
+        for b in range(c):
+            same = np.flatnonzero(np.all(pos[c] == pos[b], axis=1))
+            if same.size and (hit is None or same[0] < hit[1]):
+                hit = (b, int(same[0]))
+        out.append(hit)
+    return out
+
+
+def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", device="cuda:0") -> list:
+    """Phase A of a ``-c --choose-systems K`` / ``--choose-starts FILE`` run: the slices once, one upload, the seeds (``lec_follow_seeds``)
+    or the file's starts, ONE ``lec_follow_many`` launch -> ``<batch_dir>/choose_s01``, ``choose_s02``, ... (``write_track``) and
+    ``systems.csv``.  Returns the tracks' paths.  A chain whose first step finds nothing (or whose start is bad) is logged and left
+    out; none left: the error ``follow_system`` raises."""
+    import torch
+    length, width = (float(x) for x in (getattr(args, "choose_box", None) or DEFAULT_BOX))
+    search = float(getattr(args, "choose_search", None) or DEFAULT_SEARCH)
+    smooth = int(getattr(args, "choose_smooth", None) or 0)
+    field = getattr(args, "choose_field", None) or "zeta"
+    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
+    k, starts_file = getattr(args, "choose_systems", None), getattr(args, "choose_starts", None)
+    threshold, separation = getattr(args, "choose_threshold", None), getattr(args, "choose_separation", None)
+    u, v, hgt, lat, lon, time = search_domain_slices(args, varlist, app_logger)
+    hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
+    bounds = admissible(lat, lon, length, width)                      # (refused here, before the upload, if the box does not fit)
+    kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form, device=device)
+    what = f"the 850 hPa {'minima' if sense == _lib.FOLLOW_MIN else 'maxima'} of {field}"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.LecLibraryError("the systems are found and followed on the GPU: there is no CPU path")
+    u, v = (torch.as_tensor(a).to(dev) for a in (u, v))
+    hgt = torch.as_tensor(hgt).to(dev)
+    if starts_file is not None:
+        seed_ll = read_starts(starts_file)
+        seeds = np.array([start_index(lat, lon, st, bounds) for st in seed_ll], dtype=np.int32)
+        seed_val = np.full(len(seeds), np.nan)
+        app_logger.info(f"-c/--choose: {len(seeds)} starts from {starts_file}")
+    else:
+        sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
+        seeds, seed_val = find_systems(u[0], v[0], hgt[0], lat, lon, k=k, threshold=threshold, separation=sep, **kw)
+        ej, ei = separation_steps(lat, lon, *sep)
+        app_logger.info(f"-c/--choose: {len(seeds)} of at most {k} systems found at {pd.Timestamp(time[0])} (lec_follow_seeds: {what}, "
+                        f"no better value within {sep[0]} x {sep[1]} degrees = {ej} x {ei} grid steps"
+                        + ("" if threshold is None else f", threshold {threshold}") + ")")
+        if len(seeds) == 0:
+            raise ValueError("the first time step holds no system: nothing to follow (another --choose-threshold, --choose-separation or --choose-domain?)")
+    sj, si = window_steps(lat, lon, search)
+    app_logger.info(f"-c/--choose: following {what} ({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "")
+                    + f") on the GPU (lec_follow_many, {len(seeds)} chains in one launch): {len(time)} time steps, search domain lat {lat[0]}..{lat[-1]}, "
+                    f"lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), box {length} x {width} degrees (length x width), at most {search} degrees = "
+                    f"{sj} x {si} grid steps per time step, smoothing radius {smooth}")
+    pos, val, status = follow_systems(u, v, hgt, lat, lon, seeds=seeds, search=search, **kw)
+    shared = first_shared_centre(pos)
+    for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
+        if name.startswith("choose_s") and name[8:].isdigit():
+            os.remove(os.path.join(batch_dir, name))
+    rows, written = [], []
+    for c in range(len(seeds)):
+        name = f"choose_s{c + 1:02d}"
+        row = {"system": name, "lat": lat[seeds[c, 0]], "lon": lon[seeds[c, 1]], "value": seed_val[c], "trackfile": "",
+               "same_centre_as": "" if shared[c] is None else f"choose_s{shared[c][0] + 1:02d}",
+               "same_centre_from": "" if shared[c] is None else pd.Timestamp(time[shared[c][1]]).strftime("%Y-%m-%d-%H%M")}
+        rows.append(row)
+        if status[c, 0]:
+            app_logger.warning(f"-c/--choose: {name} (start {row['lat']}, {row['lon']}) is left out: " + ("its start is no admissible centre"
+                               if status[c, 0] == _lib.FOLLOW_BAD_START else "its first search window holds no finite value of the field"))
+            continue
+        for t in np.flatnonzero(status[c]):
+            app_logger.warning(f"-c/--choose: {name}: no finite value of {field} in the search window of {pd.Timestamp(time[t])}: the box stays where it was")
+        if shared[c] is not None:
+            app_logger.warning(f"-c/--choose: {name} sits on the same centre as {row['same_centre_as']} from {row['same_centre_from']} on: "
+                               "the chains have converged on one system (both are analysed)")
+        row["trackfile"] = write_track(os.path.join(batch_dir, name), time, lat[pos[c, :, 0]], lon[pos[c, :, 1]], length, width)
+        written.append(row["trackfile"])
+    if not written:
+        raise ValueError("the first time step's search window holds no finite value of the field: nothing to follow "
+                         "(another --choose-start or --choose-domain?)")
+    pd.DataFrame(rows).to_csv(os.path.join(batch_dir, "systems.csv"), index=False)
+    app_logger.info(f"-c/--choose: {len(written)} tracks written to {batch_dir} (track files: -t --trackfiles {' '.join(written)} repeats this run)")
+    return written

@@ -4,6 +4,12 @@ to ``lec_track_diag`` over the very windows it visited (one workgroup per step: 
 around the calls, median of ``--repeat`` after a warm-up; one JSON line.
 
     python tools/bench_follow.py [--steps 4096] [--out FILE]
+
+``--systems K [K ...]``: several systems in one run instead.  Same series, same window; per K one ``lec_follow_many`` launch of K chains
+(starts spread over the admissible centres) against K back-to-back ``lec_follow`` launches -- of the library ``--parent PATH`` names (a
+liblec_hip.so built from the parent commit, loaded beside this one; without it: this library's own ``lec_follow``) --, the chains
+compared bit for bit; ``lec_follow`` itself (one chain through the old entry) in both libraries, alternating; and ``lec_follow_seeds`` on
+one slice.  The values go under the key ``systems`` of ``--out`` (whatever else the file holds is kept).
 """
 import argparse
 import ctypes as C
@@ -21,6 +27,8 @@ def main():
     ap.add_argument("--steps", type=int, default=4096)
     ap.add_argument("--repeat", type=int, default=5)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--systems", type=int, nargs="+", metavar="K", default=None)
+    ap.add_argument("--parent", default=None, metavar="PATH")
     a = ap.parse_args()
     import torch
     from lorenzcycletoolkit_amd import _lib, diagnostics as dg, follow as fw
@@ -55,6 +63,9 @@ def main():
         return float(np.median(ms)), [round(x, 4) for x in ms]
 
     out = {"steps": nt, "slice": [ny, nx], "window": [2 * sj + 1, 2 * si + 1], "csrc_sha": _lib.source_digest()}
+    if a.systems:
+        return systems(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si, start=(js, is_),
+                                        sep=fw.separation_steps(lat, lon, fw.DEFAULT_BOX[0] / 2, fw.DEFAULT_BOX[1] / 2), nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
     for r in (0, 2):
         fa = _lib.FollowArgs(u_d=ptr(u), v_d=ptr(v), hgt_d=ptr(h), nt=nt, ny=ny, nx=nx, field=_lib.FOLLOW_ZETA, xcoef_d=ptr(xc), ycoef_d=ptr(yc),
                              curv_d=ptr(cv), sense=_lib.FOLLOW_MIN, smooth_r=r, sj=sj, si=si, jlo=bounds[0], jhi=bounds[1], ilo=bounds[2],
@@ -85,6 +96,76 @@ def main():
     if a.out:
         with open(a.out, "w") as f:
             f.write(line + "\n")
+
+
+def systems(a, lib, out, w, timed):
+    import torch
+    from lorenzcycletoolkit_amd import _lib
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    nt, dev, bounds = w["nt"], w["dev"], w["bounds"]
+    old = lib
+    if a.parent:
+        old = C.CDLL(a.parent)
+        old.lec_follow.restype, old.lec_follow.argtypes = C.c_int, [C.POINTER(_lib.FollowArgs)]
+    common = dict(u_d=ptr(w["u"]), v_d=ptr(w["v"]), hgt_d=ptr(w["h"]), ny=w["ny"], nx=w["nx"], field=_lib.FOLLOW_ZETA, xcoef_d=ptr(w["xc"]),
+                  ycoef_d=ptr(w["yc"]), curv_d=ptr(w["cv"]), sense=_lib.FOLLOW_MIN, smooth_r=0, jlo=bounds[0], jhi=bounds[1], ilo=bounds[2],
+                  ihi=bounds[3], stream=w["stream"])
+    kmax = max(a.systems)
+    rng = np.random.default_rng(2)
+    starts = np.c_[rng.integers(bounds[0], bounds[1] + 1, kmax), rng.integers(bounds[2], bounds[3] + 1, kmax)].astype(np.int32)
+    starts[0] = w["start"]                               # chain 0: the start of the tool's one-chain figures
+    start_d = torch.as_tensor(starts).to(dev)
+    pos = torch.empty((kmax, nt, 2), dtype=torch.int32, device=dev)
+    val = torch.empty((kmax, nt), dtype=torch.float64, device=dev)
+    status = torch.empty((kmax, nt), dtype=torch.int32, device=dev)
+    pos1, val1, status1 = torch.empty_like(pos), torch.empty_like(val), torch.empty_like(status)
+
+    def single(which, c):
+        fa = _lib.FollowArgs(nt=nt, sj=w["sj"], si=w["si"], j_start=int(starts[c, 0]), i_start=int(starts[c, 1]), pos_d=ptr(pos1[c]),
+                             val_d=ptr(val1[c]), status_d=ptr(status1[c]), **common)
+        rc = which.lec_follow(C.byref(fa))
+        if rc:
+            raise RuntimeError(f"lec_follow failed (code {rc})")
+
+    def singles(which, k):
+        for c in range(k):
+            single(which, c)
+
+    res = {"parent_library": bool(a.parent), "chains": {}}
+    # lec_follow itself, one chain through the old entry: the parent's kernel and this one's (the shared device function), alternating
+    for rep in range(2):
+        for name, which in (("parent", old), ("this", lib)):
+            med, all_ms = timed(lambda: single(which, 0))
+            res.setdefault(f"lec_follow_{name}_ms", []).append(round(med, 4))
+    for k in a.systems:
+        ma = _lib.FollowManyArgs(nt=nt, sj=w["sj"], si=w["si"], n_chains=k, reserved0=0, start_d=ptr(start_d), pos_d=ptr(pos), val_d=ptr(val),
+                                 status_d=ptr(status), **common)
+        med, all_ms = timed(lambda: _lib.check(lib.lec_follow_many(C.byref(ma)), "lec_follow_many"))
+        med1, all1 = timed(lambda: singles(old, k))
+        same = bool(torch.equal(pos[:k], pos1[:k]) and torch.equal(val[:k].view(torch.int64), val1[:k].view(torch.int64))
+                    and torch.equal(status[:k], status1[:k]))
+        res["chains"][str(k)] = {"lec_follow_many_ms": round(med, 4), "lec_follow_many_all_ms": all_ms, "lec_follow_back_to_back_ms": round(med1, 4),
+                                 "lec_follow_back_to_back_all_ms": all1, "same_bits": same}
+    # lec_follow_seeds on the first slice: no better value within half the default box
+    ej, ei = w["sep"]
+    work = torch.empty((w["ny"], w["nx"]), dtype=torch.float64, device=dev)
+    for k in (8, 256):
+        spos, sval, sn = torch.empty((k, 2), dtype=torch.int32, device=dev), torch.empty((k,), dtype=torch.float64, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
+        sa = _lib.FollowSeedsArgs(ej=ej, ei=ei, k_max=k, threshold=float("nan"), work_d=ptr(work), seed_pos_d=ptr(spos), seed_val_d=ptr(sval),
+                                  n_found_d=ptr(sn), **common)
+        med, all_ms = timed(lambda: _lib.check(lib.lec_follow_seeds(C.byref(sa)), "lec_follow_seeds"))
+        res[f"lec_follow_seeds_k{k}_ms"], res[f"lec_follow_seeds_k{k}_all_ms"] = round(med, 4), all_ms
+        res[f"lec_follow_seeds_k{k}_found"], res["lec_follow_seeds_neighbourhood"] = int(sn.cpu()[0]), [2 * ej + 1, 2 * ei + 1]
+    out["systems"] = res
+    print(json.dumps(out))
+    if a.out:
+        kept = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                kept = json.loads(f.read())
+        kept["systems"] = dict(res, csrc_sha=out["csrc_sha"])
+        with open(a.out, "w") as f:
+            f.write(json.dumps(kept) + "\n")
 
 
 if __name__ == "__main__":
