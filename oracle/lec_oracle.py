@@ -92,6 +92,20 @@ def select_nearest(coord: np.ndarray, value: float) -> int:
     return int(cand[-1])
 
 
+def _interp_wide(x: np.ndarray, xp: np.ndarray, fp: np.ndarray) -> np.ndarray:
+    """``np.interp(x, xp, fp, left=nan, right=nan)`` for np.longdouble values, which np.interp refuses to narrow to float64: its formula
+    slope * (x - xl) + yl between the neighbouring points of ascending ``xp``, evaluated in the values' own precision.  Only an
+    extended-precision evaluation of the oracle (tests/helpers.as_longdouble) comes here; float64 and float32 keep np.interp."""
+    x, xp = np.asarray(x, dtype=fp.dtype), np.asarray(xp, dtype=fp.dtype)
+    hi = np.clip(np.searchsorted(xp, x, side="right"), 1, max(len(xp) - 1, 1))
+    if len(xp) < 2:
+        return np.where(x == xp[0], fp[0], np.nan).astype(fp.dtype)
+    lo = hi - 1
+    out = (fp[hi] - fp[lo]) / (xp[hi] - xp[lo]) * (x - xp[lo]) + fp[lo]
+    out = np.where(x == xp[hi], fp[hi], out)            # np.interp returns the data point itself at a node
+    return np.where((x < xp[0]) | (x > xp[-1]), np.nan, out)
+
+
 def interpolate_and_drop_nan_levels(f: np.ndarray, p: np.ndarray):
     """``_handle_nans`` (energy_contents.py:190-208 and its three copies) for an array whose axis 1 is
     level ([time, level] or [time, level, lat]): linear interpolation along level across interior gaps
@@ -106,7 +120,7 @@ def interpolate_and_drop_nan_levels(f: np.ndarray, p: np.ndarray):
         row = rows[r]
         ok = ~np.isnan(row)
         if ok.any() and not ok.all():
-            filled = np.interp(p, p[ok], row[ok], left=np.nan, right=np.nan)
+            filled = _interp_wide(p, p[ok], row[ok]) if row.dtype.itemsize > 8 else np.interp(p, p[ok], row[ok], left=np.nan, right=np.nan)
             rows[r] = np.where(ok, row, filled)
     g = rows.reshape(g.shape)
     f = np.moveaxis(g, -1, 1)

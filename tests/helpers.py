@@ -39,6 +39,14 @@ def as_f64(dom: o.Domain) -> o.Domain:
                     dom.level, dom.time_s)
 
 
+def as_longdouble(dom: o.Domain) -> o.Domain:
+    """The same values and axes in np.longdouble: the oracle runs unchanged on it, and its rounding then lies far below float64's --
+    the reference the stage-2 seam tests compare with (tests/test_stage2_cases_cpu.py measures how far the fp64 oracle is from it)."""
+    c = lambda a: np.ascontiguousarray(np.asarray(a).astype(np.longdouble))
+    return o.Domain(c(dom.tair), c(dom.u), c(dom.v), c(dom.omega), c(dom.geopt), c(dom.lat), c(dom.lon),
+                    c(dom.level), c(dom.time_s))
+
+
 def scale_err(a, r):
     """max |a - r| relative to the scale of r; NaNs must sit at the same places (else inf)."""
     a = np.asarray(a, dtype=np.float64)
