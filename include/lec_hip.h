@@ -423,6 +423,79 @@ typedef struct lec_follow_many_args {
     void* stream;
 } lec_follow_many_args;
 
+/*
+ * -c --choose-lifecycle: systems that form after the first time step or end before the last (additive calls: no struct of ABI 11 changes).
+ *
+ * lec_follow_seeds_series: the seeds of EVERY time step of [nt][ny][nx] slices in one call.  Step t's outputs -- seed_pos_d[t],
+ * seed_val_d[t], n_found_d[t] -- are exactly what lec_follow_seeds gives on slice t: positions, order, n_found, the (-2, -2) / NaN marks
+ * and the value bits.  The three phases of lec_follow_seeds are batched over t through the same device functions: the smooth and the
+ * candidate kernel run over (point, step), the select kernel one workgroup per step; every index over the series has 64 bits and the grids
+ * are strided over, so no grid dimension bounds nt.  work_d is [nt][ny][nx], the caller's; the library owns no device memory.  Every
+ * scalar is validated before any HIP call, refused and never clamped (LEC_ERR_ARG names the field); a series whose nt * ny * nx does not
+ * leave the byte offsets room in 64 bits is LEC_ERR_UNSUPPORTED.
+ *
+ * lec_follow_spans: n_chains chains, each BORN at its own step and ENDED by a rule.  start_d [n_chains][3] = (t0, j, i).  The rule:
+ *   - The chain walks steps t0, t0+1, ... as lec_follow does on the sub-series starting at t0 with start (j, i).  The window, tie rule and
+ *     kept centre on a blind window are unchanged.
+ *   - A walked step is *good* when its status is 0 and its val is at least as good as end_threshold.  With a NaN threshold, status 0
+ *     alone makes it good.
+ *   - The chain *stops* after the first walked step that completes `patience` consecutive not-good steps, or at the end of the series.
+ *   - span = (first good step, last good step), or (-1, -1) when no walked step is good.
+ *   - Walked steps carry lec_follow's pos / val / status.
+ *   - Steps never walked (before t0, after the stop) carry pos -1, val NaN and the status LEC_FOLLOW_NOT_LIVE (3).
+ *   - The table lives where validation cannot see it.  An entry with t0 outside [0, nt) or (j, i) outside the admissible centres gives
+ *     LEC_FOLLOW_BAD_START at every step and span (-1, -1), and reads nothing else.  (-1, -1) as (j, i) is NOT accepted here, because a
+ *     born chain always has a start.
+ * One workgroup per chain through the device function lec_follow's kernel runs, no communication between workgroups; a stopped chain's
+ * workgroup returns at once: a short-lived system costs its own steps, not the series'.  The LDS tile, its 160 KiB refusal and the
+ * validation of the scalars are lec_follow_many's.
+ */
+#define LEC_FOLLOW_NOT_LIVE 3   /* status of a step a chain of lec_follow_spans never walked */
+
+typedef struct lec_follow_seeds_series_args {
+    const double* u_d;          /* [nt][ny][nx], as lec_follow_args */
+    const double* v_d;
+    const double* hgt_d;        /* may be NULL unless field = LEC_FOLLOW_HGT */
+    int32_t nt, ny, nx;
+    int32_t field;
+    const double* xcoef_d;
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t sense, smooth_r;
+    int32_t ej, ei;             /* >= 1, as lec_follow_seeds_args */
+    int32_t k_max;              /* 1..256 */
+    int32_t reserved0;
+    int32_t jlo, jhi, ilo, ihi;
+    double threshold;           /* NaN: none */
+    double* work_d;             /* [nt][ny][nx] caller-owned scratch */
+    int32_t* seed_pos_d;        /* [nt][k_max][2] */
+    double* seed_val_d;         /* [nt][k_max] */
+    int32_t* n_found_d;         /* [nt] */
+    void* stream;
+} lec_follow_seeds_series_args;
+
+typedef struct lec_follow_spans_args {
+    const double* u_d;          /* [nt][ny][nx], as lec_follow_many_args */
+    const double* v_d;
+    const double* hgt_d;
+    int32_t nt, ny, nx;
+    int32_t field;
+    const double* xcoef_d;
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t sense, smooth_r, sj, si;
+    int32_t jlo, jhi, ilo, ihi;
+    int32_t n_chains;           /* >= 1 */
+    int32_t patience;           /* >= 1 */
+    const int32_t* start_d;     /* [n_chains][3] DEVICE memory: (t0, j, i), 0 <= t0 < nt, (j, i) an admissible centre */
+    double end_threshold;       /* the field's own value and sign; NaN: none */
+    int32_t* pos_d;             /* [n_chains][nt][2] */
+    double* val_d;              /* [n_chains][nt] */
+    int32_t* status_d;          /* [n_chains][nt]  0, 1 as lec_follow, LEC_FOLLOW_BAD_START or LEC_FOLLOW_NOT_LIVE */
+    int32_t* span_d;            /* [n_chains][2]   (first good step, last good step) or (-1, -1) */
+    void* stream;
+} lec_follow_spans_args;
+
 int lec_version(void);
 const char* lec_last_error(void);
 
@@ -460,6 +533,8 @@ int lec_track_diag(const lec_diag_args* args);
 int lec_follow(const lec_follow_args* args);
 int lec_follow_seeds(const lec_follow_seeds_args* args);
 int lec_follow_many(const lec_follow_many_args* args);
+int lec_follow_seeds_series(const lec_follow_seeds_series_args* args);
+int lec_follow_spans(const lec_follow_spans_args* args);
 
 /*
  * What the library cannot see at launch: indices that live in DEVICE memory.  lec_rowstats validates every scalar argument, but a

@@ -14,6 +14,9 @@ runs the moving framework on that track -- the very run ``-t --trackfile <that f
 With --choose-systems K (or --choose-starts FILE) it finds the K strongest systems of the first time step (``lec_follow_seeds``),
 follows them all in one launch (``lec_follow_many``), writes ``LEC_Results/<infile>_choose_batch/choose_s01``, ``choose_s02``, ... and
 is from there on ``-t --trackfiles <those files>``: one tree ``LEC_Results/<infile>_choose_sNN_track/`` per system.
+With --choose-lifecycle (and --choose-threshold X) every time step is searched (``lec_follow_seeds_series``), a system is followed from
+the time step at which it forms until it has weakened (``lec_follow_spans``; --choose-end-threshold, --choose-patience,
+--choose-min-steps), and each track covers its system's own time steps.
 
 Several GPUs of one node: ``python lorenzcycletoolkit.py <file> -r -f --gpus N`` (this process starts N rank processes, one per
 GPU) or ``python -m torch.distributed.run --nproc-per-node N lorenzcycletoolkit.py <file> -r -f``.  The time steps are sharded
@@ -90,6 +93,17 @@ def create_arg_parser():
                         "best value within this many degrees of latitude / longitude around it (default: half the box)")
     parser.add_argument("--choose-starts", metavar="FILE", help="with -c: follow the systems that are, at the first time step, at the positions "
                         "of this Lat;Lon file (one row per system) instead of finding them; otherwise as --choose-systems")
+    parser.add_argument("--choose-lifecycle", action="store_true", default=None, help="with --choose-systems K and --choose-threshold X: systems may "
+                        "form after the first time step and end before the last.  Every time step is searched for (at most K) systems; one that no "
+                        "system of the step before explains is followed from its own time step on, until it has been weaker than "
+                        "--choose-end-threshold for --choose-patience time steps in a row.  Each track covers its system's own time steps; "
+                        "systems.csv has a row per system found")
+    parser.add_argument("--choose-end-threshold", type=float, metavar="X", help="with --choose-lifecycle: a followed system is alive while it is at "
+                        "least as strong as X (unit and sign as --choose-threshold, which is the default; X may be weaker than it, never stricter)")
+    parser.add_argument("--choose-patience", type=int, metavar="N", help="with --choose-lifecycle: a system ends after N time steps in a row below "
+                        "--choose-end-threshold (default: 2); its track ends at the last time step at which it was strong enough")
+    parser.add_argument("--choose-min-steps", type=int, metavar="N", help="with --choose-lifecycle: systems that live for fewer than N time steps "
+                        "are listed in systems.csv but not analysed (default and least value: 2)")
     parser.add_argument("--gpus", type=int, default=1, help="shard the time steps over this many GPUs of the node (one process per GPU, "
                         "results gathered over RCCL; same output files).  Under torch.distributed.run the launcher's WORLD_SIZE counts")
     parser.add_argument("-o", "--outname", type=str, help="name of the results CSV (fixed framework)")
@@ -167,7 +181,8 @@ def run_lec_analysis(data, args, results_subdirectory, figures_directory, result
 
 
 CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere",
-                  "choose_systems", "choose_threshold", "choose_separation", "choose_starts")
+                  "choose_systems", "choose_threshold", "choose_separation", "choose_starts", "choose_lifecycle", "choose_end_threshold",
+                  "choose_patience", "choose_min_steps")
 
 
 def refuse_choose_options(args):
@@ -186,6 +201,26 @@ def refuse_choose_options(args):
     for o in ("choose_threshold", "choose_separation"):
         if getattr(args, o) is not None and args.choose_systems is None:
             raise SystemExit(f"--{o.replace('_', '-')} goes with --choose-systems")
+    for o in ("choose_end_threshold", "choose_patience", "choose_min_steps"):
+        if getattr(args, o) is not None and not args.choose_lifecycle:
+            raise SystemExit(f"--{o.replace('_', '-')} goes with --choose-lifecycle")
+    if args.choose_lifecycle:
+        if args.choose_starts is not None:
+            raise SystemExit("--choose-lifecycle finds the systems of every time step itself: --choose-starts names those of the first, leave it out")
+        if args.choose_systems is None or args.choose_threshold is None:
+            raise SystemExit("--choose-lifecycle needs --choose-systems K and --choose-threshold X: without a threshold every local extremum "
+                             "of every time step is a system")
+        if args.choose_patience is not None and args.choose_patience < 1:
+            raise SystemExit("--choose-patience must be >= 1 time steps")
+        if args.choose_min_steps is not None and args.choose_min_steps < 2:
+            raise SystemExit("--choose-min-steps must be >= 2: a track has at least two time steps")
+        # stricter than --choose-threshold?  Where the options alone say which way "stronger" points, said here; otherwise the data's
+        # hemisphere decides and follow.write_lifecycle_tracks refuses
+        smaller_is_stronger = True if args.choose_field == "hgt" else {None: None, "south": True, "north": False}[args.choose_hemisphere]
+        if args.choose_end_threshold is not None and smaller_is_stronger is not None and (
+                args.choose_end_threshold < args.choose_threshold if smaller_is_stronger else args.choose_end_threshold > args.choose_threshold):
+            raise SystemExit(f"--choose-end-threshold {args.choose_end_threshold} is stricter than --choose-threshold {args.choose_threshold}: "
+                             "it may be weaker, never stricter")
     if many and (args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         stem = "".join(args.infile.split("/")[-1].split(".nc"))
         raise SystemExit("-c/--choose follows the systems on one GPU (chains over the time steps): run -c once, then "
@@ -214,15 +249,16 @@ def refuse_choose_options(args):
 
 
 def _join_threshold(argv):
-    """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5``: argparse takes a negative number in exponent form for an option."""
+    """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5`` (``--choose-end-threshold`` likewise): argparse takes a negative
+    number in exponent form for an option."""
     out = list(argv)
     for n in range(len(out) - 1):
-        if out[n] == "--choose-threshold":
+        if out[n] in ("--choose-threshold", "--choose-end-threshold"):
             try:
                 float(out[n + 1])
             except ValueError:
                 continue
-            out[n: n + 2] = [f"--choose-threshold={out[n + 1]}", None]
+            out[n: n + 2] = [f"{out[n]}={out[n + 1]}", None]
     return [x for x in out if x is not None]
 
 

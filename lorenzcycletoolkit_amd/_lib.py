@@ -43,7 +43,7 @@ def source_digest() -> str:
 EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_reduce", "lec_dropmask", "lec_ingest", "lec_track_diag",
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
-           "lec_follow_seeds", "lec_follow_many"]
+           "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans"]
 
 
 class Tuning(C.Structure):
@@ -151,6 +151,32 @@ class FollowManyArgs(C.Structure):
                 ("pos_d", C.c_void_p), ("val_d", C.c_void_p), ("status_d", C.c_void_p), ("stream", C.c_void_p)]
 
 
+FOLLOW_NOT_LIVE = 3                     # LEC_FOLLOW_NOT_LIVE: status of a step a chain of lec_follow_spans never walked
+
+
+class FollowSeedsSeriesArgs(C.Structure):
+    """struct lec_follow_seeds_series_args (include/lec_hip.h)."""
+    _fields_ = [("u_d", C.c_void_p), ("v_d", C.c_void_p), ("hgt_d", C.c_void_p),
+                ("nt", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32), ("field", C.c_int32),
+                ("xcoef_d", C.c_void_p), ("ycoef_d", C.c_void_p), ("curv_d", C.c_void_p),
+                ("sense", C.c_int32), ("smooth_r", C.c_int32), ("ej", C.c_int32), ("ei", C.c_int32),
+                ("k_max", C.c_int32), ("reserved0", C.c_int32),
+                ("jlo", C.c_int32), ("jhi", C.c_int32), ("ilo", C.c_int32), ("ihi", C.c_int32),
+                ("threshold", C.c_double), ("work_d", C.c_void_p),
+                ("seed_pos_d", C.c_void_p), ("seed_val_d", C.c_void_p), ("n_found_d", C.c_void_p), ("stream", C.c_void_p)]
+
+
+class FollowSpansArgs(C.Structure):
+    """struct lec_follow_spans_args (include/lec_hip.h)."""
+    _fields_ = [("u_d", C.c_void_p), ("v_d", C.c_void_p), ("hgt_d", C.c_void_p),
+                ("nt", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32), ("field", C.c_int32),
+                ("xcoef_d", C.c_void_p), ("ycoef_d", C.c_void_p), ("curv_d", C.c_void_p),
+                ("sense", C.c_int32), ("smooth_r", C.c_int32), ("sj", C.c_int32), ("si", C.c_int32),
+                ("jlo", C.c_int32), ("jhi", C.c_int32), ("ilo", C.c_int32), ("ihi", C.c_int32),
+                ("n_chains", C.c_int32), ("patience", C.c_int32), ("start_d", C.c_void_p), ("end_threshold", C.c_double),
+                ("pos_d", C.c_void_p), ("val_d", C.c_void_p), ("status_d", C.c_void_p), ("span_d", C.c_void_p), ("stream", C.c_void_p)]
+
+
 class DtdtArgs(C.Structure):
     """struct lec_dtdt_args (include/lec_hip.h)."""
     _fields_ = [("tm_d", C.c_void_p), ("t_d", C.c_void_p), ("tp_d", C.c_void_p), ("dtype", C.c_int32), ("n_steps", C.c_int32),
@@ -216,6 +242,10 @@ def load():
     lib.lec_follow_seeds.argtypes = [C.POINTER(FollowSeedsArgs)]
     lib.lec_follow_many.restype = C.c_int
     lib.lec_follow_many.argtypes = [C.POINTER(FollowManyArgs)]
+    lib.lec_follow_seeds_series.restype = C.c_int
+    lib.lec_follow_seeds_series.argtypes = [C.POINTER(FollowSeedsSeriesArgs)]
+    lib.lec_follow_spans.restype = C.c_int
+    lib.lec_follow_spans.argtypes = [C.POINTER(FollowSpansArgs)]
     lib.lec_check_boxes.restype = C.c_int
     lib.lec_check_boxes.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_check_maps.restype = C.c_int

@@ -73,10 +73,26 @@ __device__ __forceinline__ bool smooth_global(const FollowParams& p, const doubl
     return cnt != 0;
 }
 
+// lec_follow_spans' rule for one chain (include/lec_hip.h): born at step t0, ended by end_threshold and patience, span [2] its output
+struct SpanRule { int t0; double end_threshold; int patience; int* span; };
+
+// steps [t_begin, t_end) of a chain that does not walk them, by the whole workgroup
+__device__ __forceinline__ void not_live(int* pos, double* val, int* status, int t_begin, int t_end) {
+    for (int t = t_begin + (int)threadIdx.x; t < t_end; t += kThreads) {
+        pos[2 * (size_t)t] = -1; pos[2 * (size_t)t + 1] = -1;
+        val[t] = nan("");
+        status[t] = LEC_FOLLOW_NOT_LIVE;
+    }
+}
+
 // One chain, walked by one workgroup of kThreads: lec_follow_kernel's only one, lec_follow_many_kernel's chain blockIdx.x.  Nothing in
 // here knows which: the same start gives the same positions, status and val bits in either kernel, whatever the other workgroups do.
 // pos [nt][2], val [nt], status [nt]: this chain's; smem: kLdsFixed + the tile.
-__device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int ic, int* pos, double* val, int* status, char* smem) {
+// kSpans (lec_follow_spans): the chain is born at step sp.t0 and ended by sp's rule (include/lec_hip.h); the steps it does not walk are
+// LEC_FOLLOW_NOT_LIVE, span [2] gets (first good step, last good step).  The walked steps are the very statements of the other two.
+template <bool kSpans>
+__device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int ic, int* pos, double* val, int* status, char* smem,
+                                             const SpanRule sp = SpanRule{}) {
     double* sv = (double*)smem;                     // [kWaves]
     int* sn = (int*)(smem + 8 * kWaves);            // [kWaves]
     double* tile = (double*)(smem + kLdsFixed);
@@ -85,12 +101,14 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
     const size_t plane = (size_t)p.ny * p.nx;
     const double inf = __builtin_huge_val();
     const int none = 0x7fffffff;
+    int first = -1, last = -1, weak = 0;            // (kSpans) the good steps so far, the not-good steps in a row
+    if (kSpans) not_live(pos, val, status, 0, sp.t0);
     // (jc, ic) the centre: the same in every thread, from the partials in LDS
-    for (int t = 0; t < p.nt; ++t) {
+    for (int t = kSpans ? sp.t0 : 0; t < p.nt; ++t) {
         const double* u = p.u + t * plane;
         const double* v = p.v + t * plane;
         const double* h = p.h ? p.h + t * plane : nullptr;
-        const bool whole = jc < 0;                  // step 0 without a start: every admissible centre
+        const bool whole = !kSpans && jc < 0;       // step 0 without a start: every admissible centre
         const int j0 = whole ? p.jlo : max(p.jlo, jc - p.sj), j1 = whole ? p.jhi : min(p.jhi, jc + p.sj);
         const int i0 = whole ? p.ilo : max(p.ilo, ic - p.si), i1 = whole ? p.ihi : min(p.ihi, ic + p.si);
         const int nxw = i1 - i0 + 1, npt = nxw * (j1 - j0 + 1);
@@ -131,13 +149,20 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
             val[t] = found ? b.v : nan("");
             status[t] = found ? 0 : 1;
         }
+        if (kSpans) {
+            // b is reduce_best's result, which every thread holds: the exit is uniform and lies after the step's barriers
+            const bool good = found && (sp.end_threshold != sp.end_threshold || (want_max ? b.v >= sp.end_threshold : b.v <= sp.end_threshold));
+            if (good) { if (first < 0) first = t; last = t; weak = 0; }
+            else if (++weak == sp.patience) { not_live(pos, val, status, t + 1, p.nt); break; }
+        }
     }
+    if (kSpans && tid == 0) { sp.span[0] = first; sp.span[1] = last; }
 }
 
 // grid 1, block kThreads, dynamic LDS kLdsFixed + the tile
 __global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    follow_chain(p, p.j_start, p.i_start, p.pos, p.val, p.status, smem);
+    follow_chain<false>(p, p.j_start, p.i_start, p.pos, p.val, p.status, smem);
 }
 
 // grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks chain c from start[c].  The table lives in device
@@ -159,7 +184,29 @@ __global__ void __launch_bounds__(kThreads) lec_follow_many_kernel(const FollowP
         }
         return;
     }
-    follow_chain(p, js, is, pos, val, status, smem);
+    follow_chain<false>(p, js, is, pos, val, status, smem);
+}
+
+// grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks chain c from start[c] = (t0, j, i) until the rule
+// ends it, and returns.  The entry is checked before anything else is read; (-1, -1) is no start here.
+__global__ void __launch_bounds__(kThreads) lec_follow_spans_kernel(const FollowParams p, const int* __restrict__ start, double end_threshold,
+                                                                    int patience, int* __restrict__ span) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t c = blockIdx.x;
+    const int t0 = start[3 * c], js = start[3 * c + 1], is = start[3 * c + 2];
+    int* pos = p.pos + 2 * c * (size_t)p.nt;
+    double* val = p.val + c * (size_t)p.nt;
+    int* status = p.status + c * (size_t)p.nt;
+    if (t0 < 0 || t0 >= p.nt || js < p.jlo || js > p.jhi || is < p.ilo || is > p.ihi) {
+        for (int t = threadIdx.x; t < p.nt; t += kThreads) {
+            pos[2 * (size_t)t] = -1; pos[2 * (size_t)t + 1] = -1;
+            val[t] = nan("");
+            status[t] = LEC_FOLLOW_BAD_START;
+        }
+        if (threadIdx.x == 0) { span[2 * c] = -1; span[2 * c + 1] = -1; }
+        return;
+    }
+    follow_chain<true>(p, js, is, pos, val, status, smem, SpanRule{t0, end_threshold, patience, span + 2 * c});
 }
 
 // ---- lec_follow_seeds: the systems of ONE slice (the rule: include/lec_hip.h) ----------------------------------------------------
@@ -171,14 +218,21 @@ struct SeedParams {
     int* seed_pos; double* seed_val; int* n_found;
 };
 
+// The three phases as device functions of ONE slice's SeedParams: lec_follow_seeds' kernels run them on the slice, lec_follow_seeds_series'
+// on slice t of a series (at()), so that step t's seeds are lec_follow_seeds' on that slice by construction.
+
 // (a) S of the whole slice -> work; NaN where S is not finite.  One thread per point, row-major: the lanes run along longitude.
-__global__ void __launch_bounds__(kThreads) lec_seeds_smooth_kernel(const SeedParams q) {
+__device__ __forceinline__ void seeds_smooth(const SeedParams& q, unsigned n) {
     const FollowParams& p = q.f;
-    const unsigned n = blockIdx.x * kThreads + threadIdx.x;          // (ny * nx < 2^31: no wrap)
-    if (n >= (unsigned)(p.ny * p.nx)) return;
     double s;
     const bool any = smooth_global(p, p.u, p.v, p.h, n / p.nx, n % p.nx, s);
     q.work[n] = any && finite(s) ? s : nan("");
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_smooth_kernel(const SeedParams q) {
+    const unsigned n = blockIdx.x * kThreads + threadIdx.x;          // (ny * nx < 2^31: no wrap)
+    if (n >= (unsigned)(q.f.ny * q.f.nx)) return;
+    seeds_smooth(q, n);
 }
 
 // (b) the candidate test, one thread per admissible centre, the neighbourhood from work.  A CANDIDATE overwrites its own S with the
@@ -187,11 +241,9 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_smooth_kernel(const SeedPa
 // P's (the neighbourhood is symmetric), so S(R) is worse than S(P), or equal and later in row-major order: R fails its test on P's true
 // value and on the sentinel alike.  (Marking NON-candidates in place would not be safe: a point could lose the very neighbour that
 // disqualifies it.)  Every thread reads its own S before it may write it.  8-byte relaxed atomics: a reader sees the old or the new double.
-__global__ void __launch_bounds__(kThreads) lec_seeds_candidate_kernel(const SeedParams q) {
+__device__ __forceinline__ void seeds_candidate(const SeedParams& q, unsigned n) {
     const FollowParams& p = q.f;
-    const int nxa = p.ihi - p.ilo + 1, na = nxa * (p.jhi - p.jlo + 1);
-    const unsigned n = blockIdx.x * kThreads + threadIdx.x;
-    if (n >= (unsigned)na) return;
+    const int nxa = p.ihi - p.ilo + 1;
     const int j = p.jlo + n / nxa, i = p.ilo + n % nxa;
     const bool want_max = p.sense == LEC_FOLLOW_MAX;
     const double inf = __builtin_huge_val();
@@ -210,12 +262,17 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_candidate_kernel(const See
     __hip_atomic_store(q.work + (size_t)j * p.nx + i, want_max ? inf : -inf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+__global__ void __launch_bounds__(kThreads) lec_seeds_candidate_kernel(const SeedParams q) {
+    const int na = (q.f.ihi - q.f.ilo + 1) * (q.f.jhi - q.f.jlo + 1);
+    const unsigned n = blockIdx.x * kThreads + threadIdx.x;
+    if (n >= (unsigned)na) return;
+    seeds_candidate(q, n);
+}
+
 // (c) ONE workgroup.  First the admissible centres of work become what the selection reads: a candidate gets its S back (smooth_global
 // again: the double of phase (a)), everything else NaN.  Then k_max times: the best remaining candidate -- key: the value, then the
 // slice's row-major index, through reduce_best -- is written out and struck by the thread that scans it.
-__global__ void __launch_bounds__(kThreads) lec_seeds_select_kernel(const SeedParams q) {
-    __shared__ double sv[kWaves];
-    __shared__ int sn[kWaves];
+__device__ __forceinline__ void seeds_select(const SeedParams& q, double* sv, int* sn) {
     const FollowParams& p = q.f;
     const int tid = threadIdx.x;
     const int nxa = p.ihi - p.ilo + 1, na = nxa * (p.jhi - p.jlo + 1);
@@ -247,6 +304,49 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_select_kernel(const SeedPa
     }
     for (int k = found + tid; k < q.k_max; k += kThreads) { q.seed_pos[2 * k] = -2; q.seed_pos[2 * k + 1] = -2; q.seed_val[k] = nan(""); }
     if (tid == 0) *q.n_found = found;
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_select_kernel(const SeedParams q) {
+    __shared__ double sv[kWaves];
+    __shared__ int sn[kWaves];
+    seeds_select(q, sv, sn);
+}
+
+// ---- lec_follow_seeds_series: the three phases over (point, step); every index that runs over the series has 64 bits, and the grids are
+// capped and strided over, so that no grid dimension bounds nt --------------------------------------------------------------------------
+constexpr unsigned kSeriesGrid = 1u << 16;      // workgroups per launch at the most: each strides over the rest
+
+// q: slice 0 of the series; -> slice t
+__device__ __forceinline__ SeedParams at(const SeedParams& q, size_t t) {
+    SeedParams s = q;
+    const size_t off = t * ((size_t)q.f.ny * q.f.nx);
+    s.f.u += off; s.f.v += off;
+    if (s.f.h) s.f.h += off;
+    s.work += off;
+    s.seed_pos += 2 * t * (size_t)q.k_max; s.seed_val += t * (size_t)q.k_max; s.n_found += t;
+    return s;
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_smooth_kernel(const SeedParams q, int nt) {
+    const unsigned long long plane = (unsigned long long)q.f.ny * q.f.nx, total = plane * nt;
+    for (unsigned long long m = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; m < total; m += (unsigned long long)gridDim.x * kThreads)
+        seeds_smooth(at(q, m / plane), (unsigned)(m % plane));
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_candidate_kernel(const SeedParams q, int nt) {
+    const unsigned long long na = (unsigned long long)(q.f.ihi - q.f.ilo + 1) * (q.f.jhi - q.f.jlo + 1), total = na * nt;
+    for (unsigned long long m = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; m < total; m += (unsigned long long)gridDim.x * kThreads)
+        seeds_candidate(at(q, m / na), (unsigned)(m % na));
+}
+
+// one workgroup per step (strided).  t and its bound are the same in every thread of the workgroup: the barriers inside stay uniform.
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_select_kernel(const SeedParams q, int nt) {
+    __shared__ double sv[kWaves];
+    __shared__ int sn[kWaves];
+    for (long long t = blockIdx.x; t < nt; t += gridDim.x) {
+        seeds_select(at(q, (size_t)t), sv, sn);
+        __syncthreads();                                    // (the partials are free again before the next step's first round)
+    }
 }
 
 }  // namespace
@@ -368,13 +468,15 @@ extern "C" int lec_follow_many(const lec_follow_many_args* a) {
     return launched(who);
 }
 
-extern "C" int lec_follow_seeds(const lec_follow_seeds_args* a) {
-    const char* who = "lec_follow_seeds";
-    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+namespace {
+
+// what lec_follow_seeds and lec_follow_seeds_series share: the checks (nt = 1 for the one slice) and the kernels' parameters of slice 0
+template <class A>
+int seed_params(const char* who, const A* a, int nt, SeedParams* out) {
     const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
                              {a->work_d, "work_d"}, {a->seed_pos_d, "seed_pos_d"}, {a->seed_val_d, "seed_val_d"}, {a->n_found_d, "n_found_d"}};
     if (int rc = check_pointers(who, ptrs)) return rc;
-    if (int rc = check_slice(who, a, 1)) return rc;
+    if (int rc = check_slice(who, a, nt)) return rc;
     if (a->ej < 1 || a->ei < 1) return refuse(LEC_ERR_ARG, who, "ej and ei must be >= 1");
     if (a->k_max < 1 || a->k_max > 256) return refuse(LEC_ERR_ARG, who, "k_max must be 1..256");
     SeedParams q{};
@@ -384,10 +486,65 @@ extern "C" int lec_follow_seeds(const lec_follow_seeds_args* a) {
     if (q.f.r > (a->ny > a->nx ? a->ny : a->nx)) q.f.r = a->ny > a->nx ? a->ny : a->nx;      // likewise the smoothing radius
     q.threshold = a->threshold;
     q.work = a->work_d; q.seed_pos = a->seed_pos_d; q.seed_val = a->seed_val_d; q.n_found = a->n_found_d;
+    *out = q;
+    return LEC_OK;
+}
+
+}  // namespace
+
+extern "C" int lec_follow_seeds(const lec_follow_seeds_args* a) {
+    const char* who = "lec_follow_seeds";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    SeedParams q;
+    if (int rc = seed_params(who, a, 1, &q)) return rc;
     hipStream_t st = (hipStream_t)a->stream;
     const long long n_all = (long long)a->ny * a->nx, n_adm = (long long)(a->jhi - a->jlo + 1) * (a->ihi - a->ilo + 1);
     hipLaunchKernelGGL(lec_seeds_smooth_kernel, dim3((unsigned)((n_all + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
     hipLaunchKernelGGL(lec_seeds_candidate_kernel, dim3((unsigned)((n_adm + kThreads - 1) / kThreads)), dim3(kThreads), 0, st, q);
     hipLaunchKernelGGL(lec_seeds_select_kernel, dim3(1), dim3(kThreads), 0, st, q);
+    return launched(who);
+}
+
+extern "C" int lec_follow_seeds_series(const lec_follow_seeds_series_args* a) {
+    const char* who = "lec_follow_seeds_series";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    SeedParams q;
+    if (int rc = seed_params(who, a, a->nt, &q)) return rc;
+    // nt * ny * nx doubles: the byte offsets into the series must fit 64 bits with room to spare
+    const unsigned long long plane = (unsigned long long)a->ny * (unsigned long long)a->nx;
+    if ((unsigned long long)a->nt > (1ULL << 59) / plane) return refuse(LEC_ERR_UNSUPPORTED, who, "series too large (nt * ny * nx)");
+    hipStream_t st = (hipStream_t)a->stream;
+    const unsigned long long n_all = plane * (unsigned long long)a->nt;
+    const unsigned long long n_adm = (unsigned long long)(a->jhi - a->jlo + 1) * (unsigned long long)(a->ihi - a->ilo + 1) * (unsigned long long)a->nt;
+    const auto grid = [](unsigned long long items) {
+        const unsigned long long g = (items + kThreads - 1) / kThreads;
+        return dim3((unsigned)(g < kSeriesGrid ? g : kSeriesGrid));
+    };
+    hipLaunchKernelGGL(lec_seeds_series_smooth_kernel, grid(n_all), dim3(kThreads), 0, st, q, a->nt);
+    hipLaunchKernelGGL(lec_seeds_series_candidate_kernel, grid(n_adm), dim3(kThreads), 0, st, q, a->nt);
+    hipLaunchKernelGGL(lec_seeds_series_select_kernel, dim3((unsigned)((unsigned)a->nt < kSeriesGrid ? (unsigned)a->nt : kSeriesGrid)), dim3(kThreads), 0, st, q, a->nt);
+    return launched(who);
+}
+
+extern "C" int lec_follow_spans(const lec_follow_spans_args* a) {
+    const char* who = "lec_follow_spans";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
+                             {a->start_d, "start_d"}, {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}, {a->span_d, "span_d"}};
+    if (int rc = check_pointers(who, ptrs)) return rc;
+    if (int rc = check_slice(who, a, a->nt)) return rc;
+    if (a->n_chains < 1) return refuse(LEC_ERR_ARG, who, "n_chains must be >= 1");
+    if (a->patience < 1) return refuse(LEC_ERR_ARG, who, "patience must be >= 1");
+    long long lds;
+    if (int rc = check_window(who, a, &lds)) return rc;
+    FollowParams p = slice_params(a, a->nt);
+    p.sj = a->sj; p.si = a->si;
+    p.pos = a->pos_d; p.val = a->val_d; p.status = a->status_d;
+    hipStream_t st = (hipStream_t)a->stream;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)lec_follow_spans_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(lec_follow_spans_kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d, a->end_threshold, a->patience, a->span_d);
     return launched(who);
 }

@@ -349,8 +349,10 @@ def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", 
     """Phase A of a ``-c --choose-systems K`` / ``--choose-starts FILE`` run: the slices once, one upload, the seeds (``lec_follow_seeds``)
     or the file's starts, ONE ``lec_follow_many`` launch -> ``<batch_dir>/choose_s01``, ``choose_s02``, ... (``write_track``) and
     ``systems.csv``.  Returns the tracks' paths.  A chain whose first step finds nothing (or whose start is bad) is logged and left
-    out; none left: the error ``follow_system`` raises."""
+    out; none left: the error ``follow_system`` raises.  With ``--choose-lifecycle``: ``write_lifecycle_tracks``."""
     import torch
+    if getattr(args, "choose_lifecycle", False):
+        return write_lifecycle_tracks(args, batch_dir, app_logger, varlist, device)
     length, width = (float(x) for x in (getattr(args, "choose_box", None) or DEFAULT_BOX))
     search = float(getattr(args, "choose_search", None) or DEFAULT_SEARCH)
     smooth = int(getattr(args, "choose_smooth", None) or 0)
@@ -414,5 +416,229 @@ def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", 
         raise ValueError("the first time step's search window holds no finite value of the field: nothing to follow "
                          "(another --choose-start or --choose-domain?)")
     pd.DataFrame(rows).to_csv(os.path.join(batch_dir, "systems.csv"), index=False)
+    app_logger.info(f"-c/--choose: {len(written)} tracks written to {batch_dir} (track files: -t --trackfiles {' '.join(written)} repeats this run)")
+    return written
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# --choose-lifecycle: systems that form late or end early.  lec_follow_seeds_series seeds every time step, the seeds that no seed of
+# the step before explains are births, ONE lec_follow_spans launch walks every birth from its own step until the rule ends it
+# (include/lec_hip.h), and the bookkeeping in between -- nt x K ints -- is host NumPy.
+# ---------------------------------------------------------------------------------------------------------------------------
+MAX_BIRTHS = 256
+WORK_BYTES = 256 << 20                  # find_systems_series' default chunk keeps work_d within this
+DEFAULT_PATIENCE = 2
+DEFAULT_MIN_STEPS = 2                   # what batch.plan_batch accepts as a track
+
+
+def find_systems_series(u850, v850, hgt850, lat, lon, *, k, threshold=None, separation=None, length=DEFAULT_BOX[0], width=DEFAULT_BOX[1],
+                        smooth=0, field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0", chunk_steps=None):
+    """``lec_follow_seeds_series`` on [time, lat, lon] slices: (pos [nt][k][2], val [nt][k], n_found [nt]) -- step t's are ``find_systems``
+    on slice t, bit for bit, the unused entries (-2, -2) / NaN.  The library is called on chunks of ``chunk_steps`` steps, so that its
+    scratch stays bounded (default: as many steps as keep it within 256 MiB); the chunks are independent."""
+    import torch
+    if k != int(k) or not 1 <= int(k) <= 256:
+        raise ValueError(f"k must be a whole number of systems, 1..256, not {k!r}")
+    sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
+    if len(sep) != 2 or not min(sep) > 0:
+        raise ValueError(f"separation must be two positive numbers of degrees (latitude, longitude), not {separation!r}")
+    s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    ej, ei = separation_steps(s.lat, s.lon, *sep)
+    nt, k = int(s.u.shape[0]), int(k)
+    if chunk_steps is None:
+        chunk_steps = max(1, WORK_BYTES // (8 * s.lat.size * s.lon.size))
+    if chunk_steps != int(chunk_steps) or int(chunk_steps) < 1:
+        raise ValueError(f"chunk_steps must be a whole number of time steps >= 1, not {chunk_steps!r}")
+    chunk = min(int(chunk_steps), nt)
+    work = torch.empty((chunk, s.lat.size, s.lon.size), dtype=torch.float64, device=s.dev)
+    pos = torch.empty((nt, k, 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((nt, k), dtype=torch.float64, device=s.dev)
+    n = torch.empty((nt,), dtype=torch.int32, device=s.dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    common = s.common()
+    with torch.cuda.device(s.dev):
+        for t0 in range(0, nt, chunk):
+            t1 = min(t0 + chunk, nt)
+            part = dict(common, u_d=ptr(s.u[t0:t1]), v_d=ptr(s.v[t0:t1]), hgt_d=None if s.h is None else ptr(s.h[t0:t1]))
+            args = _lib.FollowSeedsSeriesArgs(nt=t1 - t0, ej=ej, ei=ei, k_max=k, reserved0=0,
+                                              threshold=float("nan") if threshold is None else float(threshold), work_d=ptr(work),
+                                              seed_pos_d=ptr(pos[t0:t1]), seed_val_d=ptr(val[t0:t1]), n_found_d=ptr(n[t0:t1]), **part)
+            _lib.check(s.lib.lec_follow_seeds_series(C.byref(args)), "lec_follow_seeds_series")
+    pos, val, n = pos.cpu().numpy(), val.cpu().numpy(), n.cpu().numpy()
+    used = np.arange(k)[None, :] < n[:, None]
+    if not (np.all((n >= 0) & (n <= k)) and np.all(pos[~used] == -2) and np.all(np.isnan(val[~used])) and np.all(pos[used] >= 0)):
+        raise _lib.LecLibraryError("lec_follow_seeds_series: the unused entries are not marked")
+    return pos, val, n
+
+
+def births(seed_pos, n_found, sj, si) -> np.ndarray:
+    """[n][4] (step, j, i, seed rank) of the seeds that are births, ordered by (step, seed rank): every seed of step 0, and a seed of
+    step t >= 1 unless some seed of step t - 1 lies within |dj| <= sj and |di| <= si of it (the largest move per step the chain has)."""
+    seed_pos, n_found = np.asarray(seed_pos), np.asarray(n_found)
+    out = []
+    for t in range(len(n_found)):
+        now = seed_pos[t, :n_found[t]].astype(np.int64)
+        before = seed_pos[t - 1, :n_found[t - 1]].astype(np.int64) if t else now[:0]
+        for rank, (j, i) in enumerate(now):
+            if not np.any((np.abs(before[:, 0] - j) <= sj) & (np.abs(before[:, 1] - i) <= si)):
+                out.append((t, int(j), int(i), rank))
+    return np.array(out, dtype=np.int32).reshape(-1, 4)
+
+
+def follow_spans(u850, v850, hgt850, lat, lon, *, starts, end_threshold=None, patience=DEFAULT_PATIENCE, length=DEFAULT_BOX[0],
+                 width=DEFAULT_BOX[1], search=DEFAULT_SEARCH, smooth=0, field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0"):
+    """``lec_follow_spans``: one chain per row (t0, j, i) of ``starts`` (grid indices; a host array or a device tensor, handed to the
+    kernel as it is), all in one launch -> (pos [K][nt][2], val [K][nt], status [K][nt], span [K][2]).  The rule: include/lec_hip.h.
+    ``end_threshold``: in the field's own unit and sign, None: none."""
+    import torch
+    if not search > 0:
+        raise ValueError(f"search must be > 0 degrees, not {search!r}")
+    s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    sj, si = window_steps(s.lat, s.lon, search)
+    start_d = (starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(starts, dtype=np.int32))).to(device=s.dev, dtype=torch.int32).contiguous()
+    if start_d.dim() != 2 or start_d.shape[1] != 3 or start_d.shape[0] < 1:
+        raise ValueError("starts: needs at least one (t0, j, i) triple")
+    K, nt = int(start_d.shape[0]), int(s.u.shape[0])
+    pos = torch.empty((K, nt, 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((K, nt), dtype=torch.float64, device=s.dev)
+    status = torch.empty((K, nt), dtype=torch.int32, device=s.dev)
+    span = torch.empty((K, 2), dtype=torch.int32, device=s.dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    args = _lib.FollowSpansArgs(nt=nt, sj=sj, si=si, n_chains=K, patience=int(patience), start_d=ptr(start_d),
+                                end_threshold=float("nan") if end_threshold is None else float(end_threshold),
+                                pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status), span_d=ptr(span), **s.common())
+    with torch.cuda.device(s.dev):
+        _lib.check(s.lib.lec_follow_spans(C.byref(args)), "lec_follow_spans")
+    return pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy(), span.cpu().numpy()
+
+
+def resolve(starts, pos, span, ej, ei) -> tuple:
+    """(kept [K] bool, continuation_of [K]: a chain's number or -1), going through the chains in birth order.  A chain with span (-1, -1)
+    is dropped.  A chain c is a continuation of the FIRST kept chain b with span_b[0] <= t0_c <= span_b[1] whose centre at step t0_c lies
+    within (ej, ei) of c's start; a continuation is dropped.  (A system that dips under the threshold for a step is seeded again while its
+    chain still lives: this is where the second chain goes.)"""
+    starts, pos, span = np.asarray(starts), np.asarray(pos), np.asarray(span)
+    K = len(starts)
+    kept, cont = np.zeros(K, dtype=bool), np.full(K, -1, dtype=np.int64)
+    for c in range(K):
+        if span[c, 0] < 0:
+            continue
+        t0, j, i = (int(x) for x in starts[c, :3])
+        for b in np.flatnonzero(kept[:c]):
+            if span[b, 0] <= t0 <= span[b, 1] and abs(int(pos[b, t0, 0]) - j) <= ej and abs(int(pos[b, t0, 1]) - i) <= ei:
+                cont[c] = b
+                break
+        kept[c] = cont[c] < 0
+    return kept, cont
+
+
+def first_shared_centre_live(pos, span) -> list:
+    """``first_shared_centre`` for chains with a life of their own: only the steps inside BOTH chains' spans are compared."""
+    out = []
+    for c in range(len(pos)):
+        hit = None
+        for b in range(c):
+            lo, hi = max(span[c][0], span[b][0]), min(span[c][1], span[b][1])
+            if min(span[c][0], span[b][0]) < 0 or lo > hi:
+                continue
+            same = np.flatnonzero(np.all(pos[c][lo: hi + 1] == pos[b][lo: hi + 1], axis=1))
+            if same.size and (hit is None or lo + same[0] < hit[1]):
+                hit = (b, int(lo + same[0]))
+        out.append(hit)
+    return out
+
+
+def write_lifecycle_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", device="cuda:0") -> list:
+    """Phase A of a ``-c --choose-systems K --choose-lifecycle --choose-threshold X`` run: the slices once, one upload, the seeds of every
+    step (``find_systems_series``), the births, ONE ``lec_follow_spans`` launch, ``resolve`` -> a track per kept chain over its span
+    (``choose_sNN``, NN the birth's number) and ``systems.csv`` with a row per birth.  Returns the tracks' paths."""
+    import torch
+    length, width = (float(x) for x in (getattr(args, "choose_box", None) or DEFAULT_BOX))
+    search = float(getattr(args, "choose_search", None) or DEFAULT_SEARCH)
+    smooth = int(getattr(args, "choose_smooth", None) or 0)
+    field = getattr(args, "choose_field", None) or "zeta"
+    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
+    k, threshold, separation = args.choose_systems, float(args.choose_threshold), getattr(args, "choose_separation", None)
+    end_threshold = getattr(args, "choose_end_threshold", None)
+    end_threshold = threshold if end_threshold is None else float(end_threshold)
+    patience = getattr(args, "choose_patience", None) or DEFAULT_PATIENCE
+    min_steps = getattr(args, "choose_min_steps", None) or DEFAULT_MIN_STEPS
+    u, v, hgt, lat, lon, time = search_domain_slices(args, varlist, app_logger)
+    hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
+    if (end_threshold < threshold) if sense == _lib.FOLLOW_MIN else (end_threshold > threshold):
+        raise ValueError(f"--choose-end-threshold {end_threshold} is stricter than --choose-threshold {threshold}: it may be weaker, never stricter")
+    admissible(lat, lon, length, width)                               # (refused here, before the upload, if the box does not fit)
+    kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form, device=device)
+    what = f"the 850 hPa {'minima' if sense == _lib.FOLLOW_MIN else 'maxima'} of {field}"
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.LecLibraryError("the systems are found and followed on the GPU: there is no CPU path")
+    u, v = (torch.as_tensor(a).to(dev) for a in (u, v))
+    hgt = torch.as_tensor(hgt).to(dev)
+    sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
+    ej, ei = separation_steps(lat, lon, *sep)
+    sj, si = window_steps(lat, lon, search)
+    seed_pos, seed_val, n_found = find_systems_series(u, v, hgt, lat, lon, k=k, threshold=threshold, separation=sep, **kw)
+    born = births(seed_pos, n_found, sj, si)
+    app_logger.info(f"-c/--choose: {int(n_found.sum())} seeds in {len(time)} time steps, at most {k} per step (lec_follow_seeds_series: {what}, "
+                    f"no better value within {sep[0]} x {sep[1]} degrees = {ej} x {ei} grid steps, threshold {threshold}); {len(born)} of them are births "
+                    f"(no seed of the step before within {sj} x {si} grid steps)")
+    if len(born) == 0:
+        raise ValueError("no time step holds a system: nothing to follow (another --choose-threshold, --choose-separation or --choose-domain?)")
+    if len(born) > MAX_BIRTHS:
+        app_logger.warning(f"-c/--choose: {len(born)} births found, the first {MAX_BIRTHS} of them (by time step, then strength) are followed")
+        born = born[:MAX_BIRTHS]
+    app_logger.info(f"-c/--choose: following {what} ({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "")
+                    + f") on the GPU (lec_follow_spans, {len(born)} chains in one launch, each from its own time step): {len(time)} time steps, "
+                    f"search domain lat {lat[0]}..{lat[-1]}, lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), box {length} x {width} degrees "
+                    f"(length x width), at most {search} degrees = {sj} x {si} grid steps per time step, smoothing radius {smooth}; a chain ends after "
+                    f"{patience} time steps in a row weaker than {end_threshold}")
+    pos, val, status, span = follow_spans(u, v, hgt, lat, lon, starts=born[:, :3], end_threshold=end_threshold, patience=patience, search=search, **kw)
+    kept, cont = resolve(born, pos, span, ej, ei)
+    shared = first_shared_centre_live(pos, span)
+    for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
+        if name.startswith("choose_s") and name[8:].isdigit():
+            os.remove(os.path.join(batch_dir, name))
+    stamp = lambda t: pd.Timestamp(time[t]).strftime("%Y-%m-%d-%H%M")
+    rows, written = [], []
+    for c, (t0, j, i, rank) in enumerate(born):
+        name = f"choose_s{c + 1:02d}"
+        first, last = (int(x) for x in span[c])
+        row = {"system": name, "lat": lat[j], "lon": lon[i], "value": seed_val[t0, rank], "trackfile": "",
+               "same_centre_as": "" if shared[c] is None else f"choose_s{shared[c][0] + 1:02d}",
+               "same_centre_from": "" if shared[c] is None else stamp(shared[c][1]),
+               "first_time": "" if first < 0 else stamp(first), "last_time": "" if first < 0 else stamp(last),
+               "steps": 0 if first < 0 else last - first + 1, "ended": "" if first < 0 else ("end of series" if last == len(time) - 1 else "weak"),
+               "continuation_of": "" if cont[c] < 0 else f"choose_s{cont[c] + 1:02d}", "left_out": ""}
+        rows.append(row)
+        born_at = f"{name} (born {stamp(t0)} at {row['lat']}, {row['lon']})"
+        if first < 0:
+            row["left_out"] = "never good"
+            app_logger.warning(f"-c/--choose: {born_at} is left out: " + ("its start is no admissible centre" if status[c, t0] == _lib.FOLLOW_BAD_START
+                               else f"no time step of it is as strong as {end_threshold}"))
+            continue
+        if cont[c] >= 0:
+            row["left_out"] = "continuation"
+            app_logger.info(f"-c/--choose: {born_at} is left out: it continues {row['continuation_of']}, whose box is within {ej} x {ei} grid steps of it then")
+            continue
+        if row["steps"] < min_steps:
+            row["left_out"] = "too short"
+            app_logger.info(f"-c/--choose: {born_at} is left out: too short ({row['steps']} time step{'s' if row['steps'] != 1 else ''}, --choose-min-steps {min_steps})")
+            continue
+        for t in first + np.flatnonzero(status[c, first: last + 1] == 1):
+            app_logger.warning(f"-c/--choose: {name}: no finite value of {field} in the search window of {pd.Timestamp(time[t])}: the box stays where it was")
+        if shared[c] is not None:
+            app_logger.warning(f"-c/--choose: {name} sits on the same centre as {row['same_centre_as']} from {row['same_centre_from']} on: "
+                               "the chains have converged on one system (both are analysed)")
+        live = slice(first, last + 1)
+        row["trackfile"] = write_track(os.path.join(batch_dir, name), time[live], lat[pos[c, live, 0]], lon[pos[c, live, 1]], length, width)
+        written.append(row["trackfile"])
+        app_logger.info(f"-c/--choose: {name}: {row['first_time']} .. {row['last_time']} ({row['steps']} time steps), ended: {row['ended']}")
+    pd.DataFrame(rows).to_csv(os.path.join(batch_dir, "systems.csv"), index=False)
+    if not written:
+        raise ValueError(f"no system lives for {min_steps} time steps: nothing to analyse (another --choose-threshold, --choose-end-threshold, "
+                         "--choose-patience or --choose-min-steps?)")
     app_logger.info(f"-c/--choose: {len(written)} tracks written to {batch_dir} (track files: -t --trackfiles {' '.join(written)} repeats this run)")
     return written

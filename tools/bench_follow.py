@@ -10,6 +10,12 @@ around the calls, median of ``--repeat`` after a warm-up; one JSON line.
 liblec_hip.so built from the parent commit, loaded beside this one; without it: this library's own ``lec_follow``) --, the chains
 compared bit for bit; ``lec_follow`` itself (one chain through the old entry) in both libraries, alternating; and ``lec_follow_seeds`` on
 one slice.  The values go under the key ``systems`` of ``--out`` (whatever else the file holds is kept).
+
+``--lifecycle``: the two calls of ``-c --choose-lifecycle`` instead.  Same series; ONE ``lec_follow_seeds_series`` call over all steps
+against ``steps`` back-to-back ``lec_follow_seeds`` calls of the library ``--parent PATH`` names (without it: this library's own), the
+seeds compared bit for bit; and ONE ``lec_follow_spans`` launch of ``--chains`` chains with mixed lifetimes (births spread over the
+series, the end threshold at the 0.9 quantile of the values the chains meet, patience 2) against ``lec_follow_many`` walking the same starts
+through the whole series.  The values go under the key ``lifecycle`` of ``--out``.
 """
 import argparse
 import ctypes as C
@@ -29,6 +35,8 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--systems", type=int, nargs="+", metavar="K", default=None)
     ap.add_argument("--parent", default=None, metavar="PATH")
+    ap.add_argument("--lifecycle", action="store_true")
+    ap.add_argument("--chains", type=int, default=64, help="with --lifecycle: chains of the lec_follow_spans launch")
     a = ap.parse_args()
     import torch
     from lorenzcycletoolkit_amd import _lib, diagnostics as dg, follow as fw
@@ -63,6 +71,9 @@ def main():
         return float(np.median(ms)), [round(x, 4) for x in ms]
 
     out = {"steps": nt, "slice": [ny, nx], "window": [2 * sj + 1, 2 * si + 1], "csrc_sha": _lib.source_digest()}
+    if a.lifecycle:
+        return lifecycle(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si,
+                                          sep=fw.separation_steps(lat, lon, fw.DEFAULT_BOX[0] / 2, fw.DEFAULT_BOX[1] / 2), nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
     if a.systems:
         return systems(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si, start=(js, is_),
                                         sep=fw.separation_steps(lat, lon, fw.DEFAULT_BOX[0] / 2, fw.DEFAULT_BOX[1] / 2), nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
@@ -164,6 +175,72 @@ def systems(a, lib, out, w, timed):
             with open(a.out) as f:
                 kept = json.loads(f.read())
         kept["systems"] = dict(res, csrc_sha=out["csrc_sha"])
+        with open(a.out, "w") as f:
+            f.write(json.dumps(kept) + "\n")
+
+
+def lifecycle(a, lib, out, w, timed):
+    import torch
+    from lorenzcycletoolkit_amd import _lib
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    nt, ny, nx, dev, bounds = w["nt"], w["ny"], w["nx"], w["dev"], w["bounds"]
+    old = lib
+    if a.parent:
+        old = C.CDLL(a.parent)
+        old.lec_follow_seeds.restype, old.lec_follow_seeds.argtypes = C.c_int, [C.POINTER(_lib.FollowSeedsArgs)]
+    common = dict(ny=ny, nx=nx, field=_lib.FOLLOW_ZETA, xcoef_d=ptr(w["xc"]), ycoef_d=ptr(w["yc"]), curv_d=ptr(w["cv"]), sense=_lib.FOLLOW_MIN,
+                  smooth_r=0, jlo=bounds[0], jhi=bounds[1], ilo=bounds[2], ihi=bounds[3], stream=w["stream"])
+    series = dict(common, u_d=ptr(w["u"]), v_d=ptr(w["v"]), hgt_d=ptr(w["h"]))
+    res = {"parent_library": bool(a.parent)}
+    # the seeds of every step: one call, and the parent's one-slice call step by step
+    ej, ei = w["sep"]
+    k = 8
+    work = torch.empty((nt, ny, nx), dtype=torch.float64, device=dev)
+    spos, sval, sn = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((nt, k, 2), torch.int32), ((nt, k), torch.float64), ((nt,), torch.int32)))
+    spos1, sval1, sn1 = torch.empty_like(spos), torch.empty_like(sval), torch.empty_like(sn)
+    sa = _lib.FollowSeedsSeriesArgs(nt=nt, ej=ej, ei=ei, k_max=k, reserved0=0, threshold=float("nan"), work_d=ptr(work), seed_pos_d=ptr(spos),
+                                    seed_val_d=ptr(sval), n_found_d=ptr(sn), **series)
+    one = [_lib.FollowSeedsArgs(u_d=ptr(w["u"][t]), v_d=ptr(w["v"][t]), hgt_d=ptr(w["h"][t]), ej=ej, ei=ei, k_max=k, threshold=float("nan"),
+                                work_d=ptr(work), seed_pos_d=ptr(spos1[t]), seed_val_d=ptr(sval1[t]), n_found_d=ptr(sn1[t]), **common) for t in range(nt)]
+
+    def step_by_step():
+        for t in range(nt):
+            if old.lec_follow_seeds(C.byref(one[t])):
+                raise RuntimeError("lec_follow_seeds failed")
+
+    med1, all1 = timed(step_by_step)
+    med, all_ms = timed(lambda: _lib.check(lib.lec_follow_seeds_series(C.byref(sa)), "lec_follow_seeds_series"))
+    res["seeds"] = {"k": k, "neighbourhood": [2 * ej + 1, 2 * ei + 1], "lec_follow_seeds_series_ms": round(med, 4), "lec_follow_seeds_series_all_ms": all_ms,
+                    "lec_follow_seeds_back_to_back_ms": round(med1, 4), "lec_follow_seeds_back_to_back_all_ms": all1,
+                    "same_bits": bool(torch.equal(spos, spos1) and torch.equal(sval.view(torch.int64), sval1.view(torch.int64)) and torch.equal(sn, sn1))}
+    del work
+    # chains with mixed lifetimes: lec_follow_many walks every start through the whole series, lec_follow_spans from its birth to its end
+    K = a.chains
+    rng = np.random.default_rng(2)
+    t0 = np.sort(rng.integers(0, max(1, nt - 1), K))
+    t0[0] = 0
+    table = np.c_[t0, rng.integers(bounds[0], bounds[1] + 1, K), rng.integers(bounds[2], bounds[3] + 1, K)].astype(np.int32)
+    start3, start2 = torch.as_tensor(table).to(dev), torch.as_tensor(np.ascontiguousarray(table[:, 1:])).to(dev)
+    pos, val, status = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((K, nt, 2), torch.int32), ((K, nt), torch.float64), ((K, nt), torch.int32)))
+    span = torch.empty((K, 2), dtype=torch.int32, device=dev)
+    chain = dict(series, nt=nt, sj=w["sj"], si=w["si"], n_chains=K, pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status))
+    ma = _lib.FollowManyArgs(reserved0=0, start_d=ptr(start2), **chain)
+    med_many, all_many = timed(lambda: _lib.check(lib.lec_follow_many(C.byref(ma)), "lec_follow_many"))
+    threshold = float(torch.quantile(val.flatten(), 0.9).cpu())       # nine steps in ten are good: lifetimes from a few steps to hundreds
+    pa = _lib.FollowSpansArgs(patience=2, end_threshold=threshold, start_d=ptr(start3), span_d=ptr(span), **chain)
+    med, all_ms = timed(lambda: _lib.check(lib.lec_follow_spans(C.byref(pa)), "lec_follow_spans"))
+    walked = (status != _lib.FOLLOW_NOT_LIVE).sum(dim=1).cpu().numpy()
+    res["chains"] = {"n_chains": K, "end_threshold": threshold, "patience": 2, "lec_follow_spans_ms": round(med, 4), "lec_follow_spans_all_ms": all_ms,
+                     "lec_follow_many_whole_series_ms": round(med_many, 4), "lec_follow_many_whole_series_all_ms": all_many,
+                     "walked_steps_min_median_max": [int(walked.min()), float(np.median(walked)), int(walked.max())], "walked_steps_total": int(walked.sum())}
+    out["lifecycle"] = res
+    print(json.dumps(out))
+    if a.out:
+        kept = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                kept = json.loads(f.read())
+        kept["lifecycle"] = dict(res, steps=nt, csrc_sha=out["csrc_sha"])
         with open(a.out, "w") as f:
             f.write(json.dumps(kept) + "\n")
 
