@@ -496,6 +496,71 @@ typedef struct lec_follow_spans_args {
     void* stream;
 } lec_follow_spans_args;
 
+/*
+ * -c --choose-chunk: a series longer than memory (additive call: no struct of ABI 11 changes).
+ *
+ * lec_follow_spans_chunk: lec_follow_spans on ONE CHUNK of consecutive steps of a series, with chains that can be resumed.  What the
+ * fields mean in this call: nt counts the steps of THIS chunk and u_d / v_d / hgt_d hold only those steps; t_base is the series step that
+ * slice 0 of this call holds; start_d [n_chains][3] = (t0, j, i) with t0 a series step; pos_d / val_d / status_d are [n_chains][nt], for
+ * the chunk's steps; span_d [n_chains][2] is written on every call, in series steps, from the state as it stands after the chunk.
+ * state_d [n_chains][8] int32, device memory, read and written: the state of chain c is {phase, jc, ic, weak, first, last, 0, 0}.
+ *   - phase 0 = not yet born, 1 = walking, 2 = stopped, 3 = bad start.
+ *   - jc, ic = the centre after the last walked step.
+ *   - weak = the not-good steps in a row so far.
+ *   - first, last = the good steps so far, in series steps, -1 when none.
+ *   - The caller zeroes the state before the first chunk and passes it on unchanged from then on.  A chain table may grow between calls:
+ *     new rows are appended with zeroed state rows.
+ * The rule, per chain and call:
+ *   - Bad start.  If (j, i) is outside the admissible centres or t0 < 0, the chain is phase 3 in every call.  Every step gets
+ *     LEC_FOLLOW_BAD_START, pos -1, val NaN; span is (-1, -1).  Nothing else is read.  The kernel checks start_d first, as
+ *     lec_follow_many does.  The table is device memory the validation cannot see.
+ *   - Not yet born (phase 0).  If t_base <= t0 < t_base + nt, the chain is born in this chunk.  Local steps before t0 are
+ *     LEC_FOLLOW_NOT_LIVE, and it walks from t0 with start (j, i).  If t0 lies beyond the chunk, every step is LEC_FOLLOW_NOT_LIVE and
+ *     the phase stays 0.
+ *   - Walking (phase 1).  It walks from local step 0 with the centre and counters of the state.
+ *   - Stopped (phase 2).  Every step is LEC_FOLLOW_NOT_LIVE.
+ *   - A walked step is lec_follow_spans' walked step, statement for statement.  The same window around the previous centre, the same
+ *     tile, the same row-major mean, the same extremum and tie rule, the same kept centre on a blind window.  The same good / stop
+ *     decision with end_threshold and patience.  A chain that stops marks the rest of the chunk LEC_FOLLOW_NOT_LIVE, goes to phase 2,
+ *     and its workgroup returns.
+ *   - patience = 0 is accepted here and means "never stops".  It stays refused by lec_follow_spans.  This is how the resumed form of
+ *     lec_follow / lec_follow_many is obtained.
+ * The defining property: for ANY cut of a series into consecutive chunks, the chunk calls with the state carried through give the
+ * following, bit for bit.  With patience >= 1: concatenated pos / val / status and a final span_d equal to one lec_follow_spans call on
+ * the whole series.  With patience 0 and every t0 = 0: every pos / val / status of lec_follow_many from the same starts.
+ * What the property does not cover: a t0 at or beyond the end of the series is never born here (every step LEC_FOLLOW_NOT_LIVE), where
+ * lec_follow_spans, which sees the whole series, calls it a bad start; a chain appended after the chunk of its t0 has passed is never
+ * born either; a walking state whose centre is no admissible centre (one the caller did not pass on unchanged) reads nothing and counts
+ * as stopped.
+ * One workgroup of 256 per chain, no workgroup waits for another; the state is read and written by one thread with plain vector loads
+ * and stores.  The LDS tile and its 160 KiB refusal (the message gives both figures) are lec_follow_many's.  Scalars are validated
+ * before any HIP call, refused with LEC_ERR_ARG and never clamped: everything lec_follow_spans checks, t_base >= 0, nt >= 1,
+ * patience >= 0, state_d not null, and a t_base + nt that overflows int32.
+ */
+typedef struct lec_follow_chunk_args {
+    const double* u_d;          /* [nt][ny][nx]: the chunk's steps only */
+    const double* v_d;
+    const double* hgt_d;
+    int32_t nt, ny, nx;         /* nt: the steps of this chunk */
+    int32_t field;
+    const double* xcoef_d;
+    const double* ycoef_d;
+    const double* curv_d;
+    int32_t sense, smooth_r, sj, si;
+    int32_t jlo, jhi, ilo, ihi;
+    int32_t n_chains;           /* >= 1 */
+    int32_t patience;           /* >= 0; 0: never stops */
+    const int32_t* start_d;     /* [n_chains][3] DEVICE memory: (t0, j, i), t0 a series step >= 0, (j, i) an admissible centre */
+    double end_threshold;       /* the field's own value and sign; NaN: none */
+    int32_t* pos_d;             /* [n_chains][nt][2] */
+    double* val_d;              /* [n_chains][nt] */
+    int32_t* status_d;          /* [n_chains][nt]  0, 1 as lec_follow, LEC_FOLLOW_BAD_START or LEC_FOLLOW_NOT_LIVE */
+    int32_t* span_d;            /* [n_chains][2]   series steps, from the state after this chunk */
+    void* stream;
+    int32_t t_base;             /* >= 0: the series step that slice 0 of this call holds */
+    int32_t* state_d;           /* [n_chains][8] DEVICE memory, read and written; zeroed by the caller before the first chunk */
+} lec_follow_chunk_args;
+
 int lec_version(void);
 const char* lec_last_error(void);
 
@@ -535,6 +600,7 @@ int lec_follow_seeds(const lec_follow_seeds_args* args);
 int lec_follow_many(const lec_follow_many_args* args);
 int lec_follow_seeds_series(const lec_follow_seeds_series_args* args);
 int lec_follow_spans(const lec_follow_spans_args* args);
+int lec_follow_spans_chunk(const lec_follow_chunk_args* args);
 
 /*
  * What the library cannot see at launch: indices that live in DEVICE memory.  lec_rowstats validates every scalar argument, but a

@@ -84,6 +84,9 @@ def create_arg_parser():
                         "--vorticity-form) or the geopotential height minimum")
     parser.add_argument("--choose-hemisphere", choices=["south", "north"], help="with -c and the vorticity: follow the minimum (south) or the maximum "
                         "(north); default: south when the search domain's southern edge lies south of the equator")
+    parser.add_argument("--choose-chunk", type=int, metavar="N", help="with -c: hold the 850-hPa slices of N time steps at a time, in host memory and "
+                        "on the GPU (lec_follow_spans_chunk resumes every system from chunk to chunk); the tracks are those of the run without it.  "
+                        "Default: the whole series when its slices fit 2 GiB, otherwise the largest equal chunks that do")
     parser.add_argument("--choose-systems", type=int, metavar="K", help="with -c: find the (at most) K strongest systems of the first time step, follow "
                         "them all at once and analyse every one as -t --trackfiles would: the tracks choose_s01, choose_s02, ..., systems.csv, the log "
                         "and batch.csv go to LEC_Results/<infile>_choose_batch/, each system's results to LEC_Results/<infile>_choose_sNN_track/")
@@ -182,7 +185,7 @@ def run_lec_analysis(data, args, results_subdirectory, figures_directory, result
 
 CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere",
                   "choose_systems", "choose_threshold", "choose_separation", "choose_starts", "choose_lifecycle", "choose_end_threshold",
-                  "choose_patience", "choose_min_steps")
+                  "choose_patience", "choose_min_steps", "choose_chunk")
 
 
 def refuse_choose_options(args):
@@ -238,6 +241,8 @@ def refuse_choose_options(args):
         stem = "".join(args.infile.split("/")[-1].split(".nc"))
         raise SystemExit("-c/--choose follows the system on one GPU (a chain over the time steps): run -c once, then "
                          f"-t --trackfile LEC_Results/{stem}_choose/{stem}_choose_track --gpus N for the sharded analysis of the track it wrote")
+    if args.choose_chunk is not None and args.choose_chunk < 1:
+        raise SystemExit("--choose-chunk must be >= 1 time steps")
     if args.choose_box is not None and min(args.choose_box) <= 0:
         raise SystemExit("--choose-box LENGTH WIDTH must be positive")
     if args.choose_search is not None and not args.choose_search > 0:

@@ -43,7 +43,8 @@ def source_digest() -> str:
 EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_reduce", "lec_dropmask", "lec_ingest", "lec_track_diag",
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
-           "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans"]
+           "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
+           "lec_follow_spans_chunk"]
 
 
 class Tuning(C.Structure):
@@ -177,6 +178,11 @@ class FollowSpansArgs(C.Structure):
                 ("pos_d", C.c_void_p), ("val_d", C.c_void_p), ("status_d", C.c_void_p), ("span_d", C.c_void_p), ("stream", C.c_void_p)]
 
 
+class FollowChunkArgs(C.Structure):
+    """struct lec_follow_chunk_args (include/lec_hip.h): lec_follow_spans_args' fields in the same order, then t_base and state_d."""
+    _fields_ = FollowSpansArgs._fields_ + [("t_base", C.c_int32), ("state_d", C.c_void_p)]
+
+
 class DtdtArgs(C.Structure):
     """struct lec_dtdt_args (include/lec_hip.h)."""
     _fields_ = [("tm_d", C.c_void_p), ("t_d", C.c_void_p), ("tp_d", C.c_void_p), ("dtype", C.c_int32), ("n_steps", C.c_int32),
@@ -246,6 +252,8 @@ def load():
     lib.lec_follow_seeds_series.argtypes = [C.POINTER(FollowSeedsSeriesArgs)]
     lib.lec_follow_spans.restype = C.c_int
     lib.lec_follow_spans.argtypes = [C.POINTER(FollowSpansArgs)]
+    lib.lec_follow_spans_chunk.restype = C.c_int
+    lib.lec_follow_spans_chunk.argtypes = [C.POINTER(FollowChunkArgs)]
     lib.lec_check_boxes.restype = C.c_int
     lib.lec_check_boxes.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_check_maps.restype = C.c_int

@@ -73,8 +73,15 @@ __device__ __forceinline__ bool smooth_global(const FollowParams& p, const doubl
     return cnt != 0;
 }
 
-// lec_follow_spans' rule for one chain (include/lec_hip.h): born at step t0, ended by end_threshold and patience, span [2] its output
-struct SpanRule { int t0; double end_threshold; int patience; int* span; };
+// lec_follow_spans' rule for one chain (include/lec_hip.h): born at step t0, ended by end_threshold and patience, span [2] its output.
+// The resumed form (lec_follow_spans_chunk) adds what a chunk inherits: t0 is then the first LOCAL step the chain walks, t_base the
+// series step of local step 0, weak / first / last the counters so far, state [8] where the chain leaves them for the next chunk.
+struct SpanRule { int t0; double end_threshold; int patience; int* span; int t_base, weak, first, last; int* state; };
+
+// follow_chain's compile-time variants
+constexpr int kPlain = 0, kSpans = 1, kResume = 2;
+// lec_follow_spans_chunk's phases (state[0])
+constexpr int kUnborn = 0, kWalking = 1, kStopped = 2, kBadStart = 3;
 
 // steps [t_begin, t_end) of a chain that does not walk them, by the whole workgroup
 __device__ __forceinline__ void not_live(int* pos, double* val, int* status, int t_begin, int t_end) {
@@ -90,7 +97,9 @@ __device__ __forceinline__ void not_live(int* pos, double* val, int* status, int
 // pos [nt][2], val [nt], status [nt]: this chain's; smem: kLdsFixed + the tile.
 // kSpans (lec_follow_spans): the chain is born at step sp.t0 and ended by sp's rule (include/lec_hip.h); the steps it does not walk are
 // LEC_FOLLOW_NOT_LIVE, span [2] gets (first good step, last good step).  The walked steps are the very statements of the other two.
-template <bool kSpans>
+// kResume (lec_follow_spans_chunk): kSpans on a chunk of the series -- the counters start from sp's, the good steps are counted in
+// series steps (local step + sp.t_base), and the chain's state goes to sp.state at the end.
+template <int kMode>
 __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int ic, int* pos, double* val, int* status, char* smem,
                                              const SpanRule sp = SpanRule{}) {
     double* sv = (double*)smem;                     // [kWaves]
@@ -102,13 +111,16 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
     const double inf = __builtin_huge_val();
     const int none = 0x7fffffff;
     int first = -1, last = -1, weak = 0;            // (kSpans) the good steps so far, the not-good steps in a row
-    if (kSpans) not_live(pos, val, status, 0, sp.t0);
+    if (kMode == kResume) { first = sp.first; last = sp.last; weak = sp.weak; }
+    const int tb = kMode == kResume ? sp.t_base : 0;
+    bool stopped = false;                           // (kResume)
+    if (kMode != kPlain) not_live(pos, val, status, 0, sp.t0);
     // (jc, ic) the centre: the same in every thread, from the partials in LDS
-    for (int t = kSpans ? sp.t0 : 0; t < p.nt; ++t) {
+    for (int t = kMode != kPlain ? sp.t0 : 0; t < p.nt; ++t) {
         const double* u = p.u + t * plane;
         const double* v = p.v + t * plane;
         const double* h = p.h ? p.h + t * plane : nullptr;
-        const bool whole = !kSpans && jc < 0;       // step 0 without a start: every admissible centre
+        const bool whole = kMode == kPlain && jc < 0;      // step 0 without a start: every admissible centre
         const int j0 = whole ? p.jlo : max(p.jlo, jc - p.sj), j1 = whole ? p.jhi : min(p.jhi, jc + p.sj);
         const int i0 = whole ? p.ilo : max(p.ilo, ic - p.si), i1 = whole ? p.ihi : min(p.ihi, ic + p.si);
         const int nxw = i1 - i0 + 1, npt = nxw * (j1 - j0 + 1);
@@ -149,20 +161,24 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
             val[t] = found ? b.v : nan("");
             status[t] = found ? 0 : 1;
         }
-        if (kSpans) {
+        if (kMode != kPlain) {
             // b is reduce_best's result, which every thread holds: the exit is uniform and lies after the step's barriers
             const bool good = found && (sp.end_threshold != sp.end_threshold || (want_max ? b.v >= sp.end_threshold : b.v <= sp.end_threshold));
-            if (good) { if (first < 0) first = t; last = t; weak = 0; }
-            else if (++weak == sp.patience) { not_live(pos, val, status, t + 1, p.nt); break; }
+            if (good) { if (first < 0) first = t + tb; last = t + tb; weak = 0; }
+            else if (++weak == sp.patience) { not_live(pos, val, status, t + 1, p.nt); stopped = true; break; }
         }
     }
-    if (kSpans && tid == 0) { sp.span[0] = first; sp.span[1] = last; }
+    if (kMode != kPlain && tid == 0) { sp.span[0] = first; sp.span[1] = last; }
+    if (kMode == kResume && tid == 0) {
+        sp.state[0] = stopped ? kStopped : kWalking; sp.state[1] = jc; sp.state[2] = ic; sp.state[3] = weak; sp.state[4] = first; sp.state[5] = last;
+        sp.state[6] = 0; sp.state[7] = 0;
+    }
 }
 
 // grid 1, block kThreads, dynamic LDS kLdsFixed + the tile
 __global__ void __launch_bounds__(kThreads) lec_follow_kernel(const FollowParams p) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    follow_chain<false>(p, p.j_start, p.i_start, p.pos, p.val, p.status, smem);
+    follow_chain<kPlain>(p, p.j_start, p.i_start, p.pos, p.val, p.status, smem);
 }
 
 // grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks chain c from start[c].  The table lives in device
@@ -184,7 +200,7 @@ __global__ void __launch_bounds__(kThreads) lec_follow_many_kernel(const FollowP
         }
         return;
     }
-    follow_chain<false>(p, js, is, pos, val, status, smem);
+    follow_chain<kPlain>(p, js, is, pos, val, status, smem);
 }
 
 // grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks chain c from start[c] = (t0, j, i) until the rule
@@ -206,7 +222,59 @@ __global__ void __launch_bounds__(kThreads) lec_follow_spans_kernel(const Follow
         if (threadIdx.x == 0) { span[2 * c] = -1; span[2 * c + 1] = -1; }
         return;
     }
-    follow_chain<true>(p, js, is, pos, val, status, smem, SpanRule{t0, end_threshold, patience, span + 2 * c});
+    follow_chain<kSpans>(p, js, is, pos, val, status, smem, SpanRule{t0, end_threshold, patience, span + 2 * c, 0, 0, -1, -1, nullptr});
+}
+
+// grid n_chains, block kThreads, dynamic LDS as lec_follow_kernel: workgroup c walks the steps of THIS chunk that chain c lives in, from
+// the state the chunk before left (include/lec_hip.h has the rule).  p.nt counts the chunk's steps, t_base is the series step of its
+// slice 0.  The start entry is checked before anything else is read.  The state is read by thread 0 alone and reaches the others through
+// LDS (the tile's first bytes, free until the first step fills it: the tile holds 3 x 3 doubles at the least), so the phase and with it
+// every exit is uniform.  A walking chain whose carried centre is no admissible centre -- a state the caller has not passed on
+// unchanged -- reads nothing: it is treated as stopped.
+__global__ void __launch_bounds__(kThreads) lec_follow_spans_chunk_kernel(const FollowParams p, const int* __restrict__ start, double end_threshold,
+                                                                          int patience, int* __restrict__ span, int t_base, int* state_all) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t c = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int t0 = start[3 * c], js = start[3 * c + 1], is = start[3 * c + 2];
+    int* pos = p.pos + 2 * c * (size_t)p.nt;
+    double* val = p.val + c * (size_t)p.nt;
+    int* status = p.status + c * (size_t)p.nt;
+    int* state = state_all + 8 * c;
+    if (t0 < 0 || js < p.jlo || js > p.jhi || is < p.ilo || is > p.ihi) {
+        for (int t = tid; t < p.nt; t += kThreads) {
+            pos[2 * (size_t)t] = -1; pos[2 * (size_t)t + 1] = -1;
+            val[t] = nan("");
+            status[t] = LEC_FOLLOW_BAD_START;
+        }
+        if (tid == 0) {
+            span[2 * c] = -1; span[2 * c + 1] = -1;
+            state[0] = kBadStart; state[1] = -1; state[2] = -1; state[3] = 0; state[4] = -1; state[5] = -1; state[6] = 0; state[7] = 0;
+        }
+        return;
+    }
+    int* sh = (int*)(smem + kLdsFixed);
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sh[k] = state[k];
+    }
+    __syncthreads();
+    const int phase = sh[0], jc = sh[1], ic = sh[2], weak = sh[3], first = sh[4], last = sh[5];
+    __syncthreads();                                // (the tile is free again)
+    const long long born_at = (long long)t0 - t_base;                 // the local step of the birth
+    const bool born = phase == kUnborn && born_at >= 0 && born_at < p.nt;
+    const bool walks = phase == kWalking && jc >= p.jlo && jc <= p.jhi && ic >= p.ilo && ic <= p.ihi;
+    if (!born && !walks) {
+        // not yet born (the state stays as it is), stopped, or a state that is none of the rule's: no step of this chunk is walked
+        not_live(pos, val, status, 0, p.nt);
+        const bool has_span = phase == kStopped || phase == kWalking;
+        if (tid == 0) { span[2 * c] = has_span ? first : -1; span[2 * c + 1] = has_span ? last : -1; }
+        return;
+    }
+    // born here: from the table's start with fresh counters; walking: from the state's centre with its counters
+    follow_chain<kResume>(p, born ? js : jc, born ? is : ic, pos, val, status, smem,
+                          SpanRule{born ? (int)born_at : 0, end_threshold, patience, span + 2 * c, t_base, born ? 0 : weak, born ? -1 : first,
+                                   born ? -1 : last, state});
 }
 
 // ---- lec_follow_seeds: the systems of ONE slice (the rule: include/lec_hip.h) ----------------------------------------------------
@@ -546,5 +614,32 @@ extern "C" int lec_follow_spans(const lec_follow_spans_args* a) {
         if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
     }
     hipLaunchKernelGGL(lec_follow_spans_kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d, a->end_threshold, a->patience, a->span_d);
+    return launched(who);
+}
+
+extern "C" int lec_follow_spans_chunk(const lec_follow_chunk_args* a) {
+    const char* who = "lec_follow_spans_chunk";
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
+                             {a->start_d, "start_d"}, {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}, {a->span_d, "span_d"},
+                             {a->state_d, "state_d"}};
+    if (int rc = check_pointers(who, ptrs)) return rc;
+    if (int rc = check_slice(who, a, a->nt)) return rc;
+    if (a->n_chains < 1) return refuse(LEC_ERR_ARG, who, "n_chains must be >= 1");
+    if (a->patience < 0) return refuse(LEC_ERR_ARG, who, "patience must be >= 0 (0: the chains never stop)");
+    if (a->t_base < 0) return refuse(LEC_ERR_ARG, who, "t_base must be >= 0");
+    if ((long long)a->t_base + a->nt > 0x7fffffffLL) return refuse(LEC_ERR_ARG, who, "t_base + nt must fit a 32-bit series step");
+    long long lds;
+    if (int rc = check_window(who, a, &lds)) return rc;
+    FollowParams p = slice_params(a, a->nt);
+    p.sj = a->sj; p.si = a->si;
+    p.pos = a->pos_d; p.val = a->val_d; p.status = a->status_d;
+    hipStream_t st = (hipStream_t)a->stream;
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)lec_follow_spans_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
+    }
+    hipLaunchKernelGGL(lec_follow_spans_chunk_kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d, a->end_threshold, a->patience,
+                       a->span_d, a->t_base, a->state_d);
     return launched(who);
 }

@@ -125,52 +125,109 @@ def write_track(path, time, lat_c, lon_c, length, width) -> str:
     return str(path)
 
 
-def search_domain_slices(args, varlist="inputs/namelist", app_logger=None):
+class _SliceSource:
+    """The 85000-Pa slices of u, v and geopotential height (gpm) of ``args.infile`` on the search domain, opened once and read by ranges
+    of time steps: ``lat``, ``lon``, ``time`` are the whole series', ``read((a, b))`` gives (u, v, hgt [b - a][ny][nx] float64)."""
+
+    def __init__(self, args, varlist="inputs/namelist", app_logger=None):
+        variable_list_df = ds.read_namelist(varlist, app_logger)
+        mpas = bool(getattr(args, "mpas", False))
+        self.geo_role = "Geopotential" if "Geopotential" in variable_list_df.index else "Geopotential Height"
+        self.roles = ("Eastward Wind Component", "Northward Wind Component", self.geo_role)
+        self.app_logger, self.raw, self.data, self.told = app_logger, None, None, False
+
+        def crop(px):
+            k = np.flatnonzero(px.level == 85000.0)
+            if k.size == 0:
+                raise KeyError(85000)                           # as -t: lec_moving_framework.py:653-657 selects 85000 Pa exactly
+            jj, ii = np.arange(px.lat.size), np.arange(px.lon.size)
+            if getattr(args, "choose_domain", None):
+                w, e, s, n = ds.read_box_limits(args.choose_domain)
+                jj = np.flatnonzero((px.lat >= s) & (px.lat <= n))
+                ii = np.flatnonzero((px.lon >= w) & (px.lon <= e))
+            if jj.size < 3 or ii.size < 3:
+                raise ValueError("the search domain selects fewer than 3 x 3 grid points of the data")
+            return int(k[0]), jj, ii
+
+        try:
+            raw = ds.open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
+        except ValueError as e:
+            if "order" not in str(e) and "device ingest reads" not in str(e):
+                raise
+            self.data = data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)  # another dimension order: the whole file
+            px = ds._sorted_axes(None, data.lat, data.lon, data.level, data.time, data.level_units, data.names, app_logger)
+            k, jj, ii = crop(px)
+            self.sel = (px.ik[k], px.ij[jj], px.io[ii])
+            lat, lon, time = px.lat[jj], px.lon[ii], px.time
+        else:
+            self.raw = raw
+            try:
+                px = ds._sorted_axes(None, raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, app_logger)
+                k, jj, ii = crop(px)
+                i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+                self.plan = ds.IngestPlan(np.arange(raw.time.size), i32(px.ik[k: k + 1]), i32(px.ij[jj]), i32(px.io[ii]), px.lat[jj], px.lon[ii],
+                                          px.level[k: k + 1], px.time)
+            except BaseException:
+                raw.close()
+                raise
+            lat, lon, time = self.plan.lat, self.plan.lon, self.plan.time
+        self.lat, self.lon, self.time = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64), time
+
+    def read(self, t_range=None):
+        """(u, v, hgt) of the time steps [a, b) (None: all)."""
+        if self.raw is None:
+            if t_range is not None and not self.told and self.app_logger is not None:
+                self.app_logger.info("-c/--choose: this file's dimension order takes the whole-file reader: reading the 850-hPa slices in "
+                                     "chunks bounds the GPU's memory, it does not save host memory for this file")
+                self.told = True
+            steps = slice(None) if t_range is None else slice(int(t_range[0]), int(t_range[1]))
+            ik, ij, io = self.sel
+            get = lambda role: self.data.variables[self.data.names[role]][steps][:, ik][:, ij][:, :, io].astype(np.float64)
+            u, v, g = (get(r) for r in self.roles)
+        else:
+            u, v, g = (ds.gather_on_host(self.raw.variables[self.raw.names[r]], self.plan, t_range)[:, 0].astype(np.float64) for r in self.roles)
+        return u, v, (g if self.geo_role == "Geopotential Height" else g / G)      # -> gpm, as diagnostics.track_diagnostics
+
+    def close(self):
+        if self.raw is not None:
+            self.raw.close()
+            self.raw = None
+
+
+def search_domain_slices(args, varlist="inputs/namelist", app_logger=None, t_range=None):
     """The 85000-Pa slices of u, v and geopotential height (gpm) of ALL time steps of ``args.infile`` on the search domain
     (``args.choose_domain``: a box-limits file, label slices; default: the file's whole domain), with sorted axes:
-    (u, v, hgt [nt][ny][nx] float64, lat, lon, time).  Only that level and that domain are read from the file."""
-    variable_list_df = ds.read_namelist(varlist, app_logger)
-    mpas = bool(getattr(args, "mpas", False))
-    geo_role = "Geopotential" if "Geopotential" in variable_list_df.index else "Geopotential Height"
-    roles = ("Eastward Wind Component", "Northward Wind Component", geo_role)
-
-    def crop(px):
-        k = np.flatnonzero(px.level == 85000.0)
-        if k.size == 0:
-            raise KeyError(85000)                               # as -t: lec_moving_framework.py:653-657 selects 85000 Pa exactly
-        jj, ii = np.arange(px.lat.size), np.arange(px.lon.size)
-        if getattr(args, "choose_domain", None):
-            w, e, s, n = ds.read_box_limits(args.choose_domain)
-            jj = np.flatnonzero((px.lat >= s) & (px.lat <= n))
-            ii = np.flatnonzero((px.lon >= w) & (px.lon <= e))
-        if jj.size < 3 or ii.size < 3:
-            raise ValueError("the search domain selects fewer than 3 x 3 grid points of the data")
-        return int(k[0]), jj, ii
-
+    (u, v, hgt [nt][ny][nx] float64, lat, lon, time).  Only that level and that domain are read from the file.
+    ``t_range`` (a, b): u, v and hgt hold the time steps [a, b) only, and only those are read; lat, lon and time are the whole
+    series' either way.  (A file in another dimension order is opened whole: there the range bounds nothing on the host.)"""
+    src = _SliceSource(args, varlist, app_logger)
     try:
-        raw = ds.open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
-    except ValueError as e:
-        if "order" not in str(e) and "device ingest reads" not in str(e):
-            raise
-        data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)              # another dimension order: the whole file
-        px = ds._sorted_axes(None, data.lat, data.lon, data.level, data.time, data.level_units, data.names, app_logger)
-        k, jj, ii = crop(px)
-        get = lambda role: data.variables[data.names[role]][:, px.ik[k]][:, px.ij[jj]][:, :, px.io[ii]].astype(np.float64)
-        u, v, g = (get(r) for r in roles)
-        lat, lon, time = px.lat[jj], px.lon[ii], px.time
+        u, v, hgt = src.read(t_range)
+    finally:
+        src.close()
+    return u, v, hgt, src.lat, src.lon, src.time
+
+
+SLICE_BYTES = 2 << 30                   # the 850-hPa slices held at a time (host, and again on the device): a memory bound, not a tuned figure
+
+
+def slice_chunks(nt, ny, nx, asked=None, budget=SLICE_BYTES) -> list:
+    """[(a, b)]: the consecutive ranges of time steps whose slices (u, v, hgt: 24 bytes per grid point and step) a -c run holds at a
+    time.  ``asked`` (--choose-chunk N): chunks of N steps, the last one shorter.  Without it: ONE chunk when the whole series fits
+    ``budget`` bytes, else the largest equal chunks that fit (a single step that does not fit is still a chunk)."""
+    nt = int(nt)
+    if nt < 1:
+        raise ValueError("no time steps")
+    if asked is not None:
+        if asked != int(asked) or int(asked) < 1:
+            raise ValueError(f"a chunk is a whole number of time steps >= 1, not {asked!r}")
+        size = min(int(asked), nt)
     else:
-        try:
-            px = ds._sorted_axes(None, raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, app_logger)
-            k, jj, ii = crop(px)
-            i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
-            plan = ds.IngestPlan(np.arange(raw.time.size), i32(px.ik[k: k + 1]), i32(px.ij[jj]), i32(px.io[ii]), px.lat[jj], px.lon[ii],
-                                 px.level[k: k + 1], px.time)
-            u, v, g = (ds.gather_on_host(raw.variables[raw.names[r]], plan)[:, 0].astype(np.float64) for r in roles)
-            lat, lon, time = plan.lat, plan.lon, plan.time
-        finally:
-            raw.close()
-    hgt = g if geo_role == "Geopotential Height" else g / G                        # -> gpm, as diagnostics.track_diagnostics
-    return u, v, hgt, np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64), time
+        per_step = 24 * int(ny) * int(nx)
+        most = max(1, int(budget) // per_step)                           # steps that fit
+        n_chunks = -(-nt // most)
+        size = -(-nt // n_chunks)                                         # equal chunks: no short tail beyond rounding
+    return [(a, min(a + size, nt)) for a in range(0, nt, size)]
 
 
 def write_choose_track(args, results_subdirectory, app_logger, varlist="inputs/namelist", device="cuda:0") -> str:
@@ -181,16 +238,12 @@ def write_choose_track(args, results_subdirectory, app_logger, varlist="inputs/n
     field = getattr(args, "choose_field", None) or "zeta"
     form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
     start = getattr(args, "choose_start", None)
-    u, v, hgt, lat, lon, time = search_domain_slices(args, varlist, app_logger)
-    hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
-    sj, si = window_steps(lat, lon, search)
-    app_logger.info(f"-c/--choose: following the 850 hPa {'minimum' if sense == _lib.FOLLOW_MIN else 'maximum'} of {field} "
-                    f"({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "") + f") on the GPU (lec_follow): "
-                    f"{len(time)} time steps, search domain lat {lat[0]}..{lat[-1]}, lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), "
-                    f"box {length} x {width} degrees (length x width), at most {search} degrees = {sj} x {si} grid steps per time step, "
-                    f"smoothing radius {smooth}, start {'the extremum of the whole domain' if start is None else tuple(start)}")
-    pos, val, status = follow_system(u, v, hgt, lat, lon, length=length, width=width, search=search, smooth=smooth, field=field,
-                                     hemisphere=hemisphere, start=start, formulation=form, device=device)
+    src = _SliceSource(args, varlist, app_logger)
+    try:
+        lat, lon, time = src.lat, src.lon, src.time
+        pos, val, status = _choose_track_chains(args, app_logger, src, length, width, search, smooth, field, form, start, device)
+    finally:
+        src.close()
     for t in np.flatnonzero(status):
         app_logger.warning(f"-c/--choose: no finite value of {field} in the search window of {pd.Timestamp(time[t])}: the box stays where it was")
     stem = os.path.basename(args.infile).split(".nc")[0]
@@ -203,6 +256,56 @@ def write_choose_track(args, results_subdirectory, app_logger, varlist="inputs/n
                            "degrees beside the grid's coordinates; the analysis uses them as read, as a -t run on this file does")
     app_logger.info(f"-c/--choose: track written to {path} (a track file: -t --trackfile {path} repeats this run, --gpus N included)")
     return path
+
+
+def _log_chunks(app_logger, chunks, ny, nx, how):
+    n = chunks[0][1] - chunks[0][0]
+    app_logger.info(f"-c/--choose: the 850-hPa slices are read and uploaded in {len(chunks)} chunks of {n} time steps ({24 * n * ny * nx} bytes a chunk, "
+                    f"on the host and again on the GPU); {how}")
+
+
+def _resume_chunks(src, chunks, pos, val, status, starts, *, search, device, **kw):
+    """The chunks after the first of a plain or --choose-systems run.  pos [K][n0][2], val, status [K][n0]: what lec_follow / lec_follow_many
+    gave on the first chunk; starts [K][2]: the chains' starts.  Every chain goes on from the centre of the first chunk's last step
+    through ``lec_follow_spans_chunk`` with patience 0 (it never stops) -> the arrays over the whole series."""
+    import torch
+    K = len(pos)
+    start = np.zeros((K, 3), dtype=np.int32)
+    start[:, 1:] = starts
+    state = np.zeros((K, 8), dtype=np.int32)
+    for c in range(K):
+        if status[c, 0] != _lib.FOLLOW_BAD_START:             # (a bad start is found again by the kernel, from its entry of the table)
+            state[c] = (1, pos[c, -1, 0], pos[c, -1, 1], 0, -1, -1, 0, 0)
+    start_d, state_d = torch.as_tensor(start).to(device), torch.as_tensor(state).to(device)
+    pos, val, status = [pos], [val], [status]
+    for a, b in chunks[1:]:
+        u, v, hgt = src.read((a, b))
+        p, x, st, _ = follow_spans_chunk(u, v, hgt, src.lat, src.lon, starts=start_d, state=state_d, t_base=a, patience=0, search=search, device=device, **kw)
+        del u, v, hgt
+        pos.append(p); val.append(x); status.append(st)
+    return np.concatenate(pos, axis=1), np.concatenate(val, axis=1), np.concatenate(status, axis=1)
+
+
+def _choose_track_chains(args, app_logger, src, length, width, search, smooth, field, form, start, device):
+    """write_choose_track's chain: (pos [nt][2], val [nt], status [nt]) over the whole series."""
+    chunks, u, v, hgt = _first_chunk(args, src)
+    lat, lon, time = src.lat, src.lon, src.time
+    hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
+    sj, si = window_steps(lat, lon, search)
+    app_logger.info(f"-c/--choose: following the 850 hPa {'minimum' if sense == _lib.FOLLOW_MIN else 'maximum'} of {field} "
+                    f"({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "") + f") on the GPU (lec_follow): "
+                    f"{len(time)} time steps, search domain lat {lat[0]}..{lat[-1]}, lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), "
+                    f"box {length} x {width} degrees (length x width), at most {search} degrees = {sj} x {si} grid steps per time step, "
+                    f"smoothing radius {smooth}, start {'the extremum of the whole domain' if start is None else tuple(start)}")
+    if len(chunks) > 1:
+        _log_chunks(app_logger, chunks, lat.size, lon.size, "the first chunk goes through lec_follow, every later one resumes the chain "
+                    "(lec_follow_spans_chunk)")
+    kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form)
+    pos, val, status = follow_system(u, v, hgt, lat, lon, search=search, start=start, device=device, **kw)
+    if len(chunks) > 1:
+        del u, v, hgt
+        pos, val, status = (a[0] for a in _resume_chunks(src, chunks, pos[None], val[None], status[None], pos[None, 0], search=search, device=device, **kw))
+    return pos, val, status
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -350,9 +453,28 @@ def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", 
     or the file's starts, ONE ``lec_follow_many`` launch -> ``<batch_dir>/choose_s01``, ``choose_s02``, ... (``write_track``) and
     ``systems.csv``.  Returns the tracks' paths.  A chain whose first step finds nothing (or whose start is bad) is logged and left
     out; none left: the error ``follow_system`` raises.  With ``--choose-lifecycle``: ``write_lifecycle_tracks``."""
-    import torch
     if getattr(args, "choose_lifecycle", False):
         return write_lifecycle_tracks(args, batch_dir, app_logger, varlist, device)
+    src = _SliceSource(args, varlist, app_logger)
+    try:
+        return _choose_tracks_written(args, batch_dir, app_logger, src, device)
+    finally:
+        src.close()
+
+
+def _first_chunk(args, src):
+    """(chunks, u, v, hgt of the first chunk): the whole series, and the file closed, when the planner gives one chunk."""
+    chunks = slice_chunks(len(src.time), src.lat.size, src.lon.size, getattr(args, "choose_chunk", None))
+    u, v, hgt = src.read(None if len(chunks) == 1 else chunks[0])
+    if len(chunks) == 1:
+        src.close()
+    return chunks, u, v, hgt
+
+
+def _choose_tracks_written(args, batch_dir, app_logger, src, device) -> list:
+    """write_choose_tracks on an open source of slices."""
+    import torch
+    chunks, u, v, hgt = _first_chunk(args, src)
     length, width = (float(x) for x in (getattr(args, "choose_box", None) or DEFAULT_BOX))
     search = float(getattr(args, "choose_search", None) or DEFAULT_SEARCH)
     smooth = int(getattr(args, "choose_smooth", None) or 0)
@@ -360,7 +482,7 @@ def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", 
     form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
     k, starts_file = getattr(args, "choose_systems", None), getattr(args, "choose_starts", None)
     threshold, separation = getattr(args, "choose_threshold", None), getattr(args, "choose_separation", None)
-    u, v, hgt, lat, lon, time = search_domain_slices(args, varlist, app_logger)
+    lat, lon, time = src.lat, src.lon, src.time
     hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
     bounds = admissible(lat, lon, length, width)                      # (refused here, before the upload, if the box does not fit)
     kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form, device=device)
@@ -389,7 +511,13 @@ def write_choose_tracks(args, batch_dir, app_logger, varlist="inputs/namelist", 
                     + f") on the GPU (lec_follow_many, {len(seeds)} chains in one launch): {len(time)} time steps, search domain lat {lat[0]}..{lat[-1]}, "
                     f"lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), box {length} x {width} degrees (length x width), at most {search} degrees = "
                     f"{sj} x {si} grid steps per time step, smoothing radius {smooth}")
+    if len(chunks) > 1:
+        _log_chunks(app_logger, chunks, lat.size, lon.size, "the first chunk goes through lec_follow_many, every later one resumes the chains "
+                    "(lec_follow_spans_chunk)")
     pos, val, status = follow_systems(u, v, hgt, lat, lon, seeds=seeds, search=search, **kw)
+    if len(chunks) > 1:
+        del u, v, hgt
+        pos, val, status = _resume_chunks(src, chunks, pos, val, status, seeds, search=search, **kw)
     shared = first_shared_centre(pos)
     for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
         if name.startswith("choose_s") and name[8:].isdigit():
@@ -514,6 +642,41 @@ def follow_spans(u850, v850, hgt850, lat, lon, *, starts, end_threshold=None, pa
     return pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy(), span.cpu().numpy()
 
 
+def follow_spans_chunk(u850, v850, hgt850, lat, lon, *, starts, state, t_base, end_threshold=None, patience=DEFAULT_PATIENCE,
+                       length=DEFAULT_BOX[0], width=DEFAULT_BOX[1], search=DEFAULT_SEARCH, smooth=0, field="zeta", hemisphere=None,
+                       formulation="metpy_no_crs", device="cuda:0"):
+    """``lec_follow_spans_chunk``: ``follow_spans`` on ONE CHUNK of a series -- the slices hold the steps [t_base, t_base + nt) only --
+    with chains that are resumed from ``state`` and leave it for the next chunk.  ``starts`` [K][3] (t0, j, i), t0 a series step;
+    ``state`` [K][8] an int32 DEVICE tensor, zeroed before the first chunk, passed on unchanged from then on and updated in place
+    (rows may be appended, zeroed, between calls).  -> (pos [K][nt][2], val [K][nt], status [K][nt] of the chunk's steps, span [K][2]
+    in series steps as the state stands after the chunk).  ``patience`` 0: the chains never stop.  The rule: include/lec_hip.h."""
+    import torch
+    if not search > 0:
+        raise ValueError(f"search must be > 0 degrees, not {search!r}")
+    s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
+                formulation=formulation, device=device)
+    sj, si = window_steps(s.lat, s.lon, search)
+    start_d = (starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(starts, dtype=np.int32))).to(device=s.dev, dtype=torch.int32).contiguous()
+    if start_d.dim() != 2 or start_d.shape[1] != 3 or start_d.shape[0] < 1:
+        raise ValueError("starts: needs at least one (t0, j, i) triple")
+    K, nt = int(start_d.shape[0]), int(s.u.shape[0])
+    if not (isinstance(state, torch.Tensor) and state.dtype == torch.int32 and state.device == s.u.device and state.is_contiguous()
+            and tuple(state.shape) == (K, 8)):
+        raise ValueError(f"state: needs a contiguous int32 tensor [{K}][8] on {s.u.device} (the call updates it in place)")
+    pos = torch.empty((K, nt, 2), dtype=torch.int32, device=s.dev)
+    val = torch.empty((K, nt), dtype=torch.float64, device=s.dev)
+    status = torch.empty((K, nt), dtype=torch.int32, device=s.dev)
+    span = torch.empty((K, 2), dtype=torch.int32, device=s.dev)
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    args = _lib.FollowChunkArgs(nt=nt, sj=sj, si=si, n_chains=K, patience=int(patience), start_d=ptr(start_d),
+                                end_threshold=float("nan") if end_threshold is None else float(end_threshold),
+                                pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status), span_d=ptr(span), t_base=int(t_base), state_d=ptr(state),
+                                **s.common())
+    with torch.cuda.device(s.dev):
+        _lib.check(s.lib.lec_follow_spans_chunk(C.byref(args)), "lec_follow_spans_chunk")
+    return pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy(), span.cpu().numpy()
+
+
 def resolve(starts, pos, span, ej, ei) -> tuple:
     """(kept [K] bool, continuation_of [K]: a chain's number or -1), going through the chains in birth order.  A chain with span (-1, -1)
     is dropped.  A chain c is a continuation of the FIRST kept chain b with span_b[0] <= t0_c <= span_b[1] whose centre at step t0_c lies
@@ -565,7 +728,70 @@ def write_lifecycle_tracks(args, batch_dir, app_logger, varlist="inputs/namelist
     end_threshold = threshold if end_threshold is None else float(end_threshold)
     patience = getattr(args, "choose_patience", None) or DEFAULT_PATIENCE
     min_steps = getattr(args, "choose_min_steps", None) or DEFAULT_MIN_STEPS
-    u, v, hgt, lat, lon, time = search_domain_slices(args, varlist, app_logger)
+    src = _SliceSource(args, varlist, app_logger)
+    try:
+        return _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, width, search, smooth, field, form, k, threshold,
+                                         separation, end_threshold, patience, min_steps)
+    finally:
+        src.close()
+
+
+def _lifecycle_chunks(src, chunks, first, app_logger, *, k, threshold, sep, sj, si, end_threshold, patience, search, device, **kw):
+    """The chunked form of write_lifecycle_tracks' middle: per chunk the slices (``first``: the first chunk's, already read), their
+    seeds, the births of the chunk's steps (its first step's against the seeds of the step before, kept from the chunk before), the new
+    births appended to the chain table with zeroed state rows, ONE ``lec_follow_spans_chunk`` launch for every chain known so far.
+    -> (born [K][4], value [K] of each birth's seed, pos [K][nt][2], val, status [K][nt], span [K][2], seeds in all, births in all):
+    the arrays one ``lec_follow_spans`` launch on the whole series gives."""
+    import torch
+    dev = torch.device(device)
+    nt = len(src.time)
+    start_d = torch.zeros((MAX_BIRTHS, 3), dtype=torch.int32, device=dev)
+    state_d = torch.zeros((MAX_BIRTHS, 8), dtype=torch.int32, device=dev)
+    born, born_val = np.zeros((0, 4), dtype=np.int32), np.zeros(0)
+    n_seeds = n_births = 0
+    last_pos, last_n = None, None                                    # the seeds of the step before the chunk
+    parts, span = [], None                                            # (a, b, chains then, pos, val, status)
+    for n, (a, b) in enumerate(chunks):
+        u, v, hgt = first if n == 0 else src.read((a, b))
+        first = None
+        u, v, hgt = (torch.as_tensor(x).to(dev) for x in (u, v, hgt))
+        seed_pos, seed_val, n_found = find_systems_series(u, v, hgt, src.lat, src.lon, k=k, threshold=threshold, separation=sep, device=device, **kw)
+        n_seeds += int(n_found.sum())
+        if last_pos is None:
+            new = births(seed_pos, n_found, sj, si)
+            new_val = seed_val[new[:, 0], new[:, 3]]
+        else:
+            new = births(np.concatenate([last_pos, seed_pos]), np.concatenate([last_n, n_found]), sj, si)
+            new = new[new[:, 0] >= 1]                                 # (step 0 here is the step before the chunk)
+            new[:, 0] -= 1
+            new_val = seed_val[new[:, 0], new[:, 3]]
+        new[:, 0] += a
+        last_pos, last_n = seed_pos[-1:], n_found[-1:]
+        n_births += len(new)
+        new, new_val = new[:MAX_BIRTHS - len(born)], new_val[:MAX_BIRTHS - len(born)]      # births come ordered by step: the first MAX_BIRTHS
+        if len(new):
+            start_d[len(born): len(born) + len(new)] = torch.as_tensor(np.ascontiguousarray(new[:, :3])).to(dev)
+            born, born_val = np.concatenate([born, new]), np.concatenate([born_val, new_val])
+        K = len(born)
+        if K:
+            p, x, st, span = follow_spans_chunk(u, v, hgt, src.lat, src.lon, starts=start_d[:K], state=state_d[:K], t_base=a, end_threshold=end_threshold,
+                                                patience=patience, search=search, device=device, **kw)
+            parts.append((a, b, K, p, x, st))
+        del u, v, hgt
+    K = len(born)
+    pos, val = np.full((K, nt, 2), -1, dtype=np.int32), np.full((K, nt), np.nan)
+    status = np.full((K, nt), _lib.FOLLOW_NOT_LIVE, dtype=np.int32)   # a chunk before a chain was known: before its birth
+    for a, b, Kc, p, x, st in parts:
+        pos[:Kc, a:b], val[:Kc, a:b], status[:Kc, a:b] = p, x, st
+    return born, born_val, pos, val, status, span, n_seeds, n_births
+
+
+def _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, width, search, smooth, field, form, k, threshold, separation,
+                              end_threshold, patience, min_steps) -> list:
+    """write_lifecycle_tracks on an open source of slices."""
+    import torch
+    lat, lon, time = src.lat, src.lon, src.time
+    chunks, u, v, hgt = _first_chunk(args, src)
     hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
     if (end_threshold < threshold) if sense == _lib.FOLLOW_MIN else (end_threshold > threshold):
         raise ValueError(f"--choose-end-threshold {end_threshold} is stricter than --choose-threshold {threshold}: it may be weaker, never stricter")
@@ -580,6 +806,22 @@ def write_lifecycle_tracks(args, batch_dir, app_logger, varlist="inputs/namelist
     sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
     ej, ei = separation_steps(lat, lon, *sep)
     sj, si = window_steps(lat, lon, search)
+    if len(chunks) > 1:
+        _log_chunks(app_logger, chunks, lat.size, lon.size, "per chunk the seeds (lec_follow_seeds_series), the births, and one launch that "
+                    "resumes every chain known so far (lec_follow_spans_chunk)")
+        first = (u, v, hgt)
+        del u, v, hgt
+        born, born_val, pos, val, status, span, n_seeds, n_births = _lifecycle_chunks(
+            src, chunks, first, app_logger, k=k, threshold=threshold, sep=sep, sj=sj, si=si, end_threshold=end_threshold, patience=patience,
+            search=search, **kw)
+        app_logger.info(f"-c/--choose: {n_seeds} seeds in {len(time)} time steps, at most {k} per step ({what}, no better value within {sep[0]} x {sep[1]} "
+                        f"degrees = {ej} x {ei} grid steps, threshold {threshold}); {n_births} of them are births (no seed of the step before within "
+                        f"{sj} x {si} grid steps); a chain ends after {patience} time steps in a row weaker than {end_threshold}")
+        if n_births == 0:
+            raise ValueError("no time step holds a system: nothing to follow (another --choose-threshold, --choose-separation or --choose-domain?)")
+        if n_births > MAX_BIRTHS:
+            app_logger.warning(f"-c/--choose: {n_births} births found, the first {MAX_BIRTHS} of them (by time step, then strength) are followed")
+        return _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, born_val, pos, status, span, ej, ei, field, length, width, end_threshold, min_steps)
     seed_pos, seed_val, n_found = find_systems_series(u, v, hgt, lat, lon, k=k, threshold=threshold, separation=sep, **kw)
     born = births(seed_pos, n_found, sj, si)
     app_logger.info(f"-c/--choose: {int(n_found.sum())} seeds in {len(time)} time steps, at most {k} per step (lec_follow_seeds_series: {what}, "
@@ -596,6 +838,13 @@ def write_lifecycle_tracks(args, batch_dir, app_logger, varlist="inputs/namelist
                     f"(length x width), at most {search} degrees = {sj} x {si} grid steps per time step, smoothing radius {smooth}; a chain ends after "
                     f"{patience} time steps in a row weaker than {end_threshold}")
     pos, val, status, span = follow_spans(u, v, hgt, lat, lon, starts=born[:, :3], end_threshold=end_threshold, patience=patience, search=search, **kw)
+    return _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, seed_val[born[:, 0], born[:, 3]], pos, status, span, ej, ei, field, length,
+                              width, end_threshold, min_steps)
+
+
+def _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, born_val, pos, status, span, ej, ei, field, length, width, end_threshold,
+                       min_steps) -> list:
+    """From the chains of every birth (born [K][4], born_val [K] the births' seed values) to the tracks and ``systems.csv``."""
     kept, cont = resolve(born, pos, span, ej, ei)
     shared = first_shared_centre_live(pos, span)
     for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
@@ -606,7 +855,7 @@ def write_lifecycle_tracks(args, batch_dir, app_logger, varlist="inputs/namelist
     for c, (t0, j, i, rank) in enumerate(born):
         name = f"choose_s{c + 1:02d}"
         first, last = (int(x) for x in span[c])
-        row = {"system": name, "lat": lat[j], "lon": lon[i], "value": seed_val[t0, rank], "trackfile": "",
+        row = {"system": name, "lat": lat[j], "lon": lon[i], "value": born_val[c], "trackfile": "",
                "same_centre_as": "" if shared[c] is None else f"choose_s{shared[c][0] + 1:02d}",
                "same_centre_from": "" if shared[c] is None else stamp(shared[c][1]),
                "first_time": "" if first < 0 else stamp(first), "last_time": "" if first < 0 else stamp(last),

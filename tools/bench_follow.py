@@ -16,6 +16,13 @@ against ``steps`` back-to-back ``lec_follow_seeds`` calls of the library ``--par
 seeds compared bit for bit; and ONE ``lec_follow_spans`` launch of ``--chains`` chains with mixed lifetimes (births spread over the
 series, the end threshold at the 0.9 quantile of the values the chains meet, patience 2) against ``lec_follow_many`` walking the same starts
 through the whole series.  The values go under the key ``lifecycle`` of ``--out``.
+
+``--chunked``: the resumed chains of ``-c --choose-chunk`` instead.  Same series, ``--lifecycle``'s table of ``--chains`` chains and its
+end threshold.  (a) ONE ``lec_follow_spans`` launch against the ``lec_follow_spans_chunk`` calls over chunks of 64 and of 512 steps with
+the state carried (the timed call zeroes the state and makes every chunk's call; the outputs are compared bit for bit with the one
+launch's in a pass of their own).  (b) with ``--parent PATH``: ``lec_follow_spans`` and ``lec_follow_many`` of the parent's library and
+of this one, alternating, two rounds -- what the chains' shared device function cost the existing calls when it gained the resumed
+variant.  The values go under the key ``chunked`` of ``--out``.
 """
 import argparse
 import ctypes as C
@@ -36,7 +43,8 @@ def main():
     ap.add_argument("--systems", type=int, nargs="+", metavar="K", default=None)
     ap.add_argument("--parent", default=None, metavar="PATH")
     ap.add_argument("--lifecycle", action="store_true")
-    ap.add_argument("--chains", type=int, default=64, help="with --lifecycle: chains of the lec_follow_spans launch")
+    ap.add_argument("--chunked", action="store_true")
+    ap.add_argument("--chains", type=int, default=64, help="with --lifecycle / --chunked: chains of the lec_follow_spans launch")
     a = ap.parse_args()
     import torch
     from lorenzcycletoolkit_amd import _lib, diagnostics as dg, follow as fw
@@ -71,6 +79,8 @@ def main():
         return float(np.median(ms)), [round(x, 4) for x in ms]
 
     out = {"steps": nt, "slice": [ny, nx], "window": [2 * sj + 1, 2 * si + 1], "csrc_sha": _lib.source_digest()}
+    if a.chunked:
+        return chunked(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si, nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
     if a.lifecycle:
         return lifecycle(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si,
                                           sep=fw.separation_steps(lat, lon, fw.DEFAULT_BOX[0] / 2, fw.DEFAULT_BOX[1] / 2), nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
@@ -241,6 +251,95 @@ def lifecycle(a, lib, out, w, timed):
             with open(a.out) as f:
                 kept = json.loads(f.read())
         kept["lifecycle"] = dict(res, steps=nt, csrc_sha=out["csrc_sha"])
+        with open(a.out, "w") as f:
+            f.write(json.dumps(kept) + "\n")
+
+
+def chunked(a, lib, out, w, timed):
+    import torch
+    from lorenzcycletoolkit_amd import _lib
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    nt, ny, nx, dev, bounds = w["nt"], w["ny"], w["nx"], w["dev"], w["bounds"]
+    common = dict(ny=ny, nx=nx, field=_lib.FOLLOW_ZETA, xcoef_d=ptr(w["xc"]), ycoef_d=ptr(w["yc"]), curv_d=ptr(w["cv"]), sense=_lib.FOLLOW_MIN,
+                  smooth_r=0, jlo=bounds[0], jhi=bounds[1], ilo=bounds[2], ihi=bounds[3], stream=w["stream"], sj=w["sj"], si=w["si"])
+    series = dict(common, u_d=ptr(w["u"]), v_d=ptr(w["v"]), hgt_d=ptr(w["h"]), nt=nt)
+    # --lifecycle's table: births spread over the series, the end threshold at the 0.9 quantile of the values the chains meet
+    K = a.chains
+    rng = np.random.default_rng(2)
+    t0 = np.sort(rng.integers(0, max(1, nt - 1), K))
+    t0[0] = 0
+    table = np.c_[t0, rng.integers(bounds[0], bounds[1] + 1, K), rng.integers(bounds[2], bounds[3] + 1, K)].astype(np.int32)
+    start3, start2 = torch.as_tensor(table).to(dev), torch.as_tensor(np.ascontiguousarray(table[:, 1:])).to(dev)
+    pos, val, status = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((K, nt, 2), torch.int32), ((K, nt), torch.float64), ((K, nt), torch.int32)))
+    span = torch.empty((K, 2), dtype=torch.int32, device=dev)
+    outs = dict(n_chains=K, pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status))
+    ma = _lib.FollowManyArgs(reserved0=0, start_d=ptr(start2), **series, **outs)
+    _lib.check(lib.lec_follow_many(C.byref(ma)), "lec_follow_many")
+    threshold = float(torch.quantile(val.flatten(), 0.9).cpu())
+    pa = _lib.FollowSpansArgs(patience=2, end_threshold=threshold, start_d=ptr(start3), span_d=ptr(span), **series, **outs)
+    res = {"parent_library": bool(a.parent), "n_chains": K, "end_threshold": threshold, "patience": 2}
+    # (b) first, while pos / val / status still serve both calls: the parent's kernels and this library's, alternating
+    if a.parent:
+        old = C.CDLL(a.parent)
+        old.lec_follow_spans.restype, old.lec_follow_spans.argtypes = C.c_int, [C.POINTER(_lib.FollowSpansArgs)]
+        old.lec_follow_many.restype, old.lec_follow_many.argtypes = C.c_int, [C.POINTER(_lib.FollowManyArgs)]
+
+        def run(which, call, args):
+            if getattr(which, call)(C.byref(args)):
+                raise RuntimeError(f"{call} failed")
+
+        for rep in range(2):
+            for name, which in (("parent", old), ("this", lib)):
+                for call, args in (("lec_follow_spans", pa), ("lec_follow_many", ma)):
+                    med, all_ms = timed(lambda: run(which, call, args))
+                    res.setdefault(f"{call}_{name}_ms", []).append(round(med, 4))
+                    res.setdefault(f"{call}_{name}_all_ms", []).append(all_ms)
+    # (a) one launch ...
+    med, all_ms = timed(lambda: _lib.check(lib.lec_follow_spans(C.byref(pa)), "lec_follow_spans"))
+    res["lec_follow_spans_ms"], res["lec_follow_spans_all_ms"] = round(med, 4), all_ms
+    torch.cuda.synchronize()
+    # ... and the chunk calls, the state carried
+    state = torch.zeros((K, 8), dtype=torch.int32, device=dev)
+    span_c = torch.empty((K, 2), dtype=torch.int32, device=dev)
+    res["chunks"] = {}
+    for size in (64, 512):
+        size = min(size, nt)
+        pos_c, val_c, status_c = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((K, size, 2), torch.int32), ((K, size), torch.float64), ((K, size), torch.int32)))
+        calls = []
+        for t in range(0, nt, size):
+            n = min(size, nt - t)
+            calls.append((t, n, _lib.FollowChunkArgs(
+                **dict(common, u_d=ptr(w["u"][t: t + n]), v_d=ptr(w["v"][t: t + n]), hgt_d=ptr(w["h"][t: t + n]), nt=n), n_chains=K, patience=2,
+                end_threshold=threshold, start_d=ptr(start3), pos_d=ptr(pos_c), val_d=ptr(val_c), status_d=ptr(status_c), span_d=ptr(span_c),
+                t_base=t, state_d=ptr(state))))
+
+        def all_chunks(check=None):
+            state.zero_()
+            for t, n, ca in calls:
+                _lib.check(lib.lec_follow_spans_chunk(C.byref(ca)), "lec_follow_spans_chunk")
+                if check is not None:
+                    check(t, n)
+
+        same = []
+
+        def compare(t, n):
+            same.append(bool(torch.equal(pos_c[:, :n], pos[:, t: t + n]) and torch.equal(status_c[:, :n], status[:, t: t + n])
+                             and torch.equal(val_c[:, :n].contiguous().view(torch.int64), val[:, t: t + n].contiguous().view(torch.int64))))
+
+        # (a short last chunk writes [K][n] into the front of the [K][size] buffers: compared on a view of that shape)
+        if nt % size == 0:
+            all_chunks(compare)
+        med, all_ms = timed(all_chunks)
+        res["chunks"][str(size)] = {"calls": len(calls), "lec_follow_spans_chunk_ms": round(med, 4), "lec_follow_spans_chunk_all_ms": all_ms,
+                                    "same_bits": (all(same) and bool(torch.equal(span_c, span))) if same else None}
+    out["chunked"] = res
+    print(json.dumps(out))
+    if a.out:
+        kept = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                kept = json.loads(f.read())
+        kept["chunked"] = dict(res, steps=nt, csrc_sha=out["csrc_sha"])
         with open(a.out, "w") as f:
             f.write(json.dumps(kept) + "\n")
 
