@@ -561,6 +561,53 @@ typedef struct lec_follow_chunk_args {
     int32_t* state_d;           /* [n_chains][8] DEVICE memory, read and written; zeroed by the caller before the first chunk */
 } lec_follow_chunk_args;
 
+/*
+ * -c --choose-periodic: a search domain that is a full RING of longitudes (additive calls: no struct, export or kernel result of ABI 11
+ * changes).  A ring has no preferred meridian.
+ *
+ *   int lec_follow_seeds_series_ring(const lec_follow_seeds_series_args*);
+ *   int lec_follow_spans_chunk_ring (const lec_follow_chunk_args*);
+ *
+ * They take the existing structs with the same field meanings.  The one difference: longitude is periodic, so column nx - 1 is the
+ * western neighbour of column 0.  Only the two most general calls get a ring form: one chunk with patience >= 1 is lec_follow_spans;
+ * patience 0 with t0 = 0 is lec_follow / lec_follow_many; one step of the seeds series is lec_follow_seeds.  The rule:
+ *
+ * Stencil and tables.
+ *   - The zeta stencil at column i reads columns i - 1, i, i + 1 mod nx, for every i.
+ *   - xcoef[j][i] holds the centred coefficients at all columns (the host's vorticity_tables(..., periodic=True) builds them).  The
+ *     spacing from column nx - 1 to column 0 is the arc across the seam.
+ *   - Interior columns get the same doubles as today.
+ *   - The latitude stencil and curv are unchanged.
+ * Admissible centres.
+ *   - Every column is an admissible centre.  ilo = 0 and ihi = nx - 1 are required.
+ *   - jlo / jhi keep their meaning.
+ * Window.
+ *   - Rows [jc - sj, jc + sj] are cut to [jlo, jhi], as today.
+ *   - Columns ic - si ... ic + si are never cut.  They run west to east and are taken mod nx.
+ * S (the smoothed field).
+ *   - S is the mean of the finite field values with |dj| <= r inside the slice and |di| <= r on the ring.
+ *   - It is summed in row-major order of that neighbourhood, west to east from i - r.
+ *   - A point always has 2 r + 1 columns.
+ * Extremum and ties.
+ *   - The extremum rule, the tie rule (first in row-major order of the *window*), the centre kept on a blind window, good / stop / span /
+ *     state and every status code are lec_follow_spans_chunk's, statement for statement.
+ *   - Positions are written as i mod nx.
+ *   - A walking state whose ic is outside [0, nx) counts as stopped, as an inadmissible centre does today.
+ * Seeds.
+ *   - The neighbourhood is |dj| <= ej inside the slice and ring distance <= ei.
+ *   - The tie clause keeps the slice's absolute row-major index.
+ *   - A tie is therefore the one thing that depends on where the seam lies.
+ * Validation.  Every refusal is LEC_ERR_ARG naming the field, made before any HIP call, never clamped:
+ *   - 2 si + 1 + 2 r > nx or 2 ei + 1 > nx is refused, because the window would meet itself (for the seeds, 2 r + 1 > nx likewise).
+ *   - ilo != 0 or ihi != nx - 1 is refused.
+ *   - Everything the non-ring calls check is checked here too.
+ * The kernels are the existing ones' device functions with one more compile-time parameter.  The chain's LDS tile is
+ * min(2 sj + 1 + 2 r, ny) x (2 si + 1 + 2 r) doubles, its column c ring column (ic - si - r + c) mod nx; each tile row is loaded as at
+ * most two contiguous runs, the wrap is a compare-and-subtract.  The 160 KiB refusal is as before.
+ */
+int lec_follow_seeds_series_ring(const lec_follow_seeds_series_args* args);
+int lec_follow_spans_chunk_ring(const lec_follow_chunk_args* args);
+
 int lec_version(void);
 const char* lec_last_error(void);
 

@@ -87,6 +87,9 @@ def create_arg_parser():
     parser.add_argument("--choose-chunk", type=int, metavar="N", help="with -c: hold the 850-hPa slices of N time steps at a time, in host memory and "
                         "on the GPU (lec_follow_spans_chunk resumes every system from chunk to chunk); the tracks are those of the run without it.  "
                         "Default: the whole series when its slices fit 2 GiB, otherwise the largest equal chunks that do")
+    parser.add_argument("--choose-periodic", action="store_true", default=None, help="with -c: the search domain is a full ring of longitudes "
+                        "(evenly spaced, nx * dx = 360 degrees; --choose-domain may still cut latitudes): the system is found and followed "
+                        "across the +-180 meridian, where the sorted axis has its seam (otherwise refused, with the domain's extent)")
     parser.add_argument("--choose-systems", type=int, metavar="K", help="with -c: find the (at most) K strongest systems of the first time step, follow "
                         "them all at once and analyse every one as -t --trackfiles would: the tracks choose_s01, choose_s02, ..., systems.csv, the log "
                         "and batch.csv go to LEC_Results/<infile>_choose_batch/, each system's results to LEC_Results/<infile>_choose_sNN_track/")
@@ -185,7 +188,7 @@ def run_lec_analysis(data, args, results_subdirectory, figures_directory, result
 
 CHOOSE_OPTIONS = ("choose_domain", "choose_start", "choose_box", "choose_search", "choose_smooth", "choose_field", "choose_hemisphere",
                   "choose_systems", "choose_threshold", "choose_separation", "choose_starts", "choose_lifecycle", "choose_end_threshold",
-                  "choose_patience", "choose_min_steps", "choose_chunk")
+                  "choose_patience", "choose_min_steps", "choose_chunk", "choose_periodic")
 
 
 def refuse_choose_options(args):
@@ -428,21 +431,32 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
         start_time = time.time()
         trackfiles = trackfiles_of(batch_dir, app_logger)
         variable_list_df = pd.read_csv("inputs/namelist", sep=";", index_col=0, header=0)
-        data, plan = batch.prepare_union(args, trackfiles, "inputs/namelist", app_logger)
-        phases.mark("open_decode_and_prepare")
-        directories = []
-        for tr in plan.tracks:
-            tree = os.path.join("./LEC_Results/", f"{stem}_{tr.stem}_track")
-            if not os.path.isdir(tree):
-                created.append(tree)
-            vl, fig = os.path.join(tree, "results_vertical_levels"), os.path.join(tree, "Figures")
-            for d in (fig, tree, vl):
-                os.makedirs(d, exist_ok=True)
-            directories.append((tree, fig, vl))
-        lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
-        pd.DataFrame({"trackfile": [tr.path for tr in plan.tracks], "results_directory": [d[0] for d in directories],
-                      "steps": [tr.n for tr in plan.tracks]}).to_csv(os.path.join(batch_dir, "batch.csv"), index=False)
-        app_logger.info("Analysis complete! Moving framework ran %d tracks in %.2f seconds" % (len(plan.tracks), time.time() - start_time))
+        # a track across the +-180 meridian takes the longitude axis 0..360 (dataset.track_lon_origin): the tracks are partitioned by
+        # origin, each partition (at most two) is a pass of its own; a batch whose tracks are all origin 0 is the one pass it was
+        parts = batch.partition_by_origin(args, trackfiles, "inputs/namelist", app_logger)
+        if len(parts) > 1 or parts[0][0]:
+            app_logger.info("Longitude axis per track: " + "; ".join(f"{'0..360 (across the +-180 meridian)' if origin else '-180..180'}: "
+                            + ", ".join(trackfiles[n] for n in members) for origin, members in parts) + f" -- {len(parts)} pass(es) over the data")
+        rows = [None] * len(trackfiles)
+        for origin, members in parts:
+            data, plan = batch.prepare_union(args, [trackfiles[n] for n in members], "inputs/namelist", app_logger, lon_origin=origin)
+            phases.mark("open_decode_and_prepare")
+            directories = []
+            for tr in plan.tracks:
+                tree = os.path.join("./LEC_Results/", f"{stem}_{tr.stem}_track")
+                if not os.path.isdir(tree):
+                    created.append(tree)
+                vl, fig = os.path.join(tree, "results_vertical_levels"), os.path.join(tree, "Figures")
+                for d in (fig, tree, vl):
+                    os.makedirs(d, exist_ok=True)
+                directories.append((tree, fig, vl))
+            lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
+            for n, tr, d in zip(members, plan.tracks, directories):
+                rows[n] = (tr.path, d[0], tr.n)
+            del data, plan
+        pd.DataFrame({"trackfile": [r[0] for r in rows], "results_directory": [r[1] for r in rows],
+                      "steps": [r[2] for r in rows]}).to_csv(os.path.join(batch_dir, "batch.csv"), index=False)
+        app_logger.info("Analysis complete! Moving framework ran %d tracks in %.2f seconds" % (len(rows), time.time() - start_time))
     except Exception:
         app_logger.exception("LEC analysis failed")
         for tree in created:

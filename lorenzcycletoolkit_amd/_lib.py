@@ -44,7 +44,7 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
-           "lec_follow_spans_chunk"]
+           "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring"]
 
 
 class Tuning(C.Structure):
@@ -254,6 +254,10 @@ def load():
     lib.lec_follow_spans.argtypes = [C.POINTER(FollowSpansArgs)]
     lib.lec_follow_spans_chunk.restype = C.c_int
     lib.lec_follow_spans_chunk.argtypes = [C.POINTER(FollowChunkArgs)]
+    lib.lec_follow_seeds_series_ring.restype = C.c_int
+    lib.lec_follow_seeds_series_ring.argtypes = [C.POINTER(FollowSeedsSeriesArgs)]
+    lib.lec_follow_spans_chunk_ring.restype = C.c_int
+    lib.lec_follow_spans_chunk_ring.argtypes = [C.POINTER(FollowChunkArgs)]
     lib.lec_check_boxes.restype = C.c_int
     lib.lec_check_boxes.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_check_maps.restype = C.c_int

@@ -128,15 +128,16 @@ def _refuse(path: str, e: BaseException):
     raise BatchRefusal(f"track file {path}: {msg}") from e
 
 
-def plan_batch(lat, lon, lev, time, level_units, names, trackfiles: Sequence[str], app_logger=None) -> BatchPlan:
+def plan_batch(lat, lon, lev, time, level_units, names, trackfiles: Sequence[str], app_logger=None, lon_origin: float = 0.0) -> BatchPlan:
     """The batch on the FILE's coordinates (as ``process_index`` takes them): per track the checks of a single run, its time steps,
-    its crop, its boxes, slice table and d/dt coefficients; then the union and the groups.  No data are read."""
+    its crop, its boxes, slice table and d/dt coefficients; then the union and the groups.  No data are read.
+    ``lon_origin``: the origin of the longitude axis every track of this batch takes (``partition_by_origin``)."""
     from .frameworks import get_limits
-    px = ds.process_index(lat, lon, lev, time, level_units, names, SimpleNamespace(track=False), app_logger)
+    px = ds.process_index(lat, lon, lev, time, level_units, names, SimpleNamespace(track=False, lon_origin=lon_origin), app_logger)
     raw = []
     for path in trackfiles:
         try:
-            track = ds.read_track(path, app_logger)
+            track = ds.track_on_axis(ds.read_track(path, app_logger), px.lon) if lon_origin else ds.read_track(path, app_logger)
             if len(track) < 2:
                 raise ValueError(f"a track needs at least 2 time steps, this one has {len(track)}")
             tpos = ds.select_track_times(px.time, track)
@@ -202,9 +203,24 @@ def device_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> dict:
     return {"cubes": cubes, "records": rows, "results": results, "total": cubes + rows + results}
 
 
-def prepare_union(args, trackfiles: Sequence[str], varlist: str = "inputs/namelist", app_logger=None):
+def partition_by_origin(args, trackfiles: Sequence[str], varlist: str = "inputs/namelist", app_logger=None) -> list:
+    """[(origin, [positions in ``trackfiles``])], at most two entries, origin 0.0 first: the tracks by the origin of the longitude axis
+    each one's own ``-t`` run takes (``dataset.track_lon_origin``).  A track that cannot be read counts as origin 0: ``plan_batch``
+    refuses it there with its name."""
+    lon = ds.file_longitudes(args.infile, ds.read_namelist(varlist, app_logger), bool(getattr(args, "mpas", False)))
+    parts = {}
+    for n, path in enumerate(trackfiles):
+        try:
+            origin = ds.track_lon_origin(lon, ds.read_track(path))
+        except (ValueError, KeyError, IndexError, FileNotFoundError):
+            origin = 0.0
+        parts.setdefault(origin, []).append(n)
+    return sorted(parts.items())
+
+
+def prepare_union(args, trackfiles: Sequence[str], varlist: str = "inputs/namelist", app_logger=None, lon_origin: float = 0.0):
     """``prepare_data`` for a batch: the plan, and the data set of the union (its time steps, its crop), decoded once.
-    Returns (LECDataset, BatchPlan)."""
+    Returns (LECDataset, BatchPlan).  ``lon_origin``: as ``plan_batch``."""
     variable_list_df = ds.read_namelist(varlist, app_logger)
     mpas = bool(getattr(args, "mpas", False))
     try:
@@ -213,11 +229,11 @@ def prepare_union(args, trackfiles: Sequence[str], varlist: str = "inputs/nameli
         if "order" not in str(e) and "device ingest reads" not in str(e):
             raise
         data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)
-        plan = plan_batch(data.lat, data.lon, data.level, data.time, data.level_units, data.names, trackfiles, app_logger)
-        data = ds.process_data(data, SimpleNamespace(track=False), variable_list_df, app_logger)
+        plan = plan_batch(data.lat, data.lon, data.level, data.time, data.level_units, data.names, trackfiles, app_logger, lon_origin)
+        data = ds.process_data(data, SimpleNamespace(track=False, lon_origin=lon_origin), variable_list_df, app_logger)
         return data.isel(t=plan.tpos, j=plan.js, i=plan.is_), plan
     try:
-        plan = plan_batch(raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, trackfiles, app_logger)
+        plan = plan_batch(raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, trackfiles, app_logger, lon_origin)
         px = plan.px
         i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
         ip = ds.IngestPlan(plan.tpos, i32(px.ik), i32(px.ij[plan.js]), i32(px.io[plan.is_]), plan.lat, plan.lon, px.level, plan.time)

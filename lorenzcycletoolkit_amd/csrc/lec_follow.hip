@@ -35,8 +35,12 @@ struct FollowParams {
 
 __device__ __forceinline__ bool finite(double x) { return fabs(x) < __builtin_huge_val(); }
 
+// kRing, here and below: the ring calls' compile-time variant (include/lec_hip.h) -- column nx - 1 is the western neighbour of column 0.
+// i is a ring column, 0 <= i < nx.  Done the way kMode is: the instantiations without it are the code they were.
+template <bool kRing = false>
 __device__ __forceinline__ double field_at(const FollowParams& p, const double* u, const double* v, const double* h, int j, int i) {
-    return p.field == LEC_FOLLOW_HGT ? h[(size_t)j * p.nx + i] : zeta_at(p, u, v, j, i);
+    if constexpr (kRing) return p.field == LEC_FOLLOW_HGT ? h[(size_t)j * p.nx + i] : zeta_ring_at(p, u, v, j, i);
+    else return p.field == LEC_FOLLOW_HGT ? h[(size_t)j * p.nx + i] : zeta_at(p, u, v, j, i);
 }
 
 // the extremum of the whole workgroup, in every thread: wave64 shuffles, then the waves' partials through LDS.  The caller keeps a
@@ -61,14 +65,26 @@ __device__ __forceinline__ Best reduce_best(Best b, bool want_max, double* sv, i
 
 // S at one point straight from global memory: the mean of the finite field values within r, summed in row-major order.  False (and s
 // untouched) where none is finite.  ONE function for lec_follow's first step without a start and for lec_follow_seeds: the same doubles.
+// kRing: always 2 r + 1 columns, west to east from i - r on the ring (2 r + 1 <= nx: the host's check); the wrap is a compare.
+template <bool kRing = false>
 __device__ __forceinline__ bool smooth_global(const FollowParams& p, const double* u, const double* v, const double* h, int j, int i, double& s) {
     const int r = p.r;
     double sum = 0.0; int cnt = 0;
-    for (int jj = max(j - r, 0); jj <= min(j + r, p.ny - 1); ++jj)
-        for (int ii = max(i - r, 0); ii <= min(i + r, p.nx - 1); ++ii) {
-            const double f = field_at(p, u, v, h, jj, ii);
-            if (finite(f)) { sum += f; ++cnt; }
-        }
+    if (kRing) {
+        const int iw = i - r < 0 ? i - r + p.nx : i - r;
+        for (int jj = max(j - r, 0); jj <= min(j + r, p.ny - 1); ++jj)
+            for (int k = 0, ii = iw; k <= 2 * r; ++k) {
+                const double f = field_at<true>(p, u, v, h, jj, ii);
+                if (finite(f)) { sum += f; ++cnt; }
+                if (++ii == p.nx) ii = 0;
+            }
+    } else {
+        for (int jj = max(j - r, 0); jj <= min(j + r, p.ny - 1); ++jj)
+            for (int ii = max(i - r, 0); ii <= min(i + r, p.nx - 1); ++ii) {
+                const double f = field_at(p, u, v, h, jj, ii);
+                if (finite(f)) { sum += f; ++cnt; }
+            }
+    }
     if (cnt) s = sum / cnt;
     return cnt != 0;
 }
@@ -99,7 +115,11 @@ __device__ __forceinline__ void not_live(int* pos, double* val, int* status, int
 // LEC_FOLLOW_NOT_LIVE, span [2] gets (first good step, last good step).  The walked steps are the very statements of the other two.
 // kResume (lec_follow_spans_chunk): kSpans on a chunk of the series -- the counters start from sp's, the good steps are counted in
 // series steps (local step + sp.t_base), and the chain's state goes to sp.state at the end.
-template <int kMode>
+// kRing (kResume only): the window's columns ic - si .. ic + si are never cut, they run west to east on the ring; LDS tile column c is
+// ring column (ic - si - r + c) mod nx, so a tile row is at most two contiguous runs of the slice's row and the lanes stay along
+// longitude.  i0, i1, it0, it1 are UNWRAPPED columns (i0 may be negative, i1 beyond nx - 1): only the tile's load and the new centre
+// wrap, each with a compare, and nothing in the mean's inner loop knows of the ring.  2 si + 1 + 2 r <= nx is the host's check.
+template <int kMode, bool kRing = false>
 __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int ic, int* pos, double* val, int* status, char* smem,
                                              const SpanRule sp = SpanRule{}) {
     double* sv = (double*)smem;                     // [kWaves]
@@ -122,7 +142,7 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
         const double* h = p.h ? p.h + t * plane : nullptr;
         const bool whole = kMode == kPlain && jc < 0;      // step 0 without a start: every admissible centre
         const int j0 = whole ? p.jlo : max(p.jlo, jc - p.sj), j1 = whole ? p.jhi : min(p.jhi, jc + p.sj);
-        const int i0 = whole ? p.ilo : max(p.ilo, ic - p.si), i1 = whole ? p.ihi : min(p.ihi, ic + p.si);
+        const int i0 = kRing ? ic - p.si : whole ? p.ilo : max(p.ilo, ic - p.si), i1 = kRing ? ic + p.si : whole ? p.ihi : min(p.ihi, ic + p.si);
         const int nxw = i1 - i0 + 1, npt = nxw * (j1 - j0 + 1);
         Best b{want_max ? -inf : inf, none};
         if (whole) {
@@ -133,9 +153,18 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
             }
         } else {
             // (a) the field on the window grown by r (clipped to the slice), coalesced along longitude
-            const int jt0 = max(j0 - r, 0), jt1 = min(j1 + r, p.ny - 1), it0 = max(i0 - r, 0), it1 = min(i1 + r, p.nx - 1);
+            const int jt0 = max(j0 - r, 0), jt1 = min(j1 + r, p.ny - 1);
+            const int it0 = kRing ? i0 - r : max(i0 - r, 0), it1 = kRing ? i1 + r : min(i1 + r, p.nx - 1);
             const int tw = it1 - it0 + 1, ntile = tw * (jt1 - jt0 + 1);
-            for (int n = tid; n < ntile; n += kThreads) tile[n] = field_at(p, u, v, h, jt0 + n / tw, it0 + n % tw);
+            for (int n = tid; n < ntile; n += kThreads) {
+                if (kRing) {
+                    int i = it0 + n % tw;                       // -nx < i < 2 nx
+                    i = i < 0 ? i + p.nx : i >= p.nx ? i - p.nx : i;
+                    tile[n] = field_at<true>(p, u, v, h, jt0 + n / tw, i);
+                } else {
+                    tile[n] = field_at(p, u, v, h, jt0 + n / tw, it0 + n % tw);
+                }
+            }
             __syncthreads();
             // (b) the mean of the finite neighbours, summed in row-major order; (c) this thread's extremum
             for (int n = tid; n < npt; n += kThreads) {
@@ -154,7 +183,10 @@ __device__ __forceinline__ void follow_chain(const FollowParams& p, int jc, int 
         b = reduce_best(b, want_max, sv, sn);
         const bool found = b.n != none;
         // (d) the next step's centre; a window without a finite value keeps the one it has
-        if (found) { jc = j0 + b.n / nxw; ic = i0 + b.n % nxw; }
+        if (found) {
+            jc = j0 + b.n / nxw; ic = i0 + b.n % nxw;
+            if (kRing) ic = ic < 0 ? ic + p.nx : ic >= p.nx ? ic - p.nx : ic;
+        }
         else if (whole) { jc = p.jlo; ic = p.ilo; }
         if (tid == 0) {
             pos[2 * (size_t)t] = jc; pos[2 * (size_t)t + 1] = ic;
@@ -277,6 +309,55 @@ __global__ void __launch_bounds__(kThreads) lec_follow_spans_chunk_kernel(const 
                                    born ? -1 : last, state});
 }
 
+// lec_follow_spans_chunk_ring: the kernel above, statement for statement, around the chain's ring variant.  (A copy, not a shared
+// body: with the entry checks in a function of their own the existing kernel no longer compiled to the instructions it had.)  ilo = 0
+// and ihi = nx - 1 here (the host's check): every column is a centre, and a carried ic outside [0, nx) counts as stopped.
+__global__ void __launch_bounds__(kThreads) lec_follow_spans_chunk_ring_kernel(const FollowParams p, const int* __restrict__ start, double end_threshold,
+                                                                               int patience, int* __restrict__ span, int t_base, int* state_all) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const size_t c = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int t0 = start[3 * c], js = start[3 * c + 1], is = start[3 * c + 2];
+    int* pos = p.pos + 2 * c * (size_t)p.nt;
+    double* val = p.val + c * (size_t)p.nt;
+    int* status = p.status + c * (size_t)p.nt;
+    int* state = state_all + 8 * c;
+    if (t0 < 0 || js < p.jlo || js > p.jhi || is < p.ilo || is > p.ihi) {
+        for (int t = tid; t < p.nt; t += kThreads) {
+            pos[2 * (size_t)t] = -1; pos[2 * (size_t)t + 1] = -1;
+            val[t] = nan("");
+            status[t] = LEC_FOLLOW_BAD_START;
+        }
+        if (tid == 0) {
+            span[2 * c] = -1; span[2 * c + 1] = -1;
+            state[0] = kBadStart; state[1] = -1; state[2] = -1; state[3] = 0; state[4] = -1; state[5] = -1; state[6] = 0; state[7] = 0;
+        }
+        return;
+    }
+    int* sh = (int*)(smem + kLdsFixed);
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < 6; ++k) sh[k] = state[k];
+    }
+    __syncthreads();
+    const int phase = sh[0], jc = sh[1], ic = sh[2], weak = sh[3], first = sh[4], last = sh[5];
+    __syncthreads();                                // (the tile is free again)
+    const long long born_at = (long long)t0 - t_base;                 // the local step of the birth
+    const bool born = phase == kUnborn && born_at >= 0 && born_at < p.nt;
+    const bool walks = phase == kWalking && jc >= p.jlo && jc <= p.jhi && ic >= p.ilo && ic <= p.ihi;
+    if (!born && !walks) {
+        // not yet born (the state stays as it is), stopped, or a state that is none of the rule's: no step of this chunk is walked
+        not_live(pos, val, status, 0, p.nt);
+        const bool has_span = phase == kStopped || phase == kWalking;
+        if (tid == 0) { span[2 * c] = has_span ? first : -1; span[2 * c + 1] = has_span ? last : -1; }
+        return;
+    }
+    // born here: from the table's start with fresh counters; walking: from the state's centre with its counters
+    follow_chain<kResume, true>(p, born ? js : jc, born ? is : ic, pos, val, status, smem,
+                                SpanRule{born ? (int)born_at : 0, end_threshold, patience, span + 2 * c, t_base, born ? 0 : weak, born ? -1 : first,
+                                         born ? -1 : last, state});
+}
+
 // ---- lec_follow_seeds: the systems of ONE slice (the rule: include/lec_hip.h) ----------------------------------------------------
 struct SeedParams {
     FollowParams f;             // one slice: nt = 1; the field, the tables, r, the admissible bounds
@@ -290,10 +371,11 @@ struct SeedParams {
 // on slice t of a series (at()), so that step t's seeds are lec_follow_seeds' on that slice by construction.
 
 // (a) S of the whole slice -> work; NaN where S is not finite.  One thread per point, row-major: the lanes run along longitude.
+template <bool kRing = false>
 __device__ __forceinline__ void seeds_smooth(const SeedParams& q, unsigned n) {
     const FollowParams& p = q.f;
     double s;
-    const bool any = smooth_global(p, p.u, p.v, p.h, n / p.nx, n % p.nx, s);
+    const bool any = smooth_global<kRing>(p, p.u, p.v, p.h, n / p.nx, n % p.nx, s);
     q.work[n] = any && finite(s) ? s : nan("");
 }
 
@@ -309,6 +391,9 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_smooth_kernel(const SeedPa
 // P's (the neighbourhood is symmetric), so S(R) is worse than S(P), or equal and later in row-major order: R fails its test on P's true
 // value and on the sentinel alike.  (Marking NON-candidates in place would not be safe: a point could lose the very neighbour that
 // disqualifies it.)  Every thread reads its own S before it may write it.  8-byte relaxed atomics: a reader sees the old or the new double.
+// kRing: the neighbourhood's columns are the 2 ei + 1 within ring distance ei (2 ei + 1 <= nx: the host's check), and "before" keeps the
+// slice's absolute row-major index -- a tie is the one thing that depends on where the seam lies.
+template <bool kRing = false>
 __device__ __forceinline__ void seeds_candidate(const SeedParams& q, unsigned n) {
     const FollowParams& p = q.f;
     const int nxa = p.ihi - p.ilo + 1;
@@ -318,13 +403,28 @@ __device__ __forceinline__ void seeds_candidate(const SeedParams& q, unsigned n)
     const double s = __hip_atomic_load(q.work + (size_t)j * p.nx + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (!finite(s)) return;
     if (q.threshold == q.threshold && (want_max ? s < q.threshold : s > q.threshold)) return;
-    for (int jj = max(j - q.ej, 0); jj <= min(j + q.ej, p.ny - 1); ++jj) {
-        const double* row = q.work + (size_t)jj * p.nx;
-        for (int ii = max(i - q.ei, 0); ii <= min(i + q.ei, p.nx - 1); ++ii) {
-            const double o = __hip_atomic_load(row + ii, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (o != o || (jj == j && ii == i)) continue;
-            const bool before = jj < j || (jj == j && ii < i);
-            if (want_max ? (o > s || (o == s && before)) : (o < s || (o == s && before))) return;
+    if (kRing) {
+        const int iw = i - q.ei < 0 ? i - q.ei + p.nx : i - q.ei;
+        for (int jj = max(j - q.ej, 0); jj <= min(j + q.ej, p.ny - 1); ++jj) {
+            const double* row = q.work + (size_t)jj * p.nx;
+            for (int k = 0, ii = iw; k <= 2 * q.ei; ++k) {
+                const double o = __hip_atomic_load(row + ii, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                const bool before = jj < j || (jj == j && ii < i);
+                const bool self = jj == j && ii == i;
+                if (++ii == p.nx) ii = 0;
+                if (o != o || self) continue;
+                if (want_max ? (o > s || (o == s && before)) : (o < s || (o == s && before))) return;
+            }
+        }
+    } else {
+        for (int jj = max(j - q.ej, 0); jj <= min(j + q.ej, p.ny - 1); ++jj) {
+            const double* row = q.work + (size_t)jj * p.nx;
+            for (int ii = max(i - q.ei, 0); ii <= min(i + q.ei, p.nx - 1); ++ii) {
+                const double o = __hip_atomic_load(row + ii, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                if (o != o || (jj == j && ii == i)) continue;
+                const bool before = jj < j || (jj == j && ii < i);
+                if (want_max ? (o > s || (o == s && before)) : (o < s || (o == s && before))) return;
+            }
         }
     }
     __hip_atomic_store(q.work + (size_t)j * p.nx + i, want_max ? inf : -inf, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -340,6 +440,7 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_candidate_kernel(const See
 // (c) ONE workgroup.  First the admissible centres of work become what the selection reads: a candidate gets its S back (smooth_global
 // again: the double of phase (a)), everything else NaN.  Then k_max times: the best remaining candidate -- key: the value, then the
 // slice's row-major index, through reduce_best -- is written out and struck by the thread that scans it.
+template <bool kRing = false>
 __device__ __forceinline__ void seeds_select(const SeedParams& q, double* sv, int* sn) {
     const FollowParams& p = q.f;
     const int tid = threadIdx.x;
@@ -351,7 +452,7 @@ __device__ __forceinline__ void seeds_select(const SeedParams& q, double* sv, in
         const int j = p.jlo + n / nxa, i = p.ilo + n % nxa;
         double* w = q.work + (size_t)j * p.nx + i;
         double s = nan("");
-        if (*w == (want_max ? inf : -inf)) smooth_global(p, p.u, p.v, p.h, j, i, s);
+        if (*w == (want_max ? inf : -inf)) smooth_global<kRing>(p, p.u, p.v, p.h, j, i, s);
         *w = s;
     }
     int found = 0;
@@ -417,6 +518,28 @@ __global__ void __launch_bounds__(kThreads) lec_seeds_series_select_kernel(const
     }
 }
 
+// lec_follow_seeds_series_ring: the three kernels above with the ring variants of the phases
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_smooth_ring_kernel(const SeedParams q, int nt) {
+    const unsigned long long plane = (unsigned long long)q.f.ny * q.f.nx, total = plane * nt;
+    for (unsigned long long m = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; m < total; m += (unsigned long long)gridDim.x * kThreads)
+        seeds_smooth<true>(at(q, m / plane), (unsigned)(m % plane));
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_candidate_ring_kernel(const SeedParams q, int nt) {
+    const unsigned long long na = (unsigned long long)(q.f.ihi - q.f.ilo + 1) * (q.f.jhi - q.f.jlo + 1), total = na * nt;
+    for (unsigned long long m = (unsigned long long)blockIdx.x * kThreads + threadIdx.x; m < total; m += (unsigned long long)gridDim.x * kThreads)
+        seeds_candidate<true>(at(q, m / na), (unsigned)(m % na));
+}
+
+__global__ void __launch_bounds__(kThreads) lec_seeds_series_select_ring_kernel(const SeedParams q, int nt) {
+    __shared__ double sv[kWaves];
+    __shared__ int sn[kWaves];
+    for (long long t = blockIdx.x; t < nt; t += gridDim.x) {
+        seeds_select<true>(at(q, (size_t)t), sv, sn);
+        __syncthreads();
+    }
+}
+
 }  // namespace
 
 namespace {
@@ -479,6 +602,19 @@ FollowParams slice_params(const A* a, int nt) {
     p.field = a->field; p.sense = a->sense; p.r = a->smooth_r;
     p.jlo = a->jlo; p.jhi = a->jhi; p.ilo = a->ilo; p.ihi = a->ihi; p.j_start = -1; p.i_start = -1;
     return p;
+}
+
+// what the ring calls ask on top: every column is an admissible centre, and the columns a point reads (`reach`: the tile's
+// 2 si + 1 + 2 smooth_r, a seed's 2 ei + 1 or 2 smooth_r + 1) do not meet themselves on the ring.  Refused, never clamped.
+template <class A>
+int check_ring(const char* who, const A* a, long long reach, const char* what) {
+    if (a->ilo != 0 || a->ihi != a->nx - 1) return refuse(LEC_ERR_ARG, who, "on a ring every column is an admissible centre: needs ilo = 0 and ihi = nx - 1");
+    if (reach > a->nx) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "%s = %lld columns exceed nx = %d: on a ring the window would meet itself", what, reach, a->nx);
+        return refuse(LEC_ERR_ARG, who, msg);
+    }
+    return LEC_OK;
 }
 
 int launched(const char* who) {
@@ -573,11 +709,16 @@ extern "C" int lec_follow_seeds(const lec_follow_seeds_args* a) {
     return launched(who);
 }
 
-extern "C" int lec_follow_seeds_series(const lec_follow_seeds_series_args* a) {
-    const char* who = "lec_follow_seeds_series";
+namespace {
+
+int seeds_series(const lec_follow_seeds_series_args* a, const char* who, bool ring) {
     if (!a) return refuse(LEC_ERR_ARG, who, "null args");
     SeedParams q;
     if (int rc = seed_params(who, a, a->nt, &q)) return rc;
+    if (ring) {
+        if (int rc = check_ring(who, a, 2LL * a->ei + 1, "2 ei + 1")) return rc;
+        if (int rc = check_ring(who, a, 2LL * a->smooth_r + 1, "2 smooth_r + 1")) return rc;
+    }
     // nt * ny * nx doubles: the byte offsets into the series must fit 64 bits with room to spare
     const unsigned long long plane = (unsigned long long)a->ny * (unsigned long long)a->nx;
     if ((unsigned long long)a->nt > (1ULL << 59) / plane) return refuse(LEC_ERR_UNSUPPORTED, who, "series too large (nt * ny * nx)");
@@ -588,11 +729,23 @@ extern "C" int lec_follow_seeds_series(const lec_follow_seeds_series_args* a) {
         const unsigned long long g = (items + kThreads - 1) / kThreads;
         return dim3((unsigned)(g < kSeriesGrid ? g : kSeriesGrid));
     };
-    hipLaunchKernelGGL(lec_seeds_series_smooth_kernel, grid(n_all), dim3(kThreads), 0, st, q, a->nt);
-    hipLaunchKernelGGL(lec_seeds_series_candidate_kernel, grid(n_adm), dim3(kThreads), 0, st, q, a->nt);
-    hipLaunchKernelGGL(lec_seeds_series_select_kernel, dim3((unsigned)((unsigned)a->nt < kSeriesGrid ? (unsigned)a->nt : kSeriesGrid)), dim3(kThreads), 0, st, q, a->nt);
+    const dim3 steps((unsigned)((unsigned)a->nt < kSeriesGrid ? (unsigned)a->nt : kSeriesGrid));
+    if (ring) {
+        hipLaunchKernelGGL(lec_seeds_series_smooth_ring_kernel, grid(n_all), dim3(kThreads), 0, st, q, a->nt);
+        hipLaunchKernelGGL(lec_seeds_series_candidate_ring_kernel, grid(n_adm), dim3(kThreads), 0, st, q, a->nt);
+        hipLaunchKernelGGL(lec_seeds_series_select_ring_kernel, steps, dim3(kThreads), 0, st, q, a->nt);
+    } else {
+        hipLaunchKernelGGL(lec_seeds_series_smooth_kernel, grid(n_all), dim3(kThreads), 0, st, q, a->nt);
+        hipLaunchKernelGGL(lec_seeds_series_candidate_kernel, grid(n_adm), dim3(kThreads), 0, st, q, a->nt);
+        hipLaunchKernelGGL(lec_seeds_series_select_kernel, steps, dim3(kThreads), 0, st, q, a->nt);
+    }
     return launched(who);
 }
+
+}  // namespace
+
+extern "C" int lec_follow_seeds_series(const lec_follow_seeds_series_args* a) { return seeds_series(a, "lec_follow_seeds_series", false); }
+extern "C" int lec_follow_seeds_series_ring(const lec_follow_seeds_series_args* a) { return seeds_series(a, "lec_follow_seeds_series_ring", true); }
 
 extern "C" int lec_follow_spans(const lec_follow_spans_args* a) {
     const char* who = "lec_follow_spans";
@@ -617,8 +770,9 @@ extern "C" int lec_follow_spans(const lec_follow_spans_args* a) {
     return launched(who);
 }
 
-extern "C" int lec_follow_spans_chunk(const lec_follow_chunk_args* a) {
-    const char* who = "lec_follow_spans_chunk";
+namespace {
+
+int spans_chunk_call(const lec_follow_chunk_args* a, const char* who, bool ring) {
     if (!a) return refuse(LEC_ERR_ARG, who, "null args");
     const NamedPtr ptrs[] = {{a->u_d, "u_d"}, {a->v_d, "v_d"}, {a->xcoef_d, "xcoef_d"}, {a->ycoef_d, "ycoef_d"}, {a->curv_d, "curv_d"},
                              {a->start_d, "start_d"}, {a->pos_d, "pos_d"}, {a->val_d, "val_d"}, {a->status_d, "status_d"}, {a->span_d, "span_d"},
@@ -631,15 +785,23 @@ extern "C" int lec_follow_spans_chunk(const lec_follow_chunk_args* a) {
     if ((long long)a->t_base + a->nt > 0x7fffffffLL) return refuse(LEC_ERR_ARG, who, "t_base + nt must fit a 32-bit series step");
     long long lds;
     if (int rc = check_window(who, a, &lds)) return rc;
+    if (ring)
+        if (int rc = check_ring(who, a, 2LL * a->si + 1 + 2LL * a->smooth_r, "2 si + 1 + 2 smooth_r")) return rc;
     FollowParams p = slice_params(a, a->nt);
     p.sj = a->sj; p.si = a->si;
     p.pos = a->pos_d; p.val = a->val_d; p.status = a->status_d;
     hipStream_t st = (hipStream_t)a->stream;
+    const auto kernel = ring ? lec_follow_spans_chunk_ring_kernel : lec_follow_spans_chunk_kernel;
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)lec_follow_spans_chunk_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return refuse(LEC_ERR_LAUNCH, who, hipGetErrorString(e));
     }
-    hipLaunchKernelGGL(lec_follow_spans_chunk_kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d, a->end_threshold, a->patience,
+    hipLaunchKernelGGL(kernel, dim3(a->n_chains), dim3(kThreads), (size_t)lds, st, p, a->start_d, a->end_threshold, a->patience,
                        a->span_d, a->t_base, a->state_d);
     return launched(who);
 }
+
+}  // namespace
+
+extern "C" int lec_follow_spans_chunk(const lec_follow_chunk_args* a) { return spans_chunk_call(a, "lec_follow_spans_chunk", false); }
+extern "C" int lec_follow_spans_chunk_ring(const lec_follow_chunk_args* a) { return spans_chunk_call(a, "lec_follow_spans_chunk_ring", true); }

@@ -27,3 +27,19 @@ __device__ __forceinline__ double zeta_at(const P& p, const double* u, const dou
     const double du = cy[0] * uc[0] + cy[1] * uc[p.nx] + cy[2] * uc[2 * (size_t)p.nx];
     return dv - du + p.curv[j] * u[(size_t)j * p.nx + i];
 }
+
+// zeta_at on a RING of longitudes (lec_follow.hip's ring calls): the stencil at column i reads columns i - 1, i, i + 1 mod nx for every
+// i, and xcoef holds the centred coefficients at all columns (the spacing from column nx - 1 to column 0 is the arc across the seam).
+// The latitude stencil and curv are zeta_at's; so is the expression, term for term: an interior column gives zeta_at's double.
+template <class P>
+__device__ __forceinline__ double zeta_ring_at(const P& p, const double* u, const double* v, int j, int i) {
+    const int j0 = min(max(j - 1, 0), p.ny - 3);
+    const int iw = i == 0 ? p.nx - 1 : i - 1, ie = i == p.nx - 1 ? 0 : i + 1;
+    const double* cx = p.xcoef + 3 * ((size_t)j * p.nx + i);
+    const double* cy = p.ycoef + 3 * (size_t)j;
+    const double* vr = v + (size_t)j * p.nx;
+    const double dv = cx[0] * vr[iw] + cx[1] * vr[i] + cx[2] * vr[ie];
+    const double* uc = u + (size_t)j0 * p.nx + i;
+    const double du = cy[0] * uc[0] + cy[1] * uc[p.nx] + cy[2] * uc[2 * (size_t)p.nx];
+    return dv - du + p.curv[j] * u[(size_t)j * p.nx + i];
+}

@@ -394,14 +394,90 @@ class ProcessIndex:
     time: np.ndarray
 
 
+def wrap180(x):
+    """Longitudes into [-180, 180)."""
+    return (np.asarray(x, dtype=np.float64) + 180.0) % 360.0 - 180.0
+
+
+def _box_edges(track: pd.DataFrame, lon) -> tuple:
+    """(west, east) edges of every box of a track whose centres' longitudes are ``lon``: lon -+ width / 2, 15 degrees by default."""
+    half = (track["width"].values.astype(np.float64) if "width" in track.columns else np.full(len(track), 15.0)) / 2
+    return lon - half, lon + half
+
+
+def track_lon_origin(file_lon, track: pd.DataFrame, why: Optional[list] = None) -> float:
+    """Where the longitude axis is cut for this track: 0.0 -- the axis of every run so far, -180..180 -- or 180.0 -- 0..360, the seam at
+    Greenwich -- for a track that crosses the +-180 meridian.  180.0 only when both hold:
+    (a) on -180..180 two consecutive ``Lon`` differ by more than 180 degrees, or some box edge ``Lon -+ width / 2`` lies outside [-180, 180];
+    (b) on 0..360 the file's axis covers every box edge of ``Lon mod 360`` with no spacing above 1.5 x its median in between, and the
+        track's extent there is at most 180 degrees.
+    Otherwise 0.0: the run is what it was, clamped boxes included.  ``why``: a list that receives the reason as one sentence."""
+    say = why.append if why is not None else (lambda _: None)
+    lon = track["Lon"].values.astype(np.float64)
+    west, east = _box_edges(track, lon)
+    jumps = lon.size > 1 and bool(np.any(np.abs(np.diff(lon)) > 180.0))
+    outside = bool(np.any(west < -180.0) or np.any(east > 180.0))
+    if not (jumps or outside):
+        say("the track's boxes lie inside -180..180")
+        return 0.0
+    what = "consecutive centres of the track differ by more than 180 degrees" if jumps else "a box edge of the track lies outside -180..180"
+    lon = lon % 360.0
+    west, east = _box_edges(track, lon)
+    w, e = float(west.min()), float(east.max())
+    axis = np.unique(np.asarray(file_lon, dtype=np.float64) % 360.0)
+    if lon.max() - lon.min() > 180.0:
+        say(f"{what}, but on 0..360 the track extends over more than 180 degrees")
+        return 0.0
+    if axis.size < 3 or w < axis[0] or e > axis[-1]:
+        say(f"{what}, but on 0..360 the file's longitudes ({float(axis[0])}..{float(axis[-1])}) do not cover the boxes ({w}..{e})")
+        return 0.0
+    inside = axis[max(int(np.searchsorted(axis, w, "right")) - 1, 0): int(np.searchsorted(axis, e, "left")) + 1]
+    if np.any(np.diff(inside) > 1.5 * np.median(np.diff(axis))):
+        say(f"{what}, but on 0..360 the file's longitudes have a gap between {w} and {e}")
+        return 0.0
+    say(f"{what}, and on 0..360 the file's longitudes cover its boxes ({w}..{e}) without a gap")
+    return 180.0
+
+
+def lon_origin_of_axis(lon) -> float:
+    """The origin a SORTED longitude axis was built with (``_sorted_axes``): 180.0 when it reaches beyond 180 degrees, else 0.0."""
+    return 180.0 if float(np.max(lon)) > 180.0 else 0.0
+
+
+def track_on_axis(track: pd.DataFrame, lon) -> pd.DataFrame:
+    """The track as everything downstream of the axes reads it: on an axis of origin 180 its ``Lon`` is ``Lon mod 360``."""
+    if lon_origin_of_axis(lon) == 0.0:
+        return track
+    track = track.copy()
+    track["Lon"] = track["Lon"].values.astype(np.float64) % 360.0
+    return track
+
+
+def file_longitudes(path: str, variable_list_df: pd.DataFrame, mpas: bool = False) -> np.ndarray:
+    """The longitude coordinate of a data file as stored."""
+    nc, names, geo_role, lat, lon, lev, time, level_units, want = _open_nc(path, variable_list_df, mmap=True, mpas=mpas)
+    nc.close()
+    return np.array(lon)
+
+
 def process_index(lat, lon, lev, time, level_units, names, args, app_logger=None) -> ProcessIndex:
     """process_data (preprocessing.py:149-371) on the coordinates only: track-time selection, 0..360 -> -180..180
-    longitudes, level -> Pa, sort lon / level / lat ascending, drop levels above 10 hPa."""
+    longitudes, level -> Pa, sort lon / level / lat ascending, drop levels above 10 hPa.  A track that crosses the +-180 meridian
+    gets the seam elsewhere (``track_lon_origin``, derived here from the track that is read anyway; ``args.lon_origin`` overrides)."""
     tpos = None
+    origin = getattr(args, "lon_origin", None)
     if getattr(args, "track", False):
-        tpos = select_track_times(time, read_track(args.trackfile, app_logger))
+        track = read_track(args.trackfile, app_logger)
+        if origin is None:
+            why = []
+            origin = track_lon_origin(lon, track, why)
+            if app_logger is not None and (origin or "but" in why[0]):
+                app_logger.info(f"Longitude axis of this run: {'0..360 (the seam at Greenwich)' if origin else '-180..180'}: {why[0]}"
+                                + ("; every longitude written to a file is wrapped back into -180..180" if origin else
+                                   "; the boxes are cut at the +-180 meridian as before"))
+        tpos = select_track_times(time, track)
         time = time[tpos]
-    return _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger)
+    return _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger, lon_origin=origin or 0.0)
 
 
 def select_track_times(time: np.ndarray, track: pd.DataFrame) -> np.ndarray:
@@ -425,8 +501,14 @@ def select_track_times(time: np.ndarray, track: pd.DataFrame) -> np.ndarray:
     return tpos
 
 
-def _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger=None) -> ProcessIndex:
-    if lon.min() < -180 or lon.max() > 180:
+def _sorted_axes(tpos, lat, lon, lev, time, level_units, names, app_logger=None, lon_origin: float = 0.0) -> ProcessIndex:
+    """``lon_origin`` 0.0: the longitudes on -180..180, as the reference has them; 180.0: ``lon mod 360`` in [0, 360) (a track across
+    the +-180 meridian: ``track_lon_origin``).  Either way the sort is an index map, ``io``."""
+    if lon_origin == 180.0:
+        lon = np.asarray(lon, dtype=np.float64) % 360.0
+    elif lon_origin != 0.0:
+        raise ValueError(f"the longitude axis is cut at origin 0 or 180, not {lon_origin!r}")
+    elif lon.min() < -180 or lon.max() > 180:
         lon = (lon + 180) % 360 - 180                                   # tools.py:76-92
     key = (level_units or "hPa").strip().lower()
     if level_units is None and app_logger:
@@ -465,6 +547,7 @@ def domain_slices(lat: np.ndarray, lon: np.ndarray, args, track: Optional[pd.Dat
         dx, dy = lon[1] - lon[0], lat[1] - lat[0]
         if track is None:
             track = read_track(chosen or args.trackfile or "inputs/track")
+        track = track_on_axis(track, lon)
         if "width" in track.columns:
             mw, ml = track["width"].max(), track["length"].max()
         else:

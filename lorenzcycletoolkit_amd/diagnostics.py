@@ -101,8 +101,19 @@ def great_circle_arc(phi1, lam1, phi2, lam2, radius):
     return radius * np.arctan2(y, x)
 
 
-def vorticity_tables(lat_deg, lon_deg, formulation: str = "metpy_no_crs"):
-    """(xcoef [ny][nx][3], ycoef [ny][3], curv [ny]) of struct lec_diag_args for one of FORMULATIONS (module docstring)."""
+def _three_point_ring(d: np.ndarray) -> np.ndarray:
+    """[..., n, 3]: the centred coefficients of ``_three_point`` / ``_three_point_rows`` at ALL n points of a ring whose spacings are
+    d [..., n] (d[i]: from point i to point i + 1, d[n - 1]: across the seam to point 0).  The interior points get the very doubles
+    of the open forms: the same expressions on the same spacings."""
+    d = np.asarray(d, dtype=np.float64)
+    d0, d1 = np.roll(d, 1, axis=-1), d                          # spacing left / right of every point
+    return np.stack([-d1 / (d0 * (d0 + d1)), (d1 - d0) / (d0 * d1), d0 / (d1 * (d0 + d1))], axis=-1)
+
+
+def vorticity_tables(lat_deg, lon_deg, formulation: str = "metpy_no_crs", periodic: bool = False):
+    """(xcoef [ny][nx][3], ycoef [ny][3], curv [ny]) of struct lec_diag_args for one of FORMULATIONS (module docstring).
+    ``periodic``: the longitudes are a full ring (``lec_follow``'s ring calls) -- xcoef holds the centred coefficients at every column,
+    those of columns 0 and nx - 1 over the arc across the seam; columns 1 .. nx - 2, ycoef and curv are the same doubles."""
     if formulation not in FORMULATIONS:
         raise ValueError(f"vorticity formulation must be one of {FORMULATIONS}, not {formulation!r}")
     phi = np.deg2rad(np.asarray(lat_deg, dtype=np.float64))
@@ -110,13 +121,21 @@ def vorticity_tables(lat_deg, lon_deg, formulation: str = "metpy_no_crs"):
     ny, nx = phi.size, lam.size
     if formulation == "spherical":
         from .constants import RE
-        xc = _three_point(lam)[None, :, 1:] / (RE * np.cos(phi))[:, None, None]
+        if periodic:
+            xl = _three_point_ring(np.append(np.diff(lam), 2 * np.pi - (lam[-1] - lam[0])))
+        else:
+            xl = _three_point(lam)[:, 1:]
+        xc = xl[None, :, :] / (RE * np.cos(phi))[:, None, None]
         yc = _three_point(phi)[:, 1:] / RE
         curv = np.tan(phi) / RE
     else:
         a = PYPROJ_SPHERE_RADIUS
         dx = great_circle_arc(phi[:, None], lam[None, :-1], phi[:, None], lam[None, 1:], a)        # [ny][nx - 1], along each row
-        xc = _three_point_rows(dx)
+        if periodic:
+            seam = great_circle_arc(phi[:, None], lam[None, -1:], phi[:, None], lam[None, :1] + 2 * np.pi, a)
+            xc = _three_point_ring(np.concatenate([dx, seam], axis=1))
+        else:
+            xc = _three_point_rows(dx)
         dy = great_circle_arc(phi[:-1], 0.0, phi[1:], 0.0, a)                                         # [ny - 1]: the same for every column
         yc = _three_point_rows(dy[None, :])[0]
         curv = np.zeros(ny)

@@ -39,17 +39,38 @@ DEFAULT_BOX = (15.0, 15.0)              # length, width in degrees: the referenc
 DEFAULT_SEARCH = 5.0                    # degrees per time step
 
 
-def admissible(lat, lon, length, width) -> tuple:
+def admissible(lat, lon, length, width, periodic=False) -> tuple:
     """(jlo, jhi, ilo, ihi): inclusive index bounds of the grid points whose box (lat +- length / 2, lon +- width / 2) lies inside the
-    coordinate range of the (sorted, possibly stretched) axes.  A box larger than the domain is refused."""
+    coordinate range of the (sorted, possibly stretched) axes.  A box larger than the domain is refused.  ``periodic``: the longitudes
+    are a ring -- every column is a centre (0, nx - 1); the latitude half is the same."""
     lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
     jj = np.flatnonzero((lat - length / 2 >= lat[0]) & (lat + length / 2 <= lat[-1]))
-    ii = np.flatnonzero((lon - width / 2 >= lon[0]) & (lon + width / 2 <= lon[-1]))
+    ii = np.arange(lon.size) if periodic else np.flatnonzero((lon - width / 2 >= lon[0]) & (lon + width / 2 <= lon[-1]))
     if jj.size == 0 or ii.size == 0:
         raise ValueError(f"a box of {length} x {width} degrees (length x width) does not fit into the search domain of "
                          f"{float(lat[-1] - lat[0])} x {float(lon[-1] - lon[0])} degrees (lat {float(lat[0])}..{float(lat[-1])}, "
                          f"lon {float(lon[0])}..{float(lon[-1])}): no grid point can be its centre")
     return int(jj[0]), int(jj[-1]), int(ii[0]), int(ii[-1])
+
+
+def ring_error(lon):
+    """None when the sorted longitudes are a full ring -- evenly spaced with nx * dx = 360 degrees, both to within 1e-6 dx -- else the
+    sentence that says what they are instead (--choose-periodic refuses with it)."""
+    lon = np.asarray(lon, dtype=np.float64)
+    d = np.diff(lon)
+    dx = float(np.median(d))
+    extent = f"the search domain's longitudes run from {float(lon[0])} to {float(lon[-1])} in {lon.size} columns"
+    if not (dx > 0 and np.all(np.abs(d - dx) <= 1e-6 * dx)):
+        return f"{extent}, unevenly spaced: no ring"
+    if abs(lon.size * dx - 360.0) > 1e-6 * dx:
+        return f"{extent} of {dx} degrees = {lon.size * dx} degrees, not the 360 of a full ring"
+    return None
+
+
+def ring_distance(a, b, nx):
+    """|a - b| on a ring of nx columns (arrays or ints); nx None: the plain distance."""
+    d = np.abs(np.asarray(a, dtype=np.int64) - np.asarray(b, dtype=np.int64))
+    return d if nx is None else np.minimum(d % nx, nx - d % nx)
 
 
 def window_steps(lat, lon, search) -> tuple:
@@ -58,11 +79,13 @@ def window_steps(lat, lon, search) -> tuple:
     return step(lat), step(lon)
 
 
-def start_index(lat, lon, start, bounds) -> tuple:
-    """The grid point nearest (LAT, LON) (the first of two equally near ones), clamped into the admissible centres."""
+def start_index(lat, lon, start, bounds, periodic=False) -> tuple:
+    """The grid point nearest (LAT, LON) (the first of two equally near ones), clamped into the admissible centres.  ``periodic``: the
+    longitudes are a ring, nearest is measured on it."""
     jlo, jhi, ilo, ihi = bounds
     j = int(np.argmin(np.abs(np.asarray(lat, dtype=np.float64) - float(start[0]))))
-    i = int(np.argmin(np.abs(np.asarray(lon, dtype=np.float64) - float(start[1]))))
+    di = np.abs(np.asarray(lon, dtype=np.float64) - float(start[1]))
+    i = int(np.argmin(np.minimum(di % 360.0, 360.0 - di % 360.0) if periodic else di))
     return min(max(j, jlo), jhi), min(max(i, ilo), ihi)
 
 
@@ -172,6 +195,11 @@ class _SliceSource:
                 raise
             lat, lon, time = self.plan.lat, self.plan.lon, self.plan.time
         self.lat, self.lon, self.time = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64), time
+        self.periodic = bool(getattr(args, "choose_periodic", False))
+        if self.periodic and ring_error(self.lon):
+            self.close()
+            raise ValueError("--choose-periodic needs a search domain that is a full ring of longitudes: " + ring_error(self.lon)
+                             + " (--choose-domain may cut latitudes only)")
 
     def read(self, t_range=None):
         """(u, v, hgt) of the time steps [a, b) (None: all)."""
@@ -286,12 +314,83 @@ def _resume_chunks(src, chunks, pos, val, status, starts, *, search, device, **k
     return np.concatenate(pos, axis=1), np.concatenate(val, axis=1), np.concatenate(status, axis=1)
 
 
+def _seam_notes(app_logger, src, names, last_i, si):
+    """Without --choose-periodic, on a domain that IS a ring: one line per chain whose last good step lies within si columns of either
+    edge -- it may have ended at the seam, not with its system.  last_i: per chain the column of that step, None: no good step."""
+    if src.periodic or ring_error(src.lon):
+        return
+    nx = src.lon.size
+    for name, i in zip(names, last_i):
+        if i is not None and (i <= si or i >= nx - 1 - si):
+            app_logger.info(f"-c/--choose: {name}: its last good time step lies within {si} grid steps of the domain's edge at the +-180 meridian, and "
+                            "the domain is a full ring of longitudes -- the chain may have ended at the seam: --choose-periodic (it follows a system across it)")
+
+
+def _last_good_columns(pos, status):
+    """Per chain of pos [K][nt][2], status [K][nt]: the column of the last step with status 0, or None."""
+    out = []
+    for c in range(len(pos)):
+        good = np.flatnonzero(np.asarray(status[c]) == 0)
+        out.append(int(pos[c][good[-1]][1]) if good.size else None)
+    return out
+
+
+def _ring_chains(src, chunks, first, seeds, *, search, device, **kw):
+    """The chains of a plain, --choose-systems or --choose-starts run on a ring (--choose-periodic): every chunk, the first included, goes
+    through ``lec_follow_spans_chunk_ring`` with every t0 = 0 and patience 0 -- the resumed form of lec_follow_many (include/lec_hip.h).
+    first: the first chunk's slices, already read; seeds [K][2].  -> (pos [K][nt][2], val [K][nt], status [K][nt])."""
+    import torch
+    K = len(seeds)
+    start = np.zeros((K, 3), dtype=np.int32)
+    start[:, 1:] = seeds
+    start_d = torch.as_tensor(start).to(device)
+    state_d = torch.zeros((K, 8), dtype=torch.int32, device=device)
+    pos, val, status = [], [], []
+    for n, (a, b) in enumerate(chunks):
+        u, v, hgt = first if n == 0 else src.read((a, b))
+        first = None
+        p, x, st, _ = follow_spans_chunk(u, v, hgt, src.lat, src.lon, starts=start_d, state=state_d, t_base=a, patience=0, search=search, device=device,
+                                         periodic=True, **kw)
+        del u, v, hgt
+        pos.append(p); val.append(x); status.append(st)
+    return np.concatenate(pos, axis=1), np.concatenate(val, axis=1), np.concatenate(status, axis=1)
+
+
+def _ring_start(app_logger, u, v, hgt, lat, lon, time, start, *, length, width, device, **kw):
+    """The start of a plain -c run on a ring: the grid point nearest --choose-start, or -- the ring call has no "whole domain" step --
+    seed 0 of step 0 (k_max 1, no threshold), logged."""
+    if start is not None:
+        return start_index(lat, lon, start, admissible(lat, lon, length, width, True), periodic=True)
+    seed_pos, seed_val, n_found = find_systems_series(u[:1], v[:1], None if hgt is None else hgt[:1], lat, lon, k=1, length=length, width=width,
+                                                      device=device, periodic=True, **kw)
+    if n_found[0] == 0:
+        raise ValueError("--choose-periodic: the first time step holds no system to start from: give --choose-start LAT LON")
+    j, i = (int(x) for x in seed_pos[0, 0])
+    app_logger.info(f"-c/--choose: --choose-periodic without --choose-start: the start is the strongest system of {pd.Timestamp(time[0])} "
+                    f"(lec_follow_seeds_series_ring, seed 0: {seed_val[0, 0]} at lat {lat[j]}, lon {lon[i]})")
+    return j, i
+
+
 def _choose_track_chains(args, app_logger, src, length, width, search, smooth, field, form, start, device):
     """write_choose_track's chain: (pos [nt][2], val [nt], status [nt]) over the whole series."""
     chunks, u, v, hgt = _first_chunk(args, src)
     lat, lon, time = src.lat, src.lon, src.time
     hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
     sj, si = window_steps(lat, lon, search)
+    if src.periodic:
+        kw = dict(smooth=smooth, field=field, hemisphere=hemisphere, formulation=form)
+        seed = _ring_start(app_logger, u, v, hgt, lat, lon, time, start, length=length, width=width, device=device, **kw)
+        app_logger.info(f"-c/--choose: following the 850 hPa {'minimum' if sense == _lib.FOLLOW_MIN else 'maximum'} of {field} "
+                        f"({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "") + f") on the GPU across the +-180 "
+                        f"meridian (--choose-periodic: lec_follow_spans_chunk_ring in {len(chunks)} chunk(s)): {len(time)} time steps, search domain lat "
+                        f"{lat[0]}..{lat[-1]}, a ring of {lon.size} longitudes, box {length} x {width} degrees (length x width), at most {search} degrees "
+                        f"= {sj} x {si} grid steps per time step, smoothing radius {smooth}, start lat {lat[seed[0]]}, lon {lon[seed[1]]}")
+        pos, val, status = (a[0] for a in _ring_chains(src, chunks, (u, v, hgt), np.array([seed], dtype=np.int32), search=search, device=device,
+                                                       length=length, width=width, **kw))
+        if status[0]:
+            raise ValueError("the first time step's search window holds no finite value of the field: nothing to follow "
+                             "(another --choose-start or --choose-domain?)")
+        return pos, val, status
     app_logger.info(f"-c/--choose: following the 850 hPa {'minimum' if sense == _lib.FOLLOW_MIN else 'maximum'} of {field} "
                     f"({hemisphere}ern hemisphere" + (f", vorticity formulation '{form}'" if field == "zeta" else "") + f") on the GPU (lec_follow): "
                     f"{len(time)} time steps, search domain lat {lat[0]}..{lat[-1]}, lon {lon[0]}..{lon[-1]} ({lat.size} x {lon.size} points), "
@@ -305,6 +404,7 @@ def _choose_track_chains(args, app_logger, src, length, width, search, smooth, f
     if len(chunks) > 1:
         del u, v, hgt
         pos, val, status = (a[0] for a in _resume_chunks(src, chunks, pos[None], val[None], status[None], pos[None, 0], search=search, device=device, **kw))
+    _seam_notes(app_logger, src, ["the chain"], _last_good_columns(pos[None], status[None]), si)
     return pos, val, status
 
 
@@ -339,17 +439,19 @@ def read_starts(path) -> np.ndarray:
 class _Slices:
     """What lec_follow, lec_follow_seeds and lec_follow_many share: the checked options, the slices and the vorticity tables on the device."""
 
-    def __init__(self, u, v, h, lat, lon, ndim, *, length, width, smooth, field, hemisphere, formulation, device):
+    def __init__(self, u, v, h, lat, lon, ndim, *, length, width, smooth, field, hemisphere, formulation, device, periodic=False):
         import torch
         self.lat, self.lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
         if smooth != int(smooth) or int(smooth) < 0:
             raise ValueError(f"smooth must be a whole number of grid points >= 0, not {smooth!r}")
         self.smooth, self.field = int(smooth), field
         self.hemisphere, self.sense = sense_of(field, hemisphere, self.lat)
-        self.bounds = admissible(self.lat, self.lon, length, width)
+        if periodic and ring_error(self.lon):
+            raise ValueError("the ring calls need a full ring of longitudes: " + ring_error(self.lon))
+        self.bounds = admissible(self.lat, self.lon, length, width, periodic)
         if field == "hgt" and h is None:
             raise ValueError("field 'hgt' needs the geopotential height slices")
-        tables = vorticity_tables(self.lat, self.lon, formulation)
+        tables = vorticity_tables(self.lat, self.lon, formulation, periodic=periodic)
         self.lib = _lib.load()
         self.dev = torch.device(device)
         if self.dev.type != "cuda":
@@ -484,7 +586,8 @@ def _choose_tracks_written(args, batch_dir, app_logger, src, device) -> list:
     threshold, separation = getattr(args, "choose_threshold", None), getattr(args, "choose_separation", None)
     lat, lon, time = src.lat, src.lon, src.time
     hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
-    bounds = admissible(lat, lon, length, width)                      # (refused here, before the upload, if the box does not fit)
+    periodic = src.periodic
+    bounds = admissible(lat, lon, length, width, periodic)            # (refused here, before the upload, if the box does not fit)
     kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form, device=device)
     what = f"the 850 hPa {'minima' if sense == _lib.FOLLOW_MIN else 'maxima'} of {field}"
     dev = torch.device(device)
@@ -494,14 +597,18 @@ def _choose_tracks_written(args, batch_dir, app_logger, src, device) -> list:
     hgt = torch.as_tensor(hgt).to(dev)
     if starts_file is not None:
         seed_ll = read_starts(starts_file)
-        seeds = np.array([start_index(lat, lon, st, bounds) for st in seed_ll], dtype=np.int32)
+        seeds = np.array([start_index(lat, lon, st, bounds, periodic) for st in seed_ll], dtype=np.int32)
         seed_val = np.full(len(seeds), np.nan)
         app_logger.info(f"-c/--choose: {len(seeds)} starts from {starts_file}")
     else:
         sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
-        seeds, seed_val = find_systems(u[0], v[0], hgt[0], lat, lon, k=k, threshold=threshold, separation=sep, **kw)
+        if periodic:
+            sp, sv, sn = find_systems_series(u[:1], v[:1], hgt[:1], lat, lon, k=k, threshold=threshold, separation=sep, periodic=True, **kw)
+            seeds, seed_val = sp[0, :sn[0]], sv[0, :sn[0]]
+        else:
+            seeds, seed_val = find_systems(u[0], v[0], hgt[0], lat, lon, k=k, threshold=threshold, separation=sep, **kw)
         ej, ei = separation_steps(lat, lon, *sep)
-        app_logger.info(f"-c/--choose: {len(seeds)} of at most {k} systems found at {pd.Timestamp(time[0])} (lec_follow_seeds: {what}, "
+        app_logger.info(f"-c/--choose: {len(seeds)} of at most {k} systems found at {pd.Timestamp(time[0])} ({'lec_follow_seeds_series_ring' if periodic else 'lec_follow_seeds'}: {what}, "
                         f"no better value within {sep[0]} x {sep[1]} degrees = {ej} x {ei} grid steps"
                         + ("" if threshold is None else f", threshold {threshold}") + ")")
         if len(seeds) == 0:
@@ -514,10 +621,19 @@ def _choose_tracks_written(args, batch_dir, app_logger, src, device) -> list:
     if len(chunks) > 1:
         _log_chunks(app_logger, chunks, lat.size, lon.size, "the first chunk goes through lec_follow_many, every later one resumes the chains "
                     "(lec_follow_spans_chunk)")
-    pos, val, status = follow_systems(u, v, hgt, lat, lon, seeds=seeds, search=search, **kw)
-    if len(chunks) > 1:
+    if periodic:
+        app_logger.info(f"-c/--choose: --choose-periodic: the longitudes are a ring of {lon.size} columns, the chains cross the +-180 meridian "
+                        f"(lec_follow_spans_chunk_ring in {len(chunks)} chunk(s) instead of lec_follow_many)")
+        first = (u, v, hgt)
         del u, v, hgt
-        pos, val, status = _resume_chunks(src, chunks, pos, val, status, seeds, search=search, **kw)
+        pos, val, status = _ring_chains(src, chunks, first, seeds, search=search, **kw)
+        del first
+    else:
+        pos, val, status = follow_systems(u, v, hgt, lat, lon, seeds=seeds, search=search, **kw)
+        if len(chunks) > 1:
+            del u, v, hgt
+            pos, val, status = _resume_chunks(src, chunks, pos, val, status, seeds, search=search, **kw)
+    _seam_notes(app_logger, src, [f"choose_s{c + 1:02d}" for c in range(len(seeds))], _last_good_columns(pos, status), si)
     shared = first_shared_centre(pos)
     for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
         if name.startswith("choose_s") and name[8:].isdigit():
@@ -560,10 +676,11 @@ DEFAULT_MIN_STEPS = 2                   # what batch.plan_batch accepts as a tra
 
 
 def find_systems_series(u850, v850, hgt850, lat, lon, *, k, threshold=None, separation=None, length=DEFAULT_BOX[0], width=DEFAULT_BOX[1],
-                        smooth=0, field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0", chunk_steps=None):
+                        smooth=0, field="zeta", hemisphere=None, formulation="metpy_no_crs", device="cuda:0", chunk_steps=None, periodic=False):
     """``lec_follow_seeds_series`` on [time, lat, lon] slices: (pos [nt][k][2], val [nt][k], n_found [nt]) -- step t's are ``find_systems``
     on slice t, bit for bit, the unused entries (-2, -2) / NaN.  The library is called on chunks of ``chunk_steps`` steps, so that its
-    scratch stays bounded (default: as many steps as keep it within 256 MiB); the chunks are independent."""
+    scratch stays bounded (default: as many steps as keep it within 256 MiB); the chunks are independent.
+    ``periodic``: ``lec_follow_seeds_series_ring`` -- the longitudes are a full ring (include/lec_hip.h has the rule)."""
     import torch
     if k != int(k) or not 1 <= int(k) <= 256:
         raise ValueError(f"k must be a whole number of systems, 1..256, not {k!r}")
@@ -571,9 +688,10 @@ def find_systems_series(u850, v850, hgt850, lat, lon, *, k, threshold=None, sepa
     if len(sep) != 2 or not min(sep) > 0:
         raise ValueError(f"separation must be two positive numbers of degrees (latitude, longitude), not {separation!r}")
     s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
-                formulation=formulation, device=device)
+                formulation=formulation, device=device, periodic=periodic)
     ej, ei = separation_steps(s.lat, s.lon, *sep)
     nt, k = int(s.u.shape[0]), int(k)
+    call = "lec_follow_seeds_series_ring" if periodic else "lec_follow_seeds_series"
     if chunk_steps is None:
         chunk_steps = max(1, WORK_BYTES // (8 * s.lat.size * s.lon.size))
     if chunk_steps != int(chunk_steps) or int(chunk_steps) < 1:
@@ -592,24 +710,25 @@ def find_systems_series(u850, v850, hgt850, lat, lon, *, k, threshold=None, sepa
             args = _lib.FollowSeedsSeriesArgs(nt=t1 - t0, ej=ej, ei=ei, k_max=k, reserved0=0,
                                               threshold=float("nan") if threshold is None else float(threshold), work_d=ptr(work),
                                               seed_pos_d=ptr(pos[t0:t1]), seed_val_d=ptr(val[t0:t1]), n_found_d=ptr(n[t0:t1]), **part)
-            _lib.check(s.lib.lec_follow_seeds_series(C.byref(args)), "lec_follow_seeds_series")
+            _lib.check(getattr(s.lib, call)(C.byref(args)), call)
     pos, val, n = pos.cpu().numpy(), val.cpu().numpy(), n.cpu().numpy()
     used = np.arange(k)[None, :] < n[:, None]
     if not (np.all((n >= 0) & (n <= k)) and np.all(pos[~used] == -2) and np.all(np.isnan(val[~used])) and np.all(pos[used] >= 0)):
-        raise _lib.LecLibraryError("lec_follow_seeds_series: the unused entries are not marked")
+        raise _lib.LecLibraryError(f"{call}: the unused entries are not marked")
     return pos, val, n
 
 
-def births(seed_pos, n_found, sj, si) -> np.ndarray:
+def births(seed_pos, n_found, sj, si, nx=None) -> np.ndarray:
     """[n][4] (step, j, i, seed rank) of the seeds that are births, ordered by (step, seed rank): every seed of step 0, and a seed of
-    step t >= 1 unless some seed of step t - 1 lies within |dj| <= sj and |di| <= si of it (the largest move per step the chain has)."""
+    step t >= 1 unless some seed of step t - 1 lies within |dj| <= sj and |di| <= si of it (the largest move per step the chain has).
+    ``nx``: the longitudes are a ring of nx columns, |di| is measured on it."""
     seed_pos, n_found = np.asarray(seed_pos), np.asarray(n_found)
     out = []
     for t in range(len(n_found)):
         now = seed_pos[t, :n_found[t]].astype(np.int64)
         before = seed_pos[t - 1, :n_found[t - 1]].astype(np.int64) if t else now[:0]
         for rank, (j, i) in enumerate(now):
-            if not np.any((np.abs(before[:, 0] - j) <= sj) & (np.abs(before[:, 1] - i) <= si)):
+            if not np.any((np.abs(before[:, 0] - j) <= sj) & (ring_distance(before[:, 1], i, nx) <= si)):
                 out.append((t, int(j), int(i), rank))
     return np.array(out, dtype=np.int32).reshape(-1, 4)
 
@@ -644,17 +763,19 @@ def follow_spans(u850, v850, hgt850, lat, lon, *, starts, end_threshold=None, pa
 
 def follow_spans_chunk(u850, v850, hgt850, lat, lon, *, starts, state, t_base, end_threshold=None, patience=DEFAULT_PATIENCE,
                        length=DEFAULT_BOX[0], width=DEFAULT_BOX[1], search=DEFAULT_SEARCH, smooth=0, field="zeta", hemisphere=None,
-                       formulation="metpy_no_crs", device="cuda:0"):
+                       formulation="metpy_no_crs", device="cuda:0", periodic=False):
     """``lec_follow_spans_chunk``: ``follow_spans`` on ONE CHUNK of a series -- the slices hold the steps [t_base, t_base + nt) only --
     with chains that are resumed from ``state`` and leave it for the next chunk.  ``starts`` [K][3] (t0, j, i), t0 a series step;
     ``state`` [K][8] an int32 DEVICE tensor, zeroed before the first chunk, passed on unchanged from then on and updated in place
     (rows may be appended, zeroed, between calls).  -> (pos [K][nt][2], val [K][nt], status [K][nt] of the chunk's steps, span [K][2]
-    in series steps as the state stands after the chunk).  ``patience`` 0: the chains never stop.  The rule: include/lec_hip.h."""
+    in series steps as the state stands after the chunk).  ``patience`` 0: the chains never stop.  The rule: include/lec_hip.h.
+    ``periodic``: ``lec_follow_spans_chunk_ring`` -- the longitudes are a full ring, the window crosses the seam."""
     import torch
     if not search > 0:
         raise ValueError(f"search must be > 0 degrees, not {search!r}")
     s = _Slices(u850, v850, hgt850, lat, lon, 3, length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere,
-                formulation=formulation, device=device)
+                formulation=formulation, device=device, periodic=periodic)
+    call = "lec_follow_spans_chunk_ring" if periodic else "lec_follow_spans_chunk"
     sj, si = window_steps(s.lat, s.lon, search)
     start_d = (starts if isinstance(starts, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(starts, dtype=np.int32))).to(device=s.dev, dtype=torch.int32).contiguous()
     if start_d.dim() != 2 or start_d.shape[1] != 3 or start_d.shape[0] < 1:
@@ -673,15 +794,15 @@ def follow_spans_chunk(u850, v850, hgt850, lat, lon, *, starts, state, t_base, e
                                 pos_d=ptr(pos), val_d=ptr(val), status_d=ptr(status), span_d=ptr(span), t_base=int(t_base), state_d=ptr(state),
                                 **s.common())
     with torch.cuda.device(s.dev):
-        _lib.check(s.lib.lec_follow_spans_chunk(C.byref(args)), "lec_follow_spans_chunk")
+        _lib.check(getattr(s.lib, call)(C.byref(args)), call)
     return pos.cpu().numpy(), val.cpu().numpy(), status.cpu().numpy(), span.cpu().numpy()
 
 
-def resolve(starts, pos, span, ej, ei) -> tuple:
+def resolve(starts, pos, span, ej, ei, nx=None) -> tuple:
     """(kept [K] bool, continuation_of [K]: a chain's number or -1), going through the chains in birth order.  A chain with span (-1, -1)
     is dropped.  A chain c is a continuation of the FIRST kept chain b with span_b[0] <= t0_c <= span_b[1] whose centre at step t0_c lies
     within (ej, ei) of c's start; a continuation is dropped.  (A system that dips under the threshold for a step is seeded again while its
-    chain still lives: this is where the second chain goes.)"""
+    chain still lives: this is where the second chain goes.)  ``nx``: the longitudes are a ring of nx columns, |di| is measured on it."""
     starts, pos, span = np.asarray(starts), np.asarray(pos), np.asarray(span)
     K = len(starts)
     kept, cont = np.zeros(K, dtype=bool), np.full(K, -1, dtype=np.int64)
@@ -690,7 +811,7 @@ def resolve(starts, pos, span, ej, ei) -> tuple:
             continue
         t0, j, i = (int(x) for x in starts[c, :3])
         for b in np.flatnonzero(kept[:c]):
-            if span[b, 0] <= t0 <= span[b, 1] and abs(int(pos[b, t0, 0]) - j) <= ej and abs(int(pos[b, t0, 1]) - i) <= ei:
+            if span[b, 0] <= t0 <= span[b, 1] and abs(int(pos[b, t0, 0]) - j) <= ej and int(ring_distance(pos[b, t0, 1], i, nx)) <= ei:
                 cont[c] = b
                 break
         kept[c] = cont[c] < 0
@@ -745,6 +866,7 @@ def _lifecycle_chunks(src, chunks, first, app_logger, *, k, threshold, sep, sj, 
     import torch
     dev = torch.device(device)
     nt = len(src.time)
+    nx = src.lon.size if kw.get("periodic") else None                # (a ring: |di| of the births is measured on it)
     start_d = torch.zeros((MAX_BIRTHS, 3), dtype=torch.int32, device=dev)
     state_d = torch.zeros((MAX_BIRTHS, 8), dtype=torch.int32, device=dev)
     born, born_val = np.zeros((0, 4), dtype=np.int32), np.zeros(0)
@@ -758,10 +880,10 @@ def _lifecycle_chunks(src, chunks, first, app_logger, *, k, threshold, sep, sj, 
         seed_pos, seed_val, n_found = find_systems_series(u, v, hgt, src.lat, src.lon, k=k, threshold=threshold, separation=sep, device=device, **kw)
         n_seeds += int(n_found.sum())
         if last_pos is None:
-            new = births(seed_pos, n_found, sj, si)
+            new = births(seed_pos, n_found, sj, si, nx)
             new_val = seed_val[new[:, 0], new[:, 3]]
         else:
-            new = births(np.concatenate([last_pos, seed_pos]), np.concatenate([last_n, n_found]), sj, si)
+            new = births(np.concatenate([last_pos, seed_pos]), np.concatenate([last_n, n_found]), sj, si, nx)
             new = new[new[:, 0] >= 1]                                 # (step 0 here is the step before the chunk)
             new[:, 0] -= 1
             new_val = seed_val[new[:, 0], new[:, 3]]
@@ -795,8 +917,12 @@ def _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, 
     hemisphere, sense = sense_of(field, getattr(args, "choose_hemisphere", None), lat)
     if (end_threshold < threshold) if sense == _lib.FOLLOW_MIN else (end_threshold > threshold):
         raise ValueError(f"--choose-end-threshold {end_threshold} is stricter than --choose-threshold {threshold}: it may be weaker, never stricter")
-    admissible(lat, lon, length, width)                               # (refused here, before the upload, if the box does not fit)
+    periodic = src.periodic
+    admissible(lat, lon, length, width, periodic)                     # (refused here, before the upload, if the box does not fit)
     kw = dict(length=length, width=width, smooth=smooth, field=field, hemisphere=hemisphere, formulation=form, device=device)
+    if periodic:
+        kw["periodic"] = True
+    nx = lon.size if periodic else None
     what = f"the 850 hPa {'minima' if sense == _lib.FOLLOW_MIN else 'maxima'} of {field}"
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -806,9 +932,13 @@ def _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, 
     sep = (length / 2, width / 2) if separation is None else tuple(float(x) for x in separation)
     ej, ei = separation_steps(lat, lon, *sep)
     sj, si = window_steps(lat, lon, search)
-    if len(chunks) > 1:
-        _log_chunks(app_logger, chunks, lat.size, lon.size, "per chunk the seeds (lec_follow_seeds_series), the births, and one launch that "
-                    "resumes every chain known so far (lec_follow_spans_chunk)")
+    if periodic:
+        app_logger.info(f"-c/--choose: --choose-periodic: the longitudes are a ring of {lon.size} columns, seeds, births and chains cross the +-180 "
+                        f"meridian (lec_follow_seeds_series_ring and lec_follow_spans_chunk_ring in {len(chunks)} chunk(s))")
+    if len(chunks) > 1 or periodic:                                   # (the ring calls are the chunked ones: one chunk is a chunk too)
+        if len(chunks) > 1:
+            _log_chunks(app_logger, chunks, lat.size, lon.size, "per chunk the seeds (lec_follow_seeds_series), the births, and one launch that "
+                        "resumes every chain known so far (lec_follow_spans_chunk)")
         first = (u, v, hgt)
         del u, v, hgt
         born, born_val, pos, val, status, span, n_seeds, n_births = _lifecycle_chunks(
@@ -821,7 +951,8 @@ def _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, 
             raise ValueError("no time step holds a system: nothing to follow (another --choose-threshold, --choose-separation or --choose-domain?)")
         if n_births > MAX_BIRTHS:
             app_logger.warning(f"-c/--choose: {n_births} births found, the first {MAX_BIRTHS} of them (by time step, then strength) are followed")
-        return _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, born_val, pos, status, span, ej, ei, field, length, width, end_threshold, min_steps)
+        return _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, born_val, pos, status, span, ej, ei, field, length, width, end_threshold,
+                                  min_steps, nx=nx, seam=(src, si))
     seed_pos, seed_val, n_found = find_systems_series(u, v, hgt, lat, lon, k=k, threshold=threshold, separation=sep, **kw)
     born = births(seed_pos, n_found, sj, si)
     app_logger.info(f"-c/--choose: {int(n_found.sum())} seeds in {len(time)} time steps, at most {k} per step (lec_follow_seeds_series: {what}, "
@@ -839,13 +970,17 @@ def _lifecycle_tracks_written(args, batch_dir, app_logger, src, device, length, 
                     f"{patience} time steps in a row weaker than {end_threshold}")
     pos, val, status, span = follow_spans(u, v, hgt, lat, lon, starts=born[:, :3], end_threshold=end_threshold, patience=patience, search=search, **kw)
     return _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, seed_val[born[:, 0], born[:, 3]], pos, status, span, ej, ei, field, length,
-                              width, end_threshold, min_steps)
+                              width, end_threshold, min_steps, seam=(src, si))
 
 
 def _lifecycle_outputs(batch_dir, app_logger, lat, lon, time, born, born_val, pos, status, span, ej, ei, field, length, width, end_threshold,
-                       min_steps) -> list:
-    """From the chains of every birth (born [K][4], born_val [K] the births' seed values) to the tracks and ``systems.csv``."""
-    kept, cont = resolve(born, pos, span, ej, ei)
+                       min_steps, nx=None, seam=None) -> list:
+    """From the chains of every birth (born [K][4], born_val [K] the births' seed values) to the tracks and ``systems.csv``.
+    nx: the longitudes are a ring of nx columns (``resolve``); seam (the slice source, si): for ``_seam_notes``."""
+    kept, cont = resolve(born, pos, span, ej, ei, nx)
+    if seam is not None:
+        _seam_notes(app_logger, seam[0], [f"choose_s{c + 1:02d}" for c in range(len(born))],
+                    [int(pos[c, span[c][1], 1]) if span[c][1] >= 0 and span[c][1] < len(time) - 1 else None for c in range(len(born))], seam[1])
     shared = first_shared_centre_live(pos, span)
     for name in os.listdir(batch_dir):                                # an earlier run's tracks (it may have found more systems)
         if name.startswith("choose_s") and name[8:].isdigit():

@@ -420,7 +420,7 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     times = pd.DatetimeIndex(data.time)
-    track = ds.read_track(trackfile, app_logger)
+    track = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)      # (across the +-180 meridian: Lon mod 360, as the axis)
     # handle_track_file (lec_moving_framework.py:58-160)
     if track.index[0] < times.min() or track.index[-1] > times.max():
         raise ValueError("Track time limits do not match with data time limits.")
@@ -446,12 +446,14 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     phases.mark("track_diagnostics")
     if box_obj.result is None:              # time-sharded run: rank 0 holds the gathered series and writes every file
         return None
-    return _write_moving_results(box_obj, times, data.time_s, limits, positions, results_subdirectory, form, app_logger, args)
+    return _write_moving_results(box_obj, times, data.time_s, limits, positions, results_subdirectory, form, app_logger, args,
+                                 lon_origin=ds.lon_origin_of_axis(data.lon))
 
 
-def _write_moving_results(box_obj, times, time_s, limits, positions, results_subdirectory, form, app_logger, args):
+def _write_moving_results(box_obj, times, time_s, limits, positions, results_subdirectory, form, app_logger, args, lon_origin=0.0):
     """The files of one track (after its numbers exist): terms -> DataFrame -> budgets -> results CSV -> trackfile.  ``box_obj``:
-    a BoxData or anything with its series and per-level plumbing (``_TrackResult``)."""
+    a BoxData or anything with its series and per-level plumbing (``_TrackResult``).  ``lon_origin`` 180: the run's longitudes are on
+    0..360 (dataset.track_lon_origin); every longitude written is wrapped back into [-180, 180)."""
     terms = _compute_all(box_obj, "moving", app_logger)
     df = pd.DataFrame({c: terms[c] for c in MOVING_COLUMNS}, index=times, dtype=float)
     full = budgets_and_residuals({c: df[c].values for c in df.columns}, time_s,
@@ -471,6 +473,9 @@ def _write_moving_results(box_obj, times, time_s, limits, positions, results_sub
                     "); NOT pinned against MetPy itself (--vorticity-form selects the other formulation)")
     out_track = pd.DataFrame([{**l, **p} for l, p in zip(limits, positions)])
     out_track = out_track.rename(columns={"datestr": "time", "central_lat": "Lat", "central_lon": "Lon"})
+    if lon_origin:
+        for col in [c for c in out_track.columns if c in ("Lon", "min_lon", "max_lon") or c.endswith("_lon")]:
+            out_track[col] = ds.wrap180(out_track[col].values)
     out_track.to_csv(os.path.join(results_subdirectory, f"{infile_name}_{method}_trackfile"), index=False, sep=";")
     phases.mark("csv_writes")
     return results_file, df
@@ -546,5 +551,5 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
                                       device=dev, formulation=form)
         app_logger.info(f"Track {tr.path}: {tr.n} time steps -> {results_subdirectory}")
         written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, positions, results_subdirectory,
-                                             form, app_logger, args))
+                                             form, app_logger, args, lon_origin=ds.lon_origin_of_axis(view.lon)))
     return written

@@ -23,6 +23,13 @@ the state carried (the timed call zeroes the state and makes every chunk's call;
 launch's in a pass of their own).  (b) with ``--parent PATH``: ``lec_follow_spans`` and ``lec_follow_many`` of the parent's library and
 of this one, alternating, two rounds -- what the chains' shared device function cost the existing calls when it gained the resumed
 variant.  The values go under the key ``chunked`` of ``--out``.
+
+``--ring``: the two ring calls of ``-c --choose-periodic`` instead.  Same series with its 241 columns relabelled as a full ring of
+longitudes (window 41 x 41), ``--chains`` chains from ``--lifecycle``'s table, k_max 8.  ``lec_follow_spans_chunk_ring`` (one chunk: the
+whole series) and ``lec_follow_seeds_series_ring`` of this library against ``lec_follow_spans_chunk`` and ``lec_follow_seeds_series`` of
+the library ``--parent PATH`` names (without it: this library's own) on the same arrays with the same bounds (every column a centre)
+and the open axis' tables, alternating, two rounds.  The non-ring chain cuts its window at columns 0 and nx - 1 where the ring's wraps,
+so the two do not walk the same chains: the figures compare the cost per call, not bits.  The values go under the key ``ring`` of ``--out``.
 """
 import argparse
 import ctypes as C
@@ -44,6 +51,7 @@ def main():
     ap.add_argument("--parent", default=None, metavar="PATH")
     ap.add_argument("--lifecycle", action="store_true")
     ap.add_argument("--chunked", action="store_true")
+    ap.add_argument("--ring", action="store_true")
     ap.add_argument("--chains", type=int, default=64, help="with --lifecycle / --chunked: chains of the lec_follow_spans launch")
     a = ap.parse_args()
     import torch
@@ -52,12 +60,16 @@ def main():
     dev = torch.device("cuda:0")
     # a regional 0.25-degree slice (40 x 60 degrees): the search domain of a case study; the chain's cost does not depend on its size
     lat, lon = -60.0 + 0.25 * np.arange(161), -90.0 + 0.25 * np.arange(241)
+    if a.ring:
+        lon = -180.0 + (360.0 / 241) * np.arange(241)
     nt, ny, nx = a.steps, lat.size, lon.size
     g = torch.Generator(device=dev).manual_seed(1)
     u, v, h = (torch.randn((nt, ny, nx), dtype=torch.float64, device=dev, generator=g) for _ in range(3))
     xc, yc, cv = (torch.as_tensor(t).to(dev) for t in dg.vorticity_tables(lat, lon, "metpy_no_crs"))
     bounds = fw.admissible(lat, lon, *fw.DEFAULT_BOX)
     sj, si = fw.window_steps(lat, lon, fw.DEFAULT_SEARCH)
+    if a.ring:
+        sj, si = 20, 20                                  # the window of the other modes, 41 x 41 points, on the relabelled axis
     js, is_ = fw.start_index(lat, lon, (-40.0, -60.0), bounds)
     pos = torch.empty((nt, 2), dtype=torch.int32, device=dev)
     val = torch.empty((nt,), dtype=torch.float64, device=dev)
@@ -79,6 +91,10 @@ def main():
         return float(np.median(ms)), [round(x, 4) for x in ms]
 
     out = {"steps": nt, "slice": [ny, nx], "window": [2 * sj + 1, 2 * si + 1], "csrc_sha": _lib.source_digest()}
+    if a.ring:
+        rt = [torch.as_tensor(t).to(dev) for t in dg.vorticity_tables(lat, lon, "metpy_no_crs", periodic=True)]
+        return ring(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, ring_tables=rt, bounds=(bounds[0], bounds[1], 0, nx - 1), sj=sj, si=si,
+                                     nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
     if a.chunked:
         return chunked(a, lib, out, dict(u=u, v=v, h=h, xc=xc, yc=yc, cv=cv, bounds=bounds, sj=sj, si=si, nt=nt, ny=ny, nx=nx, dev=dev, stream=stream), timed)
     if a.lifecycle:
@@ -340,6 +356,66 @@ def chunked(a, lib, out, w, timed):
             with open(a.out) as f:
                 kept = json.loads(f.read())
         kept["chunked"] = dict(res, steps=nt, csrc_sha=out["csrc_sha"])
+        with open(a.out, "w") as f:
+            f.write(json.dumps(kept) + "\n")
+
+
+def ring(a, lib, out, w, timed):
+    import torch
+    from lorenzcycletoolkit_amd import _lib
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    nt, ny, nx, dev, bounds = w["nt"], w["ny"], w["nx"], w["dev"], w["bounds"]
+    old = lib
+    if a.parent:
+        old = C.CDLL(a.parent)
+        old.lec_follow_spans_chunk.restype, old.lec_follow_spans_chunk.argtypes = C.c_int, [C.POINTER(_lib.FollowChunkArgs)]
+        old.lec_follow_seeds_series.restype, old.lec_follow_seeds_series.argtypes = C.c_int, [C.POINTER(_lib.FollowSeedsSeriesArgs)]
+    tables = lambda t: dict(xcoef_d=ptr(t[0]), ycoef_d=ptr(t[1]), curv_d=ptr(t[2]))
+    common = dict(u_d=ptr(w["u"]), v_d=ptr(w["v"]), hgt_d=ptr(w["h"]), nt=nt, ny=ny, nx=nx, field=_lib.FOLLOW_ZETA, sense=_lib.FOLLOW_MIN, smooth_r=0,
+                  jlo=bounds[0], jhi=bounds[1], ilo=bounds[2], ihi=bounds[3], stream=w["stream"])
+    open_t, ring_t = tables((w["xc"], w["yc"], w["cv"])), tables(w["ring_tables"])
+    K, k = a.chains, 8
+    rng = np.random.default_rng(2)
+    t0 = np.sort(rng.integers(0, max(1, nt - 1), K))
+    t0[0] = 0
+    table = np.c_[t0, rng.integers(bounds[0], bounds[1] + 1, K), rng.integers(bounds[2], bounds[3] + 1, K)].astype(np.int32)
+    start3 = torch.as_tensor(table).to(dev)
+    pos, val, status = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((K, nt, 2), torch.int32), ((K, nt), torch.float64), ((K, nt), torch.int32)))
+    span, state = torch.empty((K, 2), dtype=torch.int32, device=dev), torch.zeros((K, 8), dtype=torch.int32, device=dev)
+    chain = dict(common, sj=w["sj"], si=w["si"], n_chains=K, patience=0, end_threshold=float("nan"), start_d=ptr(start3), pos_d=ptr(pos), val_d=ptr(val),
+                 status_d=ptr(status), span_d=ptr(span), t_base=0, state_d=ptr(state))
+    ca_open, ca_ring = _lib.FollowChunkArgs(**chain, **open_t), _lib.FollowChunkArgs(**chain, **ring_t)
+    ej, ei = 30, 30                                      # half the default box on the 0.25-degree slice, as --lifecycle
+    work = torch.empty((nt, ny, nx), dtype=torch.float64, device=dev)
+    spos, sval, sn = (torch.empty(shape, dtype=dt, device=dev) for shape, dt in (((nt, k, 2), torch.int32), ((nt, k), torch.float64), ((nt,), torch.int32)))
+    seeds = dict(common, ej=ej, ei=ei, k_max=k, reserved0=0, threshold=float("nan"), work_d=ptr(work), seed_pos_d=ptr(spos), seed_val_d=ptr(sval), n_found_d=ptr(sn))
+    sa_open, sa_ring = _lib.FollowSeedsSeriesArgs(**seeds, **open_t), _lib.FollowSeedsSeriesArgs(**seeds, **ring_t)
+
+    def run(which, call, args, zero):
+        if zero:
+            state.zero_()
+        if getattr(which, call)(C.byref(args)):
+            raise RuntimeError(f"{call} failed: {lib.lec_last_error()}")
+
+    res = {"parent_library": bool(a.parent), "n_chains": K, "k_max": k, "window": [2 * w["sj"] + 1, 2 * w["si"] + 1], "neighbourhood": [2 * ej + 1, 2 * ei + 1]}
+    for rnd in range(2):
+        for name, which, call, args, zero in (("parent_chunk", old, "lec_follow_spans_chunk", ca_open, True),
+                                              ("ring_chunk", lib, "lec_follow_spans_chunk_ring", ca_ring, True),
+                                              ("parent_seeds", old, "lec_follow_seeds_series", sa_open, False),
+                                              ("ring_seeds", lib, "lec_follow_seeds_series_ring", sa_ring, False)):
+            med, all_ms = timed(lambda: run(which, call, args, zero))
+            res.setdefault(f"{name}_ms", []).append(round(med, 4))
+            res.setdefault(f"{name}_all_ms", []).append(all_ms)
+    res["chunk_ratio_ring_over_parent"] = [round(r / p, 4) for r, p in zip(res["ring_chunk_ms"], res["parent_chunk_ms"])]
+    res["seeds_ratio_ring_over_parent"] = [round(r / p, 4) for r, p in zip(res["ring_seeds_ms"], res["parent_seeds_ms"])]
+    out["ring"] = res
+    print(json.dumps(out))
+    if a.out:
+        kept = {}
+        if os.path.exists(a.out):
+            with open(a.out) as f:
+                kept = json.loads(f.read())
+        kept["ring"] = dict(res, steps=nt, csrc_sha=out["csrc_sha"])
         with open(a.out, "w") as f:
             f.write(json.dumps(kept) + "\n")
 
