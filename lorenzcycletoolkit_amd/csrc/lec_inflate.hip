@@ -289,7 +289,9 @@ __global__ void __launch_bounds__(64) lec_inflate_kernel(const InflateParams P) 
     {
         const uint32_t h = in.peek(lead * 8u);
         const uint32_t cmf = h & 0xffu, flg = (h >> 8) & 0xffu;
-        if (src_len < 6 || (cmf & 0x0fu) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) status = ST_HEADER;
+        // (a stream cut short behind a good header is "input ends", as zlib reads it: the block loop sees that there is no room for a block)
+        if (src_len < 2) status = ST_INPUT_END;
+        else if ((cmf & 0x0fu) != 8u || (cmf >> 4) > 7u || ((cmf << 8) | flg) % 31u != 0u || (flg & 0x20u)) status = ST_HEADER;
     }
 
     // ring -> HBM, whole 16-byte pieces (all of it when `all`)
@@ -401,7 +403,9 @@ __global__ void __launch_bounds__(64) lec_inflate_kernel(const InflateParams P) 
                 for (int r = lane; r < rep; r += 64) { const int i = have + r; L.lens[i < nlit ? i : 288 + (i - nlit)] = (uint8_t)val; }
                 have += rep; prev = val;
             }
-            if (bad) { status = ST_CODE_LENGTHS; break; }
+            // (with fewer than 32 bits left the stream is cut short whatever the list says -- there is no room for the trailer --, and
+            // the symbol that looked bad may have been read from beyond its end)
+            if (bad) { status = bitpos + 32u > src_bits ? ST_INPUT_END : ST_CODE_LENGTHS; break; }
             wave_sync();
             for (int i = nlit + lane; i < 288; i += 64) L.lens[i] = 0;
             for (int i = 288 + ndist + lane; i < 320; i += 64) L.lens[i] = 0;
@@ -545,7 +549,9 @@ __global__ void __launch_bounds__(64) lec_inflate_kernel(const InflateParams P) 
                     info = wl(pack(nty, tot & 63u, nval), pos, info);
                     continue;
                 }
-                if (ty == T_BAD) { status = ST_BAD_CODE; break; }
+                // (a token is at most 48 bits: one that could reach beyond the stream's end may owe its reading to what lies there, and a
+                // stream with so little left is cut short in any case)
+                if (ty == T_BAD) { status = bitpos + pos + 48u > src_bits ? ST_INPUT_END : ST_BAD_CODE; break; }
                 if (ty == T_EOB) { pos += inf & 63u; eob = true; break; }
                 const uint32_t n_out = inf >> 9;                                  // a match
                 if ((uint32_t)__popcll(chain) + extra_out + n_out > (uint32_t)kCap) break;       // the next round starts at this token
