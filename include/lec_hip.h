@@ -632,6 +632,41 @@ int lec_rowstats(const lec_rowstats_args* args);
  *            LEC_ERR_UNSUPPORTED (the box-tile kernel serves every call).
  */
 int lec_rowstats_steps(const lec_rowstats_args* args, const int32_t* step_d);
+
+/*
+ * -f --periodic: ONE fixed box whose columns are a full RING of longitudes -- a zonal band, a hemisphere, the globe (an additive call: no
+ * struct, export or kernel result of ABI 11 changes).  A ring has no preferred meridian.
+ *
+ *   int lec_rowstats_ring(const lec_rowstats_args*);
+ *
+ * It takes the existing struct with the same field meanings.  The one difference: the box's columns iw .. ie are a closed circle, so
+ * column ie is the western neighbour of column iw.  The rule is the reference's own formulas on the CLOSED axis:
+ *
+ * The closed axis.
+ *   - The nxb = ie - iw + 1 evenly spaced columns (step h) get column iw once more at lon[ie] + h: nxb + 1 points,
+ *     xlength = deg2rad(lon[ie] + h) - deg2rad(lon[iw]).
+ *   - The library knows no longitudes: boxtab_d carries {1 / xlength, h_rad = xlength / nxb, 1 / h_deg} (tables.build_box_tables(ring=True)).
+ *   - A box narrower than the cube is computed as if closed and reads nothing outside it; that it is a full circle is the caller's statement.
+ * Zonal means and products.
+ *   - The trapezoid over the closed axis is h * sum over the nxb columns: every column has weight 1 (a limited-area row gives its two end
+ *     columns 1/2 and leaves out the interval that closes the circle).
+ * Q.
+ *   - dT/dlon is the centred three-point difference at EVERY column: column iw reads column ie, column ie reads column iw.
+ *   - d/dphi, d/dp and d/dt are unchanged.
+ * Records.
+ *   - The same LEC_NSTAT numbers per row.  LEC_S_TE / UE / VE are written with the WEST column's values: the east column of the closed
+ *     axis is the west column, so every east-minus-west difference of the boundary terms is exactly 0 in lec_reduce, which is untouched.
+ *   - boxtab2_d of lec_reduce carries c1 = -1 / (Re xlength ylength) and xlen with the closed xlength.  The quirks the reference has in
+ *     latitude and pressure are kept (ylength from sines, Ck term 5, the second terms of BPhiE / BPhiZ, _handle_nans).
+ * Kernels.
+ *   - tuning.kernel LEC_KERNEL_AUTO or LEC_KERNEL_ROW_SWEEP: both run one wave per row (the kernel of lec_rowsweep.hip with one more
+ *     compile-time parameter, instantiated in lec_rowsweep_ring.hip; only the first and last trip of a row differ).  Any other family: LEC_ERR_UNSUPPORTED.  tuning.order keeps its meaning.
+ *   - dT/dt from the cube's time axis goes through the cross-time covariances and lec_qtime_kernel as for any fixed box.
+ * Validation.  Every refusal is LEC_ERR_ARG naming the field, made before any HIP call, never clamped:
+ *   - box_per_step != 0, n_box != 1, lon_uniform != 1, tm_d / tp_d given, nxb_max < 3 (a ring has at least 3 columns).
+ *   - Everything lec_rowstats checks is checked here too.  lec_check_boxes serves ring calls unchanged.
+ */
+int lec_rowstats_ring(const lec_rowstats_args* args);
 int lec_ingest(const lec_ingest_args* args);
 int lec_reduce(const lec_reduce_args* args);
 

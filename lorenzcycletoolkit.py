@@ -18,6 +18,10 @@ With --choose-lifecycle (and --choose-threshold X) every time step is searched (
 the time step at which it forms until it has weakened (``lec_follow_spans``; --choose-end-threshold, --choose-patience,
 --choose-min-steps), and each track covers its system's own time steps.
 
+-f --periodic: the fixed box is a full ring of longitudes (a zonal band, a hemisphere, the globe): the file's longitudes must close the
+circle and the box limits span it; zonal means run over the closed axis, d/dlon is centred across the +-180 meridian and no flux
+crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file names and columns as -f.
+
 Several GPUs of one node: ``python lorenzcycletoolkit.py <file> -r -f --gpus N`` (this process starts N rank processes, one per
 GPU) or ``python -m torch.distributed.run --nproc-per-node N lorenzcycletoolkit.py <file> -r -f``.  The time steps are sharded
 over the ranks (each reads, decodes and computes only its own block plus a one-step halo of T), rank 0 gathers the per-step
@@ -63,6 +67,11 @@ def create_arg_parser():
                         "(a directory stands for every regular file in it, sorted by name).  Each track writes LEC_Results/<infile>_<track>_track/ "
                         "with the files a --trackfile run of it writes; the log and batch.csv go to LEC_Results/<infile>_track_batch/")
     parser.add_argument("--box_limits", type=str, default="inputs/box_limits", help="box-limits file for -f (default: inputs/box_limits)")
+    parser.add_argument("--periodic", action="store_true", help="with -f: the box is a full ring of longitudes -- a zonal band, a hemisphere, the "
+                        "globe.  The file's longitudes must be evenly spaced with nx * dx = 360 degrees and the box limits' min_lon / max_lon must "
+                        "select its first and last longitude (-180 / 180 always do); min_lat / max_lat give the band.  Zonal means run over the "
+                        "closed circle, d/dlon is centred across the +-180 meridian and no flux crosses an east or west wall (otherwise the "
+                        "circle is a limited area with a seam)")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -256,6 +265,13 @@ def refuse_choose_options(args):
         raise SystemExit(f"--choose-domain: {args.choose_domain} not found")
 
 
+def refuse_periodic_options(args):
+    """--periodic is the fixed framework's ring; said before anything is created."""
+    if args.periodic and not args.fixed:
+        raise SystemExit("--periodic goes with -f/--fixed: the ring of a -t / -c run is the 0..360 longitude axis a track across the +-180 "
+                         "meridian gets by itself, and --choose-periodic for the search of -c")
+
+
 def _join_threshold(argv):
     """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5`` (``--choose-end-threshold`` likewise): argparse takes a negative
     number in exponent form for an option."""
@@ -276,6 +292,7 @@ def main(argv=None):
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
     refuse_choose_options(args)
+    refuse_periodic_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
     if args.choose and (args.choose_systems is not None or args.choose_starts is not None):

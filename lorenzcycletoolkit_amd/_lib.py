@@ -44,7 +44,7 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
-           "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring"]
+           "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring"]
 
 
 class Tuning(C.Structure):
@@ -232,6 +232,8 @@ def load():
     lib.lec_max_row.argtypes = [C.c_int, C.c_int, C.c_int]
     lib.lec_rowstats.restype = C.c_int
     lib.lec_rowstats.argtypes = [C.POINTER(RowstatsArgs)]
+    lib.lec_rowstats_ring.restype = C.c_int
+    lib.lec_rowstats_ring.argtypes = [C.POINTER(RowstatsArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

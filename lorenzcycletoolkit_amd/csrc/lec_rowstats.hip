@@ -298,6 +298,7 @@ int launch_vec(const RowParams& p, bool uniform, int mode, int nblocks, hipStrea
 }  // namespace
 
 int lec_launch_rowsweep(const lec::RowParams& p, int dtype, bool aligned, bool aligned8, bool uniform, int mode, int f32_vec, hipStream_t st);
+int lec_launch_rowsweep_ring(const lec::RowParams& p, int dtype, bool aligned, bool aligned8, bool uniform, int mode, int f32_vec, hipStream_t st);
 int lec_launch_rowblock(lec::RowParams p, int dtype, bool aligned, bool aligned8, bool uniform, int bt, int bk, int bj, hipStream_t st);
 int lec_launch_boxtile(const lec::RowParams& p, int dtype, bool uniform, int mode, hipStream_t st);
 int lec_launch_qtime(const lec::RowParams& p, hipStream_t st);
@@ -312,9 +313,17 @@ extern "C" int lec_max_row(int dtype, int aligned, int kernel) {
     return 1 << 24;
 }
 
-// lec_rowstats and lec_rowstats_steps (step_d != NULL: a per-box source-step table, box-tile kernel only)
-static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d) {
+// lec_rowstats, lec_rowstats_steps (step_d != NULL: a per-box source-step table, box-tile kernel only) and lec_rowstats_ring (ring: the
+// one fixed box's columns are a closed circle of longitudes; one wave per row only)
+static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d, bool ring = false) {
     if (!a) return lec_set_error(LEC_ERR_ARG, "lec_rowstats: null args");
+    if (ring) {
+        if (a->box_per_step != 0) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_ring: box_per_step must be 0 (one fixed box: moving boxes have no ring form)");
+        if (a->n_box != 1) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_ring: n_box must be 1");
+        if (a->lon_uniform != 1) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_ring: lon_uniform must be 1 (a ring is evenly spaced)");
+        if (a->tm_d || a->tp_d) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_ring: tm_d and tp_d must be NULL (a box-packed series has no ring form)");
+        if (a->nxb_max < 3) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_ring: nxb_max must be >= 3 (a ring has at least 3 columns)");
+    }
     if (step_d) {       // boxes of several tracks over one cube: every box names its cube step and the step's time neighbours
         if (a->box_per_step != 1 || a->n_box != a->t_count || a->t_begin != 0 || a->t_count < 1)
             return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: needs box_per_step = 1, n_box = t_count >= 1 and t_begin = 0");
@@ -400,6 +409,11 @@ static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d) {
     // 17.5-17.9 ms per 64 steps for one wave per row; fp32 storage: no gain measured); everything else on one wave per row.
     // The choice depends only on the kind of call, never on extents, so shards and chunks of one series use one family.
     int kernel = tu.kernel;
+    if (ring) {         // AUTO on a ring is one wave per row: the row-block kernel has no ring form
+        if (kernel != LEC_KERNEL_AUTO && kernel != LEC_KERNEL_ROW_SWEEP)
+            return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_rowstats_ring: only LEC_KERNEL_AUTO and LEC_KERNEL_ROW_SWEEP have a ring form (tuning.kernel)");
+        kernel = LEC_KERNEL_ROW_SWEEP;
+    }
     const bool block_ok = fixed_time_stencil && a->geopt_d && a->t_count >= 2;
     if (kernel == LEC_KERNEL_AUTO) {
         if (a->box_per_step) kernel = LEC_KERNEL_BOX_TILE;
@@ -459,7 +473,8 @@ static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d) {
             pb.order = 8; pb.tgroup = tu.tile_t ? tu.tile_t : 2; pb.jgroup = tu.tile_j ? tu.tile_j : 4;      // tile: 2 x 4 blocks at one level, levels next
             rc = lec_launch_rowblock(pb, a->dtype, aligned, aligned8, uni, bt, bk, bj, st);
         } else {
-            rc = lec_launch_rowsweep(p, a->dtype, aligned, aligned8, uni, mode, tu.f32_vec, st);
+            rc = ring ? lec_launch_rowsweep_ring(p, a->dtype, aligned, aligned8, uni, mode, tu.f32_vec, st)
+                      : lec_launch_rowsweep(p, a->dtype, aligned, aligned8, uni, mode, tu.f32_vec, st);
         }
         if (rc == LEC_OK && mode == 3) rc = lec_launch_qtime(p, st);
     }
@@ -471,6 +486,8 @@ static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d) {
 }
 
 extern "C" int lec_rowstats(const lec_rowstats_args* a) { return rowstats_impl(a, nullptr); }
+
+extern "C" int lec_rowstats_ring(const lec_rowstats_args* a) { return rowstats_impl(a, nullptr, true); }
 
 extern "C" int lec_rowstats_steps(const lec_rowstats_args* a, const int32_t* step_d) {
     if (!step_d) return lec_set_error(LEC_ERR_ARG, "lec_rowstats_steps: null step_d");

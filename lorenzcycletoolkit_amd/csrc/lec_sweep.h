@@ -73,6 +73,7 @@ struct SweepRow {
     int nxb;                        // box points in the row
     double cT, cU, cV, cW, cP;      // shifts: the row's first box element
     double cTf, cTb;                // the same for the T rows one time step ahead / back (cross-time covariances)
+    double eT;                      // ring rows only: T of the row's last element (the first element's western neighbour)
     double cx;                      // uniform longitudes: 0.5 / h_deg / dx_j  (centred d/dlon -> d/dx)
     double inv_dx;                  // table longitudes: 1 / dx_j
     const double* wl;               // table longitudes: trapezoid weights
@@ -89,7 +90,10 @@ struct QCoef { double tb_, tf_, tm, k0, k1, km, j0, j1, jm; };      // tb_ / tf_
 constexpr int kNX = 4;      // cross-time sums: <a a+>, <a+>, <a a->, <a->
 
 // element q of a vector (see sweep_elems).  EDGE = false: the element lies strictly inside its row; true: the general form (selects).
-template <int VEC, bool UNIFORM, bool EDGE, int QMODE, bool BOTH, typename OP>
+// RING: the row is a closed circle of evenly spaced longitudes (lec_rowstats_ring): every element has weight 1, and the centred
+// difference wraps -- the first element's western neighbour is the row's last element (r.eT), the last one's eastern neighbour the
+// first (r.cT).  Only EDGE trips differ.
+template <int VEC, bool UNIFORM, bool EDGE, int QMODE, bool BOTH, bool RING = false, typename OP>
 __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], double (&xacc)[kNX], const SweepRow& r, int e0, bool lane_in,
                                           const OP (&fT)[VEC], const OP (&fU)[VEC], const OP (&fV)[VEC],
                                           const OP (&fW)[VEC], const OP (&fP)[VEC], double tl_edge, double tr_edge,
@@ -99,7 +103,8 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
     const bool inside = !EDGE || ((e >= 0) && (e < r.nxb) && lane_in);
     const bool first = EDGE && inside && (e == 0), last = EDGE && inside && (e == r.nxb - 1);
     double w = 1.0;
-    if (UNIFORM) { if (EDGE) w = inside ? ((first || last) ? 0.5 : 1.0) : 0.0; }
+    static_assert(!RING || UNIFORM, "a ring has evenly spaced longitudes");
+    if (UNIFORM) { if (EDGE) w = inside ? ((!RING && (first || last)) ? 0.5 : 1.0) : 0.0; }
     else w = EDGE ? (inside ? r.wl[min(max(e, 0), r.nxb - 1)] : 0.0) : r.wl[e];
     const double Tc = (double)fT[q];
     const double Tv = inside ? Tc : r.cT;
@@ -110,12 +115,13 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
     const double a = Tv - r.cT;
     double f = 0.0;
     if (QMODE != 0) {
-        const double Tl = (q == 0) ? tl_edge : (double)fT[q > 0 ? q - 1 : 0];
-        const double Tr = (q == VEC - 1) ? tr_edge : (double)fT[q < VEC - 1 ? q + 1 : q];
+        double Tl = (q == 0) ? tl_edge : (double)fT[q > 0 ? q - 1 : 0];
+        double Tr = (q == VEC - 1) ? tr_edge : (double)fT[q < VEC - 1 ? q + 1 : q];
+        if (RING && EDGE) { Tl = first ? r.eT : Tl; Tr = last ? r.cT : Tr; }          // the circle closes: centred everywhere
         double adv;                                     // u dT/dx
         if (UNIFORM) {
             double d = Tr - Tl;
-            if (EDGE) d = first ? 2.0 * (Tr - Tv) : (last ? 2.0 * (Tv - Tl) : d);      // one-sided at the row ends
+            if (EDGE && !RING) d = first ? 2.0 * (Tr - Tv) : (last ? 2.0 * (Tv - Tl) : d);      // one-sided at the row ends
             adv = (Uv * r.cx) * d;
         } else {
             const int ec = EDGE ? min(max(e, 0), r.nxb - 1) : e;
@@ -153,7 +159,7 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
 // One vector (VEC consecutive longitudes starting at box element e0) of every operand -> the 20 sums.
 //   EDGE = false: every element of the trip lies strictly inside the row (1 <= e <= nxb - 2): no selects,
 //                 and with uniform longitudes the weight is the constant 1 (the row epilogue multiplies by h).
-//   EDGE = true : the first / last trips: half weights at the row ends, lanes outside the row contribute 0; lanes whose whole
+//   EDGE = true : the first / last trips: half weights at the row ends (RING: weight 1, wrapped difference), lanes outside the row contribute 0; lanes whose whole
 //                 vector lies past the row (the tail of the last trip) sit the element loop out instead of adding exact zeros
 //                 (same bits, and 20 fewer VGPRs in the fp32 all-terms instantiation).  Measured and NOT kept
 //                 (profiles/r03_notes.md): per element, a wave-uniform test "is any lane's element a row end or outside" choosing
@@ -169,7 +175,7 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
 //            row's forward covariance; BOTH: the row has no processed predecessor and forms the backward one too.
 // With uniform longitudes the sums carry RELATIVE trapezoid weights (1, 1/2, 0); Q is accumulated without
 // the factor cp (applied in the epilogue).  Operands arrive in their storage type OP and are converted here.
-template <int VEC, bool UNIFORM, bool EDGE, int QMODE, bool BOTH, typename OP>
+template <int VEC, bool UNIFORM, bool EDGE, int QMODE, bool BOTH, bool RING = false, typename OP>
 __device__ __forceinline__ void sweep_elems(double (&acc)[kNA], double (&xacc)[kNX], const SweepRow& r, int e0, bool lane_in,
                                             const OP (&fT)[VEC], const OP (&fU)[VEC], const OP (&fV)[VEC],
                                             const OP (&fW)[VEC], const OP (&fP)[VEC], double tl_edge, double tr_edge,
@@ -178,9 +184,9 @@ __device__ __forceinline__ void sweep_elems(double (&acc)[kNA], double (&xacc)[k
 #pragma unroll
     for (int q = 0; q < VEC; ++q) {
         if (EDGE) {
-            sweep_one<VEC, UNIFORM, true, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
+            sweep_one<VEC, UNIFORM, true, QMODE, BOTH, RING>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
         } else {
-            sweep_one<VEC, UNIFORM, false, QMODE, BOTH>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
+            sweep_one<VEC, UNIFORM, false, QMODE, BOTH, RING>(q, acc, xacc, r, e0, lane_in, fT, fU, fV, fW, fP, tl_edge, tr_edge, qr, qc);
         }
         // four-element vectors: finish one element before starting the next, or the scheduler interleaves all four and
         // their temporaries push the kernel past 128 VGPRs

@@ -136,14 +136,18 @@ class LECEngine:
         """Nearest-grid-point inclusive box, as BoxData._set_domain_limits (box_data.py:115-131)."""
         return tables.box_indices(self.lat, self.lon, west, east, south, north)
 
-    def prepare_boxes(self, boxes, nyb_min: int = 0, packed: bool = False, lon_uniform: Optional[bool] = None) -> PreparedBoxes:
+    def prepare_boxes(self, boxes, nyb_min: int = 0, packed: bool = False, lon_uniform: Optional[bool] = None, ring: bool = False) -> PreparedBoxes:
         """Index quadruples (iw, ie, js, jn) -> PreparedBoxes for ``rowstats`` / ``reduce`` / ``compute``.  ``nyb_min``: the row
         count of the record buffer the boxes will be used with (chunks of a series share the tallest box's).  ``packed``: the boxes
         of a BOX-PACKED series (``pack_boxes``; include/lec_hip.h): stage 1 then addresses every step's box at the origin of its
         slab, while every table is built from the true grid boxes as always.  ``lon_uniform``: see ``tables.build_box_tables`` (a track
-        of a batch keeps its own crop's formulation)."""
+        of a batch keeps its own crop's formulation).  ``ring``: ONE fixed box over the engine's whole longitude axis, which is a full
+        ring (``tables.build_box_tables(ring=True)`` refuses anything else): stage 1 of these boxes is ``lec_rowstats_ring`` -- zonal
+        means over the closed circle, Q's d/dlon centred across the seam, no east-west boundary flux."""
         boxes = [tuple(int(x) for x in b) for b in boxes]
-        bt, dev = self._box_tables(boxes, nyb_min, lon_uniform)
+        if ring and packed:
+            raise ValueError("a ring is one fixed box: a box-packed series has no ring form")
+        bt, dev = self._box_tables(boxes, nyb_min, lon_uniform, ring)
         if packed:
             dev = dict(dev, box_data=self._up(np.array([(0, b[1] - b[0], 0, b[3] - b[2]) for b in boxes], dtype=np.int32), torch.int32))
         return PreparedBoxes(boxes, bt, dev)
@@ -283,12 +287,12 @@ class LECEngine:
         bt, dev = self._box_tables(boxes, nyb_min)
         return boxes, bt, dev
 
-    def _box_tables(self, boxes, nyb_min: int = 0, lon_uniform: Optional[bool] = None):
-        key = (int(nyb_min), lon_uniform) + tuple(int(v) for b in boxes for v in b)
+    def _box_tables(self, boxes, nyb_min: int = 0, lon_uniform: Optional[bool] = None, ring: bool = False):
+        key = (int(nyb_min), lon_uniform, bool(ring)) + tuple(int(v) for b in boxes for v in b)
         hit = self._box_cache.get(key)
         if hit is not None:
             return hit
-        bt = tables.build_box_tables(self.lat, self.lon, boxes, nyb_min=nyb_min, lon_uniform=lon_uniform)
+        bt = tables.build_box_tables(self.lat, self.lon, boxes, nyb_min=nyb_min, lon_uniform=lon_uniform, ring=ring)
         dev = {
             "box": self._up(bt.box, torch.int32), "boxtab": self._up(bt.boxtab), "wlon": self._up(bt.wlon),
             "glon": self._up(bt.glon), "lattab": self._up(bt.lattab), "boxtab2": self._up(bt.boxtab2),
@@ -351,7 +355,7 @@ class LECEngine:
                  tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                  steps: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Stage 1: row records [t_count, nl, nyb_max, 32] of time steps [t_begin, t_begin + t_count) of the cubes.  Three kinds of call
-        share one path:
+        share one path (a fourth is the first with ``boxes`` from ``prepare_boxes(..., ring=True)``: ``lec_rowstats_ring``):
 
         * whole cubes on the engine's grid (``lec_rowstats``), dT/dt from ``time_s`` / ``tcoef`` or a ``dTdt`` cube;
         * a BOX-PACKED series (``pack_boxes``; ``boxes`` prepared with ``packed=True``): the cubes hold every step's box at the origin
@@ -409,6 +413,8 @@ class LECEngine:
             per_step_boxes = len(boxes) != 1
         if len(boxes) != (t_count if per_step_boxes else 1):
             raise ValueError("boxes: give one box, or one per processed time step" if steps is None else "steps: one box per table row")
+        if bt.ring and (per_step_boxes or packed or steps is not None):
+            raise ValueError("a ring is one fixed box on whole cubes: no per-step boxes, packed series or step table")
         shape = (t_count, nl, bt.nyb_max, _lib.LEC_NSTAT)
         rows = torch.empty(shape, dtype=torch.float64, device=tair.device) if rows_out is None else rows_out
         if rows.shape != shape or rows.dtype != torch.float64 or not rows.is_contiguous():
@@ -432,7 +438,9 @@ class LECEngine:
                 if timing is not None:
                     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                     ev0.record()
-                if steps is None:
+                if bt.ring:
+                    _lib.check(self.lib.lec_rowstats_ring(C.byref(ra)), "lec_rowstats_ring")
+                elif steps is None:
                     _lib.check(self.lib.lec_rowstats(C.byref(ra)), "lec_rowstats")
                 else:
                     _lib.check(self.lib.lec_rowstats_steps(C.byref(ra), _ptr(steps[a:b])), "lec_rowstats_steps")

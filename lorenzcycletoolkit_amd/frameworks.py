@@ -50,15 +50,25 @@ class BoxData:
     time steps from the steps it holds (own + one-step T halo; ``data.t_held``), the any-time NaN-level mask is merged across the
     ranks, and ONE gather brings the packed per-step records to rank 0, whose BoxData then looks exactly like the one-process one;
     on the other ranks ``result`` / ``scalars`` / ``levels`` are None.
+
+    ``periodic`` (fixed framework only): the box is the latitude band [south, north] over ALL of ``data``'s longitudes, which must be
+    a full ring (evenly spaced, nx * dx = 360 degrees), and the western / eastern limits must select its first / last column: zonal
+    means over the closed circle, Q's d/dlon centred across the seam, no east-west boundary flux (``lec_rowstats_ring``).
     """
 
     def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, western_limit=None, eastern_limit=None,
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
-                 boxes_limits=None):
+                 boxes_limits=None, periodic: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
+        self.periodic = bool(periodic)
+        if self.periodic:               # (host work only: refused before the GPU is touched)
+            if boxes_limits is not None:
+                raise ValueError("periodic: one fixed box (the moving framework's ring is the 0..360 axis of --choose-periodic)")
+            from .tables import box_indices
+            self.xlength = ring_box_check(data.lon, box_indices(data.lat, data.lon, western_limit, eastern_limit, southern_limit, northern_limit))
         self.args = args
         self.results_subdirectory = results_subdirectory
         self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
@@ -106,7 +116,8 @@ class BoxData:
             with ingest.refusals():       # (what --ingest auto may fall back from: an input the streamed path declines, nothing later)
                 self.result: LECResult = ingest.lec_streamed(data.raw, data.plan, variable_list_df, limits, per_step_boxes=boxes_limits is not None,
                                                              device=dev, chunk_steps=data.chunk_steps, stats=self.ingest_stats, inflate=data.inflate,
-                                                             t_range=None if shard is None else (t0, t1), merge_dropmask=merge, out=out, keep_level=keep)
+                                                             t_range=None if shard is None else (t0, t1), merge_dropmask=merge, out=out, keep_level=keep,
+                                                             ring=self.periodic)
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)
@@ -153,6 +164,8 @@ class BoxData:
                 dTdt = dTdt[h0:h1]
             dTdt_dev = torch.as_tensor(np.ascontiguousarray(dTdt, dtype=common)).to(dev)
         boxes = self.boxes[t0:t1] if self.per_step_boxes else self.boxes
+        if self.periodic:
+            boxes = self.engine.prepare_boxes(boxes, ring=True)
         if self.per_step_boxes and self.shard is not None:
             # the records of every rank have the row count of the tallest box of the WHOLE series (as the one-process run's)
             nyb = max(b[3] - b[2] + 1 for b in self.boxes)
@@ -183,6 +196,33 @@ class BoxData:
         kw = self.engine.packed_dtdt(tm, f[0], tp, tcoef)
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
                                    drop_any_time=False, merge_dropmask=merge, out=out, **kw)
+
+
+def ring_box_check(lon, box) -> float:
+    """A periodic box on the longitude axis ``lon``: the axis must be a full ring and the box (iw, ie, js, jn) must span it from its first
+    to its last column -- a periodic box of part of a circle does not exist, and nothing is clamped.  Returns the closed axis' xlength
+    in radians; raises ValueError."""
+    from .follow import ring_error
+    from .tables import ring_axis
+    lon = np.asarray(lon, dtype=np.float64)
+    why = ring_error(lon)
+    if why:
+        raise ValueError("--periodic needs a full ring of longitudes: " + why)
+    if box[0] != 0 or box[1] != lon.size - 1:
+        raise ValueError(f"--periodic: the box limits select the longitudes {float(lon[box[0]])} and {float(lon[box[1]])}, not the axis' first "
+                         f"and last ({float(lon[0])} and {float(lon[-1])}): a periodic box of part of a circle does not exist "
+                         "(min_lon -180 and max_lon 180 always select the whole ring)")
+    return ring_axis(lon)[1]
+
+
+def ring_hint(lon, box):
+    """The line a plain -f run logs when its box spans the whole longitude axis of a ring (None otherwise): the run treats the circle
+    as a limited area, --periodic closes it."""
+    from .follow import ring_error
+    if box[0] != 0 or box[1] != len(lon) - 1 or ring_error(lon):
+        return None
+    return (f"the box spans all {len(lon)} longitudes of a full ring, but is evaluated as a limited area (half weight on the two seam columns, "
+            "one-sided d/dlon there, an east-west boundary flux): --periodic closes the circle")
 
 
 def host_fields(data: ds.LECDataset, variable_list_df: pd.DataFrame):
@@ -357,17 +397,28 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
     app_logger.info(f"Bounding box: lon=[{min_lon}, {max_lon}], lat=[{min_lat}, {max_lat}]")
     shard = getattr(args, "shard", None)
     root = shard is None or shard.root
+    periodic = bool(getattr(args, "periodic", False))
+    if periodic:        # refused here, before a file is written: no ring, or limits that do not span it
+        from .tables import box_indices
+        ring_box_check(data.lon, box_indices(data.lat, data.lon, min_lon, max_lon, min_lat, max_lat))
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
-                          results_subdirectory_vertical_levels)
+                          results_subdirectory_vertical_levels, periodic=periodic)
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
     phases.mark("ingest_compute_gather")
     if box_obj.result is None:              # time-sharded run: rank 0 holds the gathered series and writes every file
         return None
+    if periodic:
+        app_logger.info(f"--periodic: the box is a ring of {len(data.lon)} longitudes, lat=[{box_obj.southern_limit}, {box_obj.northern_limit}], "
+                        f"closed xlength {box_obj.xlength!r} rad (lec_rowstats_ring)")
+    else:
+        hint = ring_hint(data.lon, box_obj.boxes[0])
+        if hint:
+            app_logger.info("Bounding box: " + hint)
     if int(box_obj.nanflag.sum()):
         app_logger.warning("NaN level values were interpolated/dropped per time step (_handle_nans semantics)")
     terms = _compute_all(box_obj, "fixed", app_logger)

@@ -676,7 +676,8 @@ def device_cube(var: ds.RawVariable, plan: IngestPlan, device="cuda:0", unit: fl
 def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_limits, *, per_step_boxes: bool = False,
                  device="cuda:0", chunk_steps: Optional[int] = None, with_q: bool = True, stats: Optional[dict] = None,
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
-                 slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None) -> LECResult:
+                 slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
+                 ring: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -696,7 +697,11 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     instead of row fragments (include/lec_hip.h "box-packed series"; the same records bit for bit).
     ``t_range`` = (t0, t1): a rank's share of a time-sharded run -- only those steps (and their one-step T halo) are staged, copied
     and computed, so N ranks move 1/N of the bytes each, over N host links; ``merge_dropmask`` / ``out``: see ``LECEngine.reduce``.
+    ``ring``: the one fixed box covers the plan's whole longitude axis, a full ring (``LECEngine.prepare_boxes(ring=True)``): every
+    chunk's stage 1 is ``lec_rowstats_ring``.
     """
+    if ring and per_step_boxes:
+        raise ValueError("ring: one fixed box (the moving framework's ring is the 0..360 axis)")
     lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -802,7 +807,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     # ... and they hold a SUB-CHUNK of `dec_steps` steps (about 1 GiB per field): a chunk's raw sub-cubes are decoded and row-passed
     # piece by piece (the raw side keeps its large chunks -- the device inflate wants ~13000 streams per batch --, the decoded side
     # does not need them: 8 steps of a 37 x 721 x 1440 grid are 213,000 rows per launch).  Same kernels on the same rows: same bits.
-    bt, _ = engine._box_tables(boxes)            # the row count of the records is the tallest box of the WHOLE series, on every rank
+    bt, _ = engine._box_tables(boxes, ring=ring)  # the row count of the records is the tallest box of the WHOLE series, on every rank
     if packed is None:
         packed = bool(per_step_boxes and with_q)
     if packed and not (per_step_boxes and with_q):
@@ -833,7 +838,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     if per_step_boxes:
         own_boxes = engine.prepare_boxes(own_boxes, nyb_min=bt.nyb_max, packed=packed)
     else:
-        fixed_box = engine.prepare_boxes(boxes, nyb_min=bt.nyb_max)
+        fixed_box = engine.prepare_boxes(boxes, nyb_min=bt.nyb_max, ring=ring)
     # Row records live for one chunk only (6.8 MB per 37 x 721 time step: a month of hourly steps would be 5 GB, 30 k steps all of
     # HBM): every chunk's records go through the level half of stage 2 at once and leave 12 KB per step in `levraw`, which is what
     # the any-time NaN mask and the pressure integrals of the WHOLE series need at the end (energy_contents.py:190-208).  One buffer,

@@ -78,22 +78,43 @@ class BoxTables:
     nxb_max: int
     nyb_max: int
     lon_uniform: bool
+    ring: bool = False    # one box whose columns are a full ring of longitudes: stage 1 is lec_rowstats_ring
+
+
+def ring_axis(lon_deg: np.ndarray):
+    """(h, xlength) of the CLOSED axis of a ring of longitudes: column 0 once more at lon[nx - 1] + h, h the axis' own step;
+    xlength = deg2rad(lon[nx - 1] + h) - deg2rad(lon[0]) (box_data.py:128 on the closed axis)."""
+    lon = np.asarray(lon_deg, dtype=np.float64)
+    h = (lon[-1] - lon[0]) / (lon.size - 1)
+    return h, float(np.deg2rad(lon[-1] + h) - np.deg2rad(lon[0]))
 
 
 def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[Sequence[int]], nyb_min: int = 0,
-                     lon_uniform: Optional[bool] = None) -> BoxTables:
+                     lon_uniform: Optional[bool] = None, ring: bool = False) -> BoxTables:
     """Per-box tables for both stages.  ``boxes`` = inclusive index quadruples (iw, ie, js, jn).
     ``nyb_min``: pad the latitude extent of the tables (and of the row records) to at least this many rows -- chunks of one
     series of moving boxes share one record buffer, whose row count is the tallest box of the whole series.
     ``lon_uniform``: the formulation's flag as decided on ANOTHER longitude axis than ``lon_deg`` -- a track of a batch (batch.py) keeps
     the flag of its own crop while its boxes are addressed in the union crop; None = decided on ``lon_deg`` (the default everywhere
-    else).  True needs every box's longitudes evenly spaced."""
+    else).  True needs every box's longitudes evenly spaced.
+    ``ring``: ONE box over the whole longitude axis, which is a full ring (``follow.ring_error``): ``boxtab`` / ``boxtab2`` carry the
+    closed axis' xlength (``ring_axis``), h_rad = xlength / nx and 1 / h_deg for ``lec_rowstats_ring``; ``wlon`` / ``glon`` stay 0 (unused)."""
     lat = np.asarray(lat_deg, dtype=np.float64)
     lon = np.asarray(lon_deg, dtype=np.float64)
     box = np.asarray(boxes, dtype=np.int32).reshape(-1, 4)
     nb = box.shape[0]
     if np.any(box[:, 0] < 0) or np.any(box[:, 1] >= lon.size) or np.any(box[:, 2] < 0) or np.any(box[:, 3] >= lat.size):
         raise ValueError("box indices outside the grid")
+    if ring:
+        from .follow import ring_error
+        why = ring_error(lon)
+        if why:
+            raise ValueError("a periodic box needs a full ring of longitudes: " + why)
+        if nb != 1 or int(box[0, 0]) != 0 or int(box[0, 1]) != lon.size - 1:
+            raise ValueError(f"a periodic box is ONE box over the whole longitude axis (columns 0..{lon.size - 1}), not columns "
+                             + ", ".join(f"{int(b[0])}..{int(b[1])}" for b in box) + ": a periodic box of part of a circle does not exist")
+        if lon_uniform is False:
+            raise ValueError("a ring of longitudes is evenly spaced: lon_uniform cannot be False")
     nxb = box[:, 1] - box[:, 0] + 1
     nyb = box[:, 3] - box[:, 2] + 1
     if np.any(nxb < 2) or np.any(nyb < 2):
@@ -103,7 +124,8 @@ def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[S
         raise ValueError("nyb_min exceeds the grid")
     t = BoxTables(box=box, boxtab=np.zeros((nb, 4)), wlon=np.zeros((nb, nxm)), glon=np.zeros((nb, nxm, 3)),
                   lattab=np.zeros((nb, nym, 4)), boxtab2=np.zeros((nb, 4)), lattab2=np.zeros((nb, nym, 8)),
-                  nxb_max=nxm, nyb_max=nym, lon_uniform=is_uniform(lon) if lon_uniform is None else bool(lon_uniform))
+                  nxb_max=nxm, nyb_max=nym, lon_uniform=True if ring else (is_uniform(lon) if lon_uniform is None else bool(lon_uniform)),
+                  ring=bool(ring))
     if lon_uniform and not all(is_uniform(lon[int(b[0]): int(b[1]) + 1]) for b in box):
         raise ValueError("lon_uniform: a box's longitudes are not evenly spaced")
     # (lon_uniform selects the kernels' fast path and is decided on the grid's whole longitude axis, not on the boxes at hand: a
@@ -126,9 +148,13 @@ def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[S
         xlen = rlon[-1] - rlon[0]                                  # box_data.py:128
         ylen = np.sin(rlat[-1]) - np.sin(rlat[0])                  # box_data.py:129-131
         n = lo.size
-        t.boxtab[b] = (1.0 / xlen, xlen / (n - 1), (n - 1) / (lo[-1] - lo[0]), 0.0)
-        t.wlon[b, :n] = trapz_weights(rlon)
-        t.glon[b, :n] = gradient_coefs(lo)
+        if ring:                                                   # the closed axis: n intervals of h, every column weight 1
+            h, xlen = ring_axis(lo)
+            t.boxtab[b] = (1.0 / xlen, xlen / n, n / ((lo[-1] + h) - lo[0]), 0.0)
+        else:
+            t.boxtab[b] = (1.0 / xlen, xlen / (n - 1), (n - 1) / (lo[-1] - lo[0]), 0.0)
+            t.wlon[b, :n] = trapz_weights(rlon)
+            t.glon[b, :n] = gradient_coefs(lo)
         m = la.size
         cosl = np.cos(rlat)
         t.lattab[b, :m, :3] = gradient_coefs(la) * inv_dy
