@@ -14,6 +14,8 @@ runs the moving framework on that track -- the very run ``-t --trackfile <that f
 With --choose-systems K (or --choose-starts FILE) it finds the K strongest systems of the first time step (``lec_follow_seeds``),
 follows them all in one launch (``lec_follow_many``), writes ``LEC_Results/<infile>_choose_batch/choose_s01``, ``choose_s02``, ... and
 is from there on ``-t --trackfiles <those files>``: one tree ``LEC_Results/<infile>_choose_sNN_track/`` per system.
+With --batch-chunk N a batch of tracks (of either kind) is analysed from the streamed file, N time steps of the tracks' union resident per
+pipeline slot (``ingest.lec_streamed_batch``), instead of from a union of all tracks' steps and crops prepared on the host: the same files.
 With --choose-lifecycle (and --choose-threshold X) every time step is searched (``lec_follow_seeds_series``), a system is followed from
 the time step at which it forms until it has weakened (``lec_follow_spans``; --choose-end-threshold, --choose-patience,
 --choose-min-steps), and each track covers its system's own time steps.
@@ -37,7 +39,7 @@ import pandas as pd
 
 from lorenzcycletoolkit_amd import phases
 from lorenzcycletoolkit_amd.dataset import prepare_data
-from lorenzcycletoolkit_amd.frameworks import lec_fixed, lec_moving, lec_moving_batch
+from lorenzcycletoolkit_amd.frameworks import lec_fixed, lec_moving, lec_moving_batch, lec_moving_batch_streamed
 
 phases.mark("imports")          # interpreter start -> here: Python, pandas, torch and the package
 
@@ -66,6 +68,11 @@ def create_arg_parser():
     parser.add_argument("--trackfiles", nargs="+", metavar="PATH", help="with -t: many track files over the same data file in ONE pass "
                         "(a directory stands for every regular file in it, sorted by name).  Each track writes LEC_Results/<infile>_<track>_track/ "
                         "with the files a --trackfile run of it writes; the log and batch.csv go to LEC_Results/<infile>_track_batch/")
+    parser.add_argument("--batch-chunk", type=int, metavar="N", help="with -t --trackfiles (or -c --choose-systems / --choose-starts): stream the "
+                        "file to the GPU N time steps of the tracks' union at a time and decode / crop every track's boxes there, instead of "
+                        "decoding the union of all tracks' time steps and crops on the host and uploading it whole: device memory then depends "
+                        "on N, not on the length of the series (a batch that is refused for its size runs this way), and a deflated NetCDF-4 file "
+                        "is inflated on the GPU.  Same output files, byte for byte.  Independent of --choose-chunk")
     parser.add_argument("--box_limits", type=str, default="inputs/box_limits", help="box-limits file for -f (default: inputs/box_limits)")
     parser.add_argument("--periodic", action="store_true", help="with -f: the box is a full ring of longitudes -- a zonal band, a hemisphere, the "
                         "globe.  The file's longitudes must be evenly spaced with nx * dx = 360 degrees and the box limits' min_lon / max_lon must "
@@ -240,9 +247,9 @@ def refuse_choose_options(args):
         stem = "".join(args.infile.split("/")[-1].split(".nc"))
         raise SystemExit("-c/--choose follows the systems on one GPU (chains over the time steps): run -c once, then "
                          f"-t --trackfile LEC_Results/{stem}_choose_batch/choose_sNN --gpus N for the sharded analysis of a track it wrote")
-    if many and (args.ingest == "device" or args.device_ingest):
+    if many and (args.ingest == "device" or args.device_ingest) and args.batch_chunk is None:
         raise SystemExit("-c --choose-systems / --choose-starts prepares the data on the host: --ingest device / --device-ingest is not supported "
-                         "for a batch of tracks")
+                         "for a batch of tracks (--batch-chunk N streams the batch to the GPU)")
     if args.choose_systems is not None and not 1 <= args.choose_systems <= 256:
         raise SystemExit("--choose-systems must be 1..256")
     if args.choose_separation is not None and min(args.choose_separation) <= 0:
@@ -272,6 +279,20 @@ def refuse_periodic_options(args):
                          "meridian gets by itself, and --choose-periodic for the search of -c")
 
 
+def refuse_batch_chunk_options(args):
+    """--batch-chunk is the streamed analysis of a batch of tracks; said before anything is created."""
+    if args.batch_chunk is None:
+        return
+    many = args.choose and (args.choose_systems is not None or args.choose_starts is not None)
+    if args.trackfiles is None and not many:
+        raise SystemExit("--batch-chunk goes with --trackfiles (or -c --choose-systems / --choose-starts): it streams a batch of tracks; "
+                         "--device-ingest streams a single -f / -t / -c run")
+    if args.batch_chunk < 1:
+        raise SystemExit("--batch-chunk must be >= 1 time steps")
+    if args.ingest == "host":
+        raise SystemExit("--batch-chunk streams the file to the GPU, --ingest host prepares it on the host: give one of the two")
+
+
 def _join_threshold(argv):
     """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5`` (``--choose-end-threshold`` likewise): argparse takes a negative
     number in exponent form for an option."""
@@ -293,6 +314,7 @@ def main(argv=None):
         raise SystemExit("--gpus must be >= 1")
     refuse_choose_options(args)
     refuse_periodic_options(args)
+    refuse_batch_chunk_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
     if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
@@ -404,8 +426,9 @@ def refuse_batch_options(args):
         raise SystemExit("--trackfiles goes with -t/--track")
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--trackfiles runs on one GPU: --gpus > 1 is not supported for a batch of tracks")
-    if args.ingest == "device" or args.device_ingest:
-        raise SystemExit("--trackfiles prepares the data on the host: --ingest device / --device-ingest is not supported for a batch of tracks")
+    if (args.ingest == "device" or args.device_ingest) and args.batch_chunk is None:
+        raise SystemExit("--trackfiles prepares the data on the host: --ingest device / --device-ingest is not supported for a batch of tracks "
+                         "(--batch-chunk N streams the batch to the GPU)")
 
 
 def main_batch(args, argv):
@@ -456,8 +479,25 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
                             + ", ".join(trackfiles[n] for n in members) for origin, members in parts) + f" -- {len(parts)} pass(es) over the data")
         rows = [None] * len(trackfiles)
         for origin, members in parts:
-            data, plan = batch.prepare_union(args, [trackfiles[n] for n in members], "inputs/namelist", app_logger, lon_origin=origin)
-            phases.mark("open_decode_and_prepare")
+            raw = None
+            if args.batch_chunk is not None:
+                # the streamed batch: the file stays memory-mapped bytes, the plan is made on its coordinates; a file the streamed path
+                # does not read is refused (the host union is what the flag exists to avoid)
+                from lorenzcycletoolkit_amd import dataset as ds
+                try:
+                    raw = ds.open_raw(args.infile, ds.read_namelist("inputs/namelist", app_logger), mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
+                except ValueError as e:
+                    raise ValueError(f"--batch-chunk: the streamed path does not read this file ({e}); without --batch-chunk the batch is prepared on the host") from e
+                try:
+                    plan = batch.plan_batch(raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, [trackfiles[n] for n in members],
+                                            app_logger, origin)
+                except Exception:
+                    raw.close()
+                    raise
+                phases.mark("open_and_plan")
+            else:
+                data, plan = batch.prepare_union(args, [trackfiles[n] for n in members], "inputs/namelist", app_logger, lon_origin=origin)
+                phases.mark("open_decode_and_prepare")
             directories = []
             for tr in plan.tracks:
                 tree = os.path.join("./LEC_Results/", f"{stem}_{tr.stem}_track")
@@ -467,10 +507,20 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
                 for d in (fig, tree, vl):
                     os.makedirs(d, exist_ok=True)
                 directories.append((tree, fig, vl))
-            lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
+            if raw is not None:
+                from lorenzcycletoolkit_amd.ingest import StreamedRefusal
+                try:
+                    lec_moving_batch_streamed(raw, variable_list_df, plan, directories, app_logger, args)
+                except StreamedRefusal as e:        # no fall-back to the host union: that is the path the flag exists to avoid
+                    raise ValueError(f"--batch-chunk: the streamed path declines this input ({e}); without --batch-chunk the batch is prepared on the host") from e
+                finally:
+                    raw.close()
+            else:
+                lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
+                del data
             for n, tr, d in zip(members, plan.tracks, directories):
                 rows[n] = (tr.path, d[0], tr.n)
-            del data, plan
+            del plan
         pd.DataFrame({"trackfile": [r[0] for r in rows], "results_directory": [r[1] for r in rows],
                       "steps": [r[2] for r in rows]}).to_csv(os.path.join(batch_dir, "batch.csv"), index=False)
         app_logger.info("Analysis complete! Moving framework ran %d tracks in %.2f seconds" % (len(rows), time.time() - start_time))

@@ -14,7 +14,11 @@ opens, decodes and crops the same file again.  Here the tracks are planned toget
   the longitude formulation of its own crop (``TrackPlan.group_key``): one engine call per group, so no track's bits depend on which
   other tracks share the batch.
 
-This module is host-only (NumPy / pandas); ``frameworks.lec_moving_batch`` runs the plan on the GPU.
+With ``--batch-chunk N`` the union is never decoded or uploaded whole: ``plan_chunks`` cuts its time steps into runs of N, each with the
+file steps to stage (T also for the time neighbours its records name in other chunks) and, per group, the records and their
+``lec_ingest`` step rows; ``ingest.lec_streamed_batch`` streams the file chunk by chunk.
+
+This module is host-only (NumPy / pandas); ``frameworks.lec_moving_batch`` / ``lec_moving_batch_streamed`` run the plan on the GPU.
 """
 from __future__ import annotations
 
@@ -181,6 +185,56 @@ def plan_batch(lat, lon, lev, time, level_units, names, trackfiles: Sequence[str
     for k, tr in enumerate(plans):
         plan.groups.setdefault(tr.group_key, []).append(k)
     return plan
+
+
+@dataclass
+class ChunkGroup:
+    """One group's records of a chunk (``plan_chunks``), in (track, step) order."""
+    track: np.ndarray            # int [n]: the record's track, an index into BatchPlan.tracks
+    pos: np.ndarray              # int [n]: the record's position in its track
+    t_rows: np.ndarray           # int32 [3, n, 3]: lec_ingest step rows of T for shift 0 / -1 / +1: {entry of ChunkPlan.t_steps, box south row, box west column}
+    f_rows: np.ndarray           # int32 [n, 3]: the same for the other four fields: {entry of ChunkPlan.steps, box south row, box west column}
+
+    @property
+    def n(self) -> int:
+        return len(self.track)
+
+
+@dataclass
+class ChunkPlan:
+    """A run of consecutive union steps [u0, u1) of a BatchPlan, as one pipeline slot of the streamed batch holds it."""
+    u0: int
+    u1: int
+    steps: np.ndarray            # file steps staged for u, v, omega, geopotential: the chunk's own union steps
+    t_steps: np.ndarray          # file steps staged for T, ascending: the own steps and every previous / next step a record of the chunk names
+    groups: Dict[Tuple[int, int, bool], ChunkGroup] = field(default_factory=dict)     # TrackPlan.group_key -> records; a group without a record is absent
+
+
+def plan_chunks(plan: BatchPlan, chunk_steps: int) -> List[ChunkPlan]:
+    """The batch cut into runs of ``chunk_steps`` consecutive union steps.  A record (one time of one track) belongs to the chunk that
+    holds its union step; its T neighbours (``TrackPlan.steps``: the step itself at the track's ends) may lie in other chunks and are
+    staged with this one.  Box offsets are entries into the union crop's index maps; staged steps count from the slot's first one."""
+    chunk_steps = int(chunk_steps)
+    if chunk_steps < 1:
+        raise ValueError("chunk_steps must be >= 1")
+    chunks = []
+    for u0 in range(0, len(plan.tpos), chunk_steps):
+        u1 = min(u0 + chunk_steps, len(plan.tpos))
+        own = [np.flatnonzero((tr.ustep >= u0) & (tr.ustep < u1)) for tr in plan.tracks]
+        named = np.unique(np.concatenate([np.arange(u0, u1)] + [tr.steps[p].ravel() for tr, p in zip(plan.tracks, own)]))
+        ch = ChunkPlan(u0, u1, np.asarray(plan.tpos[u0:u1]), np.asarray(plan.tpos[named]))
+        for key, members in plan.groups.items():
+            track = np.concatenate([np.full(own[k].size, k, dtype=np.int64) for k in members])
+            if track.size == 0:
+                continue
+            pos = np.concatenate([own[k] for k in members])
+            org = np.array([(plan.tracks[k].boxes[p][2], plan.tracks[k].boxes[p][0]) for k, p in zip(track, pos)], dtype=np.int64)
+            st = np.stack([plan.tracks[k].steps[p] for k, p in zip(track, pos)])           # [n, 3] union steps: own, previous, next
+            t_rows = np.stack([np.column_stack([np.searchsorted(named, st[:, q]), org]) for q in range(3)]).astype(np.int32)
+            f_rows = np.column_stack([st[:, 0] - u0, org]).astype(np.int32)
+            ch.groups[key] = ChunkGroup(track, pos, t_rows, f_rows)
+        chunks.append(ch)
+    return chunks
 
 
 def union_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> int:

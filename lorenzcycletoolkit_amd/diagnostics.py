@@ -155,11 +155,40 @@ def box_ranges(lat_deg, lon_deg, limits) -> tuple:
     return int(ii[0]), int(ii[-1]), int(jj[0]), int(jj[-1]), jc, ic
 
 
+def extrema_tables(lat_deg, lon_deg, limits_per_step, device, formulation="metpy_no_crs") -> dict:
+    """The device tables of ``lec_track_diag`` on one grid: {"box" int32 [nt][6] (``box_ranges`` per step), "xcoef", "ycoef", "curv"}
+    (``vorticity_tables``) -- uploaded once by a caller that launches the kernel chunk by chunk (``extrema_on_device``)."""
+    import torch
+    dev = torch.device(device)
+    xcoef, ycoef, curv = vorticity_tables(lat_deg, lon_deg, formulation)
+    box = np.array([box_ranges(lat_deg, lon_deg, lim) for lim in limits_per_step], dtype=np.int32).reshape(len(limits_per_step), 6)
+    return {"box": torch.as_tensor(box).to(dev), "xcoef": torch.as_tensor(xcoef).to(dev), "ycoef": torch.as_tensor(ycoef).to(dev),
+            "curv": torch.as_tensor(curv).to(dev)}
+
+
+def extrema_on_device(u, v, h, tabs: dict, box_d, val, pos) -> None:
+    """``lec_track_diag`` on contiguous fp64 device slices [nt, lat, lon] with the tables of ``extrema_tables`` (``box_d``: the rows of
+    its "box" for these steps), into ``val`` fp64 [nt][5] and ``pos`` int32 [nt][8] on the device, on the current stream: nothing is
+    uploaded and nothing comes back, so a chunk loop can call it without making the host wait."""
+    import torch
+    nt, ny, nx = (int(x) for x in u.shape)
+    if (ny, nx) != (int(tabs["ycoef"].shape[0]), int(tabs["xcoef"].shape[1])) or int(box_d.shape[0]) != nt or val.shape != (nt, 5) or pos.shape != (nt, 8):
+        raise ValueError("slices, coordinates and boxes do not match")
+    for t, dt in ((u, torch.float64), (v, torch.float64), (h, torch.float64), (box_d, torch.int32), (val, torch.float64), (pos, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != u.device:
+            raise ValueError("extrema_on_device: contiguous fp64 slices and results, int32 boxes and positions, on one device")
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    args = _lib.DiagArgs(u_d=ptr(u), v_d=ptr(v), hgt_d=ptr(h), nt=nt, ny=ny, nx=nx, reserved0=0, box_d=ptr(box_d), xcoef_d=ptr(tabs["xcoef"]),
+                         ycoef_d=ptr(tabs["ycoef"]), curv_d=ptr(tabs["curv"]), val_d=ptr(val), pos_d=ptr(pos),
+                         stream=C.c_void_p(torch.cuda.current_stream(u.device).cuda_stream))
+    with torch.cuda.device(u.device):
+        _lib.check(_lib.load().lec_track_diag(C.byref(args)), "lec_track_diag")
+
+
 def device_extrema(u850, v850, hgt850, lat_deg, lon_deg, limits_per_step, device="cuda:0", formulation="metpy_no_crs"):
     """``lec_track_diag`` on [time, lat, lon] slices (host arrays or device tensors): returns (val [nt][5], pos [nt][8]) as NumPy
     arrays -- zeta minimum, zeta maximum, height minimum, wind maximum, zeta at the box centre; (j, i) of the four extrema."""
     import torch
-    lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda":
         raise _lib.LecLibraryError("the track diagnostics run on the GPU: there is no CPU path")
@@ -170,17 +199,10 @@ def device_extrema(u850, v850, hgt850, lat_deg, lon_deg, limits_per_step, device
     nt, ny, nx = (int(x) for x in u.shape)
     if (ny, nx) != (np.asarray(lat_deg).size, np.asarray(lon_deg).size) or len(limits_per_step) != nt:
         raise ValueError("slices, coordinates and boxes do not match")
-    xcoef, ycoef, curv = vorticity_tables(lat_deg, lon_deg, formulation)
-    box = np.array([box_ranges(lat_deg, lon_deg, lim) for lim in limits_per_step], dtype=np.int32).reshape(nt, 6)
-    box_d, xc_d, yc_d, cv_d = torch.as_tensor(box).to(dev), torch.as_tensor(xcoef).to(dev), torch.as_tensor(ycoef).to(dev), torch.as_tensor(curv).to(dev)
+    tabs = extrema_tables(lat_deg, lon_deg, limits_per_step, dev, formulation)
     val = torch.empty((nt, 5), dtype=torch.float64, device=dev)
     pos = torch.empty((nt, 8), dtype=torch.int32, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    args = _lib.DiagArgs(u_d=ptr(u), v_d=ptr(v), hgt_d=ptr(h), nt=nt, ny=ny, nx=nx, reserved0=0, box_d=ptr(box_d), xcoef_d=ptr(xc_d),
-                         ycoef_d=ptr(yc_d), curv_d=ptr(cv_d), val_d=ptr(val), pos_d=ptr(pos),
-                         stream=C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    with torch.cuda.device(dev):
-        _lib.check(lib.lec_track_diag(C.byref(args)), "lec_track_diag")
+    extrema_on_device(u, v, h, tabs, tabs["box"], val, pos)
     return val.cpu().numpy(), pos.cpu().numpy()
 
 
@@ -243,7 +265,9 @@ def track_diagnostics(data, variable_list_df, limits_per_step, track=None, use_t
     if "Geopotential Height" in variable_list_df.index:
         hgt = f64(get("Geopotential Height"))
     else:
-        hgt = f64(get("Geopotential")) / G                     # -> gpm
+        hgt = f64(get("Geopotential"))                         # -> gpm
+        # (a device tensor by a device tensor: IEEE division, the host's bits -- by a Python number torch multiplies with 1 / G)
+        hgt = hgt / (torch.tensor(G, dtype=torch.float64, device=hgt.device) if isinstance(hgt, torch.Tensor) else G)
     val, pos = device_extrema(u, v, hgt, data.lat, data.lon, limits_per_step[t0:t1], device=device, formulation=formulation)
     out = []
     for t in range(t0, t1):

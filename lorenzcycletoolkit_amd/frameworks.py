@@ -604,3 +604,54 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
         written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, positions, results_subdirectory,
                                              form, app_logger, args, lon_origin=ds.lon_origin_of_axis(view.lon)))
     return written
+
+
+def lec_moving_batch_streamed(raw: ds.RawDataset, variable_list_df: pd.DataFrame, plan, directories, app_logger, args):
+    """``lec_moving_batch`` without the union cubes (``-t --trackfiles --batch-chunk N``): the file is streamed ``args.batch_chunk`` union
+    time steps at a time (``ingest.lec_streamed_batch``), so the device holds a chunk's buffers and 12 KB per record however long the
+    series is, and the host decodes nothing.  ``raw``: the opened file (``dataset.open_raw``); coordinates and times come from the plan.
+    Every track's files are written by the code ``lec_moving_batch`` writes them with, byte for byte the same."""
+    from types import SimpleNamespace
+    from . import ingest
+    from .diagnostics import positions, track_diagnostics
+    dev = _device(args)
+    time_name = variable_list_df.loc["Time"]["Variable"]
+    vert_name = variable_list_df.loc["Vertical Level"]["Variable"]
+    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
+    # the 850-hPa diagnostics from the bytes this pass stages, where the namelist's wind units leave the file's values as they are
+    # (BoxData's rule for the single streamed run); otherwise from three level slices per track, decoded on the host
+    plain_units = all(ds.field_scale(variable_list_df, r) == 1.0 for r in ("Eastward Wind Component", "Northward Wind Component"))
+    diag = {"formulation": form} if plain_units else None
+    st = {}
+    with ingest.refusals():
+        results = ingest.lec_streamed_batch(raw, plan, variable_list_df, chunk_steps=args.batch_chunk, device=dev,
+                                            inflate=getattr(args, "inflate", None) or "auto", stats=st, diag=diag)
+    phases.mark("ingest_compute_gather")
+    app_logger.info(f"Batch of {len(plan.tracks)} tracks, streamed: union of {len(plan.tpos)} time steps on a {len(plan.lat)} x {len(plan.lon)} crop, "
+                    f"{len(plan.groups)} group(s) of equal box extents and longitude formulation; {st['chunks']} chunk(s) of {st['chunk_steps']} "
+                    f"step(s), {st['bytes_moved'] / 1e6:.1f} MB ({st['bytes_moved']} bytes) over the link, staging {st['staging']}, inflate {st['inflate']}, "
+                    f"storage {st['storage']}, device buffers {st['device_buffer_bytes'] / 1e9:.2f} GB")
+    app_logger.info("Streamed batch seconds: " + ", ".join(f"{k} {v:.3f}" for k, v in st["seconds"].items()))
+    written = []
+    for n, (tr, res, (results_subdirectory, figures_directory, vl_directory)) in enumerate(zip(plan.tracks, results, directories)):
+        wlat, wlon = tr.window(plan.lat, plan.lon)
+        view = SimpleNamespace(lat=wlat, lon=wlon, level=plan.px.level, time=tr.time, time_s=tr.time_s)
+        _create_level_csvs(vl_directory, time_name, vert_name, view.level)
+        holder = _TrackResult(view, variable_list_df, res, results_subdirectory, vl_directory)
+        if int(holder.nanflag.sum()):
+            app_logger.warning(f"{tr.path}: NaN level values were interpolated/dropped per time step (_handle_nans semantics)")
+        use_zeta = bool(getattr(args, "zeta", False))
+        if diag is not None:
+            val, pos = diag["extrema"][n]
+            rows = [tr.track.iloc[int(np.argmin(np.abs(tr.track.index - t)))] for t in tr.time]
+            found = [positions(val[t], pos[t], wlat, wlon, tr.limits[t], rows[t], use_zeta) for t in range(tr.n)]
+        else:
+            i32 = lambda a: np.ascontiguousarray(a, dtype=np.int32)
+            px = plan.px
+            own = ds.IngestPlan(np.asarray(plan.tpos[tr.ustep]), i32(px.ik), i32(px.ij[tr.js]), i32(px.io[tr.is_]), wlat, wlon, px.level, tr.time)
+            found = track_diagnostics(ingest.StreamedDataset(raw, own), variable_list_df, tr.limits, tr.track, use_track_zeta=use_zeta,
+                                      device=dev, formulation=form)
+        app_logger.info(f"Track {tr.path}: {tr.n} time steps -> {results_subdirectory}")
+        written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, found, results_subdirectory,
+                                             form, app_logger, args, lon_origin=ds.lon_origin_of_axis(view.lon)))
+    return written

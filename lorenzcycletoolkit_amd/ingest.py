@@ -12,7 +12,8 @@ host-prepared cubes): stage 1 is per row, and every chunk carries the one-step h
 
 Both frameworks: one fixed box for the whole series, or one box per time step along a track (the analysis domain is then
 the track-extent crop of slice_domain, select_area.py:297-313, and dT/dt is differentiated over the track-selected times on
-the device, as lorenzcycletoolkit.py:184-186 does on the host).
+the device, as lorenzcycletoolkit.py:184-186 does on the host).  A batch of tracks over one file (``lec_streamed_batch``) shares the raw
+side (``_Pipeline``) and gathers every record's box out of the chunk that holds its time step.
 """
 from __future__ import annotations
 
@@ -611,6 +612,113 @@ def _make_stager(var: ds.RawVariable, steps: int, device, levels, j0: int, j1: i
     return _Stager(var, steps, device, levels, j0, j1, slots, pinned=pinned)
 
 
+class _Pipeline:
+    """The raw side of a streamed run, chunk after chunk round ``slots`` pipeline slots: every variable of a chunk is staged (thread
+    pool) or copied straight from the registered file pages, uploaded on the copy stream -- a deflated variable on its own stream, where
+    it is inflated too -- and handed to the compute stream through events; a slot is reused once the compute stream has decoded it.
+    Nothing here makes the host wait for the compute stream."""
+
+    def __init__(self, lib, dev, roles, stagers: dict, slots: int, direct: bool, spans: Optional[RegisteredSpans]):
+        self.lib, self.roles, self.stagers, self.slots, self.direct, self.spans = lib, roles, stagers, slots, direct, spans
+        self.compute = torch.cuda.current_stream(dev)
+        self.copier = torch.cuda.Stream(device=dev)
+        self.copied = [[torch.cuda.Event() for _ in roles] for _ in range(slots)]      # the variable's upload of the slot has landed
+        self.consumed = [torch.cuda.Event() for _ in range(slots)]      # the slot's raw buffers have been decoded
+        self.used = [False] * slots
+        self.moved, self.host_s = 0, 0.0
+
+    def upload(self, c: int, steps_of) -> None:
+        """Chunk ``c`` into slot ``c % slots``: ``steps_of(role)`` = (the file steps of the role, the slot row the first of them goes
+        to).  The compute stream waits for every variable's upload."""
+        slot, stagers, copier = c % self.slots, self.stagers, self.copier
+        if self.used[slot]:
+            for ev in self.copied[slot]:        # the pinned buffers of this slot may be overwritten now: EVERY variable's upload has landed
+                ev.synchronize()                # (they ride on different streams when deflated and plain variables mix: ADVICE r3)
+            if self.spans is not None:
+                self.spans.release(c - self.slots + 1)    # ... and the file spans only chunks up to c - slots used are no longer being read
+        copier_waited = False                   # has the shared copy stream waited for this slot's last decode yet?
+        for n, r in enumerate(self.roles):
+            # variable by variable: stage (thread pool), enqueue its upload, decode it -- the copy engine starts after a fifth of the
+            # chunk's staging, and the next variable is staged while this one is on the link
+            file_steps, a = steps_of(r)
+            b = a + len(file_steps)
+            t_host = time.perf_counter()
+            if not self.direct:
+                stagers[r].stage(slot, file_steps, a)
+            self.host_s += time.perf_counter() - t_host
+            up = stagers[r].streams[slot] if hasattr(stagers[r], "streams") else copier   # a deflated variable uploads and inflates on its own stream
+            stagers[r].use = c
+            with torch.cuda.stream(up):
+                if self.used[slot] and (up is not copier or not copier_waited):
+                    up.wait_event(self.consumed[slot])       # the raw device buffers of this slot have been decoded
+                    copier_waited = copier_waited or up is copier
+                if self.direct:
+                    t_host = time.perf_counter()
+                    self.moved += stagers[r].upload_direct(self.lib, self.spans, slot, file_steps, a, c, C.c_void_p(copier.cuda_stream))
+                    self.host_s += time.perf_counter() - t_host
+                else:
+                    stagers[r].upload(slot, a, b)
+                    if not isinstance(stagers[r], _ChunkStager):
+                        self.moved += (b - a) * stagers[r].step_elems * stagers[r].itemsize
+                self.copied[slot][n].record(up)
+            self.compute.wait_event(self.copied[slot][n])
+
+    def decoded(self, slot: int) -> None:
+        """Everything that reads the slot's raw buffers has been enqueued on the compute stream."""
+        self.consumed[slot].record(self.compute)
+        self.used[slot] = True
+
+    def finish(self):
+        """After the last chunk: (the roles inflated on the device, the registration counters or None); raises if a chunk did not
+        inflate."""
+        on_device = [r for r in self.roles if isinstance(self.stagers[r], _ChunkStager)]
+        for r in on_device:
+            self.stagers[r].finish()                # every chunk inflated (raises otherwise)
+            self.moved += self.stagers[r].compressed_bytes
+        reg_stats = None
+        if self.spans is not None:
+            self.copier.synchronize()               # every copy has read its span (the deflated variables' streams: finish() above)
+            reg_stats = dict(registered_bytes=self.spans.registered_bytes, register_calls=self.spans.calls)
+            self.spans.close()
+        return on_device, reg_stats
+
+
+def _staging_mode(lib, rvars: dict, roles, j0: int, j1: int, first_step: int, staging: str, inflate: str):
+    """How a streamed run's bytes leave the host (``lec_streamed``'s ``staging`` / ``inflate``): (direct -- every variable is plain mapped
+    memory that the runtime registers, copied from as it lies --, the run's RegisteredSpans or None, the roles whose deflated chunks are
+    inflated on the device, whether those chunks go out of the file's own pages too).  ``first_step``: a file step the run reads (the
+    probe registers one page of it)."""
+    if staging not in ("auto", "staged", "registered"):
+        raise ValueError("staging must be 'auto', 'staged' or 'registered'")
+    probe = {r: _Stager.__new__(_Stager) for r in roles}
+    for r in roles:
+        probe[r].var, probe[r].j0, probe[r].j1 = rvars[r], j0, j1
+    direct = staging != "staged" and all(probe[r].direct_ok() for r in roles)
+    spans = RegisteredSpans(lib) if direct else None
+    if direct and staging == "auto":            # does this host's runtime register this memory at all?  (one page of the first variable)
+        try:
+            a0 = probe[roles[0]].step_address(int(first_step))
+            spans.ensure(a0, a0 + 1, -1)
+            spans.release(0)
+        except _lib.LecLibraryError:
+            direct, spans = False, None
+    # deflated variables: their compressed chunks go out straight from the file's own pages too (one RegisteredSpans for the run)
+    chunked = [r for r in roles if inflate != "host" and getattr(rvars[r].data, "chunk_streams", lambda: None)() is not None]
+    chunk_direct = bool(chunked) and staging != "staged"
+    if chunk_direct and spans is None:
+        try:
+            spans = RegisteredSpans(lib)
+            m0 = int(np.frombuffer(rvars[chunked[0]].data.chunk_streams()["map"], dtype=np.uint8).ctypes.data)
+            spans.ensure(m0, m0 + 1, -1)
+            spans.release(0)
+        except (_lib.LecLibraryError, ValueError, TypeError):
+            chunk_direct, spans = False, None
+    if staging == "registered" and not direct and not (chunk_direct and len(chunked) == len(roles)):
+        raise ValueError("staging='registered' needs every variable as plain (mapped) memory or as device-inflated chunks; variables that are "
+                         "inflated on the host are staged")
+    return direct, spans, chunked, chunk_direct
+
+
 def _lec_code(dtype: np.dtype) -> int:
     return _lib.LEC_F64 if np.dtype(dtype) == np.float64 else _lib.LEC_F32
 
@@ -766,34 +874,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     j0, j1 = int(plan.jmap.min()), int(plan.jmap.max())
     nl_in, ny_in, nx_in = nl, j1 - j0 + 1, int(rvars["Air Temperature"].data.shape[3])
     file_levels = np.sort(plan.kmap)
-    if staging not in ("auto", "staged", "registered"):
-        raise ValueError("staging must be 'auto', 'staged' or 'registered'")
-    probe = {r: _Stager.__new__(_Stager) for r in roles}
-    for r in roles:
-        probe[r].var, probe[r].j0, probe[r].j1 = rvars[r], j0, j1
-    direct = staging != "staged" and all(probe[r].direct_ok() for r in roles)
-    spans = RegisteredSpans(lib) if direct else None
-    if direct and staging == "auto":            # does this host's runtime register this memory at all?  (one page of the first variable)
-        try:
-            a0 = probe[roles[0]].step_address(int(plan.tsel[t0]))
-            spans.ensure(a0, a0 + 1, -1)
-            spans.release(0)
-        except _lib.LecLibraryError:
-            direct, spans = False, None
-    # deflated variables: their compressed chunks go out straight from the file's own pages too (one RegisteredSpans for the run)
-    chunked = [r for r in roles if inflate != "host" and getattr(rvars[r].data, "chunk_streams", lambda: None)() is not None]
-    chunk_direct = bool(chunked) and staging != "staged"
-    if chunk_direct and spans is None:
-        try:
-            spans = RegisteredSpans(lib)
-            m0 = int(np.frombuffer(rvars[chunked[0]].data.chunk_streams()["map"], dtype=np.uint8).ctypes.data)
-            spans.ensure(m0, m0 + 1, -1)
-            spans.release(0)
-        except (_lib.LecLibraryError, ValueError, TypeError):
-            chunk_direct, spans = False, None
-    if staging == "registered" and not direct and not (chunk_direct and len(chunked) == len(roles)):
-        raise ValueError("staging='registered' needs every variable as plain (mapped) memory or as device-inflated chunks; variables that are "
-                         "inflated on the host are staged")
+    direct, spans, chunked, chunk_direct = _staging_mode(lib, rvars, roles, j0, j1, int(plan.tsel[t0]), staging, inflate)
     if not direct and not chunk_direct and chunked:
         # pinned staging buffers are paid for per byte (pinning): a short series should reuse its slots, not size them for one use each
         chunk_steps = max(1, min(chunk_steps, max(8, -(-(t1 - t0) // (2 * slots)))))
@@ -854,12 +935,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
 
     t_setup = time.perf_counter()               # (tables, staging / device buffers allocated)
     mem_setup = torch.cuda.memory_allocated(dev) - mem_enter
-    compute = torch.cuda.current_stream(dev)
-    copier = torch.cuda.Stream(device=dev)
-    copied = [[torch.cuda.Event() for _ in roles] for _ in range(slots)]      # the variable's upload of the slot has landed
-    consumed = [torch.cuda.Event() for _ in range(slots)]      # the slot's raw buffers have been decoded
-    used = [False] * slots
-    moved, host_s = 0, 0.0
+    pipe = _Pipeline(lib, dev, roles, stagers, slots, direct, spans)
+    compute = pipe.compute
     # Nothing inside the chunk loop may make the host wait for the GPU (an upload from pageable memory does: it serialised staging
     # and copies in rounds 1-2, profiles/r03_notes.md): the d/dt coefficients of the whole time axis and the tables of every box go to
     # the device once, here; a chunk uses rows / views of them.
@@ -874,38 +951,9 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         slot = c % slots
         c0, c1 = bounds[c], bounds[c + 1]
         h0, h1 = (max(c0 - 1, 0), min(c1 + 1, nt)) if with_q else (c0, c1)
-        if used[slot]:
-            for ev in copied[slot]:             # the pinned buffers of this slot may be overwritten now: EVERY variable's upload has landed
-                ev.synchronize()                # (they ride on different streams when deflated and plain variables mix: ADVICE r3)
-            if spans is not None:
-                spans.release(c - slots + 1)    # ... and the file spans only chunks up to c - slots used are no longer being read
         # only T carries the halo; the other fields start at their own first step (rows [c0 - h0, c1 - h0) of the slot)
         span_of = lambda r: (0, h1 - h0) if r == "Air Temperature" else (c0 - h0, c1 - h0)
-        copier_waited = False                   # has the shared copy stream waited for this slot's last decode yet?
-        for n, r in enumerate(roles):
-            # variable by variable: stage (thread pool), enqueue its upload, decode it -- the copy engine starts after a fifth of the
-            # chunk's staging, and the next variable is staged while this one is on the link
-            a, b = span_of(r)
-            t_host = time.perf_counter()
-            if not direct:
-                stagers[r].stage(slot, plan.tsel[h0 + a: h0 + b], a)
-            host_s += time.perf_counter() - t_host
-            up = stagers[r].streams[slot] if hasattr(stagers[r], "streams") else copier   # a deflated variable uploads and inflates on its own stream
-            stagers[r].use = c
-            with torch.cuda.stream(up):
-                if used[slot] and (up is not copier or not copier_waited):
-                    up.wait_event(consumed[slot])       # the raw device buffers of this slot have been decoded
-                    copier_waited = copier_waited or up is copier
-                if direct:
-                    t_host = time.perf_counter()
-                    moved += stagers[r].upload_direct(lib, spans, slot, plan.tsel[h0 + a: h0 + b], a, c, C.c_void_p(copier.cuda_stream))
-                    host_s += time.perf_counter() - t_host
-                else:
-                    stagers[r].upload(slot, a, b)
-                    if not isinstance(stagers[r], _ChunkStager):
-                        moved += (b - a) * stagers[r].step_elems * stagers[r].itemsize
-                copied[slot][n].record(up)
-            compute.wait_event(copied[slot][n])
+        pipe.upload(c, lambda r: (plan.tsel[h0 + span_of(r)[0]: h0 + span_of(r)[1]], span_of(r)[0]))
         # decode + row pass, sub-chunk by sub-chunk, in the layout of the call: the box-packed series (every output step holds that
         # step's box alone: lec_ingest enters the maps at the box's south-west corner, step by step -- `step_tab` --, T also from the
         # two neighbouring steps' raw slices), or the cubes with T's one-step halo of the SUB-chunk (rows of the raw slot count from h0)
@@ -945,19 +993,12 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_count=n, with_q=with_q, rows_out=rows[:n],
                             per_step_boxes=per_step_boxes, **kw)
             engine.level_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
-        consumed[slot].record(compute)
-        used[slot] = True
+        pipe.decoded(slot)
     t_loop = time.perf_counter()                # (every chunk enqueued)
     res = engine.vertical_stage(levraw, own_boxes if per_step_boxes else fixed_box, drop_any_time=not per_step_boxes,
                                 merge_dropmask=merge_dropmask, out=out)
-    on_device = [r for r in roles if isinstance(stagers[r], _ChunkStager)]
-    for r in on_device:
-        stagers[r].finish()                     # every chunk inflated (raises otherwise)
-        moved += stagers[r].compressed_bytes
-    if spans is not None:
-        copier.synchronize()                    # every copy has read its span (the deflated variables' streams: finish() above)
-        reg_stats = dict(registered_bytes=spans.registered_bytes, register_calls=spans.calls)
-        spans.close()
+    on_device, reg_stats = pipe.finish()
+    moved, host_s = pipe.moved, pipe.host_s
     if stats is not None:
         stats.update(staging="registered" if (direct or chunk_direct) else "staged", **(reg_stats if spans is not None else {}))
         if keep is not None:
@@ -975,3 +1016,199 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
 def lec_fixed_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, box_limits, **kw) -> LECResult:
     """The fixed framework on the streamed path: one box for the whole series (see lec_streamed)."""
     return lec_streamed(raw, plan, variable_list_df, [box_limits], per_step_boxes=False, **kw)
+
+
+def lec_streamed_batch(raw: ds.RawDataset, plan, variable_list_df, *, chunk_steps: int, device="cuda:0", inflate: str = "auto",
+                       staging: str = "auto", stats: Optional[dict] = None, max_records: Optional[int] = None,
+                       diag: Optional[dict] = None) -> list:
+    """All LEC terms of every track of a batch (``plan``: a ``batch.BatchPlan`` on ``raw``'s coordinates), streamed from the
+    memory-mapped file ``chunk_steps`` union time steps at a time (``batch.plan_chunks``): the union cubes that
+    ``frameworks.lec_moving_batch`` uploads whole never exist, on the host or on the device.  Returns one LECResult per track, in batch
+    order, each in the track's own step order -- the bits of the track's own streamed run.
+
+    The raw side is ``lec_streamed``'s (``_Pipeline``: slots, registered spans or pinned staging, the device inflate on its own streams)
+    on the union's latitude band; a slot holds the chunk's own steps of u, v, omega and the geopotential, and of T also every time
+    neighbour a record of the chunk names, wherever in the series it lies.  Per chunk and group of tracks (``TrackPlan.group_key``) the
+    records' boxes are gathered into box-packed slabs by ``lec_ingest`` (per-record source step and box corner), then ``packed_dtdt``,
+    stage 1 and the level half of stage 2 into the group's ``levraw`` rows -- at most ``max_records`` records per launch (default: about
+    1 GiB per field, as ``lec_streamed``'s sub-chunks; results do not depend on it).  The vertical half runs once per group at the end.
+    Every table goes to the device before the loop: nothing inside it makes the host wait for the GPU.
+
+    ``diag``: a dict with "formulation" (``diagnostics.FORMULATIONS``) asks for the 850-hPa track diagnostics too: u, v and the
+    geopotential at 85000 Pa are gathered for each chunk's records on each track's OWN crop, ``lec_track_diag`` runs on them, and the
+    dict receives "extrema" = per track (val [n][5], pos [n][8]) as NumPy arrays, copied once at the end.  (The caller asks for it only
+    where the namelist's wind units leave the file's values as they are: ``frameworks.BoxData``'s rule.)
+    ``stats`` receives chunks, chunk_steps, bytes_moved, device_buffer_bytes, inflate, staging, staged_steps = {field: file steps staged
+    over the run}, records, seconds."""
+    from . import batch as bt_
+    from . import diagnostics as dg
+    from .constants import G
+    lib = _lib.load()
+    dev = torch.device(device)
+    if dev.type != "cuda":
+        raise _lib.LecLibraryError("the device ingest needs a GPU: there is no CPU path")
+    if max_records is not None and max_records < 1:
+        raise ValueError("max_records must be >= 1")
+    t_enter = time.perf_counter()
+    chunks = bt_.plan_chunks(plan, chunk_steps)
+    chunk_steps = min(int(chunk_steps), len(plan.tpos))
+    px = plan.px
+    nl, ny, nx = px.level.size, plan.lat.size, plan.lon.size
+    geo_role = raw.geo_role
+    roles = list(_ROLE_KEYS) + [geo_role]
+    keys = {**_ROLE_KEYS, geo_role: "geopt"}
+    rvars = {r: raw.variables[raw.names[r]] for r in roles}
+    decode, common = storage_dtypes(rvars)
+    out_dtype = torch.float64 if common == np.float64 else torch.float32
+    esize = 8 if common == np.float64 else 4
+    on_gpu = inflate != "host" and any(getattr(v.data, "chunk_streams", lambda: None)() is not None for v in rvars.values())
+    slots = 3 if on_gpu else 2                  # (as lec_streamed: a third slot lets the tail of one inflate batch overlap the next two)
+    # staged sub-cube of every file time step: the kept levels x the latitude band of the UNION crop, whole longitude rows
+    jmap_f, imap_f = np.asarray(px.ij[plan.js]), np.asarray(px.io[plan.is_])
+    j0, j1 = int(jmap_f.min()), int(jmap_f.max())
+    nl_in, ny_in, nx_in = nl, j1 - j0 + 1, int(rvars["Air Temperature"].data.shape[3])
+    file_levels = np.sort(px.ik)
+    t_cap = max(len(ch.t_steps) for ch in chunks)           # T's rows per slot: the own steps and the neighbours named from other chunks
+    cap = {r: t_cap if r == "Air Temperature" else chunk_steps for r in roles}
+    # per group: the records of every chunk one after the other (chunk-major; within a chunk (track, step) order), so that a chunk's
+    # records are a run of rows of the group's tables, of its prepared boxes and of its levraw
+    groups = {}
+    for key in plan.groups:
+        parts = [ch.groups[key] for ch in chunks if key in ch.groups]
+        groups[key] = dict(track=np.concatenate([g.track for g in parts]), pos=np.concatenate([g.pos for g in parts]),
+                           t_rows=np.concatenate([g.t_rows for g in parts], axis=1), f_rows=np.concatenate([g.f_rows for g in parts]),
+                           most=max(g.n for g in parts))
+    for (nyb, nxb, _u), g in groups.items():
+        by_size = max(4, (1 << 30) // (nl * nyb * nxb * esize))
+        g["launch"] = min(g["most"], by_size if max_records is None else int(max_records))
+    slab = max(g["launch"] * nl * key[0] * key[1] for key, g in groups.items())                 # elements of one field's slabs
+    rows_elems = max(g["launch"] * nl * key[0] * _lib.LEC_NSTAT for key, g in groups.items())
+    nyp_max, nxp_max = max(k[0] for k in groups), max(k[1] for k in groups)
+    crop = max((tr.js.stop - tr.js.start) * (tr.is_.stop - tr.is_.start) for tr in plan.tracks)
+    # what the chunk buffers take, before anything is allocated: the raw sub-cubes of every slot (twice that where they are inflated on
+    # the device: compressed + inflated), the decoded slabs (five fields, T's two neighbours, dT/dt for fp64 storage), the row records,
+    # and the diagnostics' three slices of a chunk's records on the largest crop
+    raw_bytes = slots * sum(cap[r] * nl_in * ny_in * nx_in * rvars[r].data.dtype.itemsize for r in roles) * (2 if on_gpu else 1)
+    dec_bytes = slab * esize * 7 + (slab * 8 if common == np.float64 else 0)
+    diag_bytes = 0 if diag is None else 3 * chunk_steps * crop * (8 + (esize if esize != 8 else 0))
+    need = raw_bytes + dec_bytes + rows_elems * 8 + diag_bytes
+    free = torch.cuda.mem_get_info(dev)[0] + torch.cuda.memory_reserved(dev) - torch.cuda.memory_allocated(dev)      # free + what torch caches
+    if need > free // 2:
+        raise MemoryError(f"the chunk buffers of the streamed batch need {need / 1e9:.2f} GB of device memory ({slots} slots of raw sub-cubes "
+                          f"{raw_bytes / 1e9:.2f} GB, decoded slabs {dec_bytes / 1e9:.2f} GB, row records {rows_elems * 8 / 1e9:.2f} GB, diagnostics "
+                          f"{diag_bytes / 1e9:.2f} GB), more than half of the {free / 1e9:.2f} GB free: a smaller --batch-chunk")
+    mem_enter = torch.cuda.memory_allocated(dev)
+    engine = LECEngine(plan.lat, plan.lon, px.level, device=dev)
+    direct, spans, chunked, chunk_direct = _staging_mode(lib, rvars, roles, j0, j1, int(plan.tpos[0]), staging, inflate)
+    stagers = {r: _make_stager(rvars[r], cap[r], dev, file_levels, j0, j1, slots, not direct, inflate, spans if chunk_direct else None) for r in roles}
+    up = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int32).to(dev)
+    jmap_rel, imap_rel = jmap_f - j0, imap_f
+    # the maps are lengthened by a slab (their last entry repeated), as lec_streamed's: a box that ends at the crop's edge is gathered
+    # with the slab's extents -- what lies beside a box is never read by stage 1
+    maps = (up(np.searchsorted(file_levels, px.ik)), up(np.concatenate([jmap_rel, np.repeat(jmap_rel[-1:], nyp_max)])),
+            up(np.concatenate([imap_rel, np.repeat(imap_rel[-1:], nxp_max)])))
+    f64 = dict(dtype=torch.float64, device=dev)
+    flat = {k: torch.empty(slab, dtype=out_dtype, device=dev) for k in list(keys.values()) + ["tm", "tp"]}
+    dtdt_flat = torch.empty(slab, **f64) if common == np.float64 else None
+    rows_flat = torch.empty(rows_elems, **f64)
+    for key, g in groups.items():
+        g["t_tab"] = [up(g["t_rows"][q]) for q in range(3)]             # shift 0 / -1 / +1
+        g["f_tab"] = up(g["f_rows"])
+        g["tcoef"] = torch.as_tensor(np.ascontiguousarray(np.stack([plan.tracks[k].tcoef[p] for k, p in zip(g["track"], g["pos"])]), dtype=np.float64)).to(dev)
+        boxes = [plan.tracks[k].boxes[p] for k, p in zip(g["track"], g["pos"])]
+        g["boxes"] = engine.prepare_boxes(boxes, nyb_min=key[0], packed=True, lon_uniform=key[2])      # (the formulation of the tracks' own crops)
+        g["levraw"] = torch.empty((len(boxes), nl, _lib.LEC_NLEVRAW), **f64)
+        g["done"] = 0
+    phi_scale = ds.field_scale(variable_list_df, geo_role)
+    # the 850-hPa diagnostics: per track the tables of its own crop, the gather rows {staged step, the crop's corner} and the results
+    tdiag = None
+    if diag is not None:
+        k850 = int(np.flatnonzero(px.level == 85000.0)[0])
+        kmap1 = maps[0][k850: k850 + 1]
+        tdiag = []
+        for tr in plan.tracks:
+            wlat, wlon = tr.window(plan.lat, plan.lon)
+            tabs = dg.extrema_tables(wlat, wlon, tr.limits, dev, diag.get("formulation", "metpy_no_crs"))
+            own = np.column_stack([tr.ustep % chunk_steps, np.full(tr.n, tr.joff), np.full(tr.n, tr.ioff)])
+            tdiag.append(dict(tabs=tabs, rows=up(own), ny=wlat.size, nx=wlon.size, val=torch.empty((tr.n, 5), **f64),
+                              pos=torch.empty((tr.n, 8), dtype=torch.int32, device=dev)))
+        d64 = {k: torch.empty(chunk_steps * crop, **f64) for k in ("u", "v", "geopt")}
+        g_dev = torch.tensor(G, **f64)          # (a device divisor: IEEE division, the host's bits -- by a Python number torch multiplies with 1 / G)
+        dsrc = d64 if common == np.float64 else {k: torch.empty(chunk_steps * crop, dtype=out_dtype, device=dev) for k in d64}
+
+    t_setup = time.perf_counter()               # (tables, staging / device buffers allocated)
+    mem_setup = torch.cuda.memory_allocated(dev) - mem_enter
+    pipe = _Pipeline(lib, dev, roles, stagers, slots, direct, spans)
+    compute = pipe.compute
+    staged = {keys[r]: 0 for r in roles}
+    for c, ch in enumerate(chunks):
+        slot = c % slots
+        pipe.upload(c, lambda r: (ch.t_steps if r == "Air Temperature" else ch.steps, 0))
+        for r in roles:
+            staged[keys[r]] += len(ch.t_steps if r == "Air Temperature" else ch.steps)
+        held = {r: len(ch.t_steps) if r == "Air Temperature" else len(ch.steps) for r in roles}      # what bounds the tables' source steps
+        for key, cg in ch.groups.items():
+            g = groups[key]
+            nyp, nxp = key[0], key[1]
+            geom = (nl_in, ny_in, nx_in, nl, nyp, nxp)
+            for a in range(g["done"], g["done"] + cg.n, g["launch"]):
+                b = min(a + g["launch"], g["done"] + cg.n)
+                n = b - a
+                f = {k: t[: n * nl * nyp * nxp].view(n, nl, nyp, nxp) for k, t in flat.items()}
+                with torch.cuda.device(dev):
+                    for r in roles:             # ONE gather per plane and launch: every record's box through lec_ingest's per-step origins
+                        unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
+                        tabs = [(keys[r], g["t_tab"][0]), ("tm", g["t_tab"][1]), ("tp", g["t_tab"][2])] if r == "Air Temperature" else [(keys[r], g["f_tab"])]
+                        for k, tab in tabs:
+                            _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, geom, maps, unit, decode[r], common,
+                                         f[k].data_ptr(), compute, step=tab[a:b], step_base=0, nt_src=held[r])
+                    out = None if dtdt_flat is None else dtdt_flat[: n * nl * nyp * nxp].view(n, nl, nyp, nxp)
+                    kw = engine.packed_dtdt(f["tm"], f["tair"], f["tp"], g["tcoef"][a:b], out=out)
+                part = g["boxes"].part(a, b)
+                rows = rows_flat[: n * nl * nyp * _lib.LEC_NSTAT].view(n, nl, nyp, _lib.LEC_NSTAT)
+                engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_begin=0, t_count=n, with_q=True, rows_out=rows,
+                                per_step_boxes=True, **kw)
+                engine.level_stage(rows, part, g["levraw"][a:b], phi_scale=phi_scale)
+            g["done"] += cg.n
+        if tdiag is not None:
+            for tr, td in zip(plan.tracks, tdiag):
+                p0, p1 = int(np.searchsorted(tr.ustep, ch.u0)), int(np.searchsorted(tr.ustep, ch.u1))
+                if p0 == p1:
+                    continue
+                n, m = p1 - p0, (p1 - p0) * td["ny"] * td["nx"]
+                with torch.cuda.device(dev):
+                    for r, k in (("Eastward Wind Component", "u"), ("Northward Wind Component", "v"), (geo_role, "geopt")):
+                        unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
+                        _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, (nl_in, ny_in, nx_in, 1, td["ny"], td["nx"]),
+                                     (kmap1, maps[1], maps[2]), unit, decode[r], common, dsrc[k].data_ptr(), compute, step=td["rows"][p0:p1],
+                                     step_base=0, nt_src=held[r])
+                        if dsrc is not d64:
+                            d64[k][:m].copy_(dsrc[k][:m])
+                    if "Geopotential Height" not in variable_list_df.index:
+                        d64["geopt"][:m].div_(g_dev)            # -> gpm (diagnostics.track_diagnostics)
+                    sl = {k: t[:m].view(n, td["ny"], td["nx"]) for k, t in d64.items()}
+                    dg.extrema_on_device(sl["u"], sl["v"], sl["geopt"], td["tabs"], td["tabs"]["box"][p0:p1], td["val"][p0:p1], td["pos"][p0:p1])
+        pipe.decoded(slot)
+    t_loop = time.perf_counter()                # (every chunk enqueued)
+    results = [None] * len(plan.tracks)
+    for key, g in groups.items():
+        res = engine.vertical_stage(g["levraw"], g["boxes"], drop_any_time=False)
+        for k in plan.groups[key]:
+            idx = torch.as_tensor(np.flatnonzero(g["track"] == k)).to(dev)       # the track's records, in its own step order
+            packed = res.packed.index_select(0, idx)
+            results[k] = LECResult(scalars=packed[:, :_lib.LEC_NSCALAR], levels=packed[:, _lib.LEC_NSCALAR:].unflatten(1, (_lib.LEC_NLEVTAB, nl)),
+                                   nanflag=res.nanflag.index_select(0, idx), packed=packed)
+    on_device, reg_stats = pipe.finish()
+    torch.cuda.synchronize(dev)
+    if diag is not None:
+        diag["extrema"] = [(td["val"].cpu().numpy(), td["pos"].cpu().numpy()) for td in tdiag]
+    if stats is not None:
+        stats.update(staging="registered" if (direct or chunk_direct) else "staged", **(reg_stats or {}))
+        stats.update(inflate="device" if on_device else ("host" if any(hasattr(v.data, "chunk_streams") for v in rvars.values()) else "none"))
+        stats.update(device_buffer_bytes=int(mem_setup), levraw_bytes=8 * sum(g["levraw"].numel() for g in groups.values()),
+                     bytes_moved=pipe.moved, host_staging_seconds=pipe.host_s, chunks=len(chunks), chunk_steps=chunk_steps,
+                     staged_steps=staged, records=int(sum(tr.n for tr in plan.tracks)), storage=str(out_dtype).replace("torch.", ""),
+                     records_per_launch={f"{k[0]}x{k[1]}" + ("" if k[2] else " stretched"): int(g["launch"]) for k, g in groups.items()},
+                     seconds=dict(setup=t_setup - t_enter, chunk_loop_host=t_loop - t_setup, drain=time.perf_counter() - t_loop,
+                                  registering=(spans.seconds if spans is not None else 0.0)))
+    return results

@@ -12,9 +12,13 @@ a regional union crop, K tracks of ~40 six-hourly steps with 15 x 15 degree boxe
 ``--cli``: the command line instead -- K single ``-r -t --trackfile`` processes one after another against ONE ``-r -t --trackfiles``
 process over the same seeded file (synthetic.write_classic_nc: float32, 7 levels, 1 degree, 40 three-hourly steps; K tracks of 16
 steps, default 15 x 15 degree boxes), both wall clocks and whether every track's results CSV and trackfile are the same bytes.  Works
-in a temporary directory.
+in a temporary directory.  ``--cli --batch-chunk N``: on the same file and tracks, the ``--trackfiles`` run prepared on the host against
+the streamed one (``--batch-chunk N``), ``--reps`` runs of each in turn after one untimed run of each: every wall clock, the medians, the
+streamed run's own phase seconds from its log, and whether every file of every track's tree is the same bytes.  ``--host-cli PATH``: the
+host-prepared leg runs another checkout's lorenzcycletoolkit.py (the parent commit's, for a comparison that does not rest on this tree).
 
 Reads nothing outside the tree.  Usage: python tools/bench_batch.py [--tracks K] [--steps 40] [--reps 5] | --cli [--tracks K]
+       [--batch-chunk N [--reps 5] [--host-cli PATH]]
 """
 import argparse
 import json
@@ -52,31 +56,93 @@ def _events():
     return a, b
 
 
+CLI_FILE = "synthetic.write_classic_nc: float32 classic NetCDF, 7 levels, 1 degree, 40 three-hourly steps"
+
+
+def _cli_case(work: str, k: int, seed: int):
+    """The seeded file and K track files of the command-line legs, in ``work``: (data file, track files)."""
+    import shutil
+
+    import pandas as pd
+    from lorenzcycletoolkit_amd.synthetic import write_classic_nc
+    rng = np.random.default_rng(seed)
+    os.makedirs(os.path.join(work, "inputs"))
+    shutil.copy(os.path.join(ROOT, "tests", "golden", "inputs", "namelist_ERA5"), os.path.join(work, "inputs", "namelist"))
+    infile = os.path.join(work, "synth.nc")
+    write_classic_nc(infile, np.float32, nt=40, seed=seed)
+    tracks = []
+    for i in range(k):
+        t0, n = int(rng.integers(0, 20)), 16
+        rows = [f"{(pd.Timestamp('2020-01-01') + pd.Timedelta(hours=3 * (t0 + s))).strftime('%Y-%m-%d-%H%M')};"
+                f"{-35 + rng.uniform(-5, 5) - 0.2 * s:.2f};{-55 + rng.uniform(-8, 8) + 0.4 * s:.2f}" for s in range(n)]
+        p = os.path.join(work, f"trk{i:02d}")
+        with open(p, "w") as f:
+            f.write("time;Lat;Lon\n" + "\n".join(rows) + "\n")
+        tracks.append(p)
+    return infile, tracks
+
+
+def cli_streamed_batch(k: int, seed: int, chunk: int, reps: int, host_cli: str = None) -> dict:
+    """One --trackfiles process prepared on the host against one with --batch-chunk ``chunk`` (see the module docstring)."""
+    import filecmp
+    import shutil
+    import subprocess
+    import tempfile
+    cli = os.path.join(ROOT, "lorenzcycletoolkit.py")
+    host_cli = os.path.abspath(host_cli) if host_cli else cli           # (the legs run in the temporary directory)
+    with tempfile.TemporaryDirectory() as work:
+        infile, tracks = _cli_case(work, k, seed)
+        results, kept = os.path.join(work, "LEC_Results"), os.path.join(work, "host_results")
+
+        def run(program, extra):
+            shutil.rmtree(results, ignore_errors=True)
+            t0 = time.perf_counter()
+            subprocess.run([sys.executable, program, infile, "-r", "-t", "--trackfiles", *tracks, *extra], cwd=work, check=True, capture_output=True, timeout=600)
+            return time.perf_counter() - t0
+
+        legs = {"host": (host_cli, []), "streamed": (cli, ["--batch-chunk", str(chunk)])}
+        wall = {name: [] for name in legs}
+        same, seconds = None, []
+        for r in range(reps + 1):                    # (the first run of each: untimed -- page cache, code objects)
+            for name, (program, extra) in legs.items():
+                s = run(program, extra)
+                if r:
+                    wall[name].append(s)
+                if name == "host" and same is None:
+                    shutil.copytree(results, kept)
+                if name == "streamed":
+                    log = open(os.path.join(results, "synth_track_batch", "log.synth")).read()
+                    line = [x for x in log.splitlines() if "Streamed batch seconds: " in x][-1].split("Streamed batch seconds: ")[1]
+                    if r:
+                        seconds.append({p.rsplit(" ", 1)[0]: float(p.rsplit(" ", 1)[1]) for p in line.split(", ")})
+                    if same is None:
+                        same = True
+                        for p in tracks:
+                            tree = f"synth_{os.path.basename(p)}_track"
+                            for root, _dirs, files in os.walk(os.path.join(kept, tree)):
+                                for f in files:
+                                    if not f.startswith("log."):
+                                        other = os.path.join(results, os.path.relpath(os.path.join(root, f), kept))
+                                        same = same and os.path.exists(other) and filecmp.cmp(os.path.join(root, f), other, shallow=False)
+    med = {name: float(np.median(v)) for name, v in wall.items()}
+    return {"tracks": k, "steps_per_track": 16, "file": CLI_FILE, "batch_chunk": chunk, "reps": reps,
+            "what": "one `-r -t --trackfiles` process prepared on the host vs one with --batch-chunk, in turn, same file and tracks; one untimed run of each first",
+            "host_cli": os.path.relpath(host_cli, ROOT), "host_batch_s": [round(x, 3) for x in wall["host"]],
+            "streamed_batch_s": [round(x, 3) for x in wall["streamed"]], "host_batch_s_median": med["host"], "streamed_batch_s_median": med["streamed"],
+            "host_batch_s_range": [float(np.min(wall["host"])), float(np.max(wall["host"]))],
+            "streamed_batch_s_range": [float(np.min(wall["streamed"])), float(np.max(wall["streamed"]))],
+            "streamed_over_host": med["streamed"] / med["host"], "streamed_phase_seconds": seconds, "every_file_identical": bool(same)}
+
+
 def cli_wall_clock(k: int, seed: int) -> dict:
     """K single-track CLI processes against one --trackfiles process on the same file (see the module docstring)."""
     import filecmp
     import shutil
     import subprocess
     import tempfile
-
-    import pandas as pd
-    from lorenzcycletoolkit_amd.synthetic import write_classic_nc
     cli = os.path.join(ROOT, "lorenzcycletoolkit.py")
-    rng = np.random.default_rng(seed)
     with tempfile.TemporaryDirectory() as work:
-        os.makedirs(os.path.join(work, "inputs"))
-        shutil.copy(os.path.join(ROOT, "tests", "golden", "inputs", "namelist_ERA5"), os.path.join(work, "inputs", "namelist"))
-        infile = os.path.join(work, "synth.nc")
-        write_classic_nc(infile, np.float32, nt=40, seed=seed)
-        tracks = []
-        for i in range(k):
-            t0, n = int(rng.integers(0, 20)), 16
-            rows = [f"{(pd.Timestamp('2020-01-01') + pd.Timedelta(hours=3 * (t0 + s))).strftime('%Y-%m-%d-%H%M')};"
-                    f"{-35 + rng.uniform(-5, 5) - 0.2 * s:.2f};{-55 + rng.uniform(-8, 8) + 0.4 * s:.2f}" for s in range(n)]
-            p = os.path.join(work, f"trk{i:02d}")
-            with open(p, "w") as f:
-                f.write("time;Lat;Lon\n" + "\n".join(rows) + "\n")
-            tracks.append(p)
+        infile, tracks = _cli_case(work, k, seed)
         t0 = time.perf_counter()
         for p in tracks:
             subprocess.run([sys.executable, cli, infile, "-r", "-t", "--trackfile", p], cwd=work, check=True, capture_output=True, timeout=300)
@@ -88,7 +154,7 @@ def cli_wall_clock(k: int, seed: int) -> dict:
         same = all(filecmp.cmp(os.path.join(work, "single_" + os.path.basename(p), f),
                                os.path.join(work, "LEC_Results", f"synth_{os.path.basename(p)}_track", f), shallow=False)
                    for p in tracks for f in ("synth_track_results.csv", "synth_track_trackfile"))
-    return {"tracks": k, "steps_per_track": 16, "file": "synthetic.write_classic_nc: float32 classic NetCDF, 7 levels, 1 degree, 40 three-hourly steps",
+    return {"tracks": k, "steps_per_track": 16, "file": CLI_FILE,
             "what": f"{k} single `-r -t --trackfile` processes one after another vs one `-r -t --trackfiles` process, same file",
             "single_runs_s": single_s, "batch_run_s": batch_s, "speedup": single_s / batch_s, "results_and_trackfiles_identical": bool(same)}
 
@@ -103,9 +169,15 @@ def main():
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--only-steps-kernel", action="store_true", help="run the batch's stage-1 launches alone (profiler runs)")
     ap.add_argument("--cli", action="store_true", help="the command line: K single-track processes against one --trackfiles process")
+    ap.add_argument("--batch-chunk", type=int, metavar="N", help="with --cli: the --trackfiles run prepared on the host against the streamed one "
+                    "(--batch-chunk N), --reps runs of each")
+    ap.add_argument("--host-cli", metavar="PATH", help="with --cli --batch-chunk: the lorenzcycletoolkit.py the host-prepared leg runs (default: this tree's)")
     a = ap.parse_args()
+    if a.batch_chunk is not None and not a.cli:
+        ap.error("--batch-chunk goes with --cli")
     if a.cli:
-        print(json.dumps(cli_wall_clock(a.tracks, a.seed)))
+        print(json.dumps(cli_wall_clock(a.tracks, a.seed) if a.batch_chunk is None else
+                         cli_streamed_batch(a.tracks, a.seed, a.batch_chunk, a.reps, a.host_cli)))
         return
     dev = "cuda:0"
     dt = torch.float32 if a.dtype == "float32" else torch.float64
