@@ -186,7 +186,8 @@ __global__ void __launch_bounds__(NTHR, (lec_min_waves<TIN, NTHR, ITERS, MODE>()
                     dTl = first ? (Tr - T0) * inv_hdeg : (last ? (T0 - Tl) * inv_hdeg : (Tr - Tl) * (0.5 * inv_hdeg));
                 } else {
                     const int ec = min(max(e, 0), nxb - 1);
-                    dTl = gl[3 * ec + 0] * Tl + gl[3 * ec + 1] * T0 + gl[3 * ec + 2] * Tr;
+                    // (the neighbour outside the box has coefficient 0, but 0 x NaN is NaN: the centre value takes its place)
+                    dTl = gl[3 * ec + 0] * (first ? T0 : Tl) + gl[3 * ec + 1] * T0 + gl[3 * ec + 2] * (last ? T0 : Tr);
                 }
                 const double dTdt = (MODE == 1) ? (ta * tm[q] + tb * T0 + tc * tp[q]) : tm[q];
                 const double dTphi = ga * tjm[q] + gb * T0 + gc * tjp[q];

@@ -125,6 +125,9 @@ __device__ __forceinline__ void sweep_one(const int q, double (&acc)[kNA], doubl
             adv = (Uv * r.cx) * d;
         } else {
             const int ec = EDGE ? min(max(e, 0), r.nxb - 1) : e;
+            // one-sided at the row ends: the table's coefficient of the neighbour outside the box is 0, but that neighbour is whatever
+            // lies beside the box (a vector reaches past the row's ends) and 0 x NaN is NaN -- the centre value takes its place
+            if (EDGE) { Tl = first ? Tv : Tl; Tr = last ? Tv : Tr; }
             adv = Uv * fma(r.gl[3 * ec + 2], Tr, fma(r.gl[3 * ec + 1], Tv, r.gl[3 * ec + 0] * Tl)) * r.inv_dx;
         }
         const double sP = stencil3(qc.j0, (double)qr.j0[q], qc.j1, (double)qr.j1[q], qc.jm, Tc);
