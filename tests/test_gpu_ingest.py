@@ -328,6 +328,56 @@ def test_mixed_dtype_file_on_both_paths(workdir):
     assert torch.equal(a.scalars, b.scalars) and torch.equal(a.levels, b.levels) and torch.isfinite(a.scalars).all()
 
 
+def test_gaussian_latitudes_and_standard_levels_on_both_paths(workdir):
+    """The front half on uneven axes: 32 Gaussian latitudes written N -> S (the sort, the crop, ``jmap``), ten standard pressure levels
+    from the surface up, and a fixed box whose edges fall between grid latitudes and longitudes (nearest-neighbour selection).  The
+    host-prepared resident path and the streamed device ingest give the same bits, and both lie within the parity tests' 1e-9 of the
+    oracle on the oracle's own decode of the file (oracle/cf_decode.py)."""
+    from scipy.io import netcdf_file
+    from oracle import cf_decode as cf
+    from oracle import lec_oracle as o
+    from tests.helpers import as_f64, compare
+    from tests.test_gpu_parity import TOL
+    rng = np.random.default_rng(32)
+    nt, lev = 4, np.array([1000.0, 925.0, 850.0, 700.0, 600.0, 500.0, 400.0, 300.0, 250.0, 200.0])
+    lat = np.rad2deg(np.arcsin(np.polynomial.legendre.leggauss(32)[0]))[::-1]
+    lon = np.linspace(-80.0, -23.0, 20)
+    assert lat[0] > lat[-1] and np.ptp(np.diff(lat)) > 0.04         # north to south; intervals of 5.49 ... 5.54 degrees
+    path = str(workdir / "gaussian.nc")
+    f = netcdf_file(path, "w", version=2)
+    for n, s in (("time", nt), ("level", lev.size), ("lat", lat.size), ("lon", lon.size)):
+        f.createDimension(n, s)
+    tv = f.createVariable("time", "d", ("time",)); tv[:] = 6.0 * np.arange(nt); tv.units = "hours since 2001-01-01 00:00:00"
+    lv = f.createVariable("level", "d", ("level",)); lv[:] = lev; lv.units = "hPa"
+    f.createVariable("lat", "d", ("lat",))[:] = lat
+    f.createVariable("lon", "d", ("lon",))[:] = lon
+    p = lev[None, :, None, None] / 1000.0
+    phi = np.deg2rad(lat)[None, None, :, None]
+    shp = (nt, lev.size, lat.size, lon.size)
+    fields = {"t": 288 * p ** 0.19 + 10 * np.cos(2 * phi) * p + rng.standard_normal(shp), "u": 25 * np.cos(phi) * (1 - p / 1.2) + 5 * rng.standard_normal(shp),
+              "v": 3 * rng.standard_normal(shp), "w": 0.1 * rng.standard_normal(shp), "z": 9.80665 * 7000 * np.log(1 / p) + 80 * rng.standard_normal(shp)}
+    for name, a in fields.items():
+        f.createVariable(name, "f", ("time", "level", "lat", "lon"))[:] = a.astype(np.float32)
+    f.close()
+    (workdir / "inputs" / "namelist").write_text(
+        ";Variable;Units\nAir Temperature;t;K\nGeopotential;z;m**2/s**2\nOmega Velocity;w;Pa/s\n"
+        "Eastward Wind Component;u;m/s\nNorthward Wind Component;v;m/s\nLongitude;lon\nLatitude;lat\nTime;time\nVertical Level;level\n")
+    limits = (-69.6, -30.0, -52.0, -9.0)
+    (workdir / "inputs" / "box_limits").write_text("min_lon;-69.6\nmax_lon;-30\nmin_lat;-52\nmax_lat;-9\n")
+    assert not np.isin(limits[2:], lat).any() and not np.isin(limits[:2], lon).any()
+    a, b, stats = _both_paths(path, "inputs/namelist", limits, 2)
+    assert stats["storage"] == "float32"
+    assert torch.equal(a.scalars, b.scalars) and torch.equal(a.levels, b.levels) and torch.equal(a.nanflag, b.nanflag)
+    assert int(a.nanflag.sum()) == 0 and torch.isfinite(a.scalars).all()
+    names = {"tair": "t", "u": "u", "v": "v", "omega": "w", "geo": "z", "lat": "lat", "lon": "lon", "level": "level", "time": "time"}
+    dom = cf.prepare(path, names, fixed_limits=limits)
+    assert dom.tair.dtype == np.float32 and dom.lat.size == 9 and np.all(np.diff(dom.lat) > 0) and dom.level[0] == 20000.0
+    ref_s, ref_l = o.lec_fixed(as_f64(dom), *limits)
+    for what, r in (("resident", a), ("streamed", b)):
+        worst = compare(r.scalars_dict(), r.levels_dict(), ref_s, ref_l, TOL, "gaussian latitudes, " + what, time_s=dom.time_s)
+        print(what, max(worst.values()) / TOL)
+
+
 @pytest.mark.parametrize("chunk_steps", [4, 36])
 def test_registered_file_memory_equals_staged(workdir, golden_dir, chunk_steps):
     """staging="registered": the mapped file's own pages are registered with the HIP runtime and copied from directly (no pinned

@@ -9,7 +9,10 @@ and that the float64 oracle lies within 1e-11 of the extended one):
 * per-step boxes of 130, 64, 65, 2 and 100 rows in one 130-row buffer (the ``jb >= nyb`` skip inside a trip), whose low boxes alone in a
   shard take the small kernel and must give the same bits;
 * 64 ... 160 levels: the second and third pass of the lane-strided level loops, the repair scan, the any-time drop mask and the
-  k0 / k1 trimming at levels >= 64, and the box-tile kernel's level chunks past three chunks.
+  k0 / k1 trimming at levels >= 64, and the box-tile kernel's level chunks past three chunks;
+* the ``axes_*`` cases: the same seams on uneven latitudes and pressures, where the middle gradient coefficients (``lattab2[.., 5]``,
+  ``levtab2[.., 2]``) are non-zero in every interior row and level, every row has a coefficient triple of its own, the trapezoid
+  weights differ from row to row and level to level, and gaps two to five levels deep are repaired with weights that depend on p.
 
 Tolerance: TOL = 1e-9 of each term's scale, as everywhere in test_gpu_parity.py -- both sides evaluate in fp64 or better, and the
 reference's own rounding stays below 1e-11."""
@@ -51,7 +54,7 @@ def test_fixed_box_against_the_extended_oracle(case):
     assert res.rows is None and int(res.levels.shape[2]) == dom.level.size
     ref_s, ref_l = sc.reference(case)
     worst = compare(res.scalars_dict(), res.levels_dict(), ref_s, ref_l, TOL, case, time_s=dom.time_s)
-    print(case, max(worst.values()))
+    print(case, max(worst.values()) / TOL)
     got = res.scalars_dict()
     if case in sc.NAN_FIXED_IDS:
         assert int(res.nanflag.max()) > 0
@@ -60,11 +63,12 @@ def test_fixed_box_against_the_extended_oracle(case):
         assert int(res.nanflag.sum()) == 0
 
 
-def test_moving_boxes_of_mixed_heights_and_their_small_kernel_shards():
+def test_moving_boxes_of_mixed_heights_and_their_small_kernel_shards(case=sc.MOVING_ID):
     """Boxes of 130, 64, 65, 2 and 100 rows in one 130-row record buffer (the general level kernel, NaNs in it) against the oracle's moving
     framework; then the 64-row and the 2-row box each alone in a shard, where the buffer is at most 64 rows high and the small kernel
-    runs: the project's stated bit-identity of the two level kernels."""
-    dom, limits, exp = sc.build(sc.MOVING_ID)
+    runs: the project's stated bit-identity of the two level kernels.  ``axes_moving``: on uneven axes, every box from a grid row of
+    its own."""
+    dom, limits, exp = sc.build(case)
     eng = _engine(dom)
     boxes = [eng.box_from_limits(*lim) for lim in limits]
     assert boxes == exp["boxes"]
@@ -72,9 +76,9 @@ def test_moving_boxes_of_mixed_heights_and_their_small_kernel_shards():
     whole = eng.compute(*f, boxes, time_s=dom.time_s, keep_rows=True)
     torch.cuda.synchronize()
     assert whole.rows.shape[2] == 130
-    ref_s, ref_l = sc.reference(sc.MOVING_ID)
-    worst = compare(whole.scalars_dict(), whole.levels_dict(), ref_s, ref_l, TOL, sc.MOVING_ID, time_s=dom.time_s)
-    print(sc.MOVING_ID, max(worst.values()))
+    ref_s, ref_l = sc.reference(case)
+    worst = compare(whole.scalars_dict(), whole.levels_dict(), ref_s, ref_l, TOL, case, time_s=dom.time_s)
+    print(case, max(worst.values()) / TOL)
     got = whole.scalars_dict()
     assert all(np.isfinite(got[k]).all() for k in SCALARS)
     flags = whole.nanflag.cpu().numpy()
@@ -87,10 +91,15 @@ def test_moving_boxes_of_mixed_heights_and_their_small_kernel_shards():
         assert torch.equal(part.nanflag, whole.nanflag[a:b]), (a, b)
 
 
-@pytest.mark.parametrize("case", [sc.MANY_NAN_ID, "tall131_seam_omega"])
+def test_moving_boxes_on_uneven_axes_and_their_small_kernel_shards():
+    """``axes_moving``: the same heights, every box from a grid row of its own -- per-box latitude tables that differ in every row."""
+    test_moving_boxes_of_mixed_heights_and_their_small_kernel_shards(sc.AXES_MOVING_ID)
+
+
+@pytest.mark.parametrize("case", [sc.MANY_NAN_ID, "tall131_seam_omega", "axes_levels130_nan", "axes_tall131_nan"])
 def test_level_stage_then_vertical_stage_gives_the_bits_of_reduce(case):
     """The two halves of stage 2 (what a streamed series runs) on the same row records: 130 levels with NaNs in every pass of the level
-    loops, and the tall box with NaNs at its first trip seam."""
+    loops, and the tall box with NaNs at its first trip seam -- on even and on uneven axes."""
     from lorenzcycletoolkit_amd import _lib
     dom, limits, _ = sc.build(case)
     eng = _engine(dom)
@@ -105,7 +114,7 @@ def test_level_stage_then_vertical_stage_gives_the_bits_of_reduce(case):
     _same_bits(halves, whole, case)
 
 
-@pytest.mark.parametrize("case", ["tall131_bottom_rows_64_65", sc.MANY_NAN_ID])
+@pytest.mark.parametrize("case", ["tall131_bottom_rows_64_65", sc.MANY_NAN_ID, "axes_tall131_nan"])
 def test_any_time_mask_merged_from_two_time_shards(case):
     """A level that stays NaN at one step leaves the integrals of EVERY step.  The series in two time shards -- the first one (step 0)
     holds none of the steps at which the level is lost -- whose masks are merged by element-wise max through ``merge_dropmask`` (one
@@ -125,6 +134,26 @@ def test_any_time_mask_merged_from_two_time_shards(case):
     # without the merge the first shard keeps the level: the test would not notice a mask that is never applied otherwise
     alone = run_fixed(dom, limits, t_begin=0, t_count=1)
     assert not torch.equal(torch.nan_to_num(alone.scalars, nan=-7.0), torch.nan_to_num(whole.scalars[0:1], nan=-7.0))
+
+
+def test_small_and_general_kernel_agree_on_uneven_axes():
+    """``axes_small64``: a 64-row box on uneven axes takes the small level kernel.  The same row records in a buffer padded to 70 rows
+    take the general kernels (area means, then 64 staged rows with a halo row per trip), which read the same ``lattab2`` / ``levtab2``
+    rows by other indices: the same bits."""
+    dom, limits, exp = sc.build("axes_small64")
+    eng = _engine(dom)
+    box = eng.box_from_limits(*limits)
+    f = _fields(dom)
+    small = eng.compute(*f, [box], time_s=dom.time_s, keep_rows=True)
+    nt, nl, nyb, ns = small.rows.shape
+    assert nyb == exp["height"] == 64
+    padded = torch.zeros((nt, nl, 70, ns), dtype=torch.float64, device="cuda:0")
+    eng.rowstats(*f, [box], rows_out=padded, time_s=dom.time_s)
+    assert torch.equal(padded[:, :, :nyb], small.rows)
+    general = eng.reduce(padded, [box])
+    torch.cuda.synchronize()
+    _same_bits(general, small, "axes_small64: general vs small kernel")
+    assert int(small.nanflag.sum()) == 0
 
 
 @pytest.mark.parametrize("nl", [129, 160])
