@@ -668,6 +668,22 @@ int lec_rowstats_steps(const lec_rowstats_args* args, const int32_t* step_d);
  */
 int lec_rowstats_ring(const lec_rowstats_args* args);
 int lec_ingest(const lec_ingest_args* args);
+/*
+ * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with
+ * its own scale_factor / add_offset / fill value, so the steps src_d holds may differ in all three.
+ *   - pack_d[s] = {scale_factor, add_offset, fill_value} of SOURCE step s of src_d, fp64, in device memory.  s = 0 is the first step
+ *     src_d holds: with step_d that is the step step_base, and output step t takes row step_d[t][0] - step_base; without step_d output
+ *     step t takes row t.
+ *   - pack_len: rows of pack_d.  It must be nt_src when step_d is given, else nt; anything else, or pack_d == NULL, is LEC_ERR_ARG,
+ *     said before any launch.
+ *   - args->scale_factor / add_offset / fill_value are ignored.  has_packing, has_fill, decode_dtype, unit_scale, the maps and the
+ *     bounds rule of step_d apply as in lec_ingest: one series has one decode dtype, because the PRESENCE of the attributes decides it.
+ *     An out-of-range step_d entry writes NaN rows and reads neither the source nor the table.
+ *   - The arithmetic is lec_ingest's, operation by operation (contraction off; the fill comparison is against that step's fill value,
+ *     before scaling): a table whose rows are all equal gives lec_ingest's bits.  The three constants are uniform per workgroup (the
+ *     source step follows from blockIdx and step_d) and are fetched once per workgroup: 24 bytes more traffic per output row.
+ */
+int lec_ingest_series(const lec_ingest_args* args, const double* pack_d, int32_t pack_len);
 int lec_reduce(const lec_reduce_args* args);
 
 /* The any-time NaN-level mask of the time steps in `args` alone -> dropmask_d (zeroed first; non-zero = drop).

@@ -24,6 +24,10 @@ the time step at which it forms until it has weakened (``lec_follow_spans``; --c
 circle and the box limits span it; zonal means run over the closed axis, d/dlon is centred across the +-180 meridian and no flux
 crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file names and columns as -f.
 
+--series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
+grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
+``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
+
 Several GPUs of one node: ``python lorenzcycletoolkit.py <file> -r -f --gpus N`` (this process starts N rank processes, one per
 GPU) or ``python -m torch.distributed.run --nproc-per-node N lorenzcycletoolkit.py <file> -r -f``.  The time steps are sharded
 over the ranks (each reads, decodes and computes only its own block plus a one-step halo of T), rank 0 gathers the per-step
@@ -129,7 +133,24 @@ def create_arg_parser():
     parser.add_argument("--gpus", type=int, default=1, help="shard the time steps over this many GPUs of the node (one process per GPU, "
                         "results gathered over RCCL; same output files).  Under torch.distributed.run the launcher's WORLD_SIZE counts")
     parser.add_argument("-o", "--outname", type=str, help="name of the results CSV (fixed framework)")
+    # (no attribute without the option: the logged Namespace of a run without --series is what it was)
+    parser.add_argument("--series", nargs="+", metavar="FILE", default=argparse.SUPPRESS, help="the time series that infile begins continues in "
+                        "these files (one per month or day, as archives deliver them): same grid, levels and variables, time stamps that do not "
+                        "overlap; each file may pack its values with its own scale_factor / add_offset.  Any order (the files are ordered by "
+                        "their first time stamp); infile may be named again, so 'a_01.nc --series a_*.nc' works.  Every output is named after "
+                        "infile, as for one merged file of that name.  With -f, -t, --trackfiles and -c, --ingest host / device and --gpus N")
     return parser
+
+
+def refuse_series_options(args):
+    """What a --series run does not do, said before anything is created."""
+    if getattr(args, "series", None) is None:
+        return
+    if args.cdsapi:
+        raise SystemExit("--series names files that exist; --cdsapi downloads one: give one of the two")
+    if args.inflate == "device":
+        raise SystemExit("--series: the device inflate reads one file's chunk index, so the deflated parts of a series are inflated by the "
+                         "reader on the host: --inflate device is not supported with --series (leave it out, or --inflate host)")
 
 
 def setup_results_directory(args, method):
@@ -315,6 +336,7 @@ def main(argv=None):
     refuse_choose_options(args)
     refuse_periodic_options(args)
     refuse_batch_chunk_options(args)
+    refuse_series_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
     if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
@@ -478,6 +500,7 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
             app_logger.info("Longitude axis per track: " + "; ".join(f"{'0..360 (across the +-180 meridian)' if origin else '-180..180'}: "
                             + ", ".join(trackfiles[n] for n in members) for origin, members in parts) + f" -- {len(parts)} pass(es) over the data")
         rows = [None] * len(trackfiles)
+        told = False
         for origin, members in parts:
             raw = None
             if args.batch_chunk is not None:
@@ -485,9 +508,13 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
                 # does not read is refused (the host union is what the flag exists to avoid)
                 from lorenzcycletoolkit_amd import dataset as ds
                 try:
-                    raw = ds.open_raw(args.infile, ds.read_namelist("inputs/namelist", app_logger), mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
+                    raw = ds.open_raw(ds.series_paths(args), ds.read_namelist("inputs/namelist", app_logger), mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
                 except ValueError as e:
                     raise ValueError(f"--batch-chunk: the streamed path does not read this file ({e}); without --batch-chunk the batch is prepared on the host") from e
+                if not told:
+                    from lorenzcycletoolkit_amd.ingest import note_series_inflate
+                    note_series_inflate(args, raw, app_logger)
+                    told = True
                 try:
                     plan = batch.plan_batch(raw.lat, raw.lon, raw.level, raw.time, raw.level_units, raw.names, [trackfiles[n] for n in members],
                                             app_logger, origin)

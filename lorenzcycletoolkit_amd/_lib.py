@@ -44,7 +44,8 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_check_boxes", "lec_check_maps", "lec_host_register", "lec_host_unregister", "lec_copy_rows_async",
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
-           "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring"]
+           "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring",
+           "lec_ingest_series"]
 
 
 class Tuning(C.Structure):
@@ -242,6 +243,8 @@ def load():
     lib.lec_dropmask.argtypes = [C.POINTER(ReduceArgs)]
     lib.lec_ingest.restype = C.c_int
     lib.lec_ingest.argtypes = [C.POINTER(IngestArgs)]
+    lib.lec_ingest_series.restype = C.c_int
+    lib.lec_ingest_series.argtypes = [C.POINTER(IngestArgs), C.c_void_p, C.c_int32]
     lib.lec_track_diag.restype = C.c_int
     lib.lec_track_diag.argtypes = [C.POINTER(DiagArgs)]
     lib.lec_follow.restype = C.c_int

@@ -261,7 +261,7 @@ def partition_by_origin(args, trackfiles: Sequence[str], varlist: str = "inputs/
     """[(origin, [positions in ``trackfiles``])], at most two entries, origin 0.0 first: the tracks by the origin of the longitude axis
     each one's own ``-t`` run takes (``dataset.track_lon_origin``).  A track that cannot be read counts as origin 0: ``plan_batch``
     refuses it there with its name."""
-    lon = ds.file_longitudes(args.infile, ds.read_namelist(varlist, app_logger), bool(getattr(args, "mpas", False)))
+    lon = ds.file_longitudes(ds.series_paths(args, varlist), ds.read_namelist(varlist, app_logger), bool(getattr(args, "mpas", False)))
     parts = {}
     for n, path in enumerate(trackfiles):
         try:
@@ -278,11 +278,11 @@ def prepare_union(args, trackfiles: Sequence[str], varlist: str = "inputs/nameli
     variable_list_df = ds.read_namelist(varlist, app_logger)
     mpas = bool(getattr(args, "mpas", False))
     try:
-        raw = ds.open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
+        raw = ds.open_raw(ds.series_paths(args, varlist), variable_list_df, mpas=mpas, app_logger=app_logger)
     except ValueError as e:
         if "order" not in str(e) and "device ingest reads" not in str(e):
             raise
-        data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)
+        data = ds.open_dataset(ds.series_paths(args, varlist), variable_list_df, mpas=mpas)
         plan = plan_batch(data.lat, data.lon, data.level, data.time, data.level_units, data.names, trackfiles, app_logger, lon_origin)
         data = ds.process_data(data, SimpleNamespace(track=False, lon_origin=lon_origin), variable_list_df, app_logger)
         return data.isel(t=plan.tpos, j=plan.js, i=plan.is_), plan

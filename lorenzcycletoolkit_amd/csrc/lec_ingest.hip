@@ -22,6 +22,7 @@ struct IngestParams {
     double scale, offset, fill, unit;
     const int* step; int step_base;      // per-step gathers: {source step, latitude offset, longitude offset} per output step, or null
     int nt_src, jmap_len, imap_len;      // ... and what bounds that table's entries
+    const double* pack;                  // lec_ingest_series: {scale_factor, add_offset, fill_value} per SOURCE step of src, or null
 };
 
 __device__ __forceinline__ int16_t load_elem(const int16_t* p, bool swap) {
@@ -46,7 +47,10 @@ __device__ __forceinline__ double load_elem(const double* p, bool swap) {
     return __longlong_as_double((long long)b);
 }
 
-template <typename TSRC, typename TOUT>
+// SERIES: the packing constants are those of the row's SOURCE step (a series that continues across files: every file packs with its
+// own scale_factor / add_offset / fill value), read from p.pack once per workgroup -- the source step depends on blockIdx and the step
+// table alone, so the three loads are uniform -- instead of p.scale / p.offset / p.fill.  The arithmetic is the same, operation by operation.
+template <typename TSRC, typename TOUT, bool SERIES>
 __global__ void __launch_bounds__(256) lec_ingest_kernel(const IngestParams p) {
 #pragma clang fp contract(off)
     const int row = blockIdx.x;                     // (t, k, j) of the output
@@ -65,20 +69,24 @@ __global__ void __launch_bounds__(256) lec_ingest_kernel(const IngestParams p) {
     TOUT* __restrict__ out = (TOUT*)p.out + (size_t)row * p.nx;
     const int* __restrict__ imap = p.imap + oi;
     const bool swap = p.swap != 0;
+    // (ts is inside [0, nt_src) here: checked above with a table, t < nt = the table's length without one)
+    const double scale = SERIES ? p.pack[3 * (size_t)ts] : p.scale;
+    const double offset = SERIES ? p.pack[3 * (size_t)ts + 1] : p.offset;
+    const double fill = SERIES ? p.pack[3 * (size_t)ts + 2] : p.fill;
     for (int i = threadIdx.x; i < p.nx; i += blockDim.x) {
         const TSRC raw = load_elem(src + imap[i], swap);
-        const bool is_fill = p.has_fill && ((double)raw == p.fill);
+        const bool is_fill = p.has_fill && ((double)raw == fill);
         TOUT o;
         if (!p.decode_f32) {
             double v = (double)raw;
-            if (p.has_packing) { v = v * p.scale; v = v + p.offset; }
+            if (p.has_packing) { v = v * scale; v = v + offset; }
             v = v * p.unit;
             o = (TOUT)v;
         } else {
             // the reference's decode in float32 (xarray 2024.2.0 on NumPy 2: float32 data, float64 attributes -- every
             // operation is computed in float64 and rounded back to float32 by the in-place store)
             float v = (float)raw;
-            if (p.has_packing) { v = (float)((double)v * p.scale); v = (float)((double)v + p.offset); }
+            if (p.has_packing) { v = (float)((double)v * scale); v = (float)((double)v + offset); }
             v = v * (float)p.unit;
             o = (TOUT)v;
         }
@@ -90,13 +98,17 @@ template <typename TSRC>
 void launch(const IngestParams& p, int out_dtype, long long rows, hipStream_t st) {
     // one workgroup per output row; its threads walk the row: short rows (a box-packed series: 61 columns) get one wave, not four
     const dim3 block(p.nx <= 64 ? 64 : (p.nx <= 128 ? 128 : 256));
-    if (out_dtype == LEC_F64) hipLaunchKernelGGL((lec_ingest_kernel<TSRC, double>), dim3((unsigned)rows), block, 0, st, p);
-    else hipLaunchKernelGGL((lec_ingest_kernel<TSRC, float>), dim3((unsigned)rows), block, 0, st, p);
+    if (p.pack) {
+        if (out_dtype == LEC_F64) hipLaunchKernelGGL((lec_ingest_kernel<TSRC, double, true>), dim3((unsigned)rows), block, 0, st, p);
+        else hipLaunchKernelGGL((lec_ingest_kernel<TSRC, float, true>), dim3((unsigned)rows), block, 0, st, p);
+    } else {
+        if (out_dtype == LEC_F64) hipLaunchKernelGGL((lec_ingest_kernel<TSRC, double, false>), dim3((unsigned)rows), block, 0, st, p);
+        else hipLaunchKernelGGL((lec_ingest_kernel<TSRC, float, false>), dim3((unsigned)rows), block, 0, st, p);
+    }
 }
 
-}  // namespace
-
-extern "C" int lec_ingest(const lec_ingest_args* a) {
+// lec_ingest (series false: pack_d / pack_len are not looked at) and lec_ingest_series behind one validation
+int ingest(const lec_ingest_args* a, bool series, const double* pack_d, int32_t pack_len) {
     if (!a) return lec_set_error(LEC_ERR_ARG, "lec_ingest: null args");
     if (!a->src_d || !a->out_d || !a->kmap_d || !a->jmap_d || !a->imap_d) return lec_set_error(LEC_ERR_ARG, "lec_ingest: null pointer argument");
     if (a->src_dtype < LEC_F64 || a->src_dtype > LEC_I8) return lec_set_error(LEC_ERR_ARG, "lec_ingest: src_dtype must be LEC_I8, LEC_I16, LEC_I32, LEC_F32 or LEC_F64");
@@ -123,6 +135,13 @@ extern "C" int lec_ingest(const lec_ingest_args* a) {
         return lec_set_error(LEC_ERR_ARG, "lec_ingest: float64 and int32 data do not decode to float32");
     p.swap = a->swap_bytes; p.has_packing = a->has_packing; p.has_fill = a->has_fill; p.decode_f32 = a->decode_dtype == LEC_F32;
     p.scale = a->scale_factor; p.offset = a->add_offset; p.fill = a->fill_value; p.unit = a->unit_scale;
+    p.pack = nullptr;
+    if (series) {
+        if (!pack_d) return lec_set_error(LEC_ERR_ARG, "lec_ingest_series: null pack_d (the per-step packing table)");
+        if (pack_len != (a->step_d ? a->nt_src : a->nt))
+            return lec_set_error(LEC_ERR_ARG, "lec_ingest_series: pack_len must be nt_src with a step_d table, nt without one (a row per SOURCE step of src_d)");
+        p.pack = pack_d;
+    }
     hipStream_t st = (hipStream_t)a->stream;
     if (a->src_dtype == LEC_I16) launch<int16_t>(p, a->out_dtype, rows, st);
     else if (a->src_dtype == LEC_I32) launch<int32_t>(p, a->out_dtype, rows, st);
@@ -133,3 +152,9 @@ extern "C" int lec_ingest(const lec_ingest_args* a) {
     if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
     return LEC_OK;
 }
+
+}  // namespace
+
+extern "C" int lec_ingest(const lec_ingest_args* a) { return ingest(a, false, nullptr, 0); }
+
+extern "C" int lec_ingest_series(const lec_ingest_args* a, const double* pack_d, int32_t pack_len) { return ingest(a, true, pack_d, pack_len); }

@@ -316,8 +316,138 @@ def decode_values(raw: np.ndarray, scale, offset, fill) -> np.ndarray:
     return np.asarray(a, dtype=out)
 
 
-def open_dataset(path: str, variable_list_df: pd.DataFrame, mpas: bool = False, app_logger=None) -> LECDataset:
-    """Host-side decode of the whole file with the semantics of ``xr.open_dataset`` (decode_values)."""
+def as_paths(path) -> list:
+    """A path, or a sequence of paths (the parts of a series that continues across files), as a list."""
+    return [path] if isinstance(path, (str, bytes, os.PathLike)) else [p for p in path]
+
+
+def series_paths(args, varlist: str = "inputs/namelist") -> list:
+    """The files of a run: ``args.infile`` and what ``--series`` adds to it, without repeats (by ``os.path.realpath``: ``infile`` may
+    be named again, so that ``a_01.nc --series a_*.nc`` works), ordered by their first time stamp.  Without ``--series``:
+    ``[args.infile]``, and no file is opened."""
+    more = getattr(args, "series", None)
+    if not more:
+        return [args.infile]
+    paths, seen = [], set()
+    for p in [args.infile] + list(more):
+        if os.path.realpath(p) not in seen:
+            seen.add(os.path.realpath(p))
+            paths.append(p)
+    if len(paths) == 1:
+        return paths
+    name = str(read_namelist(varlist).loc["Time"]["Variable"])
+    first = []
+    for p in paths:
+        nc = _Container(p, mmap=True)
+        try:
+            if name not in nc.variables:
+                raise ValueError(f"--series: {p} has no time variable '{name}' ({paths[0]} is read with this namelist)")
+            stamps = _decode_time(nc.variables[name].values(), nc.variables[name].attr("units"))
+            if stamps.size == 0:
+                raise ValueError(f"--series: {p} holds no time step")
+            first.append(stamps[0])
+        finally:
+            nc.close()
+    return [paths[n] for n in np.argsort(np.array(first), kind="stable")]
+
+
+class _Parts:
+    """The opened parts of a series: what ``_open_nc`` gives for each, ordered by first time stamp and checked against one another
+    (``_open_parts``)."""
+
+    def __init__(self, paths, opened):
+        self.paths, self.opened = list(paths), list(opened)
+        self.ncs = [o[0] for o in opened]
+        self.counts = [int(o[6].size) for o in opened]
+        self.starts = np.concatenate([[0], np.cumsum(self.counts)]).astype(np.int64)      # global step of each part's first step, and the total
+        self.time = np.concatenate([o[6] for o in opened])
+
+    def close(self):
+        for nc in self.ncs:
+            nc.close()
+        self.ncs = []
+
+
+def _differ(a: str, b: str, what: str) -> ValueError:
+    return ValueError(f"--series: {a} and {b} differ in {what}")
+
+
+def _open_parts(paths, variable_list_df, mmap: bool, mpas: bool = False, app_logger=None) -> _Parts:
+    """Opens every part of a series (``_open_nc`` each: ``-m/--mpas`` applies to every part) and refuses parts that do not continue
+    one series on one grid: bit-equal latitude, longitude and level coordinates and equal level units; every namelist variable in every
+    part with the same dimensions, dimension order and stored dtype; the same PRESENCE of scale_factor, add_offset and a fill value
+    (their values may differ from part to part: presence decides the decode dtype, ``decode_dtypes``, and one series has one dtype);
+    time stamps -- each part's decoded with its own ``units`` -- that increase strictly over the concatenated axis (uneven spacing
+    across a seam is allowed: the d/dt coefficients take the real time axis).  Every refusal is a ValueError naming the two files."""
+    opened, done = [], []
+    try:
+        for p in paths:
+            try:
+                opened.append(_open_nc(p, variable_list_df, mmap, mpas=mpas, app_logger=app_logger))
+            except KeyError as e:
+                other = next((q for q in paths if q != p), p)
+                raise _differ(other, p, f"their variables: {e.args[0] if e.args else e}") from e
+            done.append(p)
+            if opened[-1][6].size == 0:
+                raise ValueError(f"--series: {p} holds no time step")
+        order = np.argsort(np.array([o[6][0] for o in opened]), kind="stable")
+        opened, done = [opened[n] for n in order], [done[n] for n in order]
+        a, first = done[0], opened[0]
+        for b, part in zip(done[1:], opened[1:]):
+            for what, x, y in (("latitude", first[3], part[3]), ("longitude", first[4], part[4]), ("vertical level", first[5], part[5])):
+                if x.shape != y.shape or x.dtype != y.dtype or x.tobytes() != y.tobytes():
+                    raise _differ(a, b, f"the {what} coordinate (the parts of a series lie on one grid, bit for bit)")
+            if first[7] != part[7]:
+                raise _differ(a, b, f"the units of the vertical level ('{first[7]}' and '{part[7]}')")
+            for role in FIELD_ROLES + (first[2],):
+                name = first[1][role]
+                x, y = first[0].variables[name], part[0].variables[name]
+                if tuple(x.dimensions) != tuple(y.dimensions):
+                    raise _differ(a, b, f"the dimensions of {name} ({tuple(x.dimensions)} and {tuple(y.dimensions)})")
+                if x.data.dtype != y.data.dtype:
+                    raise _differ(a, b, f"the stored dtype of {name} ({x.data.dtype} and {y.data.dtype})")
+                for attr, px, py in zip(("scale_factor", "add_offset", "a fill value (_FillValue / missing_value)"), _packing(x), _packing(y)):
+                    if (px is None) != (py is None):
+                        raise _differ(a, b, f"whether {name} has {attr}: {'absent' if px is None else 'present'} in the first, "
+                                            f"{'absent' if py is None else 'present'} in the second (its presence decides the decode dtype, "
+                                            "and one series has one dtype)")
+        for p, part in zip(done, opened):
+            if part[6].size > 1 and not np.all(np.diff(part[6]) > np.timedelta64(0, "ns")):
+                raise ValueError(f"--series: the time stamps of {p} do not increase strictly")
+        for (a, x), (b, y) in zip(zip(done[:-1], opened[:-1]), zip(done[1:], opened[1:])):
+            if y[6][0] == x[6][-1]:
+                raise ValueError(f"--series: {a} and {b} both hold the time stamp {pd.Timestamp(y[6][0])}: a time step belongs to one part")
+            if y[6][0] < x[6][-1]:
+                raise ValueError(f"--series: {a} and {b} overlap in time: {b} begins at {pd.Timestamp(y[6][0])}, not after {pd.Timestamp(x[6][-1])}, "
+                                 f"the last time stamp of {a}")
+    except BaseException:
+        for o in opened:
+            o[0].close()
+        raise
+    return _Parts(done, opened)
+
+
+def open_dataset(path, variable_list_df: pd.DataFrame, mpas: bool = False, app_logger=None) -> LECDataset:
+    """Host-side decode of the whole file with the semantics of ``xr.open_dataset`` (decode_values).  ``path``: a path, or the parts of
+    a series (``_open_parts``): each part is decoded with its own packing attributes, then the parts are joined along time."""
+    paths = as_paths(path)
+    if len(paths) > 1:
+        parts = _open_parts(paths, variable_list_df, mmap=False, mpas=mpas, app_logger=app_logger)
+        try:
+            _nc, names, geo_role, lat, lon, lev, _time, level_units, want = parts.opened[0]
+            variables = {}
+            for role in FIELD_ROLES + (geo_role,):
+                pieces = []
+                for nc in parts.ncs:
+                    v = nc.variables[names[role]]
+                    if set(v.dimensions) != set(want):
+                        raise ValueError(f"{names[role]} has dimensions {v.dimensions}, expected {want}")
+                    pieces.append(np.transpose(decode_values(v.values(), *_packing(v)), [v.dimensions.index(d) for d in want]))
+                variables[names[role]] = np.concatenate(pieces, axis=0)
+        finally:
+            parts.close()
+        return LECDataset(variables, lat, lon, lev, parts.time, names, level_units)
+    path = paths[0]
     nc, names, geo_role, lat, lon, lev, time, level_units, want = _open_nc(path, variable_list_df, mmap=False, mpas=mpas, app_logger=app_logger)
     variables = {}
     for role in FIELD_ROLES + (geo_role,):
@@ -340,6 +470,98 @@ class RawVariable:
     add_offset: Optional[float]
     fill_value: Optional[float]
 
+    uniform_packing = True            # one (scale_factor, add_offset, fill value) for every time step (a SeriesVariable may say False)
+
+    def packing_at(self, file_step: int) -> tuple:
+        """(scale_factor, add_offset, fill value) of one time step, None for absent ones: what ``decode_values`` takes."""
+        return self.scale_factor, self.add_offset, self.fill_value
+
+    def packing_table(self, file_steps) -> np.ndarray:
+        """float64 [n, 3]: {scale_factor, add_offset, fill value} of each of the time steps, absent ones as 1 / 0 / 0 (the values
+        ``lec_ingest`` is given for them; ``has_packing`` / ``has_fill`` say what is absent)."""
+        return _packing_rows([self.packing_at(0)] * len(file_steps))
+
+
+def _packing_rows(packings) -> np.ndarray:
+    rows = [(1.0 if s is None else s, 0.0 if o is None else o, 0.0 if f is None else f) for s, o, f in packings]
+    return np.array(rows, dtype=np.float64).reshape(len(rows), 3)
+
+
+class _SeriesData:
+    """The ``data`` of a variable that continues across files, as ONE [time, level, lat, lon] object: ``shape``, ``dtype`` and
+    ``data[ft]`` -- the block of global time step ``ft``, from the part that holds it.  Indexed by a time step only: nothing ever
+    joins the parts in memory."""
+
+    ndim = 4
+
+    def __init__(self, datas, starts):
+        self.parts, self.starts = list(datas), np.asarray(starts, dtype=np.int64)
+        self.dtype = self.parts[0].dtype
+        self.shape = (int(self.starts[-1]),) + tuple(int(x) for x in self.parts[0].shape[1:])
+
+    def locate(self, ft: int) -> tuple:
+        """(part, step within the part) of global time step ``ft``."""
+        ft = int(ft)
+        if not 0 <= ft < self.shape[0]:
+            raise IndexError(f"time step {ft} outside the series' {self.shape[0]} steps")
+        p = int(np.searchsorted(self.starts, ft, side="right")) - 1
+        return p, ft - int(self.starts[p])
+
+    def __len__(self):
+        return self.shape[0]
+
+    def __getitem__(self, ft):
+        if not isinstance(ft, (int, np.integer)):
+            raise TypeError("a variable of a series is indexed by one time step")
+        p, t = self.locate(ft)
+        return self.parts[p][t]
+
+    def read_step(self, ft: int, levels) -> np.ndarray:
+        """[len(levels), lat, lon] of one time step (a lazily inflated NetCDF-4 part: only the chunks of the wanted levels)."""
+        p, t = self.locate(ft)
+        d = self.parts[p]
+        return d.read_step(t, levels) if hasattr(d, "read_step") else np.asarray(d[t])[levels]
+
+    def __getattr__(self, name):
+        # what a chunked NetCDF-4 variable offers is offered where a part is one: `chunk_streams` (the device inflate's way in) answers
+        # None -- a series is inflated by the reader, on the host --, `_filters` says that there is something to inflate
+        if name == "chunk_streams" and any(hasattr(d, name) for d in self.__dict__.get("parts", ())):
+            return lambda: None
+        if name == "_filters":
+            for d in self.__dict__.get("parts", ()):
+                if getattr(d, "_filters", None):
+                    return d._filters
+        raise AttributeError(name)
+
+
+class SeriesVariable:
+    """A RawVariable that continues across files.  Every part packs with its own constants: ``packing_at`` / ``packing_table`` give
+    them per time step, ``uniform_packing`` says whether all parts share one set.  The scalar attributes ``scale_factor`` /
+    ``add_offset`` / ``fill_value`` are those of a uniform series and RAISE for any other: a consumer that was not moved to the per-step
+    accessors fails loudly instead of decoding every step with the first part's constants."""
+
+    def __init__(self, name: str, paths, datas, packings, starts):
+        self.name, self.paths, self.packings = name, list(paths), [tuple(p) for p in packings]
+        self.data = _SeriesData(datas, starts)
+        self.uniform_packing = all(p == self.packings[0] for p in self.packings[1:])
+
+    def _scalar(self, n: int, what: str):
+        if not self.uniform_packing:
+            raise ValueError(f"{self.name} is packed with other constants in {self.paths[0]} than in "
+                             f"{next(p for p, q in zip(self.paths, self.packings) if q != self.packings[0])}: there is no one {what} "
+                             "for the series (packing_at / packing_table give each time step's)")
+        return self.packings[0][n]
+
+    scale_factor = property(lambda self: self._scalar(0, "scale_factor"))
+    add_offset = property(lambda self: self._scalar(1, "add_offset"))
+    fill_value = property(lambda self: self._scalar(2, "fill value"))
+
+    def packing_at(self, file_step: int) -> tuple:
+        return self.packings[self.data.locate(file_step)[0]]
+
+    def packing_table(self, file_steps) -> np.ndarray:
+        return _packing_rows([self.packing_at(ft) for ft in file_steps])
+
 
 @dataclass
 class RawDataset:
@@ -361,8 +583,37 @@ class RawDataset:
             self._nc = None
 
 
-def open_raw(path: str, variable_list_df: pd.DataFrame, mpas: bool = False, app_logger=None) -> RawDataset:
-    """Like open_dataset, but nothing is decoded or copied: the variables stay memory-mapped file bytes."""
+_RAW_KINDS = (("i", 1), ("i", 2), ("i", 4), ("f", 4), ("f", 8))
+
+
+def _open_raw_series(paths, variable_list_df: pd.DataFrame, mpas: bool, app_logger) -> RawDataset:
+    """open_raw for the parts of a series: every variable a ``SeriesVariable``, the time axis the parts' joined; ``close()`` closes
+    every part."""
+    parts = _open_parts(paths, variable_list_df, mmap=True, mpas=mpas, app_logger=app_logger)
+    try:
+        _nc, names, geo_role, lat, lon, lev, _time, level_units, want = parts.opened[0]
+        variables = {}
+        for role in FIELD_ROLES + (geo_role,):
+            vs = [nc.variables[names[role]] for nc in parts.ncs]
+            v = vs[0]
+            if tuple(v.dimensions) != want:
+                raise ValueError(f"{names[role]} has dimensions {v.dimensions}; the device ingest needs {want} order")
+            if (v.data.dtype.kind, v.data.dtype.itemsize) not in _RAW_KINDS:
+                raise ValueError(f"{names[role]}: the device ingest reads int8, int16, int32, float32 and float64 variables, not {v.data.dtype}")
+            variables[names[role]] = SeriesVariable(names[role], parts.paths, [x.data for x in vs], [_packing(x) for x in vs], parts.starts)
+    except BaseException:
+        parts.close()
+        raise
+    return RawDataset(variables, lat, lon, lev, parts.time, names, level_units, geo_role, parts)
+
+
+def open_raw(path, variable_list_df: pd.DataFrame, mpas: bool = False, app_logger=None) -> RawDataset:
+    """Like open_dataset, but nothing is decoded or copied: the variables stay memory-mapped file bytes.  ``path``: a path, or the
+    parts of a series."""
+    paths = as_paths(path)
+    if len(paths) > 1:
+        return _open_raw_series(paths, variable_list_df, mpas, app_logger)
+    path = paths[0]
     nc, names, geo_role, lat, lon, lev, time, level_units, want = _open_nc(path, variable_list_df, mmap=True, mpas=mpas, app_logger=app_logger)
     variables = {}
     for role in FIELD_ROLES + (geo_role,):
@@ -453,9 +704,10 @@ def track_on_axis(track: pd.DataFrame, lon) -> pd.DataFrame:
     return track
 
 
-def file_longitudes(path: str, variable_list_df: pd.DataFrame, mpas: bool = False) -> np.ndarray:
-    """The longitude coordinate of a data file as stored."""
-    nc, names, geo_role, lat, lon, lev, time, level_units, want = _open_nc(path, variable_list_df, mmap=True, mpas=mpas)
+def file_longitudes(path, variable_list_df: pd.DataFrame, mpas: bool = False) -> np.ndarray:
+    """The longitude coordinate of a data file as stored (the parts of a series: of the first -- opening the series checks that they
+    all have it)."""
+    nc, names, geo_role, lat, lon, lev, time, level_units, want = _open_nc(as_paths(path)[0], variable_list_df, mmap=True, mpas=mpas)
     nc.close()
     return np.array(lon)
 
@@ -617,7 +869,7 @@ def gather_on_host(var: RawVariable, plan: IngestPlan, t_range=None) -> np.ndarr
         else:
             raw = np.asarray(var.data[int(ft)])[plan.kmap][:, plan.jmap][:, :, plan.imap]
         raw = raw.astype(raw.dtype.newbyteorder("="))
-        a = decode_values(raw, var.scale_factor, var.add_offset, var.fill_value)
+        a = decode_values(raw, *var.packing_at(int(ft)))
         if out is None:
             out = np.empty((len(tsel),) + a.shape, dtype=a.dtype)
         out[n] = a
@@ -634,12 +886,13 @@ def prepare_data(args, varlist: str = "inputs/namelist", app_logger=None) -> LEC
     variable_list_df = read_namelist(varlist, app_logger)
     shard = getattr(args, "shard", None)          # time-sharded run (parallel.ShardContext): this rank decodes its own steps + halo only
     mpas = bool(getattr(args, "mpas", False))
+    infile = series_paths(args, varlist)          # (the file, or the parts of a --series run)
     try:
-        raw = open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
+        raw = open_raw(infile, variable_list_df, mpas=mpas, app_logger=app_logger)
     except ValueError as e:
         if "order" not in str(e) and "device ingest reads" not in str(e):
             raise
-        data = open_dataset(args.infile, variable_list_df, mpas=mpas)
+        data = open_dataset(infile, variable_list_df, mpas=mpas)
         data = slice_domain(process_data(data, args, variable_list_df, app_logger), args, variable_list_df)
         return data if shard is None else data.held_steps(shard.ranges(len(data.time))[2:])
     try:

@@ -173,11 +173,11 @@ class _SliceSource:
             return int(k[0]), jj, ii
 
         try:
-            raw = ds.open_raw(args.infile, variable_list_df, mpas=mpas, app_logger=app_logger)
+            raw = ds.open_raw(ds.series_paths(args, varlist), variable_list_df, mpas=mpas, app_logger=app_logger)
         except ValueError as e:
             if "order" not in str(e) and "device ingest reads" not in str(e):
                 raise
-            self.data = data = ds.open_dataset(args.infile, variable_list_df, mpas=mpas)  # another dimension order: the whole file
+            self.data = data = ds.open_dataset(ds.series_paths(args, varlist), variable_list_df, mpas=mpas)  # another dimension order: the whole file
             px = ds._sorted_axes(None, data.lat, data.lon, data.level, data.time, data.level_units, data.names, app_logger)
             k, jj, ii = crop(px)
             self.sel = (px.ik[k], px.ij[jj], px.io[ii])

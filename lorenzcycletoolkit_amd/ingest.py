@@ -92,8 +92,16 @@ def prepare_streamed(args, varlist: str = "inputs/namelist", app_logger=None, ch
         raise NotImplementedError("the device ingest serves the fixed (-f) and the track (-t) frameworks")
     df = ds.read_namelist(varlist, app_logger)
     if raw is None:
-        raw = ds.open_raw(args.infile, df, mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
+        raw = ds.open_raw(ds.series_paths(args, varlist), df, mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
+    note_series_inflate(args, raw, app_logger)
     return StreamedDataset(raw, make_plan(raw, args, app_logger), chunk_steps, getattr(args, "inflate", None) or "auto")
+
+
+def note_series_inflate(args, raw, app_logger) -> None:
+    """Said once per streamed --series run with filtered NetCDF-4 parts: where they are inflated."""
+    if app_logger is not None and getattr(args, "series", None) and any(getattr(v.data, "_filters", None) for v in raw.variables.values()):
+        app_logger.info("--series: the deflated NetCDF-4 parts of a series are inflated by the reader on the host's threads (the device "
+                        "inflate reads one file's chunk index)")
 
 
 AUTO_DEVICE_BYTES = 1 << 30      # --ingest auto: files from this size on are streamed to the device whatever their container
@@ -122,6 +130,12 @@ def _prefers_device_ingest(args, varlist, app_logger=None):
     if not (getattr(args, "fixed", False) or getattr(args, "track", False)) or getattr(args, "cdsapi", False):
         return False, None
     try:
+        paths = ds.series_paths(args, varlist)
+        if len(paths) > 1:
+            # a series: the parts' sizes together decide; the deflated-NetCDF-4 criterion is the device inflate's, which a series does not use
+            if sum(os.path.getsize(p) for p in paths) < AUTO_DEVICE_BYTES:
+                return False, None
+            return True, ds.open_raw(paths, ds.read_namelist(varlist), mpas=bool(getattr(args, "mpas", False)), app_logger=app_logger)
         with open(args.infile, "rb") as fh:
             hdf5 = fh.read(8) == b"\x89HDF\r\n\x1a\n"
         big = os.path.getsize(args.infile) >= AUTO_DEVICE_BYTES
@@ -726,25 +740,33 @@ def _lec_code(dtype: np.dtype) -> int:
 def storage_dtypes(rvars) -> tuple:
     """Per-variable decode dtype (the reference's xarray decode rules, dataset.decode_dtypes) and the one storage dtype of the
     cubes: the widest of them (widening is exact; the engine wants one dtype, and all arithmetic is fp64 anyway)."""
-    dec = {r: ds.decode_dtypes(v.data.dtype, v.scale_factor, v.add_offset, v.fill_value)[1] for r, v in rvars.items()}
+    dec = {r: ds.decode_dtypes(v.data.dtype, *v.packing_at(0))[1] for r, v in rvars.items()}      # (presence decides: the same at every step)
     return dec, np.result_type(*dec.values())
 
 
 def _ingest_call(lib, v: ds.RawVariable, src_ptr: int, nt: int, geom, maps, unit: float, decode_dtype, out_dtype, out_ptr: int, stream,
-                 step: Optional[torch.Tensor] = None, step_base: int = 0, nt_src: int = 0):
-    """``step``: int32 [nt, 3] on the device -- per output step {source step, latitude offset, longitude offset} into the maps
+                 step: Optional[torch.Tensor] = None, step_base: int = 0, nt_src: int = 0, pack: Optional[torch.Tensor] = None):
+    """``pack``: float64 [rows, 3] on the device, a view of the table uploaded before the chunk loop -- {scale_factor, add_offset, fill
+    value} of every SOURCE step ``src_ptr`` holds (``nt_src`` rows with ``step``, else ``nt``).  It is what a variable of a series whose
+    parts differ in packing is decoded with (``lec_ingest_series``), and such a variable is refused without it; every other variable
+    takes the plain ``lec_ingest`` call with its one set of constants.
+    ``step``: int32 [nt, 3] on the device -- per output step {source step, latitude offset, longitude offset} into the maps
     (``lec_ingest_args.step_d``: a box-packed series); ``step_base``: the source step ``src_ptr`` starts with, ``nt_src``: the steps it
     holds (with the maps' lengths: what bounds the table's entries on the device).  ``LEC_CHECK_TABLES=1`` (debug runs of the Python
     host): ``lec_check_maps`` scans the maps and the table before every call -- synchronous, so not the default."""
     nl_in, ny_in, nx_in, nl, ny, nx = geom
     kmap, jmap, imap = maps
+    series = not v.uniform_packing
+    if series and pack is None:
+        raise ValueError("a variable whose parts differ in packing is decoded with the per-step table (pack)")
+    scale, offset, fill = v.packing_at(0)       # (which of them are present is the same at every step; the values only when not `series`)
     ga = _lib.IngestArgs(
         src_d=C.c_void_p(src_ptr), src_dtype=_src_code(v.data.dtype), swap_bytes=int(_swapped(v.data.dtype)),
         nt=nt, nl_in=nl_in, ny_in=ny_in, nx_in=nx_in, nl=nl, ny=ny, nx=nx,
         kmap_d=C.c_void_p(kmap.data_ptr()), jmap_d=C.c_void_p(jmap.data_ptr()), imap_d=C.c_void_p(imap.data_ptr()),
-        has_packing=int(v.scale_factor is not None or v.add_offset is not None), has_fill=int(v.fill_value is not None),
-        scale_factor=1.0 if v.scale_factor is None else v.scale_factor, add_offset=0.0 if v.add_offset is None else v.add_offset,
-        fill_value=0.0 if v.fill_value is None else v.fill_value, unit_scale=float(unit),
+        has_packing=int(scale is not None or offset is not None), has_fill=int(fill is not None),
+        scale_factor=1.0 if scale is None else scale, add_offset=0.0 if offset is None else offset,
+        fill_value=0.0 if fill is None else fill, unit_scale=float(unit),
         out_dtype=_lec_code(out_dtype), decode_dtype=_lec_code(decode_dtype),
         out_d=C.c_void_p(out_ptr), stream=C.c_void_p(stream.cuda_stream),
         step_d=None if step is None else C.c_void_p(step.data_ptr()), step_base=int(step_base), nt_src=int(nt_src),
@@ -752,7 +774,22 @@ def _ingest_call(lib, v: ds.RawVariable, src_ptr: int, nt: int, geom, maps, unit
     if os.environ.get("LEC_CHECK_TABLES", "0") == "1":
         status = torch.empty(4, dtype=torch.int32, device=kmap.device)
         _lib.check(lib.lec_check_maps(C.byref(ga), C.c_void_p(status.data_ptr())), "lec_check_maps")
-    _lib.check(lib.lec_ingest(C.byref(ga)), "lec_ingest")
+    if series:
+        if not pack.is_contiguous() or pack.dtype != torch.float64 or pack.dim() != 2 or pack.shape[1] != 3:
+            raise ValueError("pack: contiguous float64 [rows, 3]")
+        _lib.check(lib.lec_ingest_series(C.byref(ga), C.c_void_p(pack.data_ptr()), int(pack.shape[0])), "lec_ingest_series")
+    else:
+        _lib.check(lib.lec_ingest(C.byref(ga)), "lec_ingest")
+
+
+def _pack_table(var, file_steps, dev, pad: int = 0) -> Optional[torch.Tensor]:
+    """The packing constants of ``file_steps`` on the device, float64 [n + pad, 3] (``pad``: the last row repeated, so that a view of a
+    slot's length never ends past the table), for a variable of a series whose parts differ in packing; None for every other variable.
+    A blocking upload from pageable memory: before the chunk loop, never inside it."""
+    if var.uniform_packing:
+        return None
+    rows = var.packing_table(file_steps)
+    return torch.as_tensor(np.ascontiguousarray(np.concatenate([rows, np.repeat(rows[-1:], pad, axis=0)]))).to(dev)
 
 
 def device_cube(var: ds.RawVariable, plan: IngestPlan, device="cuda:0", unit: float = 1.0, out_dtype=None, inflate: str = "auto") -> torch.Tensor:
@@ -761,7 +798,7 @@ def device_cube(var: ds.RawVariable, plan: IngestPlan, device="cuda:0", unit: fl
     lib = _lib.load()
     dev = torch.device(device)
     nt, nl, ny, nx = len(plan.tsel), plan.level.size, plan.lat.size, plan.lon.size
-    decode = ds.decode_dtypes(var.data.dtype, var.scale_factor, var.add_offset, var.fill_value)[1]
+    decode = ds.decode_dtypes(var.data.dtype, *var.packing_at(0))[1]
     out_dtype = np.dtype(decode if out_dtype is None else out_dtype)
     j0, j1 = int(plan.jmap.min()), int(plan.jmap.max())
     file_levels = np.sort(plan.kmap)
@@ -774,7 +811,7 @@ def device_cube(var: ds.RawVariable, plan: IngestPlan, device="cuda:0", unit: fl
     out = torch.empty((nt, nl, ny, nx), dtype=torch.float64 if out_dtype == np.float64 else torch.float32, device=dev)
     with torch.cuda.device(dev):
         _ingest_call(lib, var, st.raw_dev[0].data_ptr(), nt, (nl, j1 - j0 + 1, int(var.data.shape[3]), nl, ny, nx), maps, unit,
-                     decode, out_dtype, out.data_ptr(), torch.cuda.current_stream(dev))
+                     decode, out_dtype, out.data_ptr(), torch.cuda.current_stream(dev), pack=_pack_table(var, plan.tsel, dev))
     torch.cuda.synchronize(dev)
     if hasattr(st, "finish"):
         st.finish()
@@ -941,6 +978,10 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     # and copies in rounds 1-2, profiles/r03_notes.md): the d/dt coefficients of the whole time axis and the tables of every box go to
     # the device once, here; a chunk uses rows / views of them.
     tcoef_all = engine.time_coefs_device(time_s) if with_q else None
+    # ... and so does the packing table of a series whose parts differ in packing: a row per PROCESSED step (row q of a slot holds the
+    # processed step h0 + q, T's halo included, so a call's rows are pack_all[r][h0 + first slot row ...]: a view)
+    pack_all = {r: _pack_table(rvars[r], plan.tsel, dev, pad=span) for r in roles}
+    pack_of = lambda r, a, b: None if pack_all[r] is None else pack_all[r][a:b]
     # chunk schedule: a short first chunk fills the pipeline quickly (the first upload cannot start before its staging is done)
     first = max(1, min(chunk_steps, 1 if (t1 - t0) > chunk_steps else chunk_steps))
     bounds = [t0, min(t0 + first, t1)]
@@ -968,13 +1009,14 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                         for key, shift in [(keys[r], 0)] + ([("tm", -1), ("tp", 1)] if r == "Air Temperature" else []):
                             _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, geom, maps, unit, decode[r], common,
                                          cubes[key][0].data_ptr(), compute, step=step_tab[shift][s0:s1], step_base=h0,
-                                         nt_src=int(stagers[r].raw_dev[slot].shape[0]))
+                                         nt_src=int(stagers[r].raw_dev[slot].shape[0]), pack=pack_of(r, h0, h0 + int(stagers[r].raw_dev[slot].shape[0])))
                     if keep is not None:        # the diagnostics' level of u, v, Phi over the whole crop: one gather of that level per field
                         kmap1 = maps[0][k_keep: k_keep + 1]
                         for r, k in (("Eastward Wind Component", "u"), ("Northward Wind Component", "v"), (geo_role, "geopt")):
                             unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
                             _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][s0 - h0].data_ptr(), n, (nl_in, ny_in, nx_in, 1, ny, nx),
-                                         (kmap1, maps[1], maps[2]), unit, decode[r], common, keep[k][s0 - t0].data_ptr(), compute)
+                                         (kmap1, maps[1], maps[2]), unit, decode[r], common, keep[k][s0 - t0].data_ptr(), compute,
+                                         pack=pack_of(r, s0, s0 + n))
                     f = {k: t[:n] for k, t in cubes.items()}
                     kw = dict(t_begin=0, **engine.packed_dtdt(f["tm"], f["tair"], f["tp"], tcoef_all[s0:s1], out=None if dtdt is None else dtdt[:n]))
                 else:
@@ -983,7 +1025,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                         a, b = (g0 - h0, g1 - h0) if r == "Air Temperature" else (s0 - h0, s1 - h0)
                         unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
                         _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][a].data_ptr(), b - a, (nl_in, ny_in, nx_in, nl, ny, nx), maps, unit,
-                                     decode[r], common, cubes[keys[r]][a - (g0 - h0)].data_ptr(), compute)
+                                     decode[r], common, cubes[keys[r]][a - (g0 - h0)].data_ptr(), compute, pack=pack_of(r, h0 + a, h0 + b))
                     f = {k: t[: g1 - g0] for k, t in cubes.items()}
                     if keep is not None:        # (u, v, geopotential start at their own first step: rows [s0 - g0, s1 - g0) of the cubes)
                         for k in keep:
@@ -1141,8 +1183,14 @@ def lec_streamed_batch(raw: ds.RawDataset, plan, variable_list_df, *, chunk_step
     pipe = _Pipeline(lib, dev, roles, stagers, slots, direct, spans)
     compute = pipe.compute
     staged = {keys[r]: 0 for r in roles}
+    # the packing tables of a series whose parts differ in packing: the rows of every chunk's slot (the file steps it stages, in its
+    # order) one chunk after the other, uploaded once, here; a chunk's calls take its run of rows
+    held_steps = lambda ch, r: ch.t_steps if r == "Air Temperature" else ch.steps
+    pack_at = {r: np.concatenate([[0], np.cumsum([len(held_steps(ch, r)) for ch in chunks])]) for r in roles}
+    pack_all = {r: _pack_table(rvars[r], np.concatenate([np.asarray(held_steps(ch, r)) for ch in chunks]), dev) for r in roles}
     for c, ch in enumerate(chunks):
         slot = c % slots
+        pack_c = {r: None if pack_all[r] is None else pack_all[r][int(pack_at[r][c]): int(pack_at[r][c + 1])] for r in roles}
         pipe.upload(c, lambda r: (ch.t_steps if r == "Air Temperature" else ch.steps, 0))
         for r in roles:
             staged[keys[r]] += len(ch.t_steps if r == "Air Temperature" else ch.steps)
@@ -1161,7 +1209,7 @@ def lec_streamed_batch(raw: ds.RawDataset, plan, variable_list_df, *, chunk_step
                         tabs = [(keys[r], g["t_tab"][0]), ("tm", g["t_tab"][1]), ("tp", g["t_tab"][2])] if r == "Air Temperature" else [(keys[r], g["f_tab"])]
                         for k, tab in tabs:
                             _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, geom, maps, unit, decode[r], common,
-                                         f[k].data_ptr(), compute, step=tab[a:b], step_base=0, nt_src=held[r])
+                                         f[k].data_ptr(), compute, step=tab[a:b], step_base=0, nt_src=held[r], pack=pack_c[r])
                     out = None if dtdt_flat is None else dtdt_flat[: n * nl * nyp * nxp].view(n, nl, nyp, nxp)
                     kw = engine.packed_dtdt(f["tm"], f["tair"], f["tp"], g["tcoef"][a:b], out=out)
                 part = g["boxes"].part(a, b)
@@ -1181,7 +1229,7 @@ def lec_streamed_batch(raw: ds.RawDataset, plan, variable_list_df, *, chunk_step
                         unit = 1.0 if r == geo_role else ds.field_scale(variable_list_df, r)
                         _ingest_call(lib, rvars[r], stagers[r].raw_dev[slot][0].data_ptr(), n, (nl_in, ny_in, nx_in, 1, td["ny"], td["nx"]),
                                      (kmap1, maps[1], maps[2]), unit, decode[r], common, dsrc[k].data_ptr(), compute, step=td["rows"][p0:p1],
-                                     step_base=0, nt_src=held[r])
+                                     step_base=0, nt_src=held[r], pack=pack_c[r])
                         if dsrc is not d64:
                             d64[k][:m].copy_(dsrc[k][:m])
                     if "Geopotential Height" not in variable_list_df.index:
