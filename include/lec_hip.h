@@ -667,6 +667,50 @@ int lec_rowstats_steps(const lec_rowstats_args* args, const int32_t* step_d);
  *   - Everything lec_rowstats checks is checked here too.  lec_check_boxes serves ring calls unchanged.
  */
 int lec_rowstats_ring(const lec_rowstats_args* args);
+
+/*
+ * -f --periodic --wavenumbers N: the ZONAL-WAVENUMBER SHARES of the eight eddy covariances of every ring row (an additive call: no
+ * struct, export or kernel result of ABI 11 changes; lec_rowspec.hip is a code object of its own, loaded by spectral calls only).
+ *
+ * On the closed, evenly spaced axis the zonal mean is the plain mean over the nx columns, so the discrete Parseval identity splits every
+ * covariance of a row a_0 .. a_{nx-1}, b_0 .. b_{nx-1} exactly:
+ *   a^_n = (1 / nx) sum_i a_i exp(-2 pi i n i / nx),    C_n(a, b) = w_n Re(a^_n conj(b^_n)),    [a'b'] = sum_{n = 1}^{nx / 2} C_n(a, b),
+ *   w_n = 2 for 1 <= n < nx / 2, w_n = 1 for n = nx / 2 (nx even: the Nyquist wavenumber).
+ * The call writes, for the rows of the latitude band js .. jn of time steps [t_begin, t_begin + t_count),
+ *   spec_d [t_count][nl][jn - js + 1][n_wave][8]:  C_n of LEC_S_TT, UU, VV, VT, WT, UV, WU, WV (slots 6 .. 13 of a row record, in that
+ *   order) for n = 1 .. n_wave.
+ * Every eddy term lec_reduce forms (Ae, Ke, Ca, Ce, Ck) is linear in those eight slots given the zonal means, so row records that carry
+ * the shares of one n in slots 6 .. 13 and everything else as lec_rowstats_ring wrote it give that term's wavenumber-n part: no
+ * second formulation of stage 2 (the Python host assembles the records).
+ *   - Cubes [nt][nl][ny][nx] as lec_rowstats_ring takes them (fp64 or fp32 storage; all nx columns are the ring).  Accumulation is fp64.
+ *   - twid_d [nx][2]: cos and sin of 2 pi m / nx, m = 0 .. nx - 1, fp64, built on the host (tables.twiddle_table), 16-byte aligned.  The
+ *     kernel indexes it with (n i) mod nx kept as an integer: no recurrence and no device sincos, so a result does not depend on how the
+ *     row is walked beyond the order of its fp64 sums.
+ *   - A row's column 0 is subtracted from the row before it is projected (T is about 288 K with eddies of about 1 K; a constant has no
+ *     share in n >= 1).
+ *   - NaN: a NaN anywhere in a row of a field makes every share that field enters NaN, for every n -- the pattern of the covariances
+ *     lec_rowstats_ring writes for that row.
+ * Validation.  Every refusal is LEC_ERR_ARG naming the field, made before any HIP call, never clamped: null tair_d / u_d / v_d /
+ * omega_d / twid_d / spec_d, dtype, nx < 3, t_begin / t_count outside the cube, js / jn outside 0 <= js <= jn < ny, n_wave < 1 or
+ * n_wave > nx / 2, twid_d / spec_d not 16-byte aligned.  n_wave > LEC_MAX_WAVENUMBERS, or more than 2^31 - 1 rows: LEC_ERR_UNSUPPORTED.
+ */
+#define LEC_MAX_WAVENUMBERS 64 /* the largest n_wave of one lec_rowspec_ring call */
+typedef struct lec_rowspec_args {
+    const void* tair_d;
+    const void* u_d;
+    const void* v_d;
+    const void* omega_d;
+    int32_t dtype;              /* enum lec_dtype (LEC_F64 or LEC_F32), common to the four cubes */
+    int32_t nt, nl, ny, nx;     /* cube dimensions; the nx columns are the ring */
+    int32_t t_begin, t_count;   /* process time steps [t_begin, t_begin + t_count) */
+    int32_t js, jn;             /* the latitude band (inclusive grid rows) */
+    int32_t n_wave;             /* wavenumbers 1 .. n_wave; 1 <= n_wave <= min(nx / 2, LEC_MAX_WAVENUMBERS) */
+    const double* twid_d;       /* [nx][2] cos, sin of 2 pi m / nx; 16-byte aligned */
+    double* spec_d;             /* out [t_count][nl][jn - js + 1][n_wave][8]; 16-byte aligned */
+    void* stream;
+} lec_rowspec_args;
+int lec_rowspec_ring(const lec_rowspec_args* args);
+
 int lec_ingest(const lec_ingest_args* args);
 /*
  * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with

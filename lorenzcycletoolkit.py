@@ -24,6 +24,10 @@ the time step at which it forms until it has weakened (``lec_follow_spans``; --c
 circle and the box limits span it; zonal means run over the closed axis, d/dlon is centred across the +-180 meridian and no flux
 crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file names and columns as -f.
 
+-f --periodic --wavenumbers N: also the shares of the zonal wavenumbers 1 .. N in the eddy terms Ae, Ke, Ca, Ce and Ck
+(``lec_rowspec_ring``; exact by the discrete Parseval identity on the closed axis), written to results_wavenumbers/<term>_n.csv; every
+other output file is unchanged.
+
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
 ``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
@@ -83,6 +87,12 @@ def create_arg_parser():
                         "select its first and last longitude (-180 / 180 always do); min_lat / max_lat give the band.  Zonal means run over the "
                         "closed circle, d/dlon is centred across the +-180 meridian and no flux crosses an east or west wall (otherwise the "
                         "circle is a limited area with a seam)")
+    # (no attribute without the option, as for --series)
+    parser.add_argument("--wavenumbers", type=int, metavar="N", default=argparse.SUPPRESS, help="with -f --periodic: also split the eddy terms "
+                        "Ae, Ke, Ca, Ce and Ck into the shares of the zonal wavenumbers 1 .. N (N <= nx / 2 and N <= 64) and write them to "
+                        "results_wavenumbers/Ae_n.csv ... Ck_n.csv: one row per time step, columns 1 .. N and 'rest' (the total minus the N "
+                        "shares), in the units of the results CSV.  The split is exact (discrete Parseval on the closed axis); every other "
+                        "output file is unchanged.  One GPU, data prepared on the host (--ingest auto resolves to host)")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -298,6 +308,21 @@ def refuse_periodic_options(args):
     if args.periodic and not args.fixed:
         raise SystemExit("--periodic goes with -f/--fixed: the ring of a -t / -c run is the 0..360 longitude axis a track across the +-180 "
                          "meridian gets by itself, and --choose-periodic for the search of -c")
+    n = getattr(args, "wavenumbers", None)
+    if n is None:
+        return
+    from lorenzcycletoolkit_amd._lib import LEC_MAX_WAVENUMBERS
+    if not (args.fixed and args.periodic):
+        raise SystemExit("--wavenumbers goes with -f --periodic: a zonal-wavenumber spectrum exists on a full ring of longitudes only")
+    if n < 1:
+        raise SystemExit("--wavenumbers must be >= 1")
+    if n > LEC_MAX_WAVENUMBERS:
+        raise SystemExit(f"--wavenumbers must be <= {LEC_MAX_WAVENUMBERS} (LEC_MAX_WAVENUMBERS, include/lec_hip.h)")
+    if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--wavenumbers runs on one GPU: --gpus > 1 is not supported for the spectra (run the totals sharded, the spectra apart)")
+    if args.ingest == "device" or args.device_ingest:
+        raise SystemExit("--wavenumbers prepares the data on the host: --ingest device / --device-ingest is not supported for the spectra "
+                         "(--ingest auto resolves to host)")
 
 
 def refuse_batch_chunk_options(args):
@@ -382,6 +407,8 @@ def main(argv=None):
         opened, auto_chose = None, False
         if args.ingest == "device":
             args.device_ingest = True
+        elif args.ingest == "auto" and getattr(args, "wavenumbers", None) is not None:
+            app_logger.info("--wavenumbers: --ingest auto resolves to host (the spectra run on host-prepared cubes)")
         elif args.ingest == "auto" and not args.device_ingest:
             from lorenzcycletoolkit_amd.ingest import prefers_device_ingest
             args.device_ingest, opened = prefers_device_ingest(args, "inputs/namelist", keep_open=True, app_logger=app_logger)

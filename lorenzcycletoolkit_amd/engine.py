@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .constants import LEVEL_TERMS, SCALAR_TERMS
+from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
 
 
 @dataclass
@@ -28,6 +28,10 @@ class LECResult:
     nanflag: torch.Tensor      # [t_count] int32: NaN level values repaired/dropped by _handle_nans
     rows: Optional[torch.Tensor] = None   # [t_count, nl, nyb_max, 32] row records (kept on request)
     packed: Optional[torch.Tensor] = None  # [t_count, 16 + 21 nl] fp64
+    # compute(..., wavenumbers=N) on a ring: the zonal-wavenumber shares of the eddy terms (constants.SPECTRUM_TERMS / SPECTRUM_LEVEL_TERMS)
+    spectrum: Optional[torch.Tensor] = None         # [t_count, 5, N] fp64: Ae, Ke, Ca, Ce, Ck of the wavenumbers 1 .. N
+    spectrum_rest: Optional[torch.Tensor] = None    # [t_count, 5] fp64: the total minus the N shares
+    spectrum_levels: Optional[torch.Tensor] = None  # [t_count, 14, N, nl] fp64
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -41,6 +45,8 @@ class LECResult:
 def _ptr(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
 
+
+_LEC_S_TT = 6      # enum lec_stat: the eight eddy covariances [T'T'] .. [w'v'] are slots 6 .. 13 of a row record
 
 _KERNELS = {"auto": _lib.KERNEL_AUTO, "two_sweep": _lib.KERNEL_TWO_SWEEP, "row_sweep": _lib.KERNEL_ROW_SWEEP,
             "row_block": _lib.KERNEL_ROW_BLOCK, "box_tile": _lib.KERNEL_BOX_TILE, "box_plane": _lib.KERNEL_BOX_PLANE}
@@ -127,6 +133,7 @@ class LECEngine:
         self._pack_maps = {}   # pack_boxes' index maps of the last grid / slab shape
         self._work = {}        # stage-2 workspaces by shape: am, levraw, dropmask (true scratch: never handed out)
         self._tcoef = None     # (time axis, its d/dt coefficients on the device) of the last call
+        self._twid = None      # the twiddle table of lec_rowspec_ring for the engine's nx longitudes
 
     # -- helpers ---------------------------------------------------------------------------
     def _up(self, a: np.ndarray, dtype=torch.float64) -> torch.Tensor:
@@ -319,7 +326,8 @@ class LECEngine:
                 merge_dropmask: Optional[Callable[[torch.Tensor], None]] = None,
                 tuning: Optional[dict] = None, per_step_boxes: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
-                tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None) -> LECResult:
+                tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
+                wavenumbers: Optional[int] = None) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -335,7 +343,15 @@ class LECEngine:
         ``merge_dropmask``: see ``reduce`` (time-sharded runs).
         ``timing``: a list that receives one (start, end) pair of HIP events recorded on the launch
         stream around every stage-1 launch (bench.py's roofline figure).
+        ``wavenumbers`` = N (boxes from ``prepare_boxes(..., ring=True)`` only): the result also carries ``spectrum``,
+        ``spectrum_rest`` and ``spectrum_levels``, the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce and Ck (``rowspec``
+        and stage 2 on row records that carry one wavenumber's covariances).  Everything else of the result is, bit for bit, what
+        the call without it returns.
         """
+        if wavenumbers is not None:
+            self._check_wavenumbers(wavenumbers, boxes, int(tair.shape[-1]) if tair.dim() == 4 else 0)
+            if merge_dropmask is not None or out is not None or steps is not None or tm is not None or tp is not None:
+                raise ValueError("wavenumbers: one ring on whole cubes in one process (no merge_dropmask, out, steps, tm / tp)")
         rows = self.rowstats(tair, u, v, omega, geopt, boxes, time_s=time_s, dTdt=dTdt, t_begin=t_begin, t_count=t_count,
                              with_q=with_q, timing=timing, tuning=tuning, per_step_boxes=per_step_boxes, tm=tm, tp=tp, tcoef=tcoef,
                              steps=steps)
@@ -343,8 +359,97 @@ class LECEngine:
             per_step_boxes = True
         if drop_any_time is None and per_step_boxes:
             drop_any_time = False
-        return self.reduce(rows, boxes, phi_scale=phi_scale, drop_any_time=drop_any_time, merge_dropmask=merge_dropmask,
-                           keep_rows=keep_rows, out=out)
+        res = self.reduce(rows, boxes, phi_scale=phi_scale, drop_any_time=drop_any_time, merge_dropmask=merge_dropmask,
+                          keep_rows=keep_rows, out=out)
+        if wavenumbers is not None:
+            self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time)
+        return res
+
+    # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
+    SPECTRUM_CHUNK_BYTES = 256 << 20     # assembled row records (N wavenumbers x a chunk of time steps) resident at once
+
+    @staticmethod
+    def _check_wavenumbers(wavenumbers, boxes, nx: int) -> None:
+        if not isinstance(boxes, PreparedBoxes) or not boxes.bt.ring:
+            raise ValueError("wavenumbers: a zonal-wavenumber spectrum exists on a ring only: boxes from prepare_boxes(..., ring=True)")
+        if boxes.bt.nyb_max != boxes.boxes[0][3] - boxes.boxes[0][2] + 1:
+            raise ValueError("wavenumbers: the ring's records must have the band's own row count (prepare_boxes without nyb_min)")
+        if isinstance(wavenumbers, bool) or not isinstance(wavenumbers, (int, np.integer)):
+            raise ValueError("wavenumbers must be an integer")
+        if wavenumbers < 1 or wavenumbers > nx // 2:
+            raise ValueError(f"wavenumbers must be 1 .. nx / 2 = {nx // 2} (a ring of {nx} columns holds no others), got {wavenumbers}")
+        if wavenumbers > _lib.LEC_MAX_WAVENUMBERS:
+            raise ValueError(f"wavenumbers must be at most {_lib.LEC_MAX_WAVENUMBERS} (LEC_MAX_WAVENUMBERS), got {wavenumbers}")
+
+    def rowspec(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, boxes: PreparedBoxes, wavenumbers: int, *,
+                t_begin: int = 0, t_count: Optional[int] = None, spec_out: Optional[torch.Tensor] = None,
+                timing: Optional[list] = None) -> torch.Tensor:
+        """``lec_rowspec_ring``: [t_count, nl, nyb, N, 8] fp64, the shares of the zonal wavenumbers 1 .. N in the eight eddy covariances
+        (slots 6 .. 13 of a row record, in that order) of every row of the ring's latitude band, for time steps
+        [t_begin, t_begin + t_count) of the cubes.  ``boxes`` from ``prepare_boxes(..., ring=True)``; ``spec_out``: a caller-owned
+        buffer; ``timing``: a list that receives one (start, end) pair of HIP events around the launch."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        self._check_wavenumbers(wavenumbers, boxes, nx)
+        n = int(wavenumbers)
+        if t_count is None:
+            t_count = nt - t_begin
+        _, _, js, jn = boxes.boxes[0]
+        shape = (t_count, nl, jn - js + 1, n, 8)
+        spec = torch.empty(shape, dtype=torch.float64, device=tair.device) if spec_out is None else spec_out
+        if spec.shape != shape or spec.dtype != torch.float64 or spec.device != tair.device or not spec.is_contiguous():
+            raise ValueError("spec_out must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the fields' device")
+        if self._twid is None:
+            self._twid = self._up(tables.twiddle_table(nx))
+        sa = _lib.RowspecArgs(
+            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
+            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, twid_d=_ptr(self._twid), spec_d=_ptr(spec),
+            stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
+        with torch.cuda.device(tair.device):
+            if timing is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _lib.check(self.lib.lec_rowspec_ring(C.byref(sa)), "lec_rowspec_ring")
+            if timing is not None:
+                ev1.record()
+                timing.append((ev0, ev1))
+        return spec
+
+    def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
+                  drop_any_time: Optional[bool]) -> None:
+        """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
+        whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
+        (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
+        level), and ONE vertical half over all (n, step) applies _handle_nans: a share is NaN exactly where its total is, so the
+        any-time mask over the batch is the totals' own."""
+        t_count, nl, nyb = (int(x) for x in rows.shape[:3])
+        dev = rows.device
+        f64 = dict(dtype=torch.float64, device=dev)
+        levraw = torch.empty((n, t_count, nl, _lib.LEC_NLEVRAW), **f64)
+        tc = max(1, min(t_count, self.SPECTRUM_CHUNK_BYTES // (n * nl * nyb * _lib.LEC_NSTAT * 8)))
+        asm = torch.empty((n, tc, nl, nyb, _lib.LEC_NSTAT), **f64)
+        spec = torch.empty((tc, nl, nyb, n, 8), **f64)
+        part = torch.empty((n, tc, nl, _lib.LEC_NLEVRAW), **f64)
+        for a in range(0, t_count, tc):
+            b = min(a + tc, t_count)
+            c = b - a
+            sp = self.rowspec(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=c, spec_out=spec[:c])
+            rec = asm[:, :c]
+            rec.copy_(rows[a:b].unsqueeze(0))
+            rec[..., _LEC_S_TT:_LEC_S_TT + 8] = sp.permute(3, 0, 1, 2, 4)
+            if c == tc:
+                self.level_stage(rec.reshape(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, part.view(n * c, nl, _lib.LEC_NLEVRAW), phi_scale=phi_scale)
+                levraw[:, a:b] = part
+            else:                       # the last, shorter chunk: a contiguous batch of its own
+                last = torch.empty((n * c, nl, _lib.LEC_NLEVRAW), **f64)
+                self.level_stage(rec.contiguous().view(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, last, phi_scale=phi_scale)
+                levraw[:, a:b] = last.view(n, c, nl, _lib.LEC_NLEVRAW)
+        shares = self.vertical_stage(levraw.view(n * t_count, nl, _lib.LEC_NLEVRAW), boxes, drop_any_time=drop_any_time)
+        si = torch.as_tensor([SCALAR_TERMS.index(x) for x in SPECTRUM_TERMS], device=dev)
+        li = torch.as_tensor([LEVEL_TERMS.index(x) for x in SPECTRUM_LEVEL_TERMS], device=dev)
+        res.spectrum = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, si].permute(1, 2, 0).contiguous()
+        res.spectrum_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, li].permute(1, 2, 0, 3).contiguous()
+        res.spectrum_rest = res.scalars[:, si] - res.spectrum.sum(dim=2)
 
     def rowstats(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor,
                  geopt: Optional[torch.Tensor], boxes: Sequence[Sequence[int]], *,

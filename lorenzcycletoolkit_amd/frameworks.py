@@ -54,12 +54,15 @@ class BoxData:
     ``periodic`` (fixed framework only): the box is the latitude band [south, north] over ALL of ``data``'s longitudes, which must be
     a full ring (evenly spaced, nx * dx = 360 degrees), and the western / eastern limits must select its first / last column: zonal
     means over the closed circle, Q's d/dlon centred across the seam, no east-west boundary flux (``lec_rowstats_ring``).
+
+    ``wavenumbers`` = N (``periodic`` only, one process, host-prepared data): ``spectrum`` [time, 5, N], ``spectrum_rest`` [time, 5] and
+    ``spectrum_levels`` [time, 14, N, level] -- the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce, Ck (``lec_rowspec_ring``).
     """
 
     def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, western_limit=None, eastern_limit=None,
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
-                 boxes_limits=None, periodic: bool = False):
+                 boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -69,6 +72,15 @@ class BoxData:
                 raise ValueError("periodic: one fixed box (the moving framework's ring is the 0..360 axis of --choose-periodic)")
             from .tables import box_indices
             self.xlength = ring_box_check(data.lon, box_indices(data.lat, data.lon, western_limit, eastern_limit, southern_limit, northern_limit))
+        self.wavenumbers = None if wavenumbers is None else int(wavenumbers)
+        self.spectrum = self.spectrum_rest = self.spectrum_levels = None
+        if wavenumbers is not None:     # (host work only, as above)
+            from .ingest import StreamedDataset as _Streamed
+            if not self.periodic:
+                raise ValueError("wavenumbers: a zonal-wavenumber spectrum exists on a ring only (periodic=True)")
+            wavenumbers_check(self.wavenumbers, len(data.lon))
+            if getattr(args, "shard", None) is not None or isinstance(data, _Streamed):
+                raise ValueError("wavenumbers: one process on host-prepared data (no time shards, no device ingest)")
         self.args = args
         self.results_subdirectory = results_subdirectory
         self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
@@ -135,6 +147,10 @@ class BoxData:
         self.scalars = self.result.scalars_dict()
         self.levels = self.result.levels_dict()
         self.nanflag = self.result.nanflag.cpu().numpy()
+        if self.result.spectrum is not None:
+            self.spectrum = self.result.spectrum.cpu().numpy()
+            self.spectrum_rest = self.result.spectrum_rest.cpu().numpy()
+            self.spectrum_levels = self.result.spectrum_levels.cpu().numpy()
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -173,7 +189,8 @@ class BoxData:
         return self.engine.compute(cubes[0], cubes[1], cubes[2], cubes[3], cubes[4], boxes,
                                    time_s=data.time_s[h0:h1] if dTdt is None else None, dTdt=dTdt_dev, phi_scale=phi_scale,
                                    t_begin=t0 - h0, t_count=t1 - t0, per_step_boxes=self.per_step_boxes,
-                                   drop_any_time=not self.per_step_boxes, merge_dropmask=merge, out=out)
+                                   drop_any_time=not self.per_step_boxes, merge_dropmask=merge, out=out,
+                                   **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -213,6 +230,35 @@ def ring_box_check(lon, box) -> float:
                          f"and last ({float(lon[0])} and {float(lon[-1])}): a periodic box of part of a circle does not exist "
                          "(min_lon -180 and max_lon 180 always select the whole ring)")
     return ring_axis(lon)[1]
+
+
+def wavenumbers_check(n: int, nx: int) -> None:
+    """--wavenumbers N on a ring of ``nx`` longitudes: 1 <= N <= nx / 2 (the ring holds no other wavenumbers) and N <= the library's
+    limit; raises ValueError, nothing is clamped."""
+    from ._lib import LEC_MAX_WAVENUMBERS
+    if n < 1 or n > nx // 2:
+        raise ValueError(f"--wavenumbers {n}: a ring of {nx} longitudes holds the zonal wavenumbers 1 .. {nx // 2}")
+    if n > LEC_MAX_WAVENUMBERS:
+        raise ValueError(f"--wavenumbers {n}: at most {LEC_MAX_WAVENUMBERS} (LEC_MAX_WAVENUMBERS)")
+
+
+def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
+    """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck: one row per time step -- the time labels and number formatting of
+    the per-level tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the units of the results CSV."""
+    from .constants import SPECTRUM_TERMS
+    os.makedirs(directory, exist_ok=True)
+    n = box_obj.spectrum.shape[2]
+    header = ",".join([str(time_name)] + [str(k) for k in range(1, n + 1)] + ["rest"]) + "\n"
+    labels = box_obj.row_labels("fixed")
+    for i, term in enumerate(SPECTRUM_TERMS):
+        table = np.concatenate([box_obj.spectrum[:, i, :], box_obj.spectrum_rest[:, i: i + 1]], axis=1)
+        path = os.path.join(directory, f"{term}_n.csv")
+        with open(path, "wb") as f:
+            f.write(header.encode("utf-8"))
+            if labels[0] is not None:
+                f.write(format_level_table(table, labels))
+        if labels[0] is None:            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
+            pd.DataFrame(table, index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
 
 
 def ring_hint(lon, box):
@@ -401,11 +447,16 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
     if periodic:        # refused here, before a file is written: no ring, or limits that do not span it
         from .tables import box_indices
         ring_box_check(data.lon, box_indices(data.lat, data.lon, min_lon, max_lon, min_lat, max_lat))
+    wavenumbers = getattr(args, "wavenumbers", None)
+    if wavenumbers is not None:     # likewise: N must fit the ring the file holds
+        if not periodic:
+            raise ValueError("--wavenumbers goes with -f --periodic")
+        wavenumbers_check(int(wavenumbers), len(data.lon))
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
-                          results_subdirectory_vertical_levels, periodic=periodic)
+                          results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers)
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -423,6 +474,11 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         app_logger.warning("NaN level values were interpolated/dropped per time step (_handle_nans semantics)")
     terms = _compute_all(box_obj, "fixed", app_logger)
     app_logger.info("Computed energy, conversion, boundary and generation terms")
+    if wavenumbers is not None:
+        spectrum_directory = os.path.join(results_subdirectory, "results_wavenumbers")
+        write_spectrum_csvs(box_obj, spectrum_directory, time_name)
+        app_logger.info(f"--wavenumbers: Ae, Ke, Ca, Ce, Ck split into the zonal wavenumbers 1 .. {int(wavenumbers)} of the ring's "
+                        f"{len(data.lon)} longitudes (lec_rowspec_kernel: N = {int(wavenumbers)}, nx = {len(data.lon)}); written to {spectrum_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]

@@ -89,6 +89,17 @@ def ring_axis(lon_deg: np.ndarray):
     return h, float(np.deg2rad(lon[-1] + h) - np.deg2rad(lon[0]))
 
 
+def twiddle_table(nx: int) -> np.ndarray:
+    """[nx, 2] fp64: cos and sin of 2 pi m / nx for m = 0 .. nx - 1 -- the one source of the twiddles of ``lec_rowspec_ring``, which
+    indexes it with (n i) mod nx as an integer (no recurrence and no device sincos: every lane reads the same correctly rounded pair
+    for the same angle)."""
+    nx = int(nx)
+    if nx < 3:
+        raise ValueError("a ring has at least 3 columns")
+    ang = 2.0 * np.pi * np.arange(nx, dtype=np.float64) / nx
+    return np.ascontiguousarray(np.stack([np.cos(ang), np.sin(ang)], axis=1))
+
+
 def build_box_tables(lat_deg: np.ndarray, lon_deg: np.ndarray, boxes: Sequence[Sequence[int]], nyb_min: int = 0,
                      lon_uniform: Optional[bool] = None, ring: bool = False) -> BoxTables:
     """Per-box tables for both stages.  ``boxes`` = inclusive index quadruples (iw, ie, js, jn).

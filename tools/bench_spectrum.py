@@ -1,0 +1,140 @@
+#!/usr/bin/env python3
+"""What the zonal-wavenumber spectra of a ring cost (-f --periodic --wavenumbers N): ``lec_rowspec_ring`` next to the ring pass
+``lec_rowstats_ring`` on the same cubes -- a global 37 x 721 x 1440 fp64 grid, box +-89.75 degrees over all longitudes -- and
+``LECEngine.compute(..., wavenumbers=N)`` next to the same ``compute`` without it, for N = 8, 20 and 64.
+
+    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--other NAME=PATH ...] [--out FILE]
+
+The calls are timed with HIP events around the call (median of ``--repeat`` after a warm-up) and ALTERNATE within a round; ``--rounds``
+rounds.  Reported per N: the spectral pass's time, its ratio to the ring pass, and the fp64 rate it achieves on the operations the
+projection needs -- 8 FMAs per (row, column, wavenumber): the four fields on cos and sin -- counted from the shapes; a rate, with the
+vector fp64 peak of the part (78.6 TFLOP/s) beside it.  ``--other NAME=PATH``: a liblec_hip.so built with another form of the kernel,
+loaded beside this one; its ``lec_rowspec_ring`` is timed in the same rounds and its records are compared with this library's (largest
+difference relative to the slot's scale).  One JSON line; ``--out`` writes it to a file."""
+import argparse
+import ctypes as C
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+FP64_VECTOR_PEAK_TFLOPS = 78.6
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=2)
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--repeat", type=int, default=5)
+    ap.add_argument("--grid", type=int, nargs=3, default=[37, 721, 1440], metavar=("NL", "NY", "NX"))
+    ap.add_argument("--n", type=int, nargs="+", default=[8, 20, 64])
+    ap.add_argument("--other", nargs="*", default=[], metavar="NAME=PATH")
+    ap.add_argument("--no-compute", action="store_true", help="time the passes only, not the whole compute calls")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    import torch
+    from lorenzcycletoolkit_amd import _lib, tables
+    from lorenzcycletoolkit_amd.engine import LECEngine
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_spectrum.py needs a GPU: a time is measured on the device or not at all")
+    lib = _lib.load()
+    dev = torch.device("cuda:0")
+    nl, ny, nx = a.grid
+    nt = a.steps
+    lat = np.linspace(-90.0, 90.0, ny)
+    lon = -180.0 + 360.0 / nx * np.arange(nx)
+    level = np.linspace(100.0, 100000.0, nl)
+    eng = LECEngine(lat, lon, level, device=dev)
+    box = (0, nx - 1, 1, ny - 2)                         # +-89.75 degrees on the 0.25-degree grid: the polar rows stay out
+    ring = eng.prepare_boxes([box], ring=True)
+    g = torch.Generator(device=dev).manual_seed(1)
+    shape = (nt, nl, ny, nx)
+    T = 250.0 + 10.0 * torch.randn(shape, dtype=torch.float64, device=dev, generator=g)
+    U, V, W, P = (torch.randn(shape, dtype=torch.float64, device=dev, generator=g) for _ in range(4))
+    time_s = 21600.0 * np.arange(nt)
+    nyb = ny - 2
+    rows_per_step = nl * nyb
+
+    others = []
+    for item in a.other:
+        name, path = item.split("=", 1)
+        o = C.CDLL(path)
+        o.lec_rowspec_ring.restype, o.lec_rowspec_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecArgs)]
+        others.append((name, o))
+    twid = eng._up(tables.twiddle_table(nx))
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+
+    def spec_call(which, n, out):
+        sa = _lib.RowspecArgs(tair_d=ptr(T), u_d=ptr(U), v_d=ptr(V), omega_d=ptr(W), dtype=_lib.LEC_F64, nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0,
+                              t_count=nt, js=1, jn=ny - 2, n_wave=n, twid_d=ptr(twid), spec_d=ptr(out), stream=stream)
+        if which.lec_rowspec_ring(C.byref(sa)):
+            raise RuntimeError(f"lec_rowspec_ring failed: {lib.lec_last_error()}")
+
+    def timed(fn):
+        fn()
+        torch.cuda.synchronize()
+        ms = []
+        for _ in range(a.repeat):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ms.append(e0.elapsed_time(e1))
+        return float(np.median(ms))
+
+    out = {"grid": [nl, ny, nx], "steps": nt, "dtype": "float64", "box_rows": nyb, "rounds": a.rounds, "repeat": a.repeat,
+           "csrc_sha": _lib.source_digest(), "fp64_vector_peak_TFLOPs": FP64_VECTOR_PEAK_TFLOPS, "n": a.n}
+    rows = torch.empty((nt, nl, nyb, _lib.LEC_NSTAT), dtype=torch.float64, device=dev)
+    calls = [("ring_pass", lambda: eng.rowstats(T, U, V, W, P, ring, time_s=time_s, rows_out=rows))]
+    bufs = {}
+    for n in a.n:
+        bufs[n] = torch.empty((nt, nl, nyb, n, 8), dtype=torch.float64, device=dev)
+        calls.append((f"spec_N{n}", lambda n=n: spec_call(lib, n, bufs[n])))
+        for name, o in others:
+            calls.append((f"spec_N{n}_{name}", lambda n=n, o=o: spec_call(o, n, bufs[n])))
+    if not a.no_compute:
+        calls.append(("compute", lambda: eng.compute(T, U, V, W, P, ring, time_s=time_s)))
+        for n in a.n:
+            calls.append((f"compute_N{n}", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n)))
+    for _ in range(a.rounds):
+        for name, fn in calls:
+            out.setdefault(f"{name}_ms", []).append(round(timed(fn), 4))
+    med = lambda k: float(np.median(out[f"{k}_ms"]))
+    out["ring_pass_ms_per_step"] = round(med("ring_pass") / nt, 4)
+    for n in a.n:
+        flop = 2.0 * 8.0 * nt * rows_per_step * nx * n
+        for name in [""] + ["_" + x for x, _ in others]:
+            k = f"spec_N{n}{name}"
+            out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
+            out[f"{k}_over_ring_pass"] = round(med(k) / med("ring_pass"), 3)
+            out[f"{k}_fp64_TFLOPs"] = round(flop / (med(k) * 1e-3) / 1e12, 3)
+        if not a.no_compute:
+            out[f"compute_N{n}_over_compute"] = round(med(f"compute_N{n}") / med("compute"), 3)
+            out[f"compute_N{n}_ms_per_step"] = round(med(f"compute_N{n}") / nt, 4)
+    if not a.no_compute:
+        out["compute_ms_per_step"] = round(med("compute") / nt, 4)
+    # other forms give the same records (reordered fp64 sums: the last bits)
+    for n in a.n:
+        if not others:
+            break
+        mine = torch.empty_like(bufs[n])
+        spec_call(lib, n, mine)
+        scale = mine.abs().amax(dim=(0, 1, 2, 3))
+        for name, o in others:
+            spec_call(o, n, bufs[n])
+            torch.cuda.synchronize()
+            out[f"spec_N{n}_{name}_max_diff_of_scale"] = float(((bufs[n] - mine).abs().amax(dim=(0, 1, 2, 3)) / scale).max())
+    line = json.dumps(out)
+    print(line)
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
