@@ -711,6 +711,50 @@ typedef struct lec_rowspec_args {
 } lec_rowspec_args;
 int lec_rowspec_ring(const lec_rowspec_args* args);
 
+/*
+ * -f --periodic --wavenumbers N --wavenumbers-generation: the ZONAL-WAVENUMBER SHARES of the generation covariance [Q'T'] of every ring
+ * row (an additive call: no struct, export or kernel result of ABI 11 changes; lec_rowspecq.hip is a code object of its own).
+ *
+ * Q itself never reaches a row record -- lec_rowstats_ring keeps its row statistics [Q] and [Q'T'] only -- so this call evaluates the
+ * diabatic-heating residual at every point of a row and projects it, beside T, onto the wavenumbers:
+ *   qspec_d [t_count][nl][jn - js + 1][n_wave]:  C_n(Q, T) = w_n Re(Q^_n conj(T^_n)), n = 1 .. n_wave  (a^_n, w_n as above), so that
+ *   [Q'T'] = sum_{n = 1}^{nx / 2} C_n(Q, T) = slot LEC_S_QT of the row's record.
+ * Ge is linear in that slot, so row records that carry C_n(Q, T) there give Ge(n) in the stage-2 batch of lec_rowspec_ring's shares.
+ *   - Q = cp (dT/dt + u dT/dx + v dT/dy - S w), the Q of lec_rowstats_ring: d/dlon the centred three-point difference at every column
+ *     (column 0 reads column nx - 1 and the reverse; inv_hdeg = boxtab[2] of the ring box, lattab_d[j][3] = 1 / dx_j); d/dlat from
+ *     lattab_d[j][0..2], the ring box's own table: one-sided at the band's first and last row, and no row outside js .. jn is read;
+ *     S from levtab_d, one-sided at the top and bottom level; dT/dt = tcoef_d[t][0] T[t-1] + tcoef_d[t][1] T[t] + tcoef_d[t][2] T[t+1]
+ *     over the CUBE's time axis (tcoef_d has nt rows; steps outside [t_begin, t_begin + t_count) are read as neighbours).  A neighbour
+ *     that does not exist is the row itself with coefficient 0.  A dT/dt cube is not supported.
+ *   - Cubes, twid_d, the integer twiddle index, fp64 accumulation and the removal of T's column 0: as lec_rowspec_ring.  The column
+ *     classes of a wavenumber are summed in a fixed order: a row's result depends on (nx, n_wave) and on nothing else.
+ *   - NaN: qspec_d of a row is NaN for every n exactly where LEC_S_QT of lec_rowstats_ring's record of that row is NaN.
+ * Validation.  Every refusal is LEC_ERR_ARG naming the field, made before any HIP call, never clamped: null tair_d / u_d / v_d /
+ * omega_d / twid_d / lattab_d / levtab_d / tcoef_d / qspec_d, dtype, nt < 2, nx < 3, t_begin / t_count outside the cube, js / jn outside
+ * 0 <= js < jn < ny (a band needs two rows for d/dlat; lec_rowstats_ring refuses a one-row box likewise), n_wave < 1 or n_wave > nx / 2,
+ * twid_d / qspec_d not 16-byte aligned, the tables not 8-byte aligned, a cube not aligned to its element.  n_wave > LEC_MAX_WAVENUMBERS,
+ * or more than 2^31 - 1 rows: LEC_ERR_UNSUPPORTED.
+ */
+typedef struct lec_rowspec_q_args {
+    const void* tair_d;
+    const void* u_d;
+    const void* v_d;
+    const void* omega_d;
+    int32_t dtype;              /* enum lec_dtype (LEC_F64 or LEC_F32), common to the four cubes */
+    int32_t nt, nl, ny, nx;     /* cube dimensions; the nx columns are the ring */
+    int32_t t_begin, t_count;   /* process time steps [t_begin, t_begin + t_count) */
+    int32_t js, jn;             /* the latitude band (inclusive grid rows), js < jn */
+    int32_t n_wave;             /* wavenumbers 1 .. n_wave; 1 <= n_wave <= min(nx / 2, LEC_MAX_WAVENUMBERS) */
+    const double* twid_d;       /* [nx][2] cos, sin of 2 pi m / nx; 16-byte aligned */
+    const double* lattab_d;     /* [jn - js + 1][4]: d/dlat a, b, c; 1 / dx_j (the ring box's lattab) */
+    const double* levtab_d;     /* [nl][3]: the static-stability coefficients of lec_rowstats */
+    const double* tcoef_d;      /* [nt][3]: np.gradient coefficients over the cube's time axis */
+    double inv_hdeg;            /* boxtab[2] of the ring box: 1 / (longitude step in degrees) */
+    double* qspec_d;            /* out [t_count][nl][jn - js + 1][n_wave]; 16-byte aligned */
+    void* stream;
+} lec_rowspec_q_args;
+int lec_rowspec_q_ring(const lec_rowspec_q_args* args);
+
 int lec_ingest(const lec_ingest_args* args);
 /*
  * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with

@@ -26,7 +26,8 @@ crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file na
 
 -f --periodic --wavenumbers N: also the shares of the zonal wavenumbers 1 .. N in the eddy terms Ae, Ke, Ca, Ce and Ck
 (``lec_rowspec_ring``; exact by the discrete Parseval identity on the closed axis), written to results_wavenumbers/<term>_n.csv; every
-other output file is unchanged.
+other output file is unchanged.  With --wavenumbers-generation also Ge (``lec_rowspec_q_ring``: Q at every point of a row, projected
+beside T), written to results_wavenumbers/Ge_n.csv.
 
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
@@ -93,6 +94,9 @@ def create_arg_parser():
                         "results_wavenumbers/Ae_n.csv ... Ck_n.csv: one row per time step, columns 1 .. N and 'rest' (the total minus the N "
                         "shares), in the units of the results CSV.  The split is exact (discrete Parseval on the closed axis); every other "
                         "output file is unchanged.  One GPU, data prepared on the host (--ingest auto resolves to host)")
+    parser.add_argument("--wavenumbers-generation", action="store_true", default=argparse.SUPPRESS, help="with --wavenumbers N: also split the "
+                        "generation term Ge and write results_wavenumbers/Ge_n.csv, in the form of its five siblings.  The diabatic-heating "
+                        "residual Q is evaluated at every point of the ring's rows once more and projected beside T (lec_rowspec_q_ring)")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -310,6 +314,8 @@ def refuse_periodic_options(args):
                          "meridian gets by itself, and --choose-periodic for the search of -c")
     n = getattr(args, "wavenumbers", None)
     if n is None:
+        if getattr(args, "wavenumbers_generation", False):
+            raise SystemExit("--wavenumbers-generation goes with --wavenumbers N: Ge(n) is one more of the zonal-wavenumber spectra")
         return
     from lorenzcycletoolkit_amd._lib import LEC_MAX_WAVENUMBERS
     if not (args.fixed and args.periodic):

@@ -18,3 +18,6 @@ LEVEL_TERMS = ["Az", "Ae", "Kz", "Ke", "Ge", "Gz", "Cz", "Cz_1", "Cz_2", "Ca", "
 # Ce_1 = Rd / (p g) is a function of level alone, the same for every wavenumber: carried so that Ce's pieces stay together)
 SPECTRUM_TERMS = ["Ae", "Ke", "Ca", "Ce", "Ck"]
 SPECTRUM_LEVEL_TERMS = ["Ae", "Ke", "Ca", "Ca_1", "Ca_2", "Ce", "Ce_1", "Ce_2", "Ck", "Ck_1", "Ck_2", "Ck_3", "Ck_4", "Ck_5"]
+# the generation term whose spectrum is asked for separately (LECResult.spectrum_ge / spectrum_ge_levels: it costs a kernel of its own,
+# lec_rowspec_q_ring, because Q never reaches a row record); a scalar and a per-level table of the same name
+SPECTRUM_GENERATION_TERM = "Ge"

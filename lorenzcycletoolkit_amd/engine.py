@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
+from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
 
 
 @dataclass
@@ -32,6 +32,10 @@ class LECResult:
     spectrum: Optional[torch.Tensor] = None         # [t_count, 5, N] fp64: Ae, Ke, Ca, Ce, Ck of the wavenumbers 1 .. N
     spectrum_rest: Optional[torch.Tensor] = None    # [t_count, 5] fp64: the total minus the N shares
     spectrum_levels: Optional[torch.Tensor] = None  # [t_count, 14, N, nl] fp64
+    # compute(..., wavenumbers=N, spectrum_generation=True): the same for the generation term Ge (``rowspec_q``)
+    spectrum_ge: Optional[torch.Tensor] = None         # [t_count, N] fp64
+    spectrum_ge_rest: Optional[torch.Tensor] = None    # [t_count] fp64: Ge minus the N shares
+    spectrum_ge_levels: Optional[torch.Tensor] = None  # [t_count, N, nl] fp64
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -47,6 +51,7 @@ def _ptr(t: Optional[torch.Tensor]):
 
 
 _LEC_S_TT = 6      # enum lec_stat: the eight eddy covariances [T'T'] .. [w'v'] are slots 6 .. 13 of a row record
+_LEC_S_QT = 15     # ... and [Q'T'] is slot 15
 
 _KERNELS = {"auto": _lib.KERNEL_AUTO, "two_sweep": _lib.KERNEL_TWO_SWEEP, "row_sweep": _lib.KERNEL_ROW_SWEEP,
             "row_block": _lib.KERNEL_ROW_BLOCK, "box_tile": _lib.KERNEL_BOX_TILE, "box_plane": _lib.KERNEL_BOX_PLANE}
@@ -327,7 +332,7 @@ class LECEngine:
                 tuning: Optional[dict] = None, per_step_boxes: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
-                wavenumbers: Optional[int] = None) -> LECResult:
+                wavenumbers: Optional[int] = None, spectrum_generation: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -347,7 +352,17 @@ class LECEngine:
         ``spectrum_rest`` and ``spectrum_levels``, the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce and Ck (``rowspec``
         and stage 2 on row records that carry one wavenumber's covariances).  Everything else of the result is, bit for bit, what
         the call without it returns.
+        ``spectrum_generation`` (with ``wavenumbers``, ``with_q`` and dT/dt from ``time_s`` / ``tcoef``, not a ``dTdt`` cube): also
+        ``spectrum_ge``, ``spectrum_ge_rest`` and ``spectrum_ge_levels``, the same shares of Ge (``rowspec_q``: Q is evaluated at every
+        point of a row once more and projected beside T).  It changes no bit of anything else.
         """
+        if spectrum_generation:
+            if wavenumbers is None:
+                raise ValueError("spectrum_generation: Ge(n) is part of the zonal-wavenumber spectra: give wavenumbers=N")
+            if not with_q:
+                raise ValueError("spectrum_generation needs with_q: Ge(n) is the spectrum of [Q'T']")
+            if dTdt is not None:
+                raise ValueError("spectrum_generation: a dTdt cube is not supported (lec_rowspec_q_ring forms dT/dt from the cube's time axis)")
         if wavenumbers is not None:
             self._check_wavenumbers(wavenumbers, boxes, int(tair.shape[-1]) if tair.dim() == 4 else 0)
             if merge_dropmask is not None or out is not None or steps is not None or tm is not None or tp is not None:
@@ -362,7 +377,8 @@ class LECEngine:
         res = self.reduce(rows, boxes, phi_scale=phi_scale, drop_any_time=drop_any_time, merge_dropmask=merge_dropmask,
                           keep_rows=keep_rows, out=out)
         if wavenumbers is not None:
-            self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time)
+            self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
+                           generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None)
         return res
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
@@ -415,13 +431,64 @@ class LECEngine:
                 timing.append((ev0, ev1))
         return spec
 
+    def rowspec_q(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, boxes: PreparedBoxes, wavenumbers: int, *,
+                  time_s=None, tcoef: Optional[torch.Tensor] = None, t_begin: int = 0, t_count: Optional[int] = None,
+                  out: Optional[torch.Tensor] = None, timing: Optional[list] = None) -> torch.Tensor:
+        """``lec_rowspec_q_ring``: [t_count, nl, nyb, N] fp64, the shares C_n(Q, T) of the zonal wavenumbers 1 .. N in [Q'T'] (slot 15 of
+        a row record) of every row of the ring's latitude band, for time steps [t_begin, t_begin + t_count) of the cubes.  Q is the ring
+        pass's, with dT/dt over the cube's time axis ``time_s`` (seconds, one entry per step of the cube; or ``tcoef``, its d/dt
+        coefficients already on the device); the tables are the prepared ring box's and the engine's own.  ``out``: a caller-owned
+        buffer; ``timing``: a list that receives one (start, end) pair of HIP events around the launch."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        self._check_wavenumbers(wavenumbers, boxes, nx)
+        n = int(wavenumbers)
+        if t_count is None:
+            t_count = nt - t_begin
+        if tcoef is None:
+            if time_s is None:
+                raise ValueError("rowspec_q needs time_s (seconds) or tcoef: Q holds dT/dt over the cube's time axis")
+            time_s = np.asarray(time_s, dtype=np.float64)
+            if time_s.size != nt:
+                raise ValueError("time_s must have one entry per time step of the cube")
+            if nt < 2:
+                raise ValueError("dT/dt by finite differences needs at least 2 time steps")
+            if self._tcoef is None or self._tcoef[0].shape != time_s.shape or not np.array_equal(self._tcoef[0], time_s):
+                self._tcoef = (time_s.copy(), self._up(tables.time_coefs(time_s)))
+            tcoef = self._tcoef[1]
+        elif tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
+            raise ValueError("tcoef must be a contiguous fp64 [nt, 3] tensor on the fields' device")
+        _, _, js, jn = boxes.boxes[0]
+        shape = (t_count, nl, jn - js + 1, n)
+        qspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
+        if qspec.shape != shape or qspec.dtype != torch.float64 or qspec.device != tair.device or not qspec.is_contiguous():
+            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the fields' device")
+        if self._twid is None:
+            self._twid = self._up(tables.twiddle_table(nx))
+        qa = _lib.RowspecQArgs(
+            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
+            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, twid_d=_ptr(self._twid),
+            lattab_d=_ptr(boxes.dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef), inv_hdeg=float(boxes.bt.boxtab[0, 2]),
+            qspec_d=_ptr(qspec), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
+        with torch.cuda.device(tair.device):
+            if timing is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _lib.check(self.lib.lec_rowspec_q_ring(C.byref(qa)), "lec_rowspec_q_ring")
+            if timing is not None:
+                ev1.record()
+                timing.append((ev0, ev1))
+        return qspec
+
     def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
-                  drop_any_time: Optional[bool]) -> None:
+                  drop_any_time: Optional[bool], generation: Optional[dict] = None) -> None:
         """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
         whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
         (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
         level), and ONE vertical half over all (n, step) applies _handle_nans: a share is NaN exactly where its total is, so the
-        any-time mask over the batch is the totals' own."""
+        any-time mask over the batch is the totals' own.  ``generation`` ({"time_s", "tcoef"} of the call): slot 15 of the assembled
+        records holds the wavenumber's share of [Q'T'] too (``rowspec_q``), which only Ge reads: Ge(n) and its table come out of the
+        same batch, and nothing else of it moves."""
         t_count, nl, nyb = (int(x) for x in rows.shape[:3])
         dev = rows.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -429,6 +496,7 @@ class LECEngine:
         tc = max(1, min(t_count, self.SPECTRUM_CHUNK_BYTES // (n * nl * nyb * _lib.LEC_NSTAT * 8)))
         asm = torch.empty((n, tc, nl, nyb, _lib.LEC_NSTAT), **f64)
         spec = torch.empty((tc, nl, nyb, n, 8), **f64)
+        qspec = torch.empty((tc, nl, nyb, n), **f64) if generation is not None else None
         part = torch.empty((n, tc, nl, _lib.LEC_NLEVRAW), **f64)
         for a in range(0, t_count, tc):
             b = min(a + tc, t_count)
@@ -437,6 +505,9 @@ class LECEngine:
             rec = asm[:, :c]
             rec.copy_(rows[a:b].unsqueeze(0))
             rec[..., _LEC_S_TT:_LEC_S_TT + 8] = sp.permute(3, 0, 1, 2, 4)
+            if generation is not None:
+                qs = self.rowspec_q(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=c, out=qspec[:c], **generation)
+                rec[..., _LEC_S_QT] = qs.permute(3, 0, 1, 2)
             if c == tc:
                 self.level_stage(rec.reshape(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, part.view(n * c, nl, _lib.LEC_NLEVRAW), phi_scale=phi_scale)
                 levraw[:, a:b] = part
@@ -450,6 +521,11 @@ class LECEngine:
         res.spectrum = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, si].permute(1, 2, 0).contiguous()
         res.spectrum_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, li].permute(1, 2, 0, 3).contiguous()
         res.spectrum_rest = res.scalars[:, si] - res.spectrum.sum(dim=2)
+        if generation is not None:
+            ge, gl = SCALAR_TERMS.index(SPECTRUM_GENERATION_TERM), LEVEL_TERMS.index(SPECTRUM_GENERATION_TERM)
+            res.spectrum_ge = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, ge].permute(1, 0).contiguous()
+            res.spectrum_ge_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, gl].permute(1, 0, 2).contiguous()
+            res.spectrum_ge_rest = res.scalars[:, ge] - res.spectrum_ge.sum(dim=1)
 
     def rowstats(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor,
                  geopt: Optional[torch.Tensor], boxes: Sequence[Sequence[int]], *,

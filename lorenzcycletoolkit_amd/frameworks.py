@@ -57,12 +57,15 @@ class BoxData:
 
     ``wavenumbers`` = N (``periodic`` only, one process, host-prepared data): ``spectrum`` [time, 5, N], ``spectrum_rest`` [time, 5] and
     ``spectrum_levels`` [time, 14, N, level] -- the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce, Ck (``lec_rowspec_ring``).
+    ``spectrum_generation`` (with ``wavenumbers``; no ``dTdt`` cube): also ``spectrum_ge`` [time, N], ``spectrum_ge_rest`` [time] and
+    ``spectrum_ge_levels`` [time, N, level], the same shares of Ge (``lec_rowspec_q_ring``).
     """
 
     def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, western_limit=None, eastern_limit=None,
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
-                 boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None):
+                 boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
+                 spectrum_generation: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -81,6 +84,13 @@ class BoxData:
             wavenumbers_check(self.wavenumbers, len(data.lon))
             if getattr(args, "shard", None) is not None or isinstance(data, _Streamed):
                 raise ValueError("wavenumbers: one process on host-prepared data (no time shards, no device ingest)")
+        self.spectrum_generation = bool(spectrum_generation)
+        self.spectrum_ge = self.spectrum_ge_rest = self.spectrum_ge_levels = None
+        if self.spectrum_generation:
+            if wavenumbers is None:
+                raise ValueError("spectrum_generation: Ge(n) is part of the zonal-wavenumber spectra: give wavenumbers=N")
+            if dTdt is not None:
+                raise ValueError("spectrum_generation: a dTdt cube is not supported (lec_rowspec_q_ring forms dT/dt from the time axis)")
         self.args = args
         self.results_subdirectory = results_subdirectory
         self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
@@ -151,6 +161,10 @@ class BoxData:
             self.spectrum = self.result.spectrum.cpu().numpy()
             self.spectrum_rest = self.result.spectrum_rest.cpu().numpy()
             self.spectrum_levels = self.result.spectrum_levels.cpu().numpy()
+        if self.result.spectrum_ge is not None:
+            self.spectrum_ge = self.result.spectrum_ge.cpu().numpy()
+            self.spectrum_ge_rest = self.result.spectrum_ge_rest.cpu().numpy()
+            self.spectrum_ge_levels = self.result.spectrum_ge_levels.cpu().numpy()
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -190,7 +204,8 @@ class BoxData:
                                    time_s=data.time_s[h0:h1] if dTdt is None else None, dTdt=dTdt_dev, phi_scale=phi_scale,
                                    t_begin=t0 - h0, t_count=t1 - t0, per_step_boxes=self.per_step_boxes,
                                    drop_any_time=not self.per_step_boxes, merge_dropmask=merge, out=out,
-                                   **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}))
+                                   **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
+                                   **({"spectrum_generation": True} if self.spectrum_generation else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -243,15 +258,19 @@ def wavenumbers_check(n: int, nx: int) -> None:
 
 
 def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
-    """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck: one row per time step -- the time labels and number formatting of
-    the per-level tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the units of the results CSV."""
-    from .constants import SPECTRUM_TERMS
+    """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck -- and Ge when its spectrum was asked for --: one row per time step -- the
+    time labels and number formatting of the per-level tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the
+    units of the results CSV."""
+    from .constants import SPECTRUM_GENERATION_TERM, SPECTRUM_TERMS
     os.makedirs(directory, exist_ok=True)
     n = box_obj.spectrum.shape[2]
     header = ",".join([str(time_name)] + [str(k) for k in range(1, n + 1)] + ["rest"]) + "\n"
     labels = box_obj.row_labels("fixed")
-    for i, term in enumerate(SPECTRUM_TERMS):
-        table = np.concatenate([box_obj.spectrum[:, i, :], box_obj.spectrum_rest[:, i: i + 1]], axis=1)
+    files = [(term, box_obj.spectrum[:, i, :], box_obj.spectrum_rest[:, i: i + 1]) for i, term in enumerate(SPECTRUM_TERMS)]
+    if box_obj.spectrum_ge is not None:
+        files.append((SPECTRUM_GENERATION_TERM, box_obj.spectrum_ge, box_obj.spectrum_ge_rest[:, None]))
+    for term, shares, rest in files:
+        table = np.concatenate([shares, rest], axis=1)
         path = os.path.join(directory, f"{term}_n.csv")
         with open(path, "wb") as f:
             f.write(header.encode("utf-8"))
@@ -452,11 +471,15 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         if not periodic:
             raise ValueError("--wavenumbers goes with -f --periodic")
         wavenumbers_check(int(wavenumbers), len(data.lon))
+    generation = bool(getattr(args, "wavenumbers_generation", False))
+    if generation and wavenumbers is None:
+        raise ValueError("--wavenumbers-generation goes with --wavenumbers N")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
-                          results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers)
+                          results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
+                          spectrum_generation=generation)
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -479,6 +502,9 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         write_spectrum_csvs(box_obj, spectrum_directory, time_name)
         app_logger.info(f"--wavenumbers: Ae, Ke, Ca, Ce, Ck split into the zonal wavenumbers 1 .. {int(wavenumbers)} of the ring's "
                         f"{len(data.lon)} longitudes (lec_rowspec_kernel: N = {int(wavenumbers)}, nx = {len(data.lon)}); written to {spectrum_directory}")
+        if generation:
+            app_logger.info(f"--wavenumbers-generation: Ge split likewise, Q evaluated at every point of the ring's rows "
+                            f"(lec_rowspec_q_kernel: N = {int(wavenumbers)}, nx = {len(data.lon)}); written to {spectrum_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]

@@ -3,14 +3,17 @@
 ``lec_rowstats_ring`` on the same cubes -- a global 37 x 721 x 1440 fp64 grid, box +-89.75 degrees over all longitudes -- and
 ``LECEngine.compute(..., wavenumbers=N)`` next to the same ``compute`` without it, for N = 8, 20 and 64.
 
-    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--other NAME=PATH ...] [--out FILE]
+    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--generation] [--other NAME=PATH ...] [--out FILE]
 
 The calls are timed with HIP events around the call (median of ``--repeat`` after a warm-up) and ALTERNATE within a round; ``--rounds``
 rounds.  Reported per N: the spectral pass's time, its ratio to the ring pass, and the fp64 rate it achieves on the operations the
 projection needs -- 8 FMAs per (row, column, wavenumber): the four fields on cos and sin -- counted from the shapes; a rate, with the
 vector fp64 peak of the part (78.6 TFLOP/s) beside it.  ``--other NAME=PATH``: a liblec_hip.so built with another form of the kernel,
 loaded beside this one; its ``lec_rowspec_ring`` is timed in the same rounds and its records are compared with this library's (largest
-difference relative to the slot's scale).  One JSON line; ``--out`` writes it to a file."""
+difference relative to the slot's scale).  ``--generation``: ``lec_rowspec_q_ring`` (the shares of [Q'T'], for Ge(n)) is timed in the same
+rounds, of this library and of every ``--other`` one, as ``specq_N<n>``: its ratio to ``lec_rowspec_ring`` at the same N is the yardstick
+(half the FMAs per twiddle -- 4 per (row, column, wavenumber) -- and 2.5 times the rows loaded), and ``compute`` with
+``spectrum_generation=True`` next to ``compute`` with the wavenumbers alone.  One JSON line; ``--out`` writes it to a file."""
 import argparse
 import ctypes as C
 import json
@@ -32,6 +35,7 @@ def main():
     ap.add_argument("--grid", type=int, nargs=3, default=[37, 721, 1440], metavar=("NL", "NY", "NX"))
     ap.add_argument("--n", type=int, nargs="+", default=[8, 20, 64])
     ap.add_argument("--other", nargs="*", default=[], metavar="NAME=PATH")
+    ap.add_argument("--generation", action="store_true", help="also time lec_rowspec_q_ring (the shares of [Q'T'])")
     ap.add_argument("--no-compute", action="store_true", help="time the passes only, not the whole compute calls")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -63,6 +67,8 @@ def main():
         name, path = item.split("=", 1)
         o = C.CDLL(path)
         o.lec_rowspec_ring.restype, o.lec_rowspec_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecArgs)]
+        if a.generation:
+            o.lec_rowspec_q_ring.restype, o.lec_rowspec_q_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecQArgs)]
         others.append((name, o))
     twid = eng._up(tables.twiddle_table(nx))
     ptr = lambda t: C.c_void_p(t.data_ptr())
@@ -73,6 +79,15 @@ def main():
                               t_count=nt, js=1, jn=ny - 2, n_wave=n, twid_d=ptr(twid), spec_d=ptr(out), stream=stream)
         if which.lec_rowspec_ring(C.byref(sa)):
             raise RuntimeError(f"lec_rowspec_ring failed: {lib.lec_last_error()}")
+
+    tcoef = eng.time_coefs_device(time_s) if nt > 1 else None
+
+    def specq_call(which, n, out):
+        qa = _lib.RowspecQArgs(tair_d=ptr(T), u_d=ptr(U), v_d=ptr(V), omega_d=ptr(W), dtype=_lib.LEC_F64, nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0,
+                               t_count=nt, js=1, jn=ny - 2, n_wave=n, twid_d=ptr(twid), lattab_d=ptr(ring.dev["lattab"]), levtab_d=ptr(eng._levtab),
+                               tcoef_d=ptr(tcoef), inv_hdeg=float(ring.bt.boxtab[0, 2]), qspec_d=ptr(out), stream=stream)
+        if which.lec_rowspec_q_ring(C.byref(qa)):
+            raise RuntimeError(f"lec_rowspec_q_ring failed: {lib.lec_last_error()}")
 
     def timed(fn):
         fn()
@@ -91,16 +106,23 @@ def main():
            "csrc_sha": _lib.source_digest(), "fp64_vector_peak_TFLOPs": FP64_VECTOR_PEAK_TFLOPS, "n": a.n}
     rows = torch.empty((nt, nl, nyb, _lib.LEC_NSTAT), dtype=torch.float64, device=dev)
     calls = [("ring_pass", lambda: eng.rowstats(T, U, V, W, P, ring, time_s=time_s, rows_out=rows))]
-    bufs = {}
+    bufs, qbufs = {}, {}
     for n in a.n:
         bufs[n] = torch.empty((nt, nl, nyb, n, 8), dtype=torch.float64, device=dev)
         calls.append((f"spec_N{n}", lambda n=n: spec_call(lib, n, bufs[n])))
         for name, o in others:
             calls.append((f"spec_N{n}_{name}", lambda n=n, o=o: spec_call(o, n, bufs[n])))
+        if a.generation:
+            qbufs[n] = torch.empty((nt, nl, nyb, n), dtype=torch.float64, device=dev)
+            calls.append((f"specq_N{n}", lambda n=n: specq_call(lib, n, qbufs[n])))
+            for name, o in others:
+                calls.append((f"specq_N{n}_{name}", lambda n=n, o=o: specq_call(o, n, qbufs[n])))
     if not a.no_compute:
         calls.append(("compute", lambda: eng.compute(T, U, V, W, P, ring, time_s=time_s)))
         for n in a.n:
             calls.append((f"compute_N{n}", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n)))
+            if a.generation:
+                calls.append((f"compute_N{n}_ge", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n, spectrum_generation=True)))
     for _ in range(a.rounds):
         for name, fn in calls:
             out.setdefault(f"{name}_ms", []).append(round(timed(fn), 4))
@@ -113,6 +135,15 @@ def main():
             out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
             out[f"{k}_over_ring_pass"] = round(med(k) / med("ring_pass"), 3)
             out[f"{k}_fp64_TFLOPs"] = round(flop / (med(k) * 1e-3) / 1e12, 3)
+            if a.generation:
+                k = f"specq_N{n}{name}"
+                out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
+                out[f"{k}_over_ring_pass"] = round(med(k) / med("ring_pass"), 3)
+                out[f"{k}_over_spec_N{n}"] = round(med(k) / med(f"spec_N{n}"), 3)
+                out[f"{k}_fp64_TFLOPs"] = round(0.5 * flop / (med(k) * 1e-3) / 1e12, 3)
+        if a.generation and not a.no_compute:
+            out[f"compute_N{n}_ge_over_compute_N{n}"] = round(med(f"compute_N{n}_ge") / med(f"compute_N{n}"), 3)
+            out[f"compute_N{n}_ge_ms_per_step"] = round(med(f"compute_N{n}_ge") / nt, 4)
         if not a.no_compute:
             out[f"compute_N{n}_over_compute"] = round(med(f"compute_N{n}") / med("compute"), 3)
             out[f"compute_N{n}_ms_per_step"] = round(med(f"compute_N{n}") / nt, 4)
@@ -129,6 +160,13 @@ def main():
             spec_call(o, n, bufs[n])
             torch.cuda.synchronize()
             out[f"spec_N{n}_{name}_max_diff_of_scale"] = float(((bufs[n] - mine).abs().amax(dim=(0, 1, 2, 3)) / scale).max())
+        if a.generation:
+            mine = torch.empty_like(qbufs[n])
+            specq_call(lib, n, mine)
+            for name, o in others:
+                specq_call(o, n, qbufs[n])
+                torch.cuda.synchronize()
+                out[f"specq_N{n}_{name}_max_diff_of_scale"] = float((qbufs[n] - mine).abs().max() / mine.abs().max())
     line = json.dumps(out)
     print(line)
     if a.out:
