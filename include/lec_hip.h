@@ -91,7 +91,12 @@ enum lec_order {
     LEC_ORDER_AUTO = 0,
     LEC_ORDER_MEMORY = 1,      /* rows in memory order */
     LEC_ORDER_XCD_LAT = 2,     /* every XCD owns a latitude chunk, walked latitude-fastest per (time, level) */
-    LEC_ORDER_XCD_TILED = 7    /* tiles of tile_t time steps x tile_j latitudes at one level, levels next (all terms on one fixed box) */
+    LEC_ORDER_XCD_TILED = 7    /* one wave per row: every XCD owns a chunk of ceil(rows / 8) latitudes (the last one what is left), walked in
+                                  tiles of tile_t time steps x tile_j latitudes at one level, levels next (all terms on one fixed box).
+                                  The row-block kernel has one order of its own, which this field does not select: the XCDs own equal
+                                  chunks of whole blocks, walked in such tiles of near-equal extent (at most tile_t blocks in time, about
+                                  tile_j and at most tile_j + 1 in latitude); the blocks left over at the north end are dealt to the XCDs
+                                  by time group (csrc/lec_schedule.h) */
 };
 
 /* Kernel selection of lec_rowstats; all zero = library defaults. */

@@ -12,8 +12,8 @@
 // The stencils are linear, so which side comes from LDS only swaps coefficients (wave-uniform, hoisted
 // out of the loop); no per-lane selects.  In time only T(t+1) is needed (cross-time covariance, see
 // sweep_elems): the earlier wave of a time pair reads it from its mate, the later one loads it.  Waves whose row lies outside the processed range still walk
-// a real neighbouring row (the halo time step of a shard, the next XCD's first latitude) so that their
-// block mates read correct data; they just do not store.
+// a real row (the halo time step of a shard; the box's last latitude again where its height is odd: the XCDs' latitude chunks are whole
+// cells, lec_schedule.h) so that their block mates read correct data; they just do not store.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,6 +22,7 @@
 #include "../../include/lec_hip.h"
 #include "lec_internal.h"
 #include "lec_rowcommon.h"
+#include "lec_schedule.h"
 #include "lec_sweep.h"
 
 using namespace lec;
@@ -35,7 +36,7 @@ __device__ __forceinline__ void lds_barrier() {
 }
 
 template <typename TIN, int VEC, bool UNIFORM, int BT, int BK, int BJ>
-__global__ void __launch_bounds__(64 * BT * BK * BJ, kMinWavesSingle) lec_rowblock_kernel(const RowParams p) {
+__global__ void __launch_bounds__(64 * BT * BK * BJ, kMinWavesSingle) lec_rowblock_kernel(const RowParams p, const BlockSchedule sch) {
     constexpr int NW = BT * BK * BJ;
     __shared__ double red[NW][kRound * red_stride(64)];
     __shared__ double tot[NW][24];
@@ -46,26 +47,16 @@ __global__ void __launch_bounds__(64 * BT * BK * BJ, kMinWavesSingle) lec_rowblo
     const int tid = threadIdx.x & 63;
     const int wt = wave % BT, wk = (wave / BT) % BK, wj = wave / (BT * BK);
 
-    // block -> cell: the XCD owns a latitude chunk; tiles of tgroup x jgroup cells at one level cell, level cells next
-    const int xcd = blockIdx.x & 7;
-    const int q = blockIdx.x >> 3;
-    const int tcells = (p.t_count + BT - 1) / BT, kcells = (p.nl + BK - 1) / BK, jcells = (p.jchunk + BJ - 1) / BJ;
-    const int tile = p.tgroup * p.jgroup;
-    int tile_id = q / tile;
-    const int within = q - tile_id * tile;
-    const int t_in = within % p.tgroup, j_in = within / p.tgroup;
-    const int kc = tile_id % kcells; tile_id /= kcells;
-    const int tgc = (tcells + p.tgroup - 1) / p.tgroup;
-    const int tc_ = (tile_id % tgc) * p.tgroup + t_in, jc_ = (tile_id / tgc) * p.jgroup + j_in;
-    if (tc_ >= tcells || jc_ >= jcells) return;              // whole workgroup
-    if (xcd * p.jchunk + jc_ * BJ >= p.nyb_max) return;       // whole workgroup
+    // block -> cell (lec_schedule.h): blockIdx & 7 labels the XCD; tiles of time x latitude cells at one level cell, level cells next
+    int tc_, kc, jc_;
+    if (!schedule_cell(sch, blockIdx.x, tc_, kc, jc_)) return;  // whole workgroup
 
-    const int tl0 = tc_ * BT + wt, k0 = kc * BK + wk, jl0 = jc_ * BJ + wj;
-    const bool store = tl0 < p.t_count && k0 < p.nl && jl0 < p.jchunk && xcd * p.jchunk + jl0 < p.nyb_max;
+    const int tl0 = tc_ * BT + wt, k0 = kc * BK + wk, jb0 = jc_ * BJ + wj;
+    const bool store = tl0 < p.t_count && k0 < p.nl && jb0 < p.nyb_max;
     const int tl = min(tl0, p.t_count - 1);                   // record index (used only when store)
     const int t = min(p.t_begin + tl0, p.nt - 1);             // data row: the real neighbour when it exists
     const int k = min(k0, p.nl - 1);
-    const int jb = min(xcd * p.jchunk + jl0, p.nyb_max - 1);
+    const int jb = min(jb0, p.nyb_max - 1);
 
     const int iw = p.box[0], ie = p.box[1], js = p.box[2];
     const int nxb = ie - iw + 1, nyb = p.nyb_max;
@@ -202,17 +193,10 @@ template <typename TIN, int VEC, bool UNIFORM>
 int launch_block(RowParams& p, int bt, int bk, int bj, hipStream_t st) {
     const int nvec = (p.nxb_max + VEC - 1) / VEC + (VEC > 1 ? 1 : 0);
     p.ntrips = (nvec + 63) / 64;
-    p.jchunk = (p.nyb_max + 7) / 8;
-    const long long tcells = (p.t_count + bt - 1) / bt, kcells = (p.nl + bk - 1) / bk, jcells = (p.jchunk + bj - 1) / bj;
-    if (p.tgroup > tcells) p.tgroup = (int)tcells;
-    if (p.jgroup > jcells) p.jgroup = (int)jcells;
-    if (p.tgroup < 1) p.tgroup = 1;
-    if (p.jgroup < 1) p.jgroup = 1;
-    const long long tgc = (tcells + p.tgroup - 1) / p.tgroup, jgc = (jcells + p.jgroup - 1) / p.jgroup;
-    const long long nblocks = 8LL * jgc * tgc * kcells * p.tgroup * p.jgroup;
-    if (nblocks > 0x7fffffffLL) return LEC_ERR_UNSUPPORTED;
-    dim3 grid((unsigned)nblocks), block(64 * bt * bk * bj);
-#define LEC_BLK(A, B, C) hipLaunchKernelGGL((lec_rowblock_kernel<TIN, VEC, UNIFORM, A, B, C>), grid, block, 0, st, p)
+    const BlockSchedule sch = make_schedule(p.nyb_max, p.t_count, p.nl, bt, bk, bj, p.tgroup, p.jgroup);
+    if (sch.blocks == 0) return LEC_ERR_UNSUPPORTED;
+    dim3 grid((unsigned)sch.blocks), block(64 * bt * bk * bj);
+#define LEC_BLK(A, B, C) hipLaunchKernelGGL((lec_rowblock_kernel<TIN, VEC, UNIFORM, A, B, C>), grid, block, 0, st, p, sch)
     const int code = bt * 100 + bk * 10 + bj;
     switch (code) {
         case 222: LEC_BLK(2, 2, 2); break;
@@ -231,7 +215,7 @@ int launch_block(RowParams& p, int bt, int bk, int bj, hipStream_t st) {
 }  // namespace
 
 // all terms, dT/dt from the cube, ONE fixed box, Phi present, fp64 or fp32 storage; p.tgroup / p.jgroup are the
-// tile extents in cells (blocks of bt time steps / bj latitudes)
+// largest tile extents in cells (blocks of bt time steps / bj latitudes; < 1 = the default, lec_schedule.h)
 int lec_launch_rowblock(lec::RowParams p, int dtype, bool aligned, bool aligned8, bool uniform, int bt, int bk, int bj, hipStream_t st) {
     if (dtype == LEC_F64) {
         if (aligned) return uniform ? launch_block<double, 2, true>(p, bt, bk, bj, st) : launch_block<double, 2, false>(p, bt, bk, bj, st);

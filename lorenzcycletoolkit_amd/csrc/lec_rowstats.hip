@@ -428,7 +428,10 @@ static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d, bool
     // Workgroup -> row order (speed only; defaults from the A/B runs on MI355X, profiles/r01_notes.md).  Workgroups are dealt
     // to the 8 XCDs round-robin, so blockIdx % 8 labels the XCD: XCD_LAT gives every XCD a contiguous latitude chunk, walked
     // latitude-fastest per (time, level); XCD_TILED (all terms on one fixed box) walks tiles of tile_t time steps x tile_j
-    // latitudes at one level, levels next; MEMORY is memory order.
+    // latitudes at one level, levels next; MEMORY is memory order.  These three are the one-wave-per-row kernel's, whose chunks are
+    // ceil(nyb_max / 8) rows each (the last XCD's is shorter).  The row-block kernel has one order of its own (lec_schedule.h): the
+    // XCDs own equal chunks of whole blocks, walked in tiles of at most tile_t x tile_j blocks of near-equal extent, and the blocks
+    // left over at the north end are dealt to the XCDs by time group.
     const bool two_sweep = kernel == LEC_KERNEL_TWO_SWEEP;
     p.order = (fixed_time_stencil && a->t_count >= 2 && !two_sweep) ? 7 : 2;
     if (tu.order == LEC_ORDER_MEMORY) p.order = 0;
@@ -471,7 +474,7 @@ static int rowstats_impl(const lec_rowstats_args* a, const int32_t* step_d, bool
         const int mode = fixed_time_stencil ? 3 : wq;
         if (kernel == LEC_KERNEL_ROW_BLOCK) {
             RowParams pb = p;
-            pb.order = 8; pb.tgroup = tu.tile_t ? tu.tile_t : 2; pb.jgroup = tu.tile_j ? tu.tile_j : 4;      // tile: 2 x 4 blocks at one level, levels next
+            pb.order = 8; pb.tgroup = tu.tile_t; pb.jgroup = tu.tile_j;      // the largest tile, in blocks; 0 = 2 x 4 (lec_schedule.h)
             rc = lec_launch_rowblock(pb, a->dtype, aligned, aligned8, uni, bt, bk, bj, st);
         } else {
             rc = ring ? lec_launch_rowsweep_ring(p, a->dtype, aligned, aligned8, uni, mode, tu.f32_vec, st)
