@@ -760,6 +760,43 @@ typedef struct lec_rowspec_q_args {
 } lec_rowspec_q_args;
 int lec_rowspec_q_ring(const lec_rowspec_q_args* args);
 
+/*
+ * Stage 2 of the spectra without assembled records: the level x latitude half of lec_reduce for all n_wave wavenumbers of a chunk of
+ * time steps (an additive call: no struct, export or kernel result of ABI 11 changes; lec_level_spec.hip is a code object of its own).
+ *
+ * For every wavenumber n, time step t and level k the call writes the LEC_NLEVRAW numbers that lec_reduce with LEC_STAGE_LEVELS writes for
+ * the row records  rows_d[t][k][j]  with slots LEC_S_TT .. LEC_S_WV (6 .. 13) replaced by  spec_d[t][k][j][n][0..7]  and, when qspec_d is
+ * given, slot LEC_S_QT (15) by  qspec_d[t][k][j][n]  -- bit for bit: the kernels are lec_reduce's two level kernels (one for bands of at
+ * most 64 rows, one for taller bands) on the same source lines, and the only difference is where those nine slots of a record come from.
+ * That is the definition of X(n); N copies of the row records are never formed.
+ *   - Nothing else of a record is replaced: zonal means, edge values, the triple products 16 .. 21 and [w'Phi'] stay the ring pass's.
+ *   - BAz's bottom-top term is repaired per latitude from the records of OTHER levels; their LEC_S_WT is read from spec_d at that level.
+ *   - The area means read no replaced slot: they are formed once per (t, k) into am_d, not once per n.
+ *   - box_d / lattab2_d / levtab2_d / phi_scale: of the ONE ring box, as lec_reduce takes them; nyb is the row count of the records.
+ *   - levraw_d: record (n, t, k) at  levraw_d + n * wave_stride + (t * nl + k) * LEC_NLEVRAW,  so a chunk of a streamed series writes into
+ *     the series' [n_wave][T][nl][LEC_NLEVRAW] buffer directly (wave_stride = T * nl * LEC_NLEVRAW, levraw_d at the chunk's first step).
+ *     lec_reduce with LEC_STAGE_VERTICAL over the n_wave * T records then gives the shares.
+ * Validation.  Every refusal names the field and is made before any HIP call.  LEC_ERR_ARG: null args, rows_d, spec_d, box_d, lattab2_d,
+ * levtab2_d, am_d or levraw_d (qspec_d may be NULL: slot 15 stays the ring pass's); rows_d / spec_d / lattab2_d not 16-byte aligned;
+ * n_wave < 1, t_count < 1, nl < 1, nyb < 2; wave_stride non-zero and smaller than dense.  LEC_ERR_UNSUPPORTED: n_wave >
+ * LEC_MAX_WAVENUMBERS, nl > LEC_MAX_LEVELS, n_wave * t_count * nl >= 2^26 (one 64-lane workgroup per (n, t, k); the caller chunks).
+ */
+typedef struct lec_level_spec_args {
+    const double* rows_d;       /* [t_count][nl][nyb][LEC_NSTAT], lec_rowstats_ring's records; 16-byte aligned */
+    const double* spec_d;       /* [t_count][nl][nyb][n_wave][8], lec_rowspec_ring's; 16-byte aligned */
+    const double* qspec_d;      /* [t_count][nl][nyb][n_wave], lec_rowspec_q_ring's, or NULL: slot 15 stays the ring pass's */
+    int32_t t_count, nl, nyb, n_wave;
+    const int32_t* box_d;       /* [1][4] */
+    const double* lattab2_d;    /* [nyb][8]; 16-byte aligned */
+    const double* levtab2_d;    /* [nl][4] */
+    double phi_scale;
+    double* am_d;               /* workspace [t_count][nl][8]: the area means */
+    double* levraw_d;           /* out: record (n, t, k) at levraw_d + n * wave_stride + (t * nl + k) * LEC_NLEVRAW */
+    int64_t wave_stride;        /* doubles between consecutive wavenumbers; 0 = dense (t_count * nl * LEC_NLEVRAW) */
+    void* stream;
+} lec_level_spec_args;
+int lec_level_spec_ring(const lec_level_spec_args* args);
+
 int lec_ingest(const lec_ingest_args* args);
 /*
  * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with

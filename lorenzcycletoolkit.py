@@ -27,7 +27,9 @@ crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file na
 -f --periodic --wavenumbers N: also the shares of the zonal wavenumbers 1 .. N in the eddy terms Ae, Ke, Ca, Ce and Ck
 (``lec_rowspec_ring``; exact by the discrete Parseval identity on the closed axis), written to results_wavenumbers/<term>_n.csv; every
 other output file is unchanged.  With --wavenumbers-generation also Ge (``lec_rowspec_q_ring``: Q at every point of a row, projected
-beside T), written to results_wavenumbers/Ge_n.csv.
+beside T), written to results_wavenumbers/Ge_n.csv.  With --wavenumbers-chunk M the file is streamed to the GPU, M time steps resident
+per pipeline slot, and the spectra are computed chunk by chunk (``lec_level_spec_ring``): the same files, for series that do not fit
+the GPU whole.
 
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
@@ -97,6 +99,10 @@ def create_arg_parser():
     parser.add_argument("--wavenumbers-generation", action="store_true", default=argparse.SUPPRESS, help="with --wavenumbers N: also split the "
                         "generation term Ge and write results_wavenumbers/Ge_n.csv, in the form of its five siblings.  The diabatic-heating "
                         "residual Q is evaluated at every point of the ring's rows once more and projected beside T (lec_rowspec_q_ring)")
+    parser.add_argument("--wavenumbers-chunk", type=int, metavar="N", default=argparse.SUPPRESS, help="with --wavenumbers: stream the file to the "
+                        "GPU with N time steps resident per pipeline slot and compute the spectra chunk by chunk (lec_level_spec_ring), instead "
+                        "of preparing the whole series on the host and holding it on the GPU: device memory then depends on N, not on the "
+                        "length of the series, and a deflated NetCDF-4 file is inflated on the GPU.  Same output files, byte for byte")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -313,7 +319,11 @@ def refuse_periodic_options(args):
         raise SystemExit("--periodic goes with -f/--fixed: the ring of a -t / -c run is the 0..360 longitude axis a track across the +-180 "
                          "meridian gets by itself, and --choose-periodic for the search of -c")
     n = getattr(args, "wavenumbers", None)
+    chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:
+        if chunk is not None:
+            raise SystemExit("--wavenumbers-chunk goes with --wavenumbers N: it streams the series of the zonal-wavenumber spectra; "
+                             "--device-ingest streams a plain -f / -t / -c run")
         if getattr(args, "wavenumbers_generation", False):
             raise SystemExit("--wavenumbers-generation goes with --wavenumbers N: Ge(n) is one more of the zonal-wavenumber spectra")
         return
@@ -326,9 +336,15 @@ def refuse_periodic_options(args):
         raise SystemExit(f"--wavenumbers must be <= {LEC_MAX_WAVENUMBERS} (LEC_MAX_WAVENUMBERS, include/lec_hip.h)")
     if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise SystemExit("--wavenumbers runs on one GPU: --gpus > 1 is not supported for the spectra (run the totals sharded, the spectra apart)")
+    if chunk is not None:
+        if chunk < 1:
+            raise SystemExit("--wavenumbers-chunk must be >= 1 time steps")
+        if args.ingest == "host":
+            raise SystemExit("--wavenumbers-chunk streams the file to the GPU, --ingest host prepares it on the host: give one of the two")
+        return
     if args.ingest == "device" or args.device_ingest:
         raise SystemExit("--wavenumbers prepares the data on the host: --ingest device / --device-ingest is not supported for the spectra "
-                         "(--ingest auto resolves to host)")
+                         "(--ingest auto resolves to host; --wavenumbers-chunk N streams the series and computes the spectra chunk by chunk)")
 
 
 def refuse_batch_chunk_options(args):
@@ -411,8 +427,12 @@ def main(argv=None):
             args = copy.copy(args)
             args.track, args.choose, args.trackfile, args.choose_track = True, False, written, written
         opened, auto_chose = None, False
-        if args.ingest == "device":
+        wave_chunk = getattr(args, "wavenumbers_chunk", None)
+        if args.ingest == "device" or wave_chunk is not None:
             args.device_ingest = True
+            if wave_chunk is not None:
+                app_logger.info(f"--wavenumbers-chunk {wave_chunk}: the file is streamed to the GPU, {wave_chunk} time steps per pipeline slot, "
+                                "and the spectra are computed chunk by chunk (lec_level_spec_ring: no assembled row records)")
         elif args.ingest == "auto" and getattr(args, "wavenumbers", None) is not None:
             app_logger.info("--wavenumbers: --ingest auto resolves to host (the spectra run on host-prepared cubes)")
         elif args.ingest == "auto" and not args.device_ingest:
@@ -429,7 +449,7 @@ def main(argv=None):
             refused = None
             try:
                 with refusals():
-                    data = prepare_streamed(args, "inputs/namelist", app_logger, raw=opened)
+                    data = prepare_streamed(args, "inputs/namelist", app_logger, chunk_steps=wave_chunk, raw=opened)
                 phases.mark("open_and_plan")
                 try:
                     analyse(data)

@@ -332,7 +332,7 @@ class LECEngine:
                 tuning: Optional[dict] = None, per_step_boxes: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
-                wavenumbers: Optional[int] = None, spectrum_generation: bool = False) -> LECResult:
+                wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -355,7 +355,12 @@ class LECEngine:
         ``spectrum_generation`` (with ``wavenumbers``, ``with_q`` and dT/dt from ``time_s`` / ``tcoef``, not a ``dTdt`` cube): also
         ``spectrum_ge``, ``spectrum_ge_rest`` and ``spectrum_ge_levels``, the same shares of Ge (``rowspec_q``: Q is evaluated at every
         point of a row once more and projected beside T).  It changes no bit of anything else.
+        ``spectrum_fused`` (with ``wavenumbers``): stage 2 of the spectra by ``spectrum_level_stage`` (``lec_level_spec_ring``), which
+        takes a wavenumber's shares straight from the spectral records instead of from N assembled copies of the row records.  The
+        same bits; the default stays the assembled form, the yardstick the fused kernels are tested against.
         """
+        if spectrum_fused and wavenumbers is None:
+            raise ValueError("spectrum_fused: a form of the zonal-wavenumber spectra: give wavenumbers=N")
         if spectrum_generation:
             if wavenumbers is None:
                 raise ValueError("spectrum_generation: Ge(n) is part of the zonal-wavenumber spectra: give wavenumbers=N")
@@ -378,11 +383,12 @@ class LECEngine:
                           keep_rows=keep_rows, out=out)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
-                           generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None)
+                           generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused)
         return res
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
-    SPECTRUM_CHUNK_BYTES = 256 << 20     # assembled row records (N wavenumbers x a chunk of time steps) resident at once
+    # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records
+    SPECTRUM_CHUNK_BYTES = 256 << 20
 
     @staticmethod
     def _check_wavenumbers(wavenumbers, boxes, nx: int) -> None:
@@ -480,19 +486,71 @@ class LECEngine:
                 timing.append((ev0, ev1))
         return qspec
 
+    def spectrum_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int) -> int:
+        """Time steps per spectral call of the fused form: the chunk's ``spec`` records ([tc, nl, nyb, N, 8] fp64) stay within
+        ``SPECTRUM_CHUNK_BYTES``."""
+        return max(1, min(int(t_count), self.SPECTRUM_CHUNK_BYTES // (nl * nyb * n * 64)))
+
+    def spectrum_level_stage(self, rows: torch.Tensor, spec: torch.Tensor, qspec: Optional[torch.Tensor], boxes, levraw_out: torch.Tensor, *,
+                             phi_scale: float = 1.0) -> None:
+        """``lec_level_spec_ring``: rows [t_count, nl, nyb, 32], ``spec`` [t_count, nl, nyb, N, 8] (``rowspec``) and ``qspec``
+        [t_count, nl, nyb, N] (``rowspec_q``) or None -> ``levraw_out`` [N, t_count, nl, 40]: what ``level_stage`` gives on the row
+        records that carry wavenumber n's shares in slots 6 .. 13 (and 15), for every n, without those records being assembled.
+        ``levraw_out`` may be a time slice of a larger [N, T, nl, 40] tensor (contiguous in its last two dimensions)."""
+        t_count, nl = int(rows.shape[0]), int(rows.shape[1])
+        boxes, bt, dev = self._stage2_input(rows, boxes)
+        if len(boxes) != 1 or not bt.ring:
+            raise ValueError("spectrum_level_stage: one ring box (prepare_boxes(..., ring=True))")
+        nyb = bt.nyb_max
+        if (spec.dim() != 5 or spec.shape[:3] != (t_count, nl, nyb) or spec.shape[4] != 8 or spec.dtype != torch.float64
+                or spec.device != rows.device or not spec.is_contiguous()):
+            raise ValueError("spec must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the rows' device")
+        n = int(spec.shape[3])
+        if qspec is not None and (qspec.shape != (t_count, nl, nyb, n) or qspec.dtype != torch.float64 or qspec.device != rows.device
+                                  or not qspec.is_contiguous()):
+            raise ValueError("qspec must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the rows' device")
+        step = nl * _lib.LEC_NLEVRAW
+        if (levraw_out.shape != (n, t_count, nl, _lib.LEC_NLEVRAW) or levraw_out.dtype != torch.float64 or levraw_out.device != rows.device
+                or tuple(levraw_out.stride()[2:]) != (_lib.LEC_NLEVRAW, 1) or (t_count > 1 and levraw_out.stride(1) != step)
+                or (n > 1 and levraw_out.stride(0) < t_count * step)):
+            raise ValueError("levraw_out must be an fp64 [N, t_count, nl, 40] tensor on the rows' device, contiguous in its last two "
+                             "dimensions (a time slice of an [N, T, nl, 40] tensor)")
+        am = self._workspace(t_count, nl, rows.device, am_only=True)
+        la = _lib.LevelSpecArgs(
+            rows_d=_ptr(rows), spec_d=_ptr(spec), qspec_d=_ptr(qspec), t_count=t_count, nl=nl, nyb=nyb, n_wave=n,
+            box_d=_ptr(dev["box"]), lattab2_d=_ptr(dev["lattab2"]), levtab2_d=_ptr(self._levtab2), phi_scale=float(phi_scale),
+            am_d=_ptr(am), levraw_d=_ptr(levraw_out), wave_stride=int(levraw_out.stride(0)) if n > 1 else 0,
+            stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+        with torch.cuda.device(rows.device):
+            _lib.check(self.lib.lec_level_spec_ring(C.byref(la)), "lec_level_spec_ring")
+
     def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
-                  drop_any_time: Optional[bool], generation: Optional[dict] = None) -> None:
+                  drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False) -> None:
         """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
         whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
         (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
         level), and ONE vertical half over all (n, step) applies _handle_nans: a share is NaN exactly where its total is, so the
         any-time mask over the batch is the totals' own.  ``generation`` ({"time_s", "tcoef"} of the call): slot 15 of the assembled
         records holds the wavenumber's share of [Q'T'] too (``rowspec_q``), which only Ge reads: Ge(n) and its table come out of the
-        same batch, and nothing else of it moves."""
+        same batch, and nothing else of it moves.  ``fused``: no assembled records -- ``spectrum_level_stage`` reads the ring
+        pass's records and the chunk's ``spec`` / ``qspec`` (the chunk is bounded by ``spec``), the same bits."""
         t_count, nl, nyb = (int(x) for x in rows.shape[:3])
         dev = rows.device
         f64 = dict(dtype=torch.float64, device=dev)
         levraw = torch.empty((n, t_count, nl, _lib.LEC_NLEVRAW), **f64)
+        if fused:
+            tc = self.spectrum_chunk_steps(t_count, nl, nyb, n)
+            spec = torch.empty((tc, nl, nyb, n, 8), **f64)
+            qspec = torch.empty((tc, nl, nyb, n), **f64) if generation is not None else None
+            for a in range(0, t_count, tc):
+                b = min(a + tc, t_count)
+                sp = self.rowspec(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=b - a, spec_out=spec[:b - a])
+                qs = None
+                if generation is not None:
+                    qs = self.rowspec_q(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=b - a, out=qspec[:b - a], **generation)
+                self.spectrum_level_stage(rows[a:b], sp, qs, boxes, levraw[:, a:b], phi_scale=phi_scale)
+            self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None)
+            return
         tc = max(1, min(t_count, self.SPECTRUM_CHUNK_BYTES // (n * nl * nyb * _lib.LEC_NSTAT * 8)))
         asm = torch.empty((n, tc, nl, nyb, _lib.LEC_NSTAT), **f64)
         spec = torch.empty((tc, nl, nyb, n, 8), **f64)
@@ -515,13 +573,20 @@ class LECEngine:
                 last = torch.empty((n * c, nl, _lib.LEC_NLEVRAW), **f64)
                 self.level_stage(rec.contiguous().view(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, last, phi_scale=phi_scale)
                 levraw[:, a:b] = last.view(n, c, nl, _lib.LEC_NLEVRAW)
+        self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None)
+
+    def _spectrum_shares(self, res: LECResult, levraw: torch.Tensor, boxes, drop_any_time: Optional[bool], generation: bool) -> None:
+        """The tail of the spectra: ``levraw`` [N, t_count, nl, 40] of all wavenumbers and steps -> ONE vertical half over the (n, step)
+        batch and ``res.spectrum*`` (``res`` holds the totals)."""
+        n, t_count, nl = (int(x) for x in levraw.shape[:3])
+        dev = levraw.device
         shares = self.vertical_stage(levraw.view(n * t_count, nl, _lib.LEC_NLEVRAW), boxes, drop_any_time=drop_any_time)
         si = torch.as_tensor([SCALAR_TERMS.index(x) for x in SPECTRUM_TERMS], device=dev)
         li = torch.as_tensor([LEVEL_TERMS.index(x) for x in SPECTRUM_LEVEL_TERMS], device=dev)
         res.spectrum = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, si].permute(1, 2, 0).contiguous()
         res.spectrum_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, li].permute(1, 2, 0, 3).contiguous()
         res.spectrum_rest = res.scalars[:, si] - res.spectrum.sum(dim=2)
-        if generation is not None:
+        if generation:
             ge, gl = SCALAR_TERMS.index(SPECTRUM_GENERATION_TERM), LEVEL_TERMS.index(SPECTRUM_GENERATION_TERM)
             res.spectrum_ge = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, ge].permute(1, 0).contiguous()
             res.spectrum_ge_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, gl].permute(1, 0, 2).contiguous()

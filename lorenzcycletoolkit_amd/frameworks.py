@@ -55,7 +55,7 @@ class BoxData:
     a full ring (evenly spaced, nx * dx = 360 degrees), and the western / eastern limits must select its first / last column: zonal
     means over the closed circle, Q's d/dlon centred across the seam, no east-west boundary flux (``lec_rowstats_ring``).
 
-    ``wavenumbers`` = N (``periodic`` only, one process, host-prepared data): ``spectrum`` [time, 5, N], ``spectrum_rest`` [time, 5] and
+    ``wavenumbers`` = N (``periodic`` only, one process; a ``StreamedDataset`` computes them chunk by chunk): ``spectrum`` [time, 5, N], ``spectrum_rest`` [time, 5] and
     ``spectrum_levels`` [time, 14, N, level] -- the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce, Ck (``lec_rowspec_ring``).
     ``spectrum_generation`` (with ``wavenumbers``; no ``dTdt`` cube): also ``spectrum_ge`` [time, N], ``spectrum_ge_rest`` [time] and
     ``spectrum_ge_levels`` [time, N, level], the same shares of Ge (``lec_rowspec_q_ring``).
@@ -82,8 +82,8 @@ class BoxData:
             if not self.periodic:
                 raise ValueError("wavenumbers: a zonal-wavenumber spectrum exists on a ring only (periodic=True)")
             wavenumbers_check(self.wavenumbers, len(data.lon))
-            if getattr(args, "shard", None) is not None or isinstance(data, _Streamed):
-                raise ValueError("wavenumbers: one process on host-prepared data (no time shards, no device ingest)")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("wavenumbers: one process (no time shards)")
         self.spectrum_generation = bool(spectrum_generation)
         self.spectrum_ge = self.spectrum_ge_rest = self.spectrum_ge_levels = None
         if self.spectrum_generation:
@@ -139,7 +139,9 @@ class BoxData:
                 self.result: LECResult = ingest.lec_streamed(data.raw, data.plan, variable_list_df, limits, per_step_boxes=boxes_limits is not None,
                                                              device=dev, chunk_steps=data.chunk_steps, stats=self.ingest_stats, inflate=data.inflate,
                                                              t_range=None if shard is None else (t0, t1), merge_dropmask=merge, out=out, keep_level=keep,
-                                                             ring=self.periodic)
+                                                             ring=self.periodic,
+                                                             **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
+                                                             **({"spectrum_generation": True} if self.spectrum_generation else {}))
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)

@@ -822,7 +822,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                  device="cuda:0", chunk_steps: Optional[int] = None, with_q: bool = True, stats: Optional[dict] = None,
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
                  slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
-                 ring: bool = False) -> LECResult:
+                 ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -844,9 +844,25 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     and computed, so N ranks move 1/N of the bytes each, over N host links; ``merge_dropmask`` / ``out``: see ``LECEngine.reduce``.
     ``ring``: the one fixed box covers the plan's whole longitude axis, a full ring (``LECEngine.prepare_boxes(ring=True)``): every
     chunk's stage 1 is ``lec_rowstats_ring``.
+    ``wavenumbers`` = N (with ``ring``) / ``spectrum_generation``: the result also carries the zonal-wavenumber spectra of
+    ``LECEngine.compute(..., wavenumbers=N)``, the same bits: every decoded sub-chunk goes through ``rowspec`` (and ``rowspec_q``) beside
+    the ring pass and ``spectrum_level_stage`` leaves 40 numbers per (n, step, level) in ONE buffer of the whole series; the spectral
+    records live for a sub-chunk (or a piece of one: ``LECEngine.SPECTRUM_CHUNK_BYTES``) only.  ``stats["spectrum_levraw_bytes"]`` /
+    ``stats["spectrum_buffer_bytes"]``: that buffer and the spectral records.
     """
     if ring and per_step_boxes:
         raise ValueError("ring: one fixed box (the moving framework's ring is the 0..360 axis)")
+    if spectrum_generation and wavenumbers is None:
+        raise ValueError("spectrum_generation: Ge(n) is part of the zonal-wavenumber spectra: give wavenumbers=N")
+    if wavenumbers is not None:
+        if per_step_boxes:
+            raise ValueError("wavenumbers: one fixed ring box, not per_step_boxes")
+        if not ring:
+            raise ValueError("wavenumbers: a zonal-wavenumber spectrum exists on a ring only: give ring=True")
+        if t_range is not None or merge_dropmask is not None or out is not None:
+            raise ValueError("wavenumbers: the whole series in one process (no t_range, merge_dropmask, out)")
+        if spectrum_generation and not with_q:
+            raise ValueError("spectrum_generation needs with_q: Ge(n) is the spectrum of [Q'T']")
     lib = _lib.load()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -860,6 +876,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         raise ValueError("boxes_limits: one box, or one per time step with per_step_boxes")
     if with_q and nt < 2:
         raise ValueError("dT/dt by finite differences needs at least 2 time steps")
+    if wavenumbers is not None:
+        engine._check_wavenumbers(wavenumbers, engine.prepare_boxes(boxes, ring=True), nx)
     t0, t1 = (0, nt) if t_range is None else (int(t_range[0]), int(t_range[1]))
     if not (0 <= t0 < t1 <= nt):
         raise ValueError("t_range outside the series")
@@ -967,6 +985,14 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         keep = {k: torch.empty((t1 - t0, ny, nx), dtype=out_dtype, device=dev) for k in ("u", "v", "geopt")}
     rows = torch.empty((dec_steps, nl, bt.nyb_max, _lib.LEC_NSTAT), dtype=torch.float64, device=dev)
     levraw = torch.empty((t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
+    if wavenumbers is not None:
+        # the spectral records of a sub-chunk, or of a piece of one (1.7 GB per 37 x 721 time step at N = 64), and the series' levraw
+        # of every wavenumber
+        nw = int(wavenumbers)
+        spec_steps = engine.spectrum_chunk_steps(dec_steps, nl, bt.nyb_max, nw)
+        spec = torch.empty((spec_steps, nl, bt.nyb_max, nw, 8), dtype=torch.float64, device=dev)
+        qspec = torch.empty((spec_steps, nl, bt.nyb_max, nw), dtype=torch.float64, device=dev) if spectrum_generation else None
+        levraw_spec = torch.empty((nw, t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
     time_s = plan.time_s
     phi_scale = ds.field_scale(variable_list_df, geo_role)
 
@@ -1035,10 +1061,21 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_count=n, with_q=with_q, rows_out=rows[:n],
                             per_step_boxes=per_step_boxes, **kw)
             engine.level_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
+            if wavenumbers is not None:         # (never packed: the cubes hold T's halo, and rowspec_q reads T[t - 1], T[t + 1] from them)
+                fields = (f["tair"], f["u"], f["v"], f["omega"])
+                for a in range(0, n, spec_steps):
+                    b = min(a + spec_steps, n)
+                    sp = engine.rowspec(*fields, fixed_box, nw, t_begin=kw["t_begin"] + a, t_count=b - a, spec_out=spec[:b - a])
+                    qs = None
+                    if spectrum_generation:
+                        qs = engine.rowspec_q(*fields, fixed_box, nw, tcoef=kw["tcoef"], t_begin=kw["t_begin"] + a, t_count=b - a, out=qspec[:b - a])
+                    engine.spectrum_level_stage(rows[a:b], sp, qs, fixed_box, levraw_spec[:, s0 - t0 + a: s0 - t0 + b], phi_scale=phi_scale)
         pipe.decoded(slot)
     t_loop = time.perf_counter()                # (every chunk enqueued)
     res = engine.vertical_stage(levraw, own_boxes if per_step_boxes else fixed_box, drop_any_time=not per_step_boxes,
                                 merge_dropmask=merge_dropmask, out=out)
+    if wavenumbers is not None:
+        engine._spectrum_shares(res, levraw_spec, fixed_box, True, spectrum_generation)
     on_device, reg_stats = pipe.finish()
     moved, host_s = pipe.moved, pipe.host_s
     if stats is not None:
@@ -1047,6 +1084,9 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             stats["level_slices"] = keep
         stats.update(inflate="device" if on_device else ("host" if any(hasattr(v.data, "chunk_streams") for v in rvars.values()) else "none"))
         stats.update(row_record_bytes=rows.numel() * 8, levraw_bytes=levraw.numel() * 8, device_buffer_bytes=int(mem_setup))
+        if wavenumbers is not None:
+            stats.update(spectrum_levraw_bytes=levraw_spec.numel() * 8,
+                         spectrum_buffer_bytes=(spec.numel() + (qspec.numel() if qspec is not None else 0)) * 8)
         torch.cuda.synchronize(dev)
         stats.update(seconds=dict(setup=t_setup - t_enter, chunk_loop_host=t_loop - t_setup, drain=time.perf_counter() - t_loop,
                                   registering=(spans.seconds if spans is not None else 0.0)))

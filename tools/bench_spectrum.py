@@ -3,7 +3,7 @@
 ``lec_rowstats_ring`` on the same cubes -- a global 37 x 721 x 1440 fp64 grid, box +-89.75 degrees over all longitudes -- and
 ``LECEngine.compute(..., wavenumbers=N)`` next to the same ``compute`` without it, for N = 8, 20 and 64.
 
-    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--generation] [--other NAME=PATH ...] [--out FILE]
+    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--generation] [--fused] [--other NAME=PATH ...] [--out FILE]
 
 The calls are timed with HIP events around the call (median of ``--repeat`` after a warm-up) and ALTERNATE within a round; ``--rounds``
 rounds.  Reported per N: the spectral pass's time, its ratio to the ring pass, and the fp64 rate it achieves on the operations the
@@ -13,7 +13,10 @@ loaded beside this one; its ``lec_rowspec_ring`` is timed in the same rounds and
 difference relative to the slot's scale).  ``--generation``: ``lec_rowspec_q_ring`` (the shares of [Q'T'], for Ge(n)) is timed in the same
 rounds, of this library and of every ``--other`` one, as ``specq_N<n>``: its ratio to ``lec_rowspec_ring`` at the same N is the yardstick
 (half the FMAs per twiddle -- 4 per (row, column, wavenumber) -- and 2.5 times the rows loaded), and ``compute`` with
-``spectrum_generation=True`` next to ``compute`` with the wavenumbers alone.  One JSON line; ``--out`` writes it to a file."""
+``spectrum_generation=True`` next to ``compute`` with the wavenumbers alone.  ``--fused``: ``compute(..., spectrum_fused=True)`` (stage 2 of
+the spectra by ``lec_level_spec_ring``, no assembled records) in the same rounds next to the assembled form: both medians, what the fused
+form saves per step, the spread of each between the rounds (largest minus smallest), and the bytes of the chunk's spectral records next
+to the bytes of the assembled records the other form would hold at the same chunk size.  One JSON line; ``--out`` writes it to a file."""
 import argparse
 import ctypes as C
 import json
@@ -36,6 +39,7 @@ def main():
     ap.add_argument("--n", type=int, nargs="+", default=[8, 20, 64])
     ap.add_argument("--other", nargs="*", default=[], metavar="NAME=PATH")
     ap.add_argument("--generation", action="store_true", help="also time lec_rowspec_q_ring (the shares of [Q'T'])")
+    ap.add_argument("--fused", action="store_true", help="also time compute(..., spectrum_fused=True) next to the assembled form")
     ap.add_argument("--no-compute", action="store_true", help="time the passes only, not the whole compute calls")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -121,8 +125,13 @@ def main():
         calls.append(("compute", lambda: eng.compute(T, U, V, W, P, ring, time_s=time_s)))
         for n in a.n:
             calls.append((f"compute_N{n}", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n)))
+            if a.fused:
+                calls.append((f"compute_N{n}_fused", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n, spectrum_fused=True)))
             if a.generation:
                 calls.append((f"compute_N{n}_ge", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n, spectrum_generation=True)))
+                if a.fused:
+                    calls.append((f"compute_N{n}_ge_fused", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n,
+                                                                                    spectrum_generation=True, spectrum_fused=True)))
     for _ in range(a.rounds):
         for name, fn in calls:
             out.setdefault(f"{name}_ms", []).append(round(timed(fn), 4))
@@ -144,6 +153,16 @@ def main():
         if a.generation and not a.no_compute:
             out[f"compute_N{n}_ge_over_compute_N{n}"] = round(med(f"compute_N{n}_ge") / med(f"compute_N{n}"), 3)
             out[f"compute_N{n}_ge_ms_per_step"] = round(med(f"compute_N{n}_ge") / nt, 4)
+        if a.fused and not a.no_compute:
+            spread = lambda k: round(max(out[f"{k}_ms"]) - min(out[f"{k}_ms"]), 4)
+            for k in [f"compute_N{n}"] + ([f"compute_N{n}_ge"] if a.generation else []):
+                out[f"{k}_fused_ms_per_step"] = round(med(k + "_fused") / nt, 4)
+                out[f"{k}_fused_saves_ms_per_step"] = round((med(k) - med(k + "_fused")) / nt, 4)
+                out[f"{k}_spread_ms"], out[f"{k}_fused_spread_ms"] = spread(k), spread(k + "_fused")
+            tc = eng.spectrum_chunk_steps(nt, nl, nyb, n)
+            out[f"N{n}_fused_chunk_steps"] = tc
+            out[f"N{n}_spectrum_buffer_bytes"] = tc * rows_per_step * n * (64 + (8 if a.generation else 0))
+            out[f"N{n}_assembled_bytes_at_that_chunk"] = tc * rows_per_step * n * _lib.LEC_NSTAT * 8
         if not a.no_compute:
             out[f"compute_N{n}_over_compute"] = round(med(f"compute_N{n}") / med("compute"), 3)
             out[f"compute_N{n}_ms_per_step"] = round(med(f"compute_N{n}") / nt, 4)
