@@ -761,6 +761,60 @@ typedef struct lec_rowspec_q_args {
 int lec_rowspec_q_ring(const lec_rowspec_q_args* args);
 
 /*
+ * -f --periodic --wavenumbers N --wavenumbers-interactions: the ZONAL-WAVENUMBER SHARES of the NON-LINEAR (eddy-eddy, triad) transfers of
+ * every ring row (an additive call: no struct, export or kernel result of ABI 11 changes; lec_rowspec_nl.hip is a code object of its own).
+ *
+ * Ae is linear in the row covariance [T'T'] and Ke in [u'u'] + [v'v'].  With A_x the eddy-eddy advective tendency of x, the change of
+ * [x'x'] / 2 by that advection is -[A_x' x'], so row records that carry -2 C_n(A_T, T) in slot LEC_S_TT give S(n) -- the available
+ * potential energy wavenumber n receives from all the other eddies -- in the Ae place of stage 2, and records that carry
+ * -2 C_n(A_u, u) / -2 C_n(A_v, v) in LEC_S_UU / LEC_S_VV give L(n), the same for kinetic energy, in the Ke place (Saltzman's S(n) and
+ * L(n); positive: wavenumber n gains).  The call evaluates the tendencies at every point of a row and projects them beside T, u and v.
+ *   For a row (t, k, j) of the band js .. jn, [x] = the row's zonal mean as lec_rowstats_ring wrote it into rows_d, x' = x - [x]:
+ *     D_lambda x (i) = cx_j (x[i+1] - x[i-1]), wrapped indices, cx_j = 0.5 inv_hdeg lattab_d[j][3] (the stencil of lec_rowspec_q_ring);
+ *     D_phi x = lattab_d[j][0] x[j-1] + lattab_d[j][1] x[j] + lattab_d[j][2] x[j+1], one-sided at the band's first and last row;
+ *     D_p x = ptab_d[k][0] x[k-1] + ptab_d[k][1] x[k] + ptab_d[k][2] x[k+1], the coefficients of np.gradient(edge_order=1) over the
+ *       levels in Pa, one-sided at the top and bottom level (tables.pressure_coefs; all 0 when nl = 1);
+ *     A_T = u' D_lambda T + v' (D_phi T - D_phi [T]) + w' (D_p T - D_p [T])
+ *     A_u = u' D_lambda u + v' (D_phi u - D_phi [u]) + w' (D_p u - D_p [u]) - m_j u' v'
+ *     A_v = u' D_lambda v + v' (D_phi v - D_phi [v]) + w' (D_p v - D_p [v]) + m_j u' u',     m_j = tan(lat_j) / Re = lattab_d[j][4].
+ *   A neighbour that does not exist is the row itself with coefficient 0: nothing outside the band, the levels or the requested steps
+ *   is read.  The zonal means of the neighbour rows are taken from the neighbours' records in rows_d, not summed again.  There is no
+ *   time stencil: a chunk of a streamed series needs no halo.
+ *   nlspec_d [t_count][nl][jn - js + 1][n_wave][8]:  slot 0 = -2 C_n(A_T, T), slot 1 = -2 C_n(A_u, u), slot 2 = -2 C_n(A_v, v), slots
+ *     3 .. 7 = 0 (C_n, w_n and the Nyquist weight as above): the layout of lec_rowspec_ring's spec_d, so lec_level_spec_ring takes it.
+ *   nltot_d [t_count][nl][jn - js + 1][8]:  the same three slots for the whole eddy covariance, summed in physical space:
+ *     -2 ((1 / nx) sum_i A_x(i) x'(i) - [A_x] [x']); slots 3 .. 7 = 0.  By Parseval the n_wave = nx / 2 shares sum to it.
+ *   - Cubes, twid_d, the integer twiddle index and fp64 accumulation: as lec_rowspec_ring.  The column classes of a wavenumber are
+ *     summed in a fixed order: a row's result depends on (nx, n_wave) and on nothing else.
+ *   - NaN: slots 0 .. 2 of a row are NaN for every n -- and in nltot_d -- exactly where any value the row's stencil reads is NaN: the
+ *     row itself, its existing j +- 1 / k +- 1 neighbours of T, u, v, or a record mean.  Slots 3 .. 7 are 0 even then.
+ * Validation.  Every refusal names the field, is made before any HIP call, never clamped.  LEC_ERR_ARG: null tair_d / u_d / v_d /
+ * omega_d / rows_d / twid_d / lattab_d / ptab_d / nlspec_d / nltot_d, dtype, nx < 3, nl < 1, ny < 2, t_begin / t_count outside the cube,
+ * js / jn outside 0 <= js < jn < ny, n_wave < 1 or n_wave > nx / 2, twid_d / rows_d / nlspec_d / nltot_d not 16-byte aligned, the tables
+ * not 8-byte aligned, a cube not aligned to its element.  LEC_ERR_UNSUPPORTED: n_wave > LEC_MAX_WAVENUMBERS, more than 2^31 - 1 rows.
+ */
+typedef struct lec_rowspec_nl_args {
+    const void* tair_d;
+    const void* u_d;
+    const void* v_d;
+    const void* omega_d;
+    int32_t dtype;              /* enum lec_dtype (LEC_F64 or LEC_F32), common to the four cubes */
+    int32_t nt, nl, ny, nx;     /* cube dimensions; the nx columns are the ring */
+    int32_t t_begin, t_count;   /* process time steps [t_begin, t_begin + t_count) */
+    int32_t js, jn;             /* the latitude band (inclusive grid rows), js < jn */
+    int32_t n_wave;             /* wavenumbers 1 .. n_wave; 1 <= n_wave <= min(nx / 2, LEC_MAX_WAVENUMBERS) */
+    const double* rows_d;       /* [t_count][nl][jn - js + 1][LEC_NSTAT], lec_rowstats_ring's records of the same steps and band; 16-byte aligned */
+    const double* twid_d;       /* [nx][2] cos, sin of 2 pi m / nx; 16-byte aligned */
+    const double* lattab_d;     /* [jn - js + 1][5]: d/dlat a, b, c; 1 / dx_j; tan(lat_j) / Re (tables.nl_lat_table) */
+    const double* ptab_d;       /* [nl][3]: np.gradient coefficients over the levels in Pa (tables.pressure_coefs) */
+    double inv_hdeg;            /* boxtab[2] of the ring box: 1 / (longitude step in degrees) */
+    double* nlspec_d;           /* out [t_count][nl][jn - js + 1][n_wave][8]; 16-byte aligned */
+    double* nltot_d;            /* out [t_count][nl][jn - js + 1][8]; 16-byte aligned */
+    void* stream;
+} lec_rowspec_nl_args;
+int lec_rowspec_nl_ring(const lec_rowspec_nl_args* args);
+
+/*
  * Stage 2 of the spectra without assembled records: the level x latitude half of lec_reduce for all n_wave wavenumbers of a chunk of
  * time steps (an additive call: no struct, export or kernel result of ABI 11 changes; lec_level_spec.hip is a code object of its own).
  *

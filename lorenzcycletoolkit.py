@@ -27,7 +27,9 @@ crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file na
 -f --periodic --wavenumbers N: also the shares of the zonal wavenumbers 1 .. N in the eddy terms Ae, Ke, Ca, Ce and Ck
 (``lec_rowspec_ring``; exact by the discrete Parseval identity on the closed axis), written to results_wavenumbers/<term>_n.csv; every
 other output file is unchanged.  With --wavenumbers-generation also Ge (``lec_rowspec_q_ring``: Q at every point of a row, projected
-beside T), written to results_wavenumbers/Ge_n.csv.  With --wavenumbers-chunk M the file is streamed to the GPU, M time steps resident
+beside T), written to results_wavenumbers/Ge_n.csv.  With --wavenumbers-interactions also the non-linear eddy-eddy (triad) transfers S(n)
+into Ae and L(n) into Ke (``lec_rowspec_nl_ring``: the advective tendencies at every point of a row, projected beside T, u and v), written
+to results_wavenumbers/S_n.csv and L_n.csv in W m-2, positive where wavenumber n gains.  With --wavenumbers-chunk M the file is streamed to the GPU, M time steps resident
 per pipeline slot, and the spectra are computed chunk by chunk (``lec_level_spec_ring``): the same files, for series that do not fit
 the GPU whole.
 
@@ -99,6 +101,11 @@ def create_arg_parser():
     parser.add_argument("--wavenumbers-generation", action="store_true", default=argparse.SUPPRESS, help="with --wavenumbers N: also split the "
                         "generation term Ge and write results_wavenumbers/Ge_n.csv, in the form of its five siblings.  The diabatic-heating "
                         "residual Q is evaluated at every point of the ring's rows once more and projected beside T (lec_rowspec_q_ring)")
+    parser.add_argument("--wavenumbers-interactions", action="store_true", default=argparse.SUPPRESS, help="with --wavenumbers N: also the "
+                        "non-linear eddy-eddy (triad) transfers S(n) into Ae and L(n) into Ke, written to results_wavenumbers/S_n.csv and L_n.csv "
+                        "in the form of their siblings (W m-2, positive: wavenumber n gains; 'rest' is the total, summed in physical space, minus "
+                        "the N shares).  The eddy-eddy advective tendencies of T, u and v are evaluated at every point of the ring's rows and "
+                        "projected beside T, u and v (lec_rowspec_nl_ring)")
     parser.add_argument("--wavenumbers-chunk", type=int, metavar="N", default=argparse.SUPPRESS, help="with --wavenumbers: stream the file to the "
                         "GPU with N time steps resident per pipeline slot and compute the spectra chunk by chunk (lec_level_spec_ring), instead "
                         "of preparing the whole series on the host and holding it on the GPU: device memory then depends on N, not on the "
@@ -326,6 +333,8 @@ def refuse_periodic_options(args):
                              "--device-ingest streams a plain -f / -t / -c run")
         if getattr(args, "wavenumbers_generation", False):
             raise SystemExit("--wavenumbers-generation goes with --wavenumbers N: Ge(n) is one more of the zonal-wavenumber spectra")
+        if getattr(args, "wavenumbers_interactions", False):
+            raise SystemExit("--wavenumbers-interactions goes with --wavenumbers N: S(n) and L(n) are two more of the zonal-wavenumber spectra")
         return
     from lorenzcycletoolkit_amd._lib import LEC_MAX_WAVENUMBERS
     if not (args.fixed and args.periodic):

@@ -46,7 +46,8 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_inflate", "lec_inflate_status_text", "lec_chunk_scatter", "lec_format_csv_rows", "lec_dtdt", "lec_rowstats_steps", "lec_follow",
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
            "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring",
-           "lec_ingest_series", "lec_rowspec_ring", "lec_rowspec_q_ring", "lec_level_spec_ring"]
+           "lec_ingest_series", "lec_rowspec_ring", "lec_rowspec_q_ring", "lec_level_spec_ring",
+           "lec_rowspec_nl_ring"]
 
 
 class Tuning(C.Structure):
@@ -93,6 +94,17 @@ class RowspecQArgs(C.Structure):
         ("t_begin", C.c_int32), ("t_count", C.c_int32), ("js", C.c_int32), ("jn", C.c_int32), ("n_wave", C.c_int32),
         ("twid_d", C.c_void_p), ("lattab_d", C.c_void_p), ("levtab_d", C.c_void_p), ("tcoef_d", C.c_void_p),
         ("inv_hdeg", C.c_double), ("qspec_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class RowspecNlArgs(C.Structure):
+    """struct lec_rowspec_nl_args (include/lec_hip.h)."""
+    _fields_ = [
+        ("tair_d", C.c_void_p), ("u_d", C.c_void_p), ("v_d", C.c_void_p), ("omega_d", C.c_void_p),
+        ("dtype", C.c_int32), ("nt", C.c_int32), ("nl", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+        ("t_begin", C.c_int32), ("t_count", C.c_int32), ("js", C.c_int32), ("jn", C.c_int32), ("n_wave", C.c_int32),
+        ("rows_d", C.c_void_p), ("twid_d", C.c_void_p), ("lattab_d", C.c_void_p), ("ptab_d", C.c_void_p),
+        ("inv_hdeg", C.c_double), ("nlspec_d", C.c_void_p), ("nltot_d", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -272,6 +284,8 @@ def load():
     lib.lec_rowspec_ring.argtypes = [C.POINTER(RowspecArgs)]
     lib.lec_rowspec_q_ring.restype = C.c_int
     lib.lec_rowspec_q_ring.argtypes = [C.POINTER(RowspecQArgs)]
+    lib.lec_rowspec_nl_ring.restype = C.c_int
+    lib.lec_rowspec_nl_ring.argtypes = [C.POINTER(RowspecNlArgs)]
     lib.lec_level_spec_ring.restype = C.c_int
     lib.lec_level_spec_ring.argtypes = [C.POINTER(LevelSpecArgs)]
     lib.lec_rowstats_steps.restype = C.c_int

@@ -21,3 +21,7 @@ SPECTRUM_LEVEL_TERMS = ["Ae", "Ke", "Ca", "Ca_1", "Ca_2", "Ce", "Ce_1", "Ce_2", 
 # the generation term whose spectrum is asked for separately (LECResult.spectrum_ge / spectrum_ge_levels: it costs a kernel of its own,
 # lec_rowspec_q_ring, because Q never reaches a row record); a scalar and a per-level table of the same name
 SPECTRUM_GENERATION_TERM = "Ge"
+# the non-linear eddy-eddy transfers (LECResult.spectrum_nl / spectrum_nl_levels; lec_rowspec_nl_ring): S(n) into Ae and L(n) into Ke, and
+# the places of stage 2 they are read from (Ae is linear in [T'T'], Ke in [u'u'] + [v'v'])
+SPECTRUM_INTERACTION_TERMS = ["S", "L"]
+SPECTRUM_INTERACTION_PLACES = ["Ae", "Ke"]

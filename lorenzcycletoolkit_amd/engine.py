@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
+from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_PLACES, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
 
 
 @dataclass
@@ -36,6 +36,12 @@ class LECResult:
     spectrum_ge: Optional[torch.Tensor] = None         # [t_count, N] fp64
     spectrum_ge_rest: Optional[torch.Tensor] = None    # [t_count] fp64: Ge minus the N shares
     spectrum_ge_levels: Optional[torch.Tensor] = None  # [t_count, N, nl] fp64
+    # compute(..., wavenumbers=N, spectrum_interactions=True): the non-linear (eddy-eddy) transfers S(n), L(n) (``rowspec_nl``), W m-2,
+    # positive: wavenumber n gains
+    spectrum_nl: Optional[torch.Tensor] = None         # [t_count, 2, N] fp64: S, L
+    spectrum_nl_total: Optional[torch.Tensor] = None   # [t_count, 2] fp64: the same for the whole eddy covariance (summed in physical space)
+    spectrum_nl_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64: the total minus the N shares
+    spectrum_nl_levels: Optional[torch.Tensor] = None  # [t_count, 2, N, nl] fp64
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -138,6 +144,7 @@ class LECEngine:
         self._pack_maps = {}   # pack_boxes' index maps of the last grid / slab shape
         self._work = {}        # stage-2 workspaces by shape: am, levraw, dropmask (true scratch: never handed out)
         self._tcoef = None     # (time axis, its d/dt coefficients on the device) of the last call
+        self._ptab = None      # the d/dp coefficients of lec_rowspec_nl_ring for the engine's levels
         self._twid = None      # the twiddle table of lec_rowspec_ring for the engine's nx longitudes
 
     # -- helpers ---------------------------------------------------------------------------
@@ -332,7 +339,8 @@ class LECEngine:
                 tuning: Optional[dict] = None, per_step_boxes: Optional[bool] = None,
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
-                wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False) -> LECResult:
+                wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
+                spectrum_interactions: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -358,7 +366,12 @@ class LECEngine:
         ``spectrum_fused`` (with ``wavenumbers``): stage 2 of the spectra by ``spectrum_level_stage`` (``lec_level_spec_ring``), which
         takes a wavenumber's shares straight from the spectral records instead of from N assembled copies of the row records.  The
         same bits; the default stays the assembled form, the yardstick the fused kernels are tested against.
+        ``spectrum_interactions`` (with ``wavenumbers``): also ``spectrum_nl``, ``spectrum_nl_total``, ``spectrum_nl_rest`` and
+        ``spectrum_nl_levels``, the non-linear eddy-eddy transfers S(n) (into Ae) and L(n) (into Ke) of the wavenumbers 1 .. N
+        (``rowspec_nl`` and ``spectrum_level_stage`` on its records).  It changes no bit of anything else.
         """
+        if spectrum_interactions and wavenumbers is None:
+            raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
         if spectrum_fused and wavenumbers is None:
             raise ValueError("spectrum_fused: a form of the zonal-wavenumber spectra: give wavenumbers=N")
         if spectrum_generation:
@@ -383,7 +396,8 @@ class LECEngine:
                           keep_rows=keep_rows, out=out)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
-                           generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused)
+                           generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
+                           interactions=spectrum_interactions)
         return res
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
@@ -486,6 +500,91 @@ class LECEngine:
                 timing.append((ev0, ev1))
         return qspec
 
+    def rowspec_nl(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes: PreparedBoxes,
+                   n: int, *, t_begin: int = 0, t_count: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                   out_total: Optional[torch.Tensor] = None, timing: Optional[list] = None):
+        """``lec_rowspec_nl_ring``: (nlspec [t_count, nl, nyb, N, 8], nltot [t_count, nl, nyb, 8]) fp64 -- slots 0, 1, 2 hold
+        -2 C_n(A_T, T), -2 C_n(A_u, u), -2 C_n(A_v, v) of the eddy-eddy advective tendencies A_x of every row of the ring's latitude band,
+        for the wavenumbers 1 .. N and for the whole eddy covariance, slots 3 .. 7 are 0: ``spectrum_level_stage`` takes either as
+        ``spec``.  ``rows`` [t_count, nl, nyb, 32]: the ring pass's records of the same steps [t_begin, t_begin + t_count) (their zonal
+        means are the eddies' reference).  ``out`` / ``out_total``: caller-owned buffers; ``timing``: as ``rowspec``."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        self._check_wavenumbers(n, boxes, nx)
+        n = int(n)
+        if t_count is None:
+            t_count = nt - t_begin
+        _, _, js, jn = boxes.boxes[0]
+        nyb = jn - js + 1
+        if (rows.shape != (t_count, nl, nyb, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or rows.device != tair.device
+                or not rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb, 32] tensor on the fields' device: the ring pass's records of the same steps")
+        shape = (t_count, nl, nyb, n, 8)
+        nlspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
+        if nlspec.shape != shape or nlspec.dtype != torch.float64 or nlspec.device != tair.device or not nlspec.is_contiguous():
+            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the fields' device")
+        nltot = torch.empty((t_count, nl, nyb, 8), dtype=torch.float64, device=tair.device) if out_total is None else out_total
+        if nltot.shape != (t_count, nl, nyb, 8) or nltot.dtype != torch.float64 or nltot.device != tair.device or not nltot.is_contiguous():
+            raise ValueError("out_total must be a contiguous fp64 [t_count, nl, nyb, 8] tensor on the fields' device")
+        if self._twid is None:
+            self._twid = self._up(tables.twiddle_table(nx))
+        if self._ptab is None:
+            self._ptab = self._up(tables.pressure_coefs(self.level))
+        if "nl_lattab" not in boxes.dev:
+            boxes.dev["nl_lattab"] = self._up(tables.nl_lat_table(boxes.bt.lattab[0], self.lat[js:jn + 1]))
+        na = _lib.RowspecNlArgs(
+            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
+            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, rows_d=_ptr(rows), twid_d=_ptr(self._twid),
+            lattab_d=_ptr(boxes.dev["nl_lattab"]), ptab_d=_ptr(self._ptab), inv_hdeg=float(boxes.bt.boxtab[0, 2]),
+            nlspec_d=_ptr(nlspec), nltot_d=_ptr(nltot), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
+        with torch.cuda.device(tair.device):
+            if timing is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _lib.check(self.lib.lec_rowspec_nl_ring(C.byref(na)), "lec_rowspec_nl_ring")
+            if timing is not None:
+                ev1.record()
+                timing.append((ev0, ev1))
+        return nlspec, nltot
+
+    def spectrum_nl_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int) -> int:
+        """Time steps per ``rowspec_nl`` call: the chunk's records ([tc, nl, nyb, N + 1, 8] fp64, shares and total) stay within
+        ``SPECTRUM_CHUNK_BYTES``."""
+        return max(1, min(int(t_count), self.SPECTRUM_CHUNK_BYTES // (nl * nyb * (n + 1) * 64)))
+
+    def spectrum_nl_stage(self, tair, u, v, omega, rows: torch.Tensor, boxes: PreparedBoxes, n: int, levraw_nl: torch.Tensor, *,
+                          t_begin: int = 0, phi_scale: float = 1.0, buffers=None) -> None:
+        """``rowspec_nl`` and the level x latitude half of stage 2 for the steps [t_begin, t_begin + rows.shape[0]) of the cubes, in chunks
+        of ``spectrum_nl_chunk_steps``: ``levraw_nl`` [N + 1, t_count, nl, 40] (a time slice of the series' buffer) receives the records
+        of the N shares and, at index N, of the total.  ``buffers``: (nlspec, nltot) of at least one chunk, to be reused between calls."""
+        t_count, nl, nyb = (int(x) for x in rows.shape[:3])
+        tc = self.spectrum_nl_chunk_steps(t_count, nl, nyb, n)
+        if buffers is None:
+            f64 = dict(dtype=torch.float64, device=rows.device)
+            buffers = (torch.empty((tc, nl, nyb, n, 8), **f64), torch.empty((tc, nl, nyb, 8), **f64))
+        tc = min(tc, int(buffers[0].shape[0]))
+        for a in range(0, t_count, tc):
+            b = min(a + tc, t_count)
+            ns, ntot = self.rowspec_nl(tair, u, v, omega, rows[a:b], boxes, n, t_begin=t_begin + a, t_count=b - a,
+                                       out=buffers[0][:b - a], out_total=buffers[1][:b - a])
+            self.spectrum_level_stage(rows[a:b], ns, None, boxes, levraw_nl[:n, a:b], phi_scale=phi_scale)
+            self.spectrum_level_stage(rows[a:b], ntot.unsqueeze(3), None, boxes, levraw_nl[n:, a:b], phi_scale=phi_scale)
+
+    def _spectrum_nl_shares(self, res: LECResult, levraw_nl: torch.Tensor, boxes, drop_any_time: Optional[bool]) -> None:
+        """The tail of the interactions: ``levraw_nl`` [N + 1, t_count, nl, 40] -> ONE vertical half over the (n, step) batch (_handle_nans
+        sees the shares and the total together: they are NaN at the same levels) and ``res.spectrum_nl*``: S from the Ae place, L from the
+        Ke place of stage 2; the other places of these records mean nothing and are ignored."""
+        n1, t_count, nl = (int(x) for x in levraw_nl.shape[:3])
+        n = n1 - 1
+        shares = self.vertical_stage(levraw_nl.view(n1 * t_count, nl, _lib.LEC_NLEVRAW), boxes, drop_any_time=drop_any_time)
+        si = torch.as_tensor([SCALAR_TERMS.index(x) for x in SPECTRUM_INTERACTION_PLACES], device=levraw_nl.device)
+        li = torch.as_tensor([LEVEL_TERMS.index(x) for x in SPECTRUM_INTERACTION_PLACES], device=levraw_nl.device)
+        sc = shares.scalars.reshape(n1, t_count, _lib.LEC_NSCALAR)[:, :, si]
+        res.spectrum_nl = sc[:n].permute(1, 2, 0).contiguous()
+        res.spectrum_nl_total = sc[n].contiguous()
+        res.spectrum_nl_rest = res.spectrum_nl_total - res.spectrum_nl.sum(dim=2)
+        res.spectrum_nl_levels = shares.levels.reshape(n1, t_count, _lib.LEC_NLEVTAB, nl)[:n][:, :, li].permute(1, 2, 0, 3).contiguous()
+
     def spectrum_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int) -> int:
         """Time steps per spectral call of the fused form: the chunk's ``spec`` records ([tc, nl, nyb, N, 8] fp64) stay within
         ``SPECTRUM_CHUNK_BYTES``."""
@@ -525,7 +624,7 @@ class LECEngine:
             _lib.check(self.lib.lec_level_spec_ring(C.byref(la)), "lec_level_spec_ring")
 
     def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
-                  drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False) -> None:
+                  drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False, interactions: bool = False) -> None:
         """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
         whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
         (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
@@ -533,10 +632,15 @@ class LECEngine:
         any-time mask over the batch is the totals' own.  ``generation`` ({"time_s", "tcoef"} of the call): slot 15 of the assembled
         records holds the wavenumber's share of [Q'T'] too (``rowspec_q``), which only Ge reads: Ge(n) and its table come out of the
         same batch, and nothing else of it moves.  ``fused``: no assembled records -- ``spectrum_level_stage`` reads the ring
-        pass's records and the chunk's ``spec`` / ``qspec`` (the chunk is bounded by ``spec``), the same bits."""
+        pass's records and the chunk's ``spec`` / ``qspec`` (the chunk is bounded by ``spec``), the same bits.  ``interactions``: S(n)
+        and L(n) by ``spectrum_nl_stage`` in time chunks of its own records, a batch of its own."""
         t_count, nl, nyb = (int(x) for x in rows.shape[:3])
         dev = rows.device
         f64 = dict(dtype=torch.float64, device=dev)
+        if interactions:
+            levraw_nl = torch.empty((n + 1, t_count, nl, _lib.LEC_NLEVRAW), **f64)
+            self.spectrum_nl_stage(tair, u, v, omega, rows, boxes, n, levraw_nl, t_begin=t_begin, phi_scale=phi_scale)
+            self._spectrum_nl_shares(res, levraw_nl, boxes, drop_any_time)
         levraw = torch.empty((n, t_count, nl, _lib.LEC_NLEVRAW), **f64)
         if fused:
             tc = self.spectrum_chunk_steps(t_count, nl, nyb, n)

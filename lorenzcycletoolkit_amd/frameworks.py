@@ -59,13 +59,16 @@ class BoxData:
     ``spectrum_levels`` [time, 14, N, level] -- the shares of the zonal wavenumbers 1 .. N in Ae, Ke, Ca, Ce, Ck (``lec_rowspec_ring``).
     ``spectrum_generation`` (with ``wavenumbers``; no ``dTdt`` cube): also ``spectrum_ge`` [time, N], ``spectrum_ge_rest`` [time] and
     ``spectrum_ge_levels`` [time, N, level], the same shares of Ge (``lec_rowspec_q_ring``).
+    ``spectrum_interactions`` (with ``wavenumbers``): also ``spectrum_nl`` [time, 2, N], ``spectrum_nl_total`` [time, 2],
+    ``spectrum_nl_rest`` [time, 2] and ``spectrum_nl_levels`` [time, 2, N, level], the non-linear eddy-eddy transfers S(n) into Ae and
+    L(n) into Ke (``lec_rowspec_nl_ring``).
     """
 
     def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, western_limit=None, eastern_limit=None,
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
-                 spectrum_generation: bool = False):
+                 spectrum_generation: bool = False, spectrum_interactions: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -91,6 +94,10 @@ class BoxData:
                 raise ValueError("spectrum_generation: Ge(n) is part of the zonal-wavenumber spectra: give wavenumbers=N")
             if dTdt is not None:
                 raise ValueError("spectrum_generation: a dTdt cube is not supported (lec_rowspec_q_ring forms dT/dt from the time axis)")
+        self.spectrum_interactions = bool(spectrum_interactions)
+        self.spectrum_nl = self.spectrum_nl_total = self.spectrum_nl_rest = self.spectrum_nl_levels = None
+        if self.spectrum_interactions and wavenumbers is None:
+            raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
         self.args = args
         self.results_subdirectory = results_subdirectory
         self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
@@ -141,7 +148,8 @@ class BoxData:
                                                              t_range=None if shard is None else (t0, t1), merge_dropmask=merge, out=out, keep_level=keep,
                                                              ring=self.periodic,
                                                              **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
-                                                             **({"spectrum_generation": True} if self.spectrum_generation else {}))
+                                                             **({"spectrum_generation": True} if self.spectrum_generation else {}),
+                                                             **({"spectrum_interactions": True} if self.spectrum_interactions else {}))
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)
@@ -167,6 +175,11 @@ class BoxData:
             self.spectrum_ge = self.result.spectrum_ge.cpu().numpy()
             self.spectrum_ge_rest = self.result.spectrum_ge_rest.cpu().numpy()
             self.spectrum_ge_levels = self.result.spectrum_ge_levels.cpu().numpy()
+        if self.result.spectrum_nl is not None:
+            self.spectrum_nl = self.result.spectrum_nl.cpu().numpy()
+            self.spectrum_nl_total = self.result.spectrum_nl_total.cpu().numpy()
+            self.spectrum_nl_rest = self.result.spectrum_nl_rest.cpu().numpy()
+            self.spectrum_nl_levels = self.result.spectrum_nl_levels.cpu().numpy()
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -207,7 +220,8 @@ class BoxData:
                                    t_begin=t0 - h0, t_count=t1 - t0, per_step_boxes=self.per_step_boxes,
                                    drop_any_time=not self.per_step_boxes, merge_dropmask=merge, out=out,
                                    **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
-                                   **({"spectrum_generation": True} if self.spectrum_generation else {}))
+                                   **({"spectrum_generation": True} if self.spectrum_generation else {}),
+                                   **({"spectrum_interactions": True} if self.spectrum_interactions else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -260,10 +274,10 @@ def wavenumbers_check(n: int, nx: int) -> None:
 
 
 def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
-    """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck -- and Ge when its spectrum was asked for --: one row per time step -- the
-    time labels and number formatting of the per-level tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the
-    units of the results CSV."""
-    from .constants import SPECTRUM_GENERATION_TERM, SPECTRUM_TERMS
+    """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck -- and Ge, and the non-linear transfers S and L (W m-2, positive: wavenumber
+    n gains), when their spectra were asked for --: one row per time step -- the time labels and number formatting of the per-level
+    tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the units of the results CSV."""
+    from .constants import SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_TERMS, SPECTRUM_TERMS
     os.makedirs(directory, exist_ok=True)
     n = box_obj.spectrum.shape[2]
     header = ",".join([str(time_name)] + [str(k) for k in range(1, n + 1)] + ["rest"]) + "\n"
@@ -271,6 +285,8 @@ def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> N
     files = [(term, box_obj.spectrum[:, i, :], box_obj.spectrum_rest[:, i: i + 1]) for i, term in enumerate(SPECTRUM_TERMS)]
     if box_obj.spectrum_ge is not None:
         files.append((SPECTRUM_GENERATION_TERM, box_obj.spectrum_ge, box_obj.spectrum_ge_rest[:, None]))
+    if getattr(box_obj, "spectrum_nl", None) is not None:
+        files += [(term, box_obj.spectrum_nl[:, i, :], box_obj.spectrum_nl_rest[:, i: i + 1]) for i, term in enumerate(SPECTRUM_INTERACTION_TERMS)]
     for term, shares, rest in files:
         table = np.concatenate([shares, rest], axis=1)
         path = os.path.join(directory, f"{term}_n.csv")
@@ -476,12 +492,15 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
     generation = bool(getattr(args, "wavenumbers_generation", False))
     if generation and wavenumbers is None:
         raise ValueError("--wavenumbers-generation goes with --wavenumbers N")
+    interactions = bool(getattr(args, "wavenumbers_interactions", False))
+    if interactions and wavenumbers is None:
+        raise ValueError("--wavenumbers-interactions goes with --wavenumbers N")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
                           results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
-                          spectrum_generation=generation)
+                          spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}))
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -507,6 +526,10 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         if generation:
             app_logger.info(f"--wavenumbers-generation: Ge split likewise, Q evaluated at every point of the ring's rows "
                             f"(lec_rowspec_q_kernel: N = {int(wavenumbers)}, nx = {len(data.lon)}); written to {spectrum_directory}")
+        if interactions:
+            app_logger.info(f"--wavenumbers-interactions: the non-linear eddy-eddy transfers S(n) into Ae and L(n) into Ke, the advective "
+                            f"tendencies evaluated at every point of the ring's rows (lec_rowspec_nl_kernel: N = {int(wavenumbers)}, "
+                            f"nx = {len(data.lon)}); written to {spectrum_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]

@@ -822,7 +822,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                  device="cuda:0", chunk_steps: Optional[int] = None, with_q: bool = True, stats: Optional[dict] = None,
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
                  slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
-                 ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False) -> LECResult:
+                 ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False,
+                 spectrum_interactions: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -849,7 +850,11 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     the ring pass and ``spectrum_level_stage`` leaves 40 numbers per (n, step, level) in ONE buffer of the whole series; the spectral
     records live for a sub-chunk (or a piece of one: ``LECEngine.SPECTRUM_CHUNK_BYTES``) only.  ``stats["spectrum_levraw_bytes"]`` /
     ``stats["spectrum_buffer_bytes"]``: that buffer and the spectral records.
+    ``spectrum_interactions`` (with ``wavenumbers``): also S(n) and L(n) of ``LECEngine.compute(..., spectrum_interactions=True)``, the
+    same bits: every sub-chunk goes through ``spectrum_nl_stage`` (``rowspec_nl`` has no time stencil: no halo).
     """
+    if spectrum_interactions and wavenumbers is None:
+        raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
     if ring and per_step_boxes:
         raise ValueError("ring: one fixed box (the moving framework's ring is the 0..360 axis)")
     if spectrum_generation and wavenumbers is None:
@@ -993,6 +998,11 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         spec = torch.empty((spec_steps, nl, bt.nyb_max, nw, 8), dtype=torch.float64, device=dev)
         qspec = torch.empty((spec_steps, nl, bt.nyb_max, nw), dtype=torch.float64, device=dev) if spectrum_generation else None
         levraw_spec = torch.empty((nw, t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
+        if spectrum_interactions:
+            nl_steps = engine.spectrum_nl_chunk_steps(dec_steps, nl, bt.nyb_max, nw)
+            nl_buffers = (torch.empty((nl_steps, nl, bt.nyb_max, nw, 8), dtype=torch.float64, device=dev),
+                          torch.empty((nl_steps, nl, bt.nyb_max, 8), dtype=torch.float64, device=dev))
+            levraw_nl = torch.empty((nw + 1, t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
     time_s = plan.time_s
     phi_scale = ds.field_scale(variable_list_df, geo_role)
 
@@ -1070,12 +1080,17 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                     if spectrum_generation:
                         qs = engine.rowspec_q(*fields, fixed_box, nw, tcoef=kw["tcoef"], t_begin=kw["t_begin"] + a, t_count=b - a, out=qspec[:b - a])
                     engine.spectrum_level_stage(rows[a:b], sp, qs, fixed_box, levraw_spec[:, s0 - t0 + a: s0 - t0 + b], phi_scale=phi_scale)
+                if spectrum_interactions:
+                    engine.spectrum_nl_stage(*fields, rows[:n], fixed_box, nw, levraw_nl[:, s0 - t0: s1 - t0], t_begin=kw["t_begin"],
+                                             phi_scale=phi_scale, buffers=nl_buffers)
         pipe.decoded(slot)
     t_loop = time.perf_counter()                # (every chunk enqueued)
     res = engine.vertical_stage(levraw, own_boxes if per_step_boxes else fixed_box, drop_any_time=not per_step_boxes,
                                 merge_dropmask=merge_dropmask, out=out)
     if wavenumbers is not None:
         engine._spectrum_shares(res, levraw_spec, fixed_box, True, spectrum_generation)
+        if spectrum_interactions:
+            engine._spectrum_nl_shares(res, levraw_nl, fixed_box, True)
     on_device, reg_stats = pipe.finish()
     moved, host_s = pipe.moved, pipe.host_s
     if stats is not None:
@@ -1087,6 +1102,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         if wavenumbers is not None:
             stats.update(spectrum_levraw_bytes=levraw_spec.numel() * 8,
                          spectrum_buffer_bytes=(spec.numel() + (qspec.numel() if qspec is not None else 0)) * 8)
+            if spectrum_interactions:
+                stats.update(spectrum_nl_levraw_bytes=levraw_nl.numel() * 8, spectrum_nl_buffer_bytes=(nl_buffers[0].numel() + nl_buffers[1].numel()) * 8)
         torch.cuda.synchronize(dev)
         stats.update(seconds=dict(setup=t_setup - t_enter, chunk_loop_host=t_loop - t_setup, drain=time.perf_counter() - t_loop,
                                   registering=(spans.seconds if spans is not None else 0.0)))

@@ -202,6 +202,29 @@ def time_coefs(time_s: np.ndarray) -> np.ndarray:
     return gradient_coefs(np.asarray(time_s, dtype=np.float64))
 
 
+def pressure_coefs(level_pa: np.ndarray) -> np.ndarray:
+    """ptab [nl, 3] of ``lec_rowspec_nl_ring``: np.gradient(edge_order=1) coefficients over the level axis in Pa, one-sided at the top
+    and bottom level; one level has no pressure derivative: all 0."""
+    p = np.asarray(level_pa, dtype=np.float64)
+    if p.size < 2:
+        return np.zeros((p.size, 3), dtype=np.float64)
+    return gradient_coefs(p)
+
+
+def nl_lat_table(lattab: np.ndarray, lat_deg: np.ndarray) -> np.ndarray:
+    """The [nyb, 5] latitude table of ``lec_rowspec_nl_ring``: the four columns of the ring box's ``lattab`` (d/dlat a, b, c; 1 / dx_j:
+    what ``lec_rowspec_q_ring`` takes) and m_j = tan(lat_j) / Re, the metric factor of the advection of u and v -- 0 on a pole row,
+    where the curvature terms have no meaning (and 1 / dx_j is whatever the box's table carries)."""
+    lat = np.asarray(lat_deg, dtype=np.float64)
+    lattab = np.asarray(lattab, dtype=np.float64)
+    if lattab.shape != (lat.size, 4):
+        raise ValueError("nl_lat_table: lattab must be the band's [nyb, 4] table")
+    out = np.empty((lat.size, 5), dtype=np.float64)
+    out[:, :4] = lattab
+    out[:, 4] = np.where(np.abs(lat) >= 90.0, 0.0, np.tan(np.deg2rad(lat)) / RE)
+    return out
+
+
 def budgets_and_residuals(scalars: dict, time_s: np.ndarray, residuals: bool = True) -> dict:
     """Budget (dX/dt by np.gradient with dt = t[1]-t[0]) and residual columns of the results CSV
     (calc_budget_and_residual.py:32-56,131-154 of the reference).  O(nt) host work on the gathered
