@@ -815,6 +815,53 @@ typedef struct lec_rowspec_nl_args {
 int lec_rowspec_nl_ring(const lec_rowspec_nl_args* args);
 
 /*
+ * -f --periodic --wavenumbers N --wavenumbers-budget: the ZONAL-WAVENUMBER SHARES of the TRIPLE PRODUCTS behind the boundary terms of the
+ * eddy budgets, BAe(n) and BKe(n), of every ring row (an additive call: no struct, export or kernel result of ABI 11 changes;
+ * lec_rowspec_b.hip is a code object of its own).
+ *
+ * On a ring the east-west pieces of the boundary terms vanish (the ring pass writes the west column into the east slots), so stage 2
+ * forms BAe from slots LEC_S_VTT (the band's first and last row) and LEC_S_WTT (bottom minus top level) of a row record and BKe from
+ * LEC_S_EV and LEC_S_EW.  A triple product [a b'b'] is the covariance of the pointwise product P = a b' with b, because [b'] = 0:
+ * [a b'b'] = [P'b'] = sum_n C_n(P, b), exactly, by the discrete Parseval identity of lec_rowspec_ring.
+ *   For a row (t, k, j) of the band js .. jn, [x] = the row's zonal mean as lec_rowstats_ring wrote it into rows_d, x' = x - [x], v and w
+ *   the FULL fields (their zonal means included: the transport by the mean flow and the triad part are both in a share):
+ *   bspec_d [t_count][nl][jn - js + 1][n_wave][4]:
+ *     slot 0  VTT(n) = C_n(v T', T)                      sum over n = 1 .. nx / 2:  [v T'T']  = slot LEC_S_VTT (16) of the row's record
+ *     slot 1  WTT(n) = C_n(w T', T)                                                 [w T'T']  = slot LEC_S_WTT (17)
+ *     slot 2  EV(n)  = C_n(v u', u) + C_n(v v', v)                                  [E v]     = slot LEC_S_EV  (20),  E = u'^2 + v'^2
+ *     slot 3  EW(n)  = C_n(w u', u) + C_n(w v', v)                                  [E w]     = slot LEC_S_EW  (21)
+ *   (C_n, w_n and the Nyquist weight as above.)  Slots 0 and 2 are computed for the rows j = js and j = jn only -- stage 2 reads them
+ *   nowhere else -- and are 0.0 for every other row; slots 1 and 3 for every row and level (_handle_nans can move "bottom" and "top" to
+ *   any level).  Row records that carry the four slots in places 16, 17, 20, 21 beside lec_rowspec_ring's shares in 6 .. 13 give BAe(n) and
+ *   BKe(n) in the BAe and BKe places of stage 2 (lec_level_spec_b_ring).
+ *   - Cubes, twid_d, the integer twiddle index and fp64 accumulation: as lec_rowspec_ring.  The products are formed with contraction
+ *     off; the column classes of a wavenumber are summed in a fixed order: a row's result depends on (nx, n_wave) and on nothing else.
+ *   - No derivative and no neighbour row is read, and there is no time stencil: a chunk of a streamed series needs no halo.
+ *   - NaN: a computed slot of a row is NaN for every n exactly where the corresponding slot of the row's record is NaN (a NaN in any
+ *     field the product reads, or in a record mean).  The skipped slots of interior rows stay 0.
+ * Validation.  Every refusal names the field, is made before any HIP call, never clamped.  LEC_ERR_ARG: null tair_d / u_d / v_d /
+ * omega_d / rows_d / twid_d / bspec_d, dtype, nx < 3, nl < 1, ny < 2, t_begin / t_count outside the cube, js / jn outside
+ * 0 <= js < jn < ny, n_wave < 1 or n_wave > nx / 2, twid_d / rows_d / bspec_d not 16-byte aligned, a cube not aligned to its element.
+ * LEC_ERR_UNSUPPORTED: n_wave > LEC_MAX_WAVENUMBERS, more than 2^31 - 1 rows.
+ */
+typedef struct lec_rowspec_b_args {
+    const void* tair_d;
+    const void* u_d;
+    const void* v_d;
+    const void* omega_d;
+    int32_t dtype;              /* enum lec_dtype (LEC_F64 or LEC_F32), common to the four cubes */
+    int32_t nt, nl, ny, nx;     /* cube dimensions; the nx columns are the ring */
+    int32_t t_begin, t_count;   /* process time steps [t_begin, t_begin + t_count) */
+    int32_t js, jn;             /* the latitude band (inclusive grid rows), js < jn */
+    int32_t n_wave;             /* wavenumbers 1 .. n_wave; 1 <= n_wave <= min(nx / 2, LEC_MAX_WAVENUMBERS) */
+    const double* rows_d;       /* [t_count][nl][jn - js + 1][LEC_NSTAT], lec_rowstats_ring's records of the same steps and band; 16-byte aligned */
+    const double* twid_d;       /* [nx][2] cos, sin of 2 pi m / nx; 16-byte aligned */
+    double* bspec_d;            /* out [t_count][nl][jn - js + 1][n_wave][4]; 16-byte aligned */
+    void* stream;
+} lec_rowspec_b_args;
+int lec_rowspec_b_ring(const lec_rowspec_b_args* args);
+
+/*
  * Stage 2 of the spectra without assembled records: the level x latitude half of lec_reduce for all n_wave wavenumbers of a chunk of
  * time steps (an additive call: no struct, export or kernel result of ABI 11 changes; lec_level_spec.hip is a code object of its own).
  *
@@ -850,6 +897,21 @@ typedef struct lec_level_spec_args {
     void* stream;
 } lec_level_spec_args;
 int lec_level_spec_ring(const lec_level_spec_args* args);
+/*
+ * lec_level_spec_ring with the boundary terms' triple products replaced too (--wavenumbers-budget; an additive call, ABI 11 unchanged):
+ * besides what lec_level_spec_ring replaces, slots LEC_S_VTT, LEC_S_WTT, LEC_S_EV, LEC_S_EW (16, 17, 20, 21) of the record of row
+ * (t, k, j) are  bspec_d[t][k][j][n][0..3]  of lec_rowspec_b_ring.  With lec_reduce's LEC_STAGE_VERTICAL over the (n, step) records the BAe
+ * and BKe columns of the scalars are then BAe(n) and BKe(n); _handle_nans and the bottom-minus-top difference stay the totals'.  The
+ * kernels are instantiations of their own of the same source: lec_level_spec_ring's results keep their bits, and every number of this
+ * call that reads none of the four slots has lec_level_spec_ring's bits.  With bspec_d holding the records' own four slots for every
+ * n the call reproduces lec_level_spec_ring bit for bit.
+ * Validation: lec_level_spec_ring's, under this call's name; LEC_ERR_ARG also for a null bspec_d or one not 16-byte aligned.
+ */
+typedef struct lec_level_spec_b_args {
+    lec_level_spec_args spec;   /* as lec_level_spec_ring takes it */
+    const double* bspec_d;      /* [t_count][nl][nyb][n_wave][4], lec_rowspec_b_ring's; 16-byte aligned */
+} lec_level_spec_b_args;
+int lec_level_spec_b_ring(const lec_level_spec_b_args* args);
 
 int lec_ingest(const lec_ingest_args* args);
 /*

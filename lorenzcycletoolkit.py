@@ -29,7 +29,10 @@ crosses an east or west wall (``lec_rowstats_ring``).  Same output tree, file na
 other output file is unchanged.  With --wavenumbers-generation also Ge (``lec_rowspec_q_ring``: Q at every point of a row, projected
 beside T), written to results_wavenumbers/Ge_n.csv.  With --wavenumbers-interactions also the non-linear eddy-eddy (triad) transfers S(n)
 into Ae and L(n) into Ke (``lec_rowspec_nl_ring``: the advective tendencies at every point of a row, projected beside T, u and v), written
-to results_wavenumbers/S_n.csv and L_n.csv in W m-2, positive where wavenumber n gains.  With --wavenumbers-chunk M the file is streamed to the GPU, M time steps resident
+to results_wavenumbers/S_n.csv and L_n.csv in W m-2, positive where wavenumber n gains.  With --wavenumbers-budget also the boundary terms
+BAe(n) and BKe(n) (``lec_rowspec_b_ring``: the triple products of a row as covariances of pointwise products, projected beside T, u and
+v), the finite-difference tendencies and the residuals RGe(n) and RKe(n) as the results CSV defines them for the totals, written to
+results_wavenumbers/BAe_n.csv, BKe_n.csv, dAedt_n.csv, dKedt_n.csv, RGe_n.csv and RKe_n.csv.  With --wavenumbers-chunk M the file is streamed to the GPU, M time steps resident
 per pipeline slot, and the spectra are computed chunk by chunk (``lec_level_spec_ring``): the same files, for series that do not fit
 the GPU whole.
 
@@ -106,6 +109,13 @@ def create_arg_parser():
                         "in the form of their siblings (W m-2, positive: wavenumber n gains; 'rest' is the total, summed in physical space, minus "
                         "the N shares).  The eddy-eddy advective tendencies of T, u and v are evaluated at every point of the ring's rows and "
                         "projected beside T, u and v (lec_rowspec_nl_ring)")
+    parser.add_argument("--wavenumbers-budget", action="store_true", default=argparse.SUPPRESS, help="with --wavenumbers N: also the budget of "
+                        "every wavenumber's Ae and Ke on the open band: the boundary terms BAe(n) and BKe(n) (the flux through the band's north "
+                        "and south walls and through its top and bottom level), the tendencies dAe(n)/dt and dKe(n)/dt (np.gradient with the "
+                        "run's dt: the series needs at least 2 time steps) and the residuals RGe(n) = dAe/dt - Ca + Ce - BAe and RKe(n) = dKe/dt "
+                        "- Ce + Ck - BKe, written to results_wavenumbers/BAe_n.csv, BKe_n.csv, dAedt_n.csv, dKedt_n.csv, RGe_n.csv and RKe_n.csv "
+                        "in the form of their siblings.  The four triple products behind BAe and BKe are split as covariances of pointwise "
+                        "products (lec_rowspec_b_ring)")
     parser.add_argument("--wavenumbers-chunk", type=int, metavar="N", default=argparse.SUPPRESS, help="with --wavenumbers: stream the file to the "
                         "GPU with N time steps resident per pipeline slot and compute the spectra chunk by chunk (lec_level_spec_ring), instead "
                         "of preparing the whole series on the host and holding it on the GPU: device memory then depends on N, not on the "
@@ -335,6 +345,8 @@ def refuse_periodic_options(args):
             raise SystemExit("--wavenumbers-generation goes with --wavenumbers N: Ge(n) is one more of the zonal-wavenumber spectra")
         if getattr(args, "wavenumbers_interactions", False):
             raise SystemExit("--wavenumbers-interactions goes with --wavenumbers N: S(n) and L(n) are two more of the zonal-wavenumber spectra")
+        if getattr(args, "wavenumbers_budget", False):
+            raise SystemExit("--wavenumbers-budget goes with --wavenumbers N: BAe(n), BKe(n) and the residuals are more of the zonal-wavenumber spectra")
         return
     from lorenzcycletoolkit_amd._lib import LEC_MAX_WAVENUMBERS
     if not (args.fixed and args.periodic):

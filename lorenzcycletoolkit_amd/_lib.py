@@ -47,7 +47,7 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
            "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring",
            "lec_ingest_series", "lec_rowspec_ring", "lec_rowspec_q_ring", "lec_level_spec_ring",
-           "lec_rowspec_nl_ring"]
+           "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring"]
 
 
 class Tuning(C.Structure):
@@ -117,6 +117,21 @@ class LevelSpecArgs(C.Structure):
         ("phi_scale", C.c_double), ("am_d", C.c_void_p), ("levraw_d", C.c_void_p),
         ("wave_stride", C.c_int64), ("stream", C.c_void_p),
     ]
+
+
+class RowspecBArgs(C.Structure):
+    """struct lec_rowspec_b_args (include/lec_hip.h)."""
+    _fields_ = [
+        ("tair_d", C.c_void_p), ("u_d", C.c_void_p), ("v_d", C.c_void_p), ("omega_d", C.c_void_p),
+        ("dtype", C.c_int32), ("nt", C.c_int32), ("nl", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+        ("t_begin", C.c_int32), ("t_count", C.c_int32), ("js", C.c_int32), ("jn", C.c_int32), ("n_wave", C.c_int32),
+        ("rows_d", C.c_void_p), ("twid_d", C.c_void_p), ("bspec_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class LevelSpecBArgs(C.Structure):
+    """struct lec_level_spec_b_args (include/lec_hip.h)."""
+    _fields_ = [("spec", LevelSpecArgs), ("bspec_d", C.c_void_p)]
 
 
 class ReduceArgs(C.Structure):
@@ -288,6 +303,10 @@ def load():
     lib.lec_rowspec_nl_ring.argtypes = [C.POINTER(RowspecNlArgs)]
     lib.lec_level_spec_ring.restype = C.c_int
     lib.lec_level_spec_ring.argtypes = [C.POINTER(LevelSpecArgs)]
+    lib.lec_rowspec_b_ring.restype = C.c_int
+    lib.lec_rowspec_b_ring.argtypes = [C.POINTER(RowspecBArgs)]
+    lib.lec_level_spec_b_ring.restype = C.c_int
+    lib.lec_level_spec_b_ring.argtypes = [C.POINTER(LevelSpecBArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

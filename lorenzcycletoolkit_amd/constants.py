@@ -25,3 +25,9 @@ SPECTRUM_GENERATION_TERM = "Ge"
 # the places of stage 2 they are read from (Ae is linear in [T'T'], Ke in [u'u'] + [v'v'])
 SPECTRUM_INTERACTION_TERMS = ["S", "L"]
 SPECTRUM_INTERACTION_PLACES = ["Ae", "Ke"]
+# the per-wavenumber budget of the eddy reservoirs (LECResult.spectrum_b / spectrum_tendency / spectrum_residual; lec_rowspec_b_ring):
+# the boundary terms read from their own places of stage 2, the finite-difference tendencies and the residuals of the reference's budget
+SPECTRUM_BUDGET_TERMS = ["BAe", "BKe"]
+SPECTRUM_TENDENCY_TERMS = ["Ae", "Ke"]
+SPECTRUM_TENDENCY_FILES = ["dAedt", "dKedt"]
+SPECTRUM_RESIDUAL_TERMS = ["RGe", "RKe"]

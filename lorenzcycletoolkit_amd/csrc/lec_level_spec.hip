@@ -14,6 +14,7 @@
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
+#include <stdio.h>
 
 #include "../../include/lec_hip.h"
 #include "lec_internal.h"
@@ -32,6 +33,7 @@ constexpr int kRecStride = LEC_NSTAT + 1, kLatStride = 9;
 constexpr int kSmallRows = 64;
 constexpr int kSmallRound = 18;    // sums per reduction round of the small kernel (two rounds: 15 + 18)
 constexpr int kSpecSlots = 8;      // LEC_S_TT .. LEC_S_WV
+constexpr int kBudgetSlots = 4;    // lec_rowspec_b_ring's: LEC_S_VTT, LEC_S_WTT, LEC_S_EV, LEC_S_EW
 static_assert(LEC_S_WV - LEC_S_TT + 1 == kSpecSlots && LEC_S_QT == LEC_S_WV + 2, "slots 6 .. 13 and 15 are the replaced ones");
 
 // the levraw record of lec_reduce.hip
@@ -53,6 +55,7 @@ struct SpecLevParams {
     double* am;             // [t_count][nl][8]
     double* levraw;
     long long wstride;      // doubles between consecutive wavenumbers of levraw
+    const double* bspec;    // [t_count][nl][nyb][n_wave][4], the instantiations of lec_level_spec_b_ring only
 };
 
 __device__ __forceinline__ double wave_sum(double v) {
@@ -136,6 +139,9 @@ __device__ __forceinline__ double level_divisor(int s, double sig) {
 
 // grid (n_wave * t_count * nl) -- level fastest, then time step, then wavenumber --, block 64.  lec_level_terms_kernel with the nine
 // slots of the lane's own row replaced in the LDS tile (the rows j - 1 / j + 1 are read for [T] [u] [v] only).
+// B (lec_level_spec_b_ring): slots LEC_S_VTT, LEC_S_WTT, LEC_S_EV, LEC_S_EW likewise, from bspec_d; an instantiation of its own, the
+// instantiation without it is the kernel lec_level_spec_ring has always launched.
+template <bool B>
 __global__ void __launch_bounds__(64) lec_spec_level_terms_kernel(const SpecLevParams p) {
     const int nl = p.nl, nyb_max = p.nyb, lane = threadIdx.x;
     const int per_wave = p.t_count * nl;
@@ -178,6 +184,11 @@ __global__ void __launch_bounds__(64) lec_spec_level_terms_kernel(const SpecLevP
         const dbl2_t* sp = reinterpret_cast<const dbl2_t*>(p.spec + srow * kSpecSlots);
         const dbl2_t s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
         const double sq = p.qspec ? p.qspec[srow] : 0.0;
+        dbl2_t b0 = {0.0, 0.0}, b1 = {0.0, 0.0};
+        if (B) {
+            const dbl2_t* bp = reinterpret_cast<const dbl2_t*>(p.bspec + srow * kBudgetSlots);
+            b0 = bp[0]; b1 = bp[1];
+        }
         if (j0 == 0) {
             nyb = box_rows(p);
             aT = am[8 * k + 0]; aW = am[8 * k + 3]; aP = am[8 * k + 4]; aQ = am[8 * k + 5];
@@ -202,6 +213,7 @@ __global__ void __launch_bounds__(64) lec_spec_level_terms_kernel(const SpecLevP
             d[LEC_S_TT + 0] = s0.x; d[LEC_S_TT + 1] = s0.y; d[LEC_S_TT + 2] = s1.x; d[LEC_S_TT + 3] = s1.y;
             d[LEC_S_TT + 4] = s2.x; d[LEC_S_TT + 5] = s2.y; d[LEC_S_TT + 6] = s3.x; d[LEC_S_TT + 7] = s3.y;
             if (p.qspec) d[LEC_S_QT] = sq;
+            if (B) { d[LEC_S_VTT] = b0.x; d[LEC_S_WTT] = b0.y; d[LEC_S_EV] = b1.x; d[LEC_S_EW] = b1.y; }
         }
         const int jm = jb > 0 ? jb - 1 : jb, jp = jb < nyb - 1 ? jb + 1 : jb;
         const double* r = tile + (jb - jlo) * kRecStride;
@@ -262,6 +274,8 @@ struct LaneSums {
 
 // grid (n_wave * t_count * nl), block 64; requires nyb <= 64.  lec_level_small_kernel with the nine slots replaced in the register
 // array; the area means -- the same butterflies, formed once per (time step, level) by lec_spec_area_means_kernel -- come from `am`.
+// B: as in lec_spec_level_terms_kernel.
+template <bool B>
 __global__ void __launch_bounds__(64, 4) lec_spec_level_small_kernel(const SpecLevParams p) {
     __shared__ double part[kSmallRound * kPartStride];
     const int nl = p.nl, nyb_max = p.nyb, lane = threadIdx.x;
@@ -282,6 +296,11 @@ __global__ void __launch_bounds__(64, 4) lec_spec_level_small_kernel(const SpecL
     const dbl2_t* sp = reinterpret_cast<const dbl2_t*>(p.spec + srow * kSpecSlots);
     const dbl2_t s0 = sp[0], s1 = sp[1], s2 = sp[2], s3 = sp[3];
     const double sq = p.qspec ? p.qspec[srow] : 0.0;
+    dbl2_t b0 = {0.0, 0.0}, b1 = {0.0, 0.0};
+    if (B) {
+        const dbl2_t* bp = reinterpret_cast<const dbl2_t*>(p.bspec + srow * kBudgetSlots);
+        b0 = bp[0]; b1 = bp[1];
+    }
     const dbl2_t km2 = *reinterpret_cast<const dbl2_t*>(p.rows + (size_t)(tl * nl + km) * lstride + (size_t)jbc * LEC_NSTAT);
     const dbl2_t kp2 = *reinterpret_cast<const dbl2_t*>(p.rows + (size_t)(tl * nl + kp) * lstride + (size_t)jbc * LEC_NSTAT);
     const dbl2_t* ll = reinterpret_cast<const dbl2_t*>(lt + (size_t)jbc * 8);
@@ -299,6 +318,7 @@ __global__ void __launch_bounds__(64, 4) lec_spec_level_small_kernel(const SpecL
     r[LEC_S_TT + 0] = s0.x; r[LEC_S_TT + 1] = s0.y; r[LEC_S_TT + 2] = s1.x; r[LEC_S_TT + 3] = s1.y;
     r[LEC_S_TT + 4] = s2.x; r[LEC_S_TT + 5] = s2.y; r[LEC_S_TT + 6] = s3.x; r[LEC_S_TT + 7] = s3.y;
     if (p.qspec) r[LEC_S_QT] = sq;
+    if (B) { r[LEC_S_VTT] = b0.x; r[LEC_S_WTT] = b0.y; r[LEC_S_EV] = b1.x; r[LEC_S_EW] = b1.y; }
     const double cw = L0.x, wphi = L0.y, c = L1.x, tn = L1.y, gra = L2.x, grb = L2.y, grc = L3.x;
 
     // rows j-1 / j+1 from the neighbouring lanes (the first and last row of the band see themselves)
@@ -351,43 +371,65 @@ __global__ void __launch_bounds__(64, 4) lec_spec_level_small_kernel(const SpecL
     if (lane < LEC_NLEVRAW - V_SIG) out[V_SIG + lane] = (lane == 0) ? sig : 0.0;
 }
 
-}  // namespace
+// a refusal of either call, under the call's own name
+int refuse(int code, const char* who, const char* what) {
+    char msg[256];
+    snprintf(msg, sizeof(msg), "%s: %s", who, what);
+    return lec_set_error(code, msg);
+}
 
-extern "C" int lec_level_spec_ring(const lec_level_spec_args* a) {
-    if (!a) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null args");
-    if (!a->rows_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null rows_d");
-    if (!a->spec_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null spec_d");
-    if (!a->box_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null box_d");
-    if (!a->lattab2_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null lattab2_d");
-    if (!a->levtab2_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null levtab2_d");
-    if (!a->am_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null am_d");
-    if (!a->levraw_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: null levraw_d");
-    if ((uintptr_t)a->rows_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: rows_d must be 16-byte aligned");
-    if ((uintptr_t)a->spec_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: spec_d must be 16-byte aligned");
-    if ((uintptr_t)a->lattab2_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: lattab2_d must be 16-byte aligned");
-    if (a->n_wave < 1) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: n_wave must be >= 1");
-    if (a->t_count < 1) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: t_count must be >= 1");
-    if (a->nl < 1) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: nl must be >= 1");
-    if (a->nyb < 2) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: nyb must be >= 2 (a band needs two rows)");
-    if (a->n_wave > LEC_MAX_WAVENUMBERS) return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_level_spec_ring: n_wave above LEC_MAX_WAVENUMBERS");
-    if (a->nl > LEC_MAX_LEVELS) return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_level_spec_ring: nl above LEC_MAX_LEVELS");
+// both calls: `who` names the call, `bspec` is lec_level_spec_b_ring's fourth input (checked by the caller) or null
+int level_spec(const lec_level_spec_args* a, const double* bspec, const char* who) {
+    if (!a) return refuse(LEC_ERR_ARG, who, "null args");
+    if (!a->rows_d) return refuse(LEC_ERR_ARG, who, "null rows_d");
+    if (!a->spec_d) return refuse(LEC_ERR_ARG, who, "null spec_d");
+    if (!a->box_d) return refuse(LEC_ERR_ARG, who, "null box_d");
+    if (!a->lattab2_d) return refuse(LEC_ERR_ARG, who, "null lattab2_d");
+    if (!a->levtab2_d) return refuse(LEC_ERR_ARG, who, "null levtab2_d");
+    if (!a->am_d) return refuse(LEC_ERR_ARG, who, "null am_d");
+    if (!a->levraw_d) return refuse(LEC_ERR_ARG, who, "null levraw_d");
+    if ((uintptr_t)a->rows_d % 16) return refuse(LEC_ERR_ARG, who, "rows_d must be 16-byte aligned");
+    if ((uintptr_t)a->spec_d % 16) return refuse(LEC_ERR_ARG, who, "spec_d must be 16-byte aligned");
+    if ((uintptr_t)a->lattab2_d % 16) return refuse(LEC_ERR_ARG, who, "lattab2_d must be 16-byte aligned");
+    if (a->n_wave < 1) return refuse(LEC_ERR_ARG, who, "n_wave must be >= 1");
+    if (a->t_count < 1) return refuse(LEC_ERR_ARG, who, "t_count must be >= 1");
+    if (a->nl < 1) return refuse(LEC_ERR_ARG, who, "nl must be >= 1");
+    if (a->nyb < 2) return refuse(LEC_ERR_ARG, who, "nyb must be >= 2 (a band needs two rows)");
+    if (a->n_wave > LEC_MAX_WAVENUMBERS) return refuse(LEC_ERR_UNSUPPORTED, who, "n_wave above LEC_MAX_WAVENUMBERS");
+    if (a->nl > LEC_MAX_LEVELS) return refuse(LEC_ERR_UNSUPPORTED, who, "nl above LEC_MAX_LEVELS");
     // one 64-lane workgroup per (n, t, k), and HIP takes fewer than 2^32 threads per launch
     if ((long long)a->n_wave * a->t_count * a->nl >= (1LL << 26))
-        return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_level_spec_ring: n_wave * t_count * nl must stay below 2^26 in one call (cut the series into several calls)");
+        return refuse(LEC_ERR_UNSUPPORTED, who, "n_wave * t_count * nl must stay below 2^26 in one call (cut the series into several calls)");
     const long long dense = (long long)a->t_count * a->nl * LEC_NLEVRAW;
     if (a->wave_stride != 0 && a->wave_stride < dense)
-        return lec_set_error(LEC_ERR_ARG, "lec_level_spec_ring: wave_stride must be 0 (dense) or at least t_count * nl * LEC_NLEVRAW");
+        return refuse(LEC_ERR_ARG, who, "wave_stride must be 0 (dense) or at least t_count * nl * LEC_NLEVRAW");
     SpecLevParams p;
-    p.rows = a->rows_d; p.spec = a->spec_d; p.qspec = a->qspec_d;
+    p.rows = a->rows_d; p.spec = a->spec_d; p.qspec = a->qspec_d; p.bspec = bspec;
     p.t_count = a->t_count; p.nl = a->nl; p.nyb = a->nyb; p.n_wave = a->n_wave;
     p.box = a->box_d; p.lattab2 = a->lattab2_d; p.levtab2 = a->levtab2_d; p.phi_scale = a->phi_scale;
     p.am = a->am_d; p.levraw = a->levraw_d; p.wstride = a->wave_stride ? a->wave_stride : dense;
     hipStream_t st = (hipStream_t)a->stream;
     const dim3 grid_tk((unsigned)(a->t_count * a->nl)), grid((unsigned)(a->n_wave * a->t_count * a->nl));
     hipLaunchKernelGGL(lec_spec_area_means_kernel, grid_tk, dim3(64), 0, st, p);
-    if (a->nyb <= kSmallRows) hipLaunchKernelGGL(lec_spec_level_small_kernel, grid, dim3(64), 0, st, p);
-    else hipLaunchKernelGGL(lec_spec_level_terms_kernel, grid, dim3(64), 0, st, p);
+    if (bspec) {
+        if (a->nyb <= kSmallRows) hipLaunchKernelGGL(lec_spec_level_small_kernel<true>, grid, dim3(64), 0, st, p);
+        else hipLaunchKernelGGL(lec_spec_level_terms_kernel<true>, grid, dim3(64), 0, st, p);
+    } else {
+        if (a->nyb <= kSmallRows) hipLaunchKernelGGL(lec_spec_level_small_kernel<false>, grid, dim3(64), 0, st, p);
+        else hipLaunchKernelGGL(lec_spec_level_terms_kernel<false>, grid, dim3(64), 0, st, p);
+    }
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
     return LEC_OK;
+}
+
+}  // namespace
+
+extern "C" int lec_level_spec_ring(const lec_level_spec_args* a) { return level_spec(a, nullptr, "lec_level_spec_ring"); }
+
+extern "C" int lec_level_spec_b_ring(const lec_level_spec_b_args* a) {
+    if (!a) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_b_ring: null args");
+    if (!a->bspec_d) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_b_ring: null bspec_d");
+    if ((uintptr_t)a->bspec_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_level_spec_b_ring: bspec_d must be 16-byte aligned");
+    return level_spec(&a->spec, a->bspec_d, "lec_level_spec_b_ring");
 }

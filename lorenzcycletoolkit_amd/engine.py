@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .constants import LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_PLACES, SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS
+from .constants import (LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_BUDGET_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_PLACES,
+                        SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS)
 
 
 @dataclass
@@ -42,6 +43,15 @@ class LECResult:
     spectrum_nl_total: Optional[torch.Tensor] = None   # [t_count, 2] fp64: the same for the whole eddy covariance (summed in physical space)
     spectrum_nl_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64: the total minus the N shares
     spectrum_nl_levels: Optional[torch.Tensor] = None  # [t_count, 2, N, nl] fp64
+    # compute(..., wavenumbers=N, spectrum_budget=True): the boundary terms BAe(n), BKe(n) (``rowspec_b``), the finite-difference
+    # tendencies dAe(n)/dt, dKe(n)/dt and the residuals RGe(n), RKe(n) of the wavenumbers 1 .. N (constants.SPECTRUM_BUDGET_*); the
+    # ``rest`` of each is formed from the ``rest`` columns in the same way
+    spectrum_b: Optional[torch.Tensor] = None                # [t_count, 2, N] fp64: BAe, BKe
+    spectrum_b_rest: Optional[torch.Tensor] = None           # [t_count, 2] fp64: the total minus the N shares
+    spectrum_tendency: Optional[torch.Tensor] = None         # [t_count, 2, N] fp64: dAe/dt, dKe/dt
+    spectrum_tendency_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64
+    spectrum_residual: Optional[torch.Tensor] = None         # [t_count, 2, N] fp64: RGe, RKe
+    spectrum_residual_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -58,6 +68,7 @@ def _ptr(t: Optional[torch.Tensor]):
 
 _LEC_S_TT = 6      # enum lec_stat: the eight eddy covariances [T'T'] .. [w'v'] are slots 6 .. 13 of a row record
 _LEC_S_QT = 15     # ... and [Q'T'] is slot 15
+_LEC_S_BUDGET = (16, 17, 20, 21)   # ... and [vT'T'] [wT'T'] [Ev] [Ew], the slots lec_rowspec_b_ring splits
 
 _KERNELS = {"auto": _lib.KERNEL_AUTO, "two_sweep": _lib.KERNEL_TWO_SWEEP, "row_sweep": _lib.KERNEL_ROW_SWEEP,
             "row_block": _lib.KERNEL_ROW_BLOCK, "box_tile": _lib.KERNEL_BOX_TILE, "box_plane": _lib.KERNEL_BOX_PLANE}
@@ -340,7 +351,7 @@ class LECEngine:
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
                 wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
-                spectrum_interactions: bool = False) -> LECResult:
+                spectrum_interactions: bool = False, spectrum_budget: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -369,7 +380,19 @@ class LECEngine:
         ``spectrum_interactions`` (with ``wavenumbers``): also ``spectrum_nl``, ``spectrum_nl_total``, ``spectrum_nl_rest`` and
         ``spectrum_nl_levels``, the non-linear eddy-eddy transfers S(n) (into Ae) and L(n) (into Ke) of the wavenumbers 1 .. N
         (``rowspec_nl`` and ``spectrum_level_stage`` on its records).  It changes no bit of anything else.
+        ``spectrum_budget`` (with ``wavenumbers`` and ``time_s``, at least two processed steps): also ``spectrum_b`` (BAe(n), BKe(n):
+        ``rowspec_b``, whose four shares enter the same stage-2 batch in slots 16, 17, 20, 21), ``spectrum_tendency`` (dAe(n)/dt,
+        dKe(n)/dt by ``tables.budgets_and_residuals``: np.gradient with dt = time_s[1] - time_s[0]) and ``spectrum_residual`` (RGe(n),
+        RKe(n)), each with its ``_rest``.  It changes no bit of anything else; both ``spectrum_fused`` forms give the same bits.
         """
+        if spectrum_budget:
+            if wavenumbers is None:
+                raise ValueError("spectrum_budget: BAe(n), BKe(n) and the residuals are part of the zonal-wavenumber spectra: give wavenumbers=N")
+            if time_s is None:
+                raise ValueError("spectrum_budget needs time_s (seconds): the tendencies are np.gradient with dt = time_s[1] - time_s[0]")
+            n_steps = (int(tair.shape[0]) - t_begin) if t_count is None else int(t_count)
+            if n_steps < 2 or np.asarray(time_s).size < 2:
+                raise ValueError("spectrum_budget: the tendencies are finite differences in time: at least 2 time steps")
         if spectrum_interactions and wavenumbers is None:
             raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
         if spectrum_fused and wavenumbers is None:
@@ -397,7 +420,9 @@ class LECEngine:
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
-                           interactions=spectrum_interactions)
+                           interactions=spectrum_interactions, budget=spectrum_budget)
+            if spectrum_budget:
+                self.spectrum_budget_terms(res, time_s)
         return res
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
@@ -547,6 +572,57 @@ class LECEngine:
                 timing.append((ev0, ev1))
         return nlspec, nltot
 
+    def rowspec_b(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes: PreparedBoxes,
+                  n: int, *, t_begin: int = 0, t_count: Optional[int] = None, out: Optional[torch.Tensor] = None,
+                  timing: Optional[list] = None) -> torch.Tensor:
+        """``lec_rowspec_b_ring``: bspec [t_count, nl, nyb, N, 4] fp64 -- the shares VTT(n), WTT(n), EV(n), EW(n) of the wavenumbers
+        1 .. N in slots 16, 17, 20, 21 of every row record of the ring's latitude band (the triple products behind BAe and BKe); VTT and
+        EV at the band's first and last row only, 0 elsewhere.  ``rows`` [t_count, nl, nyb, 32]: the ring pass's records of the same
+        steps [t_begin, t_begin + t_count).  ``out``: a caller-owned buffer; ``timing``: as ``rowspec``.  One call per time chunk: the
+        callers keep ``out`` within ``SPECTRUM_CHUNK_BYTES`` (``spectrum_chunk_steps``)."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        self._check_wavenumbers(n, boxes, nx)
+        n = int(n)
+        if t_count is None:
+            t_count = nt - t_begin
+        _, _, js, jn = boxes.boxes[0]
+        nyb = jn - js + 1
+        if (rows.shape != (t_count, nl, nyb, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or rows.device != tair.device
+                or not rows.is_contiguous()):
+            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb, 32] tensor on the fields' device: the ring pass's records of the same steps")
+        shape = (t_count, nl, nyb, n, 4)
+        bspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
+        if bspec.shape != shape or bspec.dtype != torch.float64 or bspec.device != tair.device or not bspec.is_contiguous():
+            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N, 4] tensor on the fields' device")
+        if self._twid is None:
+            self._twid = self._up(tables.twiddle_table(nx))
+        ba = _lib.RowspecBArgs(
+            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
+            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, rows_d=_ptr(rows), twid_d=_ptr(self._twid),
+            bspec_d=_ptr(bspec), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
+        with torch.cuda.device(tair.device):
+            if timing is not None:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _lib.check(self.lib.lec_rowspec_b_ring(C.byref(ba)), "lec_rowspec_b_ring")
+            if timing is not None:
+                ev1.record()
+                timing.append((ev0, ev1))
+        return bspec
+
+    def spectrum_budget_terms(self, res: LECResult, time_s) -> None:
+        """``res.spectrum_tendency*`` and ``res.spectrum_residual*`` from ``res.spectrum*`` and ``res.spectrum_b*`` of a whole series
+        (host arithmetic on [time, N] arrays by ``tables.spectrum_budgets``); ``time_s``: the run's time axis in seconds."""
+        if res.spectrum is None or res.spectrum_b is None:
+            raise ValueError("spectrum_budget_terms: a result of compute(..., wavenumbers=N, spectrum_budget=True)")
+        dev = res.spectrum.device
+        host = lambda x: x.cpu().numpy()
+        b = tables.spectrum_budgets(host(res.spectrum), host(res.spectrum_rest), host(res.spectrum_b), host(res.spectrum_b_rest), time_s)
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        res.spectrum_tendency, res.spectrum_tendency_rest = up(b["tendency"]), up(b["tendency_rest"])
+        res.spectrum_residual, res.spectrum_residual_rest = up(b["residual"]), up(b["residual_rest"])
+
     def spectrum_nl_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int) -> int:
         """Time steps per ``rowspec_nl`` call: the chunk's records ([tc, nl, nyb, N + 1, 8] fp64, shares and total) stay within
         ``SPECTRUM_CHUNK_BYTES``."""
@@ -585,17 +661,18 @@ class LECEngine:
         res.spectrum_nl_rest = res.spectrum_nl_total - res.spectrum_nl.sum(dim=2)
         res.spectrum_nl_levels = shares.levels.reshape(n1, t_count, _lib.LEC_NLEVTAB, nl)[:n][:, :, li].permute(1, 2, 0, 3).contiguous()
 
-    def spectrum_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int) -> int:
-        """Time steps per spectral call of the fused form: the chunk's ``spec`` records ([tc, nl, nyb, N, 8] fp64) stay within
-        ``SPECTRUM_CHUNK_BYTES``."""
-        return max(1, min(int(t_count), self.SPECTRUM_CHUNK_BYTES // (nl * nyb * n * 64)))
+    def spectrum_chunk_steps(self, t_count: int, nl: int, nyb: int, n: int, budget: bool = False) -> int:
+        """Time steps per spectral call of the fused form: the chunk's ``spec`` records ([tc, nl, nyb, N, 8] fp64) -- with ``budget``
+        together with ``rowspec_b``'s ([tc, nl, nyb, N, 4]) -- stay within ``SPECTRUM_CHUNK_BYTES``."""
+        return max(1, min(int(t_count), self.SPECTRUM_CHUNK_BYTES // (nl * nyb * n * (96 if budget else 64))))
 
     def spectrum_level_stage(self, rows: torch.Tensor, spec: torch.Tensor, qspec: Optional[torch.Tensor], boxes, levraw_out: torch.Tensor, *,
-                             phi_scale: float = 1.0) -> None:
+                             phi_scale: float = 1.0, bspec: Optional[torch.Tensor] = None) -> None:
         """``lec_level_spec_ring``: rows [t_count, nl, nyb, 32], ``spec`` [t_count, nl, nyb, N, 8] (``rowspec``) and ``qspec``
         [t_count, nl, nyb, N] (``rowspec_q``) or None -> ``levraw_out`` [N, t_count, nl, 40]: what ``level_stage`` gives on the row
         records that carry wavenumber n's shares in slots 6 .. 13 (and 15), for every n, without those records being assembled.
-        ``levraw_out`` may be a time slice of a larger [N, T, nl, 40] tensor (contiguous in its last two dimensions)."""
+        ``levraw_out`` may be a time slice of a larger [N, T, nl, 40] tensor (contiguous in its last two dimensions).  ``bspec``
+        [t_count, nl, nyb, N, 4] (``rowspec_b``): ``lec_level_spec_b_ring``, slots 16, 17, 20, 21 replaced too."""
         t_count, nl = int(rows.shape[0]), int(rows.shape[1])
         boxes, bt, dev = self._stage2_input(rows, boxes)
         if len(boxes) != 1 or not bt.ring:
@@ -608,6 +685,9 @@ class LECEngine:
         if qspec is not None and (qspec.shape != (t_count, nl, nyb, n) or qspec.dtype != torch.float64 or qspec.device != rows.device
                                   or not qspec.is_contiguous()):
             raise ValueError("qspec must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the rows' device")
+        if bspec is not None and (bspec.shape != (t_count, nl, nyb, n, 4) or bspec.dtype != torch.float64 or bspec.device != rows.device
+                                  or not bspec.is_contiguous()):
+            raise ValueError("bspec must be a contiguous fp64 [t_count, nl, nyb, N, 4] tensor on the rows' device")
         step = nl * _lib.LEC_NLEVRAW
         if (levraw_out.shape != (n, t_count, nl, _lib.LEC_NLEVRAW) or levraw_out.dtype != torch.float64 or levraw_out.device != rows.device
                 or tuple(levraw_out.stride()[2:]) != (_lib.LEC_NLEVRAW, 1) or (t_count > 1 and levraw_out.stride(1) != step)
@@ -621,10 +701,15 @@ class LECEngine:
             am_d=_ptr(am), levraw_d=_ptr(levraw_out), wave_stride=int(levraw_out.stride(0)) if n > 1 else 0,
             stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
         with torch.cuda.device(rows.device):
-            _lib.check(self.lib.lec_level_spec_ring(C.byref(la)), "lec_level_spec_ring")
+            if bspec is not None:
+                lb = _lib.LevelSpecBArgs(spec=la, bspec_d=_ptr(bspec))
+                _lib.check(self.lib.lec_level_spec_b_ring(C.byref(lb)), "lec_level_spec_b_ring")
+            else:
+                _lib.check(self.lib.lec_level_spec_ring(C.byref(la)), "lec_level_spec_ring")
 
     def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
-                  drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False, interactions: bool = False) -> None:
+                  drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False, interactions: bool = False,
+                  budget: bool = False) -> None:
         """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
         whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
         (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
@@ -633,7 +718,9 @@ class LECEngine:
         records holds the wavenumber's share of [Q'T'] too (``rowspec_q``), which only Ge reads: Ge(n) and its table come out of the
         same batch, and nothing else of it moves.  ``fused``: no assembled records -- ``spectrum_level_stage`` reads the ring
         pass's records and the chunk's ``spec`` / ``qspec`` (the chunk is bounded by ``spec``), the same bits.  ``interactions``: S(n)
-        and L(n) by ``spectrum_nl_stage`` in time chunks of its own records, a batch of its own."""
+        and L(n) by ``spectrum_nl_stage`` in time chunks of its own records, a batch of its own.  ``budget``: slots 16, 17, 20, 21 of
+        the same records hold ``rowspec_b``'s shares, which only the BAe and BKe columns read: BAe(n) and BKe(n) come out of the same
+        batch, and nothing else of it moves."""
         t_count, nl, nyb = (int(x) for x in rows.shape[:3])
         dev = rows.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -643,22 +730,27 @@ class LECEngine:
             self._spectrum_nl_shares(res, levraw_nl, boxes, drop_any_time)
         levraw = torch.empty((n, t_count, nl, _lib.LEC_NLEVRAW), **f64)
         if fused:
-            tc = self.spectrum_chunk_steps(t_count, nl, nyb, n)
+            tc = self.spectrum_chunk_steps(t_count, nl, nyb, n, budget)
             spec = torch.empty((tc, nl, nyb, n, 8), **f64)
             qspec = torch.empty((tc, nl, nyb, n), **f64) if generation is not None else None
+            bspec = torch.empty((tc, nl, nyb, n, 4), **f64) if budget else None
             for a in range(0, t_count, tc):
                 b = min(a + tc, t_count)
                 sp = self.rowspec(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=b - a, spec_out=spec[:b - a])
                 qs = None
                 if generation is not None:
                     qs = self.rowspec_q(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=b - a, out=qspec[:b - a], **generation)
-                self.spectrum_level_stage(rows[a:b], sp, qs, boxes, levraw[:, a:b], phi_scale=phi_scale)
-            self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None)
+                bs = None
+                if budget:
+                    bs = self.rowspec_b(tair, u, v, omega, rows[a:b], boxes, n, t_begin=t_begin + a, t_count=b - a, out=bspec[:b - a])
+                self.spectrum_level_stage(rows[a:b], sp, qs, boxes, levraw[:, a:b], phi_scale=phi_scale, bspec=bs)
+            self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None, budget)
             return
         tc = max(1, min(t_count, self.SPECTRUM_CHUNK_BYTES // (n * nl * nyb * _lib.LEC_NSTAT * 8)))
         asm = torch.empty((n, tc, nl, nyb, _lib.LEC_NSTAT), **f64)
         spec = torch.empty((tc, nl, nyb, n, 8), **f64)
         qspec = torch.empty((tc, nl, nyb, n), **f64) if generation is not None else None
+        bspec = torch.empty((tc, nl, nyb, n, 4), **f64) if budget else None
         part = torch.empty((n, tc, nl, _lib.LEC_NLEVRAW), **f64)
         for a in range(0, t_count, tc):
             b = min(a + tc, t_count)
@@ -670,6 +762,9 @@ class LECEngine:
             if generation is not None:
                 qs = self.rowspec_q(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=c, out=qspec[:c], **generation)
                 rec[..., _LEC_S_QT] = qs.permute(3, 0, 1, 2)
+            if budget:
+                bs = self.rowspec_b(tair, u, v, omega, rows[a:b], boxes, n, t_begin=t_begin + a, t_count=c, out=bspec[:c]).permute(3, 0, 1, 2, 4)
+                rec.index_copy_(4, torch.as_tensor(_LEC_S_BUDGET, device=dev), bs)
             if c == tc:
                 self.level_stage(rec.reshape(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, part.view(n * c, nl, _lib.LEC_NLEVRAW), phi_scale=phi_scale)
                 levraw[:, a:b] = part
@@ -677,9 +772,10 @@ class LECEngine:
                 last = torch.empty((n * c, nl, _lib.LEC_NLEVRAW), **f64)
                 self.level_stage(rec.contiguous().view(n * c, nl, nyb, _lib.LEC_NSTAT), boxes, last, phi_scale=phi_scale)
                 levraw[:, a:b] = last.view(n, c, nl, _lib.LEC_NLEVRAW)
-        self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None)
+        self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None, budget)
 
-    def _spectrum_shares(self, res: LECResult, levraw: torch.Tensor, boxes, drop_any_time: Optional[bool], generation: bool) -> None:
+    def _spectrum_shares(self, res: LECResult, levraw: torch.Tensor, boxes, drop_any_time: Optional[bool], generation: bool,
+                         budget: bool = False) -> None:
         """The tail of the spectra: ``levraw`` [N, t_count, nl, 40] of all wavenumbers and steps -> ONE vertical half over the (n, step)
         batch and ``res.spectrum*`` (``res`` holds the totals)."""
         n, t_count, nl = (int(x) for x in levraw.shape[:3])
@@ -695,6 +791,10 @@ class LECEngine:
             res.spectrum_ge = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, ge].permute(1, 0).contiguous()
             res.spectrum_ge_levels = shares.levels.reshape(n, t_count, _lib.LEC_NLEVTAB, nl)[:, :, gl].permute(1, 0, 2).contiguous()
             res.spectrum_ge_rest = res.scalars[:, ge] - res.spectrum_ge.sum(dim=1)
+        if budget:
+            bi = torch.as_tensor([SCALAR_TERMS.index(x) for x in SPECTRUM_BUDGET_TERMS], device=dev)
+            res.spectrum_b = shares.scalars.reshape(n, t_count, _lib.LEC_NSCALAR)[:, :, bi].permute(1, 2, 0).contiguous()
+            res.spectrum_b_rest = res.scalars[:, bi] - res.spectrum_b.sum(dim=2)
 
     def rowstats(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor,
                  geopt: Optional[torch.Tensor], boxes: Sequence[Sequence[int]], *,

@@ -62,13 +62,16 @@ class BoxData:
     ``spectrum_interactions`` (with ``wavenumbers``): also ``spectrum_nl`` [time, 2, N], ``spectrum_nl_total`` [time, 2],
     ``spectrum_nl_rest`` [time, 2] and ``spectrum_nl_levels`` [time, 2, N, level], the non-linear eddy-eddy transfers S(n) into Ae and
     L(n) into Ke (``lec_rowspec_nl_ring``).
+    ``spectrum_budget`` (with ``wavenumbers``; at least two time steps): also ``spectrum_b`` [time, 2, N] (BAe(n), BKe(n):
+    ``lec_rowspec_b_ring``), ``spectrum_tendency`` [time, 2, N] (dAe(n)/dt, dKe(n)/dt) and ``spectrum_residual`` [time, 2, N] (RGe(n),
+    RKe(n)), each with its ``_rest`` [time, 2].
     """
 
     def __init__(self, data: ds.LECDataset, variable_list_df: pd.DataFrame, western_limit=None, eastern_limit=None,
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
-                 spectrum_generation: bool = False, spectrum_interactions: bool = False):
+                 spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -98,6 +101,14 @@ class BoxData:
         self.spectrum_nl = self.spectrum_nl_total = self.spectrum_nl_rest = self.spectrum_nl_levels = None
         if self.spectrum_interactions and wavenumbers is None:
             raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
+        self.spectrum_budget = bool(spectrum_budget)
+        self.spectrum_b = self.spectrum_b_rest = self.spectrum_tendency = self.spectrum_tendency_rest = None
+        self.spectrum_residual = self.spectrum_residual_rest = None
+        if self.spectrum_budget:
+            if wavenumbers is None:
+                raise ValueError("spectrum_budget: BAe(n), BKe(n) and the residuals are part of the zonal-wavenumber spectra: give wavenumbers=N")
+            if len(data.time) < 2:
+                raise ValueError("spectrum_budget: the tendencies are finite differences in time: at least 2 time steps")
         self.args = args
         self.results_subdirectory = results_subdirectory
         self.results_subdirectory_vertical_levels = results_subdirectory_vertical_levels
@@ -149,7 +160,8 @@ class BoxData:
                                                              ring=self.periodic,
                                                              **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
                                                              **({"spectrum_generation": True} if self.spectrum_generation else {}),
-                                                             **({"spectrum_interactions": True} if self.spectrum_interactions else {}))
+                                                             **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
+                                                             **({"spectrum_budget": True} if self.spectrum_budget else {}))
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)
@@ -180,6 +192,10 @@ class BoxData:
             self.spectrum_nl_total = self.result.spectrum_nl_total.cpu().numpy()
             self.spectrum_nl_rest = self.result.spectrum_nl_rest.cpu().numpy()
             self.spectrum_nl_levels = self.result.spectrum_nl_levels.cpu().numpy()
+        if self.result.spectrum_b is not None:
+            for name in ("spectrum_b", "spectrum_tendency", "spectrum_residual"):
+                setattr(self, name, getattr(self.result, name).cpu().numpy())
+                setattr(self, name + "_rest", getattr(self.result, name + "_rest").cpu().numpy())
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -216,12 +232,13 @@ class BoxData:
             nyb = max(b[3] - b[2] + 1 for b in self.boxes)
             boxes = self.engine.prepare_boxes(boxes, nyb_min=nyb)
         return self.engine.compute(cubes[0], cubes[1], cubes[2], cubes[3], cubes[4], boxes,
-                                   time_s=data.time_s[h0:h1] if dTdt is None else None, dTdt=dTdt_dev, phi_scale=phi_scale,
-                                   t_begin=t0 - h0, t_count=t1 - t0, per_step_boxes=self.per_step_boxes,
+                                   time_s=data.time_s[h0:h1] if dTdt is None or self.spectrum_budget else None, dTdt=dTdt_dev,
+                                   phi_scale=phi_scale, t_begin=t0 - h0, t_count=t1 - t0, per_step_boxes=self.per_step_boxes,
                                    drop_any_time=not self.per_step_boxes, merge_dropmask=merge, out=out,
                                    **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
                                    **({"spectrum_generation": True} if self.spectrum_generation else {}),
-                                   **({"spectrum_interactions": True} if self.spectrum_interactions else {}))
+                                   **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
+                                   **({"spectrum_budget": True} if self.spectrum_budget else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -275,9 +292,10 @@ def wavenumbers_check(n: int, nx: int) -> None:
 
 def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
     """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck -- and Ge, and the non-linear transfers S and L (W m-2, positive: wavenumber
-    n gains), when their spectra were asked for --: one row per time step -- the time labels and number formatting of the per-level
+    n gains), and the budget's BAe, BKe, dAedt, dKedt, RGe, RKe, when their spectra were asked for --: one row per time step -- the time labels and number formatting of the per-level
     tables --, columns 1 .. N and ``rest`` (the total minus the N shares), in the units of the results CSV."""
-    from .constants import SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_TERMS, SPECTRUM_TERMS
+    from .constants import (SPECTRUM_BUDGET_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_TERMS, SPECTRUM_RESIDUAL_TERMS,
+                            SPECTRUM_TENDENCY_FILES, SPECTRUM_TERMS)
     os.makedirs(directory, exist_ok=True)
     n = box_obj.spectrum.shape[2]
     header = ",".join([str(time_name)] + [str(k) for k in range(1, n + 1)] + ["rest"]) + "\n"
@@ -287,6 +305,11 @@ def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> N
         files.append((SPECTRUM_GENERATION_TERM, box_obj.spectrum_ge, box_obj.spectrum_ge_rest[:, None]))
     if getattr(box_obj, "spectrum_nl", None) is not None:
         files += [(term, box_obj.spectrum_nl[:, i, :], box_obj.spectrum_nl_rest[:, i: i + 1]) for i, term in enumerate(SPECTRUM_INTERACTION_TERMS)]
+    if getattr(box_obj, "spectrum_b", None) is not None:
+        for names, field in ((SPECTRUM_BUDGET_TERMS, "spectrum_b"), (SPECTRUM_TENDENCY_FILES, "spectrum_tendency"),
+                             (SPECTRUM_RESIDUAL_TERMS, "spectrum_residual")):
+            shares_, rest_ = getattr(box_obj, field), getattr(box_obj, field + "_rest")
+            files += [(term, shares_[:, i, :], rest_[:, i: i + 1]) for i, term in enumerate(names)]
     for term, shares, rest in files:
         table = np.concatenate([shares, rest], axis=1)
         path = os.path.join(directory, f"{term}_n.csv")
@@ -495,12 +518,18 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
     interactions = bool(getattr(args, "wavenumbers_interactions", False))
     if interactions and wavenumbers is None:
         raise ValueError("--wavenumbers-interactions goes with --wavenumbers N")
+    budget = bool(getattr(args, "wavenumbers_budget", False))
+    if budget and wavenumbers is None:
+        raise ValueError("--wavenumbers-budget goes with --wavenumbers N")
+    if budget and len(data.time) < 2:
+        raise ValueError("--wavenumbers-budget: the tendencies are finite differences in time: the series needs at least 2 time steps")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
                           results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
-                          spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}))
+                          spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}),
+                          **({"spectrum_budget": True} if budget else {}))
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -529,6 +558,10 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         if interactions:
             app_logger.info(f"--wavenumbers-interactions: the non-linear eddy-eddy transfers S(n) into Ae and L(n) into Ke, the advective "
                             f"tendencies evaluated at every point of the ring's rows (lec_rowspec_nl_kernel: N = {int(wavenumbers)}, "
+                            f"nx = {len(data.lon)}); written to {spectrum_directory}")
+        if budget:
+            app_logger.info(f"--wavenumbers-budget: BAe(n) and BKe(n) from the shares of the four triple products of the ring's rows, "
+                            f"the tendencies dAe(n)/dt, dKe(n)/dt and the residuals RGe(n), RKe(n) (lec_rowspec_b_kernel: N = {int(wavenumbers)}, "
                             f"nx = {len(data.lon)}); written to {spectrum_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)

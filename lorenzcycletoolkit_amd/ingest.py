@@ -823,7 +823,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
                  slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
                  ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False,
-                 spectrum_interactions: bool = False) -> LECResult:
+                 spectrum_interactions: bool = False, spectrum_budget: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -852,7 +852,12 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     ``stats["spectrum_buffer_bytes"]``: that buffer and the spectral records.
     ``spectrum_interactions`` (with ``wavenumbers``): also S(n) and L(n) of ``LECEngine.compute(..., spectrum_interactions=True)``, the
     same bits: every sub-chunk goes through ``spectrum_nl_stage`` (``rowspec_nl`` has no time stencil: no halo).
+    ``spectrum_budget`` (with ``wavenumbers``; at least two time steps): also BAe(n), BKe(n), the tendencies and the residuals of
+    ``LECEngine.compute(..., spectrum_budget=True)``, the same bits: every sub-chunk goes through ``rowspec_b`` beside ``rowspec`` (no
+    time stencil: no halo) and ``lec_level_spec_b_ring``; tendencies and residuals are formed once the series' [T, N] shares exist.
     """
+    if spectrum_budget and wavenumbers is None:
+        raise ValueError("spectrum_budget: BAe(n), BKe(n) and the residuals are part of the zonal-wavenumber spectra: give wavenumbers=N")
     if spectrum_interactions and wavenumbers is None:
         raise ValueError("spectrum_interactions: S(n) and L(n) are part of the zonal-wavenumber spectra: give wavenumbers=N")
     if ring and per_step_boxes:
@@ -883,6 +888,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         raise ValueError("dT/dt by finite differences needs at least 2 time steps")
     if wavenumbers is not None:
         engine._check_wavenumbers(wavenumbers, engine.prepare_boxes(boxes, ring=True), nx)
+    if spectrum_budget and nt < 2:
+        raise ValueError("spectrum_budget: the tendencies are finite differences in time: at least 2 time steps")
     t0, t1 = (0, nt) if t_range is None else (int(t_range[0]), int(t_range[1]))
     if not (0 <= t0 < t1 <= nt):
         raise ValueError("t_range outside the series")
@@ -994,9 +1001,10 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         # the spectral records of a sub-chunk, or of a piece of one (1.7 GB per 37 x 721 time step at N = 64), and the series' levraw
         # of every wavenumber
         nw = int(wavenumbers)
-        spec_steps = engine.spectrum_chunk_steps(dec_steps, nl, bt.nyb_max, nw)
+        spec_steps = engine.spectrum_chunk_steps(dec_steps, nl, bt.nyb_max, nw, spectrum_budget)
         spec = torch.empty((spec_steps, nl, bt.nyb_max, nw, 8), dtype=torch.float64, device=dev)
         qspec = torch.empty((spec_steps, nl, bt.nyb_max, nw), dtype=torch.float64, device=dev) if spectrum_generation else None
+        bspec = torch.empty((spec_steps, nl, bt.nyb_max, nw, 4), dtype=torch.float64, device=dev) if spectrum_budget else None
         levraw_spec = torch.empty((nw, t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
         if spectrum_interactions:
             nl_steps = engine.spectrum_nl_chunk_steps(dec_steps, nl, bt.nyb_max, nw)
@@ -1079,7 +1087,11 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                     qs = None
                     if spectrum_generation:
                         qs = engine.rowspec_q(*fields, fixed_box, nw, tcoef=kw["tcoef"], t_begin=kw["t_begin"] + a, t_count=b - a, out=qspec[:b - a])
-                    engine.spectrum_level_stage(rows[a:b], sp, qs, fixed_box, levraw_spec[:, s0 - t0 + a: s0 - t0 + b], phi_scale=phi_scale)
+                    bs = None
+                    if spectrum_budget:
+                        bs = engine.rowspec_b(*fields, rows[a:b], fixed_box, nw, t_begin=kw["t_begin"] + a, t_count=b - a, out=bspec[:b - a])
+                    engine.spectrum_level_stage(rows[a:b], sp, qs, fixed_box, levraw_spec[:, s0 - t0 + a: s0 - t0 + b], phi_scale=phi_scale,
+                                                bspec=bs)
                 if spectrum_interactions:
                     engine.spectrum_nl_stage(*fields, rows[:n], fixed_box, nw, levraw_nl[:, s0 - t0: s1 - t0], t_begin=kw["t_begin"],
                                              phi_scale=phi_scale, buffers=nl_buffers)
@@ -1088,7 +1100,9 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     res = engine.vertical_stage(levraw, own_boxes if per_step_boxes else fixed_box, drop_any_time=not per_step_boxes,
                                 merge_dropmask=merge_dropmask, out=out)
     if wavenumbers is not None:
-        engine._spectrum_shares(res, levraw_spec, fixed_box, True, spectrum_generation)
+        engine._spectrum_shares(res, levraw_spec, fixed_box, True, spectrum_generation, spectrum_budget)
+        if spectrum_budget:
+            engine.spectrum_budget_terms(res, time_s)
         if spectrum_interactions:
             engine._spectrum_nl_shares(res, levraw_nl, fixed_box, True)
     on_device, reg_stats = pipe.finish()
@@ -1101,7 +1115,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
         stats.update(row_record_bytes=rows.numel() * 8, levraw_bytes=levraw.numel() * 8, device_buffer_bytes=int(mem_setup))
         if wavenumbers is not None:
             stats.update(spectrum_levraw_bytes=levraw_spec.numel() * 8,
-                         spectrum_buffer_bytes=(spec.numel() + (qspec.numel() if qspec is not None else 0)) * 8)
+                         spectrum_buffer_bytes=(spec.numel() + (qspec.numel() if qspec is not None else 0)
+                                                + (bspec.numel() if bspec is not None else 0)) * 8)
             if spectrum_interactions:
                 stats.update(spectrum_nl_levraw_bytes=levraw_nl.numel() * 8, spectrum_nl_buffer_bytes=(nl_buffers[0].numel() + nl_buffers[1].numel()) * 8)
         torch.cuda.synchronize(dev)

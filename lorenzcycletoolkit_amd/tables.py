@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .constants import KAPPA, P0_PA, RE
+from .constants import KAPPA, P0_PA, RE, SPECTRUM_BUDGET_TERMS, SPECTRUM_RESIDUAL_TERMS, SPECTRUM_TENDENCY_TERMS, SPECTRUM_TERMS
 
 
 def gradient_coefs(x: np.ndarray) -> np.ndarray:
@@ -239,3 +239,31 @@ def budgets_and_residuals(scalars: dict, time_s: np.ndarray, residuals: bool = T
         out["RGe"] = out["∂Ae/∂t (finite diff.)"] - out["Ca"] + out["Ce"] - out["BAe"]
         out["RKe"] = out["∂Ke/∂t (finite diff.)"] - out["Ce"] + out["Ck"] - out["BKe"]
     return out
+
+
+def spectrum_budgets(spectrum: np.ndarray, spectrum_rest: np.ndarray, spectrum_b: np.ndarray, spectrum_b_rest: np.ndarray,
+                     time_s: np.ndarray) -> dict:
+    """The per-wavenumber budget of the eddy reservoirs: ``spectrum`` [time, 5, N] (Ae, Ke, Ca, Ce, Ck of SPECTRUM_TERMS) and
+    ``spectrum_b`` [time, 2, N] (BAe, BKe) with their ``rest`` columns -> ``tendency`` [time, 2, N] (dAe(n)/dt, dKe(n)/dt),
+    ``residual`` [time, 2, N] (RGe(n), RKe(n)) and ``tendency_rest`` / ``residual_rest`` [time, 2].  Every column -- a wavenumber or
+    the rest -- goes through ``budgets_and_residuals``, the function that forms the totals' budget, with the zonal reservoir's terms 0:
+    np.gradient with dt = time_s[1] - time_s[0], RGe = dAe/dt - Ca + Ce - BAe, RKe = dKe/dt - Ce + Ck - BKe.  Linear, so the columns and
+    the rest sum to the totals' figures to rounding."""
+    spectrum, spectrum_b = np.asarray(spectrum, dtype=np.float64), np.asarray(spectrum_b, dtype=np.float64)
+    nt, _, n = spectrum.shape
+    if nt < 2 or np.asarray(time_s).size < 2:
+        raise ValueError("the tendencies are finite differences in time: at least 2 time steps")
+    cols = np.concatenate([spectrum, np.asarray(spectrum_rest, dtype=np.float64)[:, :, None]], axis=2)
+    bcols = np.concatenate([spectrum_b, np.asarray(spectrum_b_rest, dtype=np.float64)[:, :, None]], axis=2)
+    tend, resid = np.empty((nt, 2, n + 1)), np.empty((nt, 2, n + 1))
+    zero = np.zeros(nt)
+    for i in range(n + 1):
+        col = {term: cols[:, k, i] for k, term in enumerate(SPECTRUM_TERMS)}
+        col.update({term: bcols[:, k, i] for k, term in enumerate(SPECTRUM_BUDGET_TERMS)})
+        col.update({term: zero for term in ("Az", "Kz", "Cz", "BAz", "BKz")})
+        out = budgets_and_residuals(col, time_s, residuals=True)
+        for k, term in enumerate(SPECTRUM_TENDENCY_TERMS):
+            tend[:, k, i] = out[f"∂{term}/∂t (finite diff.)"]
+        for k, term in enumerate(SPECTRUM_RESIDUAL_TERMS):
+            resid[:, k, i] = out[term]
+    return {"tendency": tend[:, :, :n], "tendency_rest": tend[:, :, n], "residual": resid[:, :, :n], "residual_rest": resid[:, :, n]}

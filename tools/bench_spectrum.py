@@ -3,7 +3,7 @@
 ``lec_rowstats_ring`` on the same cubes -- a global 37 x 721 x 1440 fp64 grid, box +-89.75 degrees over all longitudes -- and
 ``LECEngine.compute(..., wavenumbers=N)`` next to the same ``compute`` without it, for N = 8, 20 and 64.
 
-    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--generation] [--fused] [--other NAME=PATH ...] [--out FILE]
+    python tools/bench_spectrum.py [--steps 2] [--rounds 3] [--repeat 5] [--n 8 20 64] [--generation] [--fused] [--budget] [--other NAME=PATH ...] [--out FILE]
 
 The calls are timed with HIP events around the call (median of ``--repeat`` after a warm-up) and ALTERNATE within a round; ``--rounds``
 rounds.  Reported per N: the spectral pass's time, its ratio to the ring pass, and the fp64 rate it achieves on the operations the
@@ -16,7 +16,12 @@ rounds, of this library and of every ``--other`` one, as ``specq_N<n>``: its rat
 ``spectrum_generation=True`` next to ``compute`` with the wavenumbers alone.  ``--fused``: ``compute(..., spectrum_fused=True)`` (stage 2 of
 the spectra by ``lec_level_spec_ring``, no assembled records) in the same rounds next to the assembled form: both medians, what the fused
 form saves per step, the spread of each between the rounds (largest minus smallest), and the bytes of the chunk's spectral records next
-to the bytes of the assembled records the other form would hold at the same chunk size.  One JSON line; ``--out`` writes it to a file."""
+to the bytes of the assembled records the other form would hold at the same chunk size.  ``--budget``: ``lec_rowspec_b_ring`` (the shares
+of the four triple products behind BAe(n) and BKe(n)) as ``specb_N<n>``, with ``lec_rowspec_nl_ring`` (``specnl_N<n>``) and
+``lec_rowspec_q_ring`` (``specq_N<n>``) timed in the same rounds beside it: ms per step, its ratio to either, and the part of the vector
+fp64 FMA rate (half the peak: 39.3 T FMA/s) that its 18 FMAs per (wall row, column, n) and 12 per (interior row, column, n) amount to --
+a count from the shapes; of every ``--other`` library that exports the call too (another trip length), with the largest difference of
+its records; and ``compute`` with ``spectrum_budget=True`` next to ``compute`` with the wavenumbers alone.  One JSON line; ``--out`` writes it to a file."""
 import argparse
 import ctypes as C
 import json
@@ -40,6 +45,7 @@ def main():
     ap.add_argument("--other", nargs="*", default=[], metavar="NAME=PATH")
     ap.add_argument("--generation", action="store_true", help="also time lec_rowspec_q_ring (the shares of [Q'T'])")
     ap.add_argument("--fused", action="store_true", help="also time compute(..., spectrum_fused=True) next to the assembled form")
+    ap.add_argument("--budget", action="store_true", help="also time lec_rowspec_b_ring beside lec_rowspec_nl_ring and lec_rowspec_q_ring")
     ap.add_argument("--no-compute", action="store_true", help="time the passes only, not the whole compute calls")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
@@ -71,6 +77,8 @@ def main():
         name, path = item.split("=", 1)
         o = C.CDLL(path)
         o.lec_rowspec_ring.restype, o.lec_rowspec_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecArgs)]
+        if a.budget and hasattr(o, "lec_rowspec_b_ring"):
+            o.lec_rowspec_b_ring.restype, o.lec_rowspec_b_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecBArgs)]
         if a.generation:
             o.lec_rowspec_q_ring.restype, o.lec_rowspec_q_ring.argtypes = C.c_int, [C.POINTER(_lib.RowspecQArgs)]
         others.append((name, o))
@@ -93,6 +101,19 @@ def main():
         if which.lec_rowspec_q_ring(C.byref(qa)):
             raise RuntimeError(f"lec_rowspec_q_ring failed: {lib.lec_last_error()}")
 
+    def specb_call(which, n, out):
+        ba = _lib.RowspecBArgs(tair_d=ptr(T), u_d=ptr(U), v_d=ptr(V), omega_d=ptr(W), dtype=_lib.LEC_F64, nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0,
+                               t_count=nt, js=1, jn=ny - 2, n_wave=n, rows_d=ptr(rows), twid_d=ptr(twid), bspec_d=ptr(out), stream=stream)
+        if which.lec_rowspec_b_ring(C.byref(ba)):
+            raise RuntimeError(f"lec_rowspec_b_ring failed: {lib.lec_last_error()}")
+
+    def specnl_call(n, out, tot):
+        na = _lib.RowspecNlArgs(tair_d=ptr(T), u_d=ptr(U), v_d=ptr(V), omega_d=ptr(W), dtype=_lib.LEC_F64, nt=nt, nl=nl, ny=ny, nx=nx, t_begin=0,
+                                t_count=nt, js=1, jn=ny - 2, n_wave=n, rows_d=ptr(rows), twid_d=ptr(twid), lattab_d=ptr(lat5), ptab_d=ptr(ptab),
+                                inv_hdeg=float(ring.bt.boxtab[0, 2]), nlspec_d=ptr(out), nltot_d=ptr(tot), stream=stream)
+        if lib.lec_rowspec_nl_ring(C.byref(na)):
+            raise RuntimeError(f"lec_rowspec_nl_ring failed: {lib.lec_last_error()}")
+
     def timed(fn):
         fn()
         torch.cuda.synchronize()
@@ -110,21 +131,35 @@ def main():
            "csrc_sha": _lib.source_digest(), "fp64_vector_peak_TFLOPs": FP64_VECTOR_PEAK_TFLOPS, "n": a.n}
     rows = torch.empty((nt, nl, nyb, _lib.LEC_NSTAT), dtype=torch.float64, device=dev)
     calls = [("ring_pass", lambda: eng.rowstats(T, U, V, W, P, ring, time_s=time_s, rows_out=rows))]
-    bufs, qbufs = {}, {}
+    bufs, qbufs, bbufs = {}, {}, {}
+    with_q = a.generation or (a.budget and nt > 1)
+    if a.budget:
+        lat5 = eng._up(tables.nl_lat_table(ring.bt.lattab[0], lat[1:ny - 1]))
+        ptab = eng._up(tables.pressure_coefs(level))
+        nltot = torch.empty((nt, nl, nyb, 8), dtype=torch.float64, device=dev)
     for n in a.n:
         bufs[n] = torch.empty((nt, nl, nyb, n, 8), dtype=torch.float64, device=dev)
         calls.append((f"spec_N{n}", lambda n=n: spec_call(lib, n, bufs[n])))
         for name, o in others:
             calls.append((f"spec_N{n}_{name}", lambda n=n, o=o: spec_call(o, n, bufs[n])))
-        if a.generation:
+        if a.budget:
+            bbufs[n] = torch.empty((nt, nl, nyb, n, 4), dtype=torch.float64, device=dev)
+            calls.append((f"specb_N{n}", lambda n=n: specb_call(lib, n, bbufs[n])))
+            for name, o in others:
+                if hasattr(o, "lec_rowspec_b_ring"):
+                    calls.append((f"specb_N{n}_{name}", lambda n=n, o=o: specb_call(o, n, bbufs[n])))
+            calls.append((f"specnl_N{n}", lambda n=n: specnl_call(n, bufs[n], nltot)))
+        if with_q:
             qbufs[n] = torch.empty((nt, nl, nyb, n), dtype=torch.float64, device=dev)
             calls.append((f"specq_N{n}", lambda n=n: specq_call(lib, n, qbufs[n])))
-            for name, o in others:
+            for name, o in others if a.generation else []:
                 calls.append((f"specq_N{n}_{name}", lambda n=n, o=o: specq_call(o, n, qbufs[n])))
     if not a.no_compute:
         calls.append(("compute", lambda: eng.compute(T, U, V, W, P, ring, time_s=time_s)))
         for n in a.n:
             calls.append((f"compute_N{n}", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n)))
+            if a.budget:
+                calls.append((f"compute_N{n}_budget", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n, spectrum_budget=True)))
             if a.fused:
                 calls.append((f"compute_N{n}_fused", lambda n=n: eng.compute(T, U, V, W, P, ring, time_s=time_s, wavenumbers=n, spectrum_fused=True)))
             if a.generation:
@@ -144,12 +179,27 @@ def main():
             out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
             out[f"{k}_over_ring_pass"] = round(med(k) / med("ring_pass"), 3)
             out[f"{k}_fp64_TFLOPs"] = round(flop / (med(k) * 1e-3) / 1e12, 3)
-            if a.generation:
+            if a.generation or (with_q and not name):
                 k = f"specq_N{n}{name}"
                 out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
                 out[f"{k}_over_ring_pass"] = round(med(k) / med("ring_pass"), 3)
                 out[f"{k}_over_spec_N{n}"] = round(med(k) / med(f"spec_N{n}"), 3)
                 out[f"{k}_fp64_TFLOPs"] = round(0.5 * flop / (med(k) * 1e-3) / 1e12, 3)
+        if a.budget:
+            fma = float(nt) * nl * nx * n * (18.0 * 2 + 12.0 * (nyb - 2))
+            bnames = [""] + ["_" + x for x, o in others if hasattr(o, "lec_rowspec_b_ring")]
+            for name in bnames:
+                k = f"specb_N{n}{name}"
+                out[f"{k}_ms_per_step"] = round(med(k) / nt, 4)
+                out[f"{k}_fraction_of_fp64_fma_rate"] = round(fma / (med(k) * 1e-3) / (FP64_VECTOR_PEAK_TFLOPS * 1e12 / 2), 4)
+            out[f"specnl_N{n}_ms_per_step"] = round(med(f"specnl_N{n}") / nt, 4)
+            out[f"specb_N{n}_over_specnl_N{n}"] = round(med(f"specb_N{n}") / med(f"specnl_N{n}"), 3)
+            if with_q:
+                out[f"specq_N{n}_ms_per_step"] = round(med(f"specq_N{n}") / nt, 4)
+                out[f"specb_N{n}_over_specq_N{n}"] = round(med(f"specb_N{n}") / med(f"specq_N{n}"), 3)
+            if not a.no_compute:
+                out[f"compute_N{n}_budget_ms_per_step"] = round(med(f"compute_N{n}_budget") / nt, 4)
+                out[f"compute_N{n}_budget_over_compute_N{n}"] = round(med(f"compute_N{n}_budget") / med(f"compute_N{n}"), 3)
         if a.generation and not a.no_compute:
             out[f"compute_N{n}_ge_over_compute_N{n}"] = round(med(f"compute_N{n}_ge") / med(f"compute_N{n}"), 3)
             out[f"compute_N{n}_ge_ms_per_step"] = round(med(f"compute_N{n}_ge") / nt, 4)
@@ -179,6 +229,14 @@ def main():
             spec_call(o, n, bufs[n])
             torch.cuda.synchronize()
             out[f"spec_N{n}_{name}_max_diff_of_scale"] = float(((bufs[n] - mine).abs().amax(dim=(0, 1, 2, 3)) / scale).max())
+        if a.budget:
+            mine = torch.empty_like(bbufs[n])
+            specb_call(lib, n, mine)
+            for name, o in others:
+                if hasattr(o, "lec_rowspec_b_ring"):
+                    specb_call(o, n, bbufs[n])
+                    torch.cuda.synchronize()
+                    out[f"specb_N{n}_{name}_max_diff_of_scale"] = float((bbufs[n] - mine).abs().max() / mine.abs().max())
         if a.generation:
             mine = torch.empty_like(qbufs[n])
             specq_call(lib, n, mine)
