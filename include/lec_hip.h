@@ -913,6 +913,63 @@ typedef struct lec_level_spec_b_args {
 } lec_level_spec_b_args;
 int lec_level_spec_b_ring(const lec_level_spec_b_args* args);
 
+/*
+ * -f [--periodic] --sections: the LATITUDE x PRESSURE SECTIONS of the ten terms of the cycle on one fixed box (an additive call: no
+ * struct, export or kernel result of ABI 11 changes; lec_sections.hip is a code object of its own).
+ *
+ * The level stage of lec_reduce forms, for every row j of a (time step t, level k), the row's contribution to the per-level sums and
+ * keeps only their cw-weighted sum over rows.  The section X_f(t, k, j) is that contribution itself -- the same source lines
+ * (csrc/lec_level_row.inc) with cw = 1, then the level's divisor and sign -- with sigma READ from slot LEC_LEVRAW_SIGMA of levraw_d, so
+ * it is the clamped sigma the totals used.  Names as in lec_level_row.inc, c1k = Rd / (p_k g):
+ *   f = 0 Az  Ts Ts / (2 sigma)              1 Ae  sTT / (2 sigma)         2 Kz  mU^2 + mV^2           3 Ke  sUU + sVV
+ *   4 Cz  -c1k Ws Ts                         5 Ca  -(sVT dphiTc / (2 Re sigma) + sWT dpT / sigma)
+ *   6 Ck  c sUV / Re dphiUc + sVV / Re dphiV + tn sUU mV / Re + sWU dpU + sWV dpU              7 Ce  -c1k sWT
+ *   8 Gz  Qs Ts / (cp sigma)                 9 Ge  sQT / (cp sigma)
+ * so that sum_j cw_j X_f(t, k, j), cw_j = lattab2_d[j][0], is term f of the per-level table of (t, k).  The boundary terms have none.
+ *   sec_d    [t_count][nl][LEC_NSECTION][nyb]  X_f(t, k, j): term-major, lanes over rows store consecutive doubles
+ *   col_d    [t_count][LEC_NSECTION][nyb]      C_f(t, j) = s_f * trapezoid of X_f over the levels' pressures, s_f = 1 / (2 g) for Kz and
+ *            Ke, 1 / g for Ck, else 1: on data without NaN sum_j cw_j C_f(t, j) is the step's scalar.  NaN rule, per (t, j, f), the
+ *            vertical kernel's with drop_any_time = 0: interior NaN levels are bridged linearly in p, NaN levels at either end are left
+ *            out, a column without a finite level is NaN (not the 0.0 of the totals' empty integral).  The totals' any-time mask is
+ *            NOT applied (it is known only after the whole series), so with NaN levels the closure on the scalars is not claimed.
+ *   secsum_d [nl][LEC_NSECTION][nyb]           += sum over the call's steps of X_f, added step by step in time order; the caller zeroes it
+ *            once and divides by the number of steps: a NaN at any step makes the mean NaN.
+ * With spec_d (a ring's records; qspec_d optional): the same for X_f^n, f in {Ae, Ke, Ca, Ce, Ck} (and Ge with qspec_d), n = 1 .. n_wave:
+ * the same expression with slots 6 .. 13 of the record taken from spec_d[t][k][j][n - 1] (and slot 15 from qspec_d), lec_level_spec_ring's
+ * definition of X(n).
+ *   specsec_d    workspace [t_count][nl][n_wave][F][nyb], F = 5 (6 with qspec_d)
+ *   speccolsum_d [n_wave][F][nyb]              += sum over the call's steps of the column value of X_f^n, in time order
+ * Rows of the record buffer beyond the box's own (nyb > jn - js + 1) are written as NaN.  Every output element has ONE writer and the
+ * time sums are added in time order: the numbers do not depend on the launch or on how a series is cut into calls, bit for bit.
+ * Validation.  Every refusal names the field and is made before any HIP call, never clamped.  LEC_ERR_ARG: null args, rows_d, box_d,
+ * lattab2_d, levtab2_d, levraw_d, sec_d, col_d, secsum_d; n_box != 1; t_count < 1, nl < 2, nyb < 2; n_wave < 0; reserved0 != 0; qspec_d
+ * without spec_d; n_wave > 0 without spec_d, spec_d with n_wave < 1 or without specsec_d / speccolsum_d; rows_d, lattab2_d, spec_d not
+ * 16-byte aligned.  LEC_ERR_UNSUPPORTED: nl > LEC_MAX_LEVELS, n_wave > LEC_MAX_WAVENUMBERS, (1 + n_wave) * t_count * nl >= 2^26 or
+ * functions * nyb >= 2^32 - 64 (HIP takes fewer than 2^32 threads per launch; the caller chunks).
+ */
+#define LEC_NSECTION 10      /* Az Ae Kz Ke Cz Ca Ck Ce Gz Ge */
+#define LEC_LEVRAW_SIGMA 33  /* the slot of a levraw record that holds the clamped static stability of (t, k) */
+typedef struct lec_sections_args {
+    const double* rows_d;       /* [t_count][nl][nyb][LEC_NSTAT], the chunk's row records; 16-byte aligned */
+    int32_t t_count, nl;
+    int32_t n_box, nyb;         /* n_box must be 1 */
+    const int32_t* box_d;       /* [1][4] */
+    const double* lattab2_d;    /* [nyb][8], as lec_reduce takes it; 16-byte aligned */
+    const double* levtab2_d;    /* [nl][4] */
+    const double* levraw_d;     /* [t_count][nl][LEC_NLEVRAW] as lec_reduce's level stage left it for these steps */
+    double* sec_d;              /* out [t_count][nl][LEC_NSECTION][nyb] */
+    double* col_d;              /* out [t_count][LEC_NSECTION][nyb] */
+    double* secsum_d;           /* in/out [nl][LEC_NSECTION][nyb], accumulated */
+    const double* spec_d;       /* [t_count][nl][nyb][n_wave][8] or NULL; 16-byte aligned */
+    const double* qspec_d;      /* [t_count][nl][nyb][n_wave] or NULL */
+    int32_t n_wave;             /* 0 without spec_d, else 1 .. LEC_MAX_WAVENUMBERS */
+    int32_t reserved0;          /* must be 0 */
+    double* specsec_d;          /* workspace [t_count][nl][n_wave][F][nyb] (with spec_d) */
+    double* speccolsum_d;       /* in/out [n_wave][F][nyb], accumulated (with spec_d) */
+    void* stream;
+} lec_sections_args;
+int lec_sections(const lec_sections_args* args);
+
 int lec_ingest(const lec_ingest_args* args);
 /*
  * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with

@@ -36,6 +36,10 @@ results_wavenumbers/BAe_n.csv, BKe_n.csv, dAedt_n.csv, dKedt_n.csv, RGe_n.csv an
 per pipeline slot, and the spectra are computed chunk by chunk (``lec_level_spec_ring``): the same files, for series that do not fit
 the GPU whole.
 
+-f [--periodic] --sections: also the latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge on the box's rows
+(``lec_sections``: the row's own contribution to the per-level sums of stage 2), written to results_sections/<term>_lat_lv.csv (the time
+mean, levels x latitudes) and <term>_lat.csv (the vertical integral, time steps x latitudes); with --wavenumbers N also <term>_n_lat.csv.
+
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
 ``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
@@ -120,6 +124,13 @@ def create_arg_parser():
                         "GPU with N time steps resident per pipeline slot and compute the spectra chunk by chunk (lec_level_spec_ring), instead "
                         "of preparing the whole series on the host and holding it on the GPU: device memory then depends on N, not on the "
                         "length of the series, and a deflated NetCDF-4 file is inflated on the GPU.  Same output files, byte for byte")
+    parser.add_argument("--sections", action="store_true", default=argparse.SUPPRESS, help="with -f [--periodic]: also the latitude-pressure "
+                        "sections of the ten terms Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz and Ge (lec_sections), written to results_sections/: "
+                        "<term>_lat_lv.csv, the time mean of the term's section (rows: levels, columns: the box's latitudes; its "
+                        "area-weighted sum over the latitudes is the term's per-level table) and <term>_lat.csv, the vertical integral at "
+                        "every time step (rows: time steps, in the units of the results CSV).  With --wavenumbers N also <term>_n_lat.csv "
+                        "for the spectral terms: the time mean of the vertical integral of every wavenumber's share (rows 1 .. N and "
+                        "'rest').  Every other output file is unchanged.  One GPU; not for -t / -c")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -335,6 +346,12 @@ def refuse_periodic_options(args):
     if args.periodic and not args.fixed:
         raise SystemExit("--periodic goes with -f/--fixed: the ring of a -t / -c run is the 0..360 longitude axis a track across the +-180 "
                          "meridian gets by itself, and --choose-periodic for the search of -c")
+    if getattr(args, "sections", False):
+        if not args.fixed:
+            raise SystemExit("--sections goes with -f/--fixed: a section lies on the rows of ONE fixed box; the boxes of a -t / -c run "
+                             "move, and their sections would be system-relative composites")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--sections runs on one GPU: --gpus > 1 is not supported for the sections (run the totals sharded, the sections apart)")
     n = getattr(args, "wavenumbers", None)
     chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:

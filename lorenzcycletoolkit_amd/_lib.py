@@ -17,6 +17,9 @@ LEC_NSCALAR = 16
 LEC_NLEVTAB = 21
 LEC_NLEVFUN = 28
 LEC_MAX_WAVENUMBERS = 64      # the largest n_wave of one lec_rowspec_ring call
+LEC_NSECTION = 10             # Az Ae Kz Ke Cz Ca Ck Ce Gz Ge: the terms that have a latitude-pressure section (lec_sections)
+LEC_LEVRAW_SIGMA = 33
+LEC_MAX_LEVELS = 160
 LEC_F64, LEC_F32, LEC_I16, LEC_I32, LEC_I8 = 0, 1, 2, 3, 4
 
 # enum lec_kernel / enum lec_order (include/lec_hip.h)
@@ -47,7 +50,7 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
            "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring",
            "lec_ingest_series", "lec_rowspec_ring", "lec_rowspec_q_ring", "lec_level_spec_ring",
-           "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring"]
+           "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring", "lec_sections"]
 
 
 class Tuning(C.Structure):
@@ -132,6 +135,17 @@ class RowspecBArgs(C.Structure):
 class LevelSpecBArgs(C.Structure):
     """struct lec_level_spec_b_args (include/lec_hip.h)."""
     _fields_ = [("spec", LevelSpecArgs), ("bspec_d", C.c_void_p)]
+
+
+class SectionsArgs(C.Structure):
+    """struct lec_sections_args (include/lec_hip.h)."""
+    _fields_ = [
+        ("rows_d", C.c_void_p), ("t_count", C.c_int32), ("nl", C.c_int32), ("n_box", C.c_int32), ("nyb", C.c_int32),
+        ("box_d", C.c_void_p), ("lattab2_d", C.c_void_p), ("levtab2_d", C.c_void_p), ("levraw_d", C.c_void_p),
+        ("sec_d", C.c_void_p), ("col_d", C.c_void_p), ("secsum_d", C.c_void_p),
+        ("spec_d", C.c_void_p), ("qspec_d", C.c_void_p), ("n_wave", C.c_int32), ("reserved0", C.c_int32),
+        ("specsec_d", C.c_void_p), ("speccolsum_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
 
 
 class ReduceArgs(C.Structure):
@@ -307,6 +321,8 @@ def load():
     lib.lec_rowspec_b_ring.argtypes = [C.POINTER(RowspecBArgs)]
     lib.lec_level_spec_b_ring.restype = C.c_int
     lib.lec_level_spec_b_ring.argtypes = [C.POINTER(LevelSpecBArgs)]
+    lib.lec_sections.restype = C.c_int
+    lib.lec_sections.argtypes = [C.POINTER(SectionsArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

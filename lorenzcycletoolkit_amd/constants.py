@@ -14,6 +14,8 @@ SCALAR_TERMS = ["Az", "Ae", "Kz", "Ke", "Cz", "Ca", "Ck", "Ce",
 # table order of the `levels` output (lec_fixed_framework.py:172-194 of the reference)
 LEVEL_TERMS = ["Az", "Ae", "Kz", "Ke", "Ge", "Gz", "Cz", "Cz_1", "Cz_2", "Ca", "Ca_1", "Ca_2",
                "Ce", "Ce_1", "Ce_2", "Ck", "Ck_1", "Ck_2", "Ck_3", "Ck_4", "Ck_5"]
+# the terms that have a latitude-pressure section (LECResult.section_*; lec_sections), in the kernel's order
+SECTION_TERMS = ["Az", "Ae", "Kz", "Ke", "Cz", "Ca", "Ck", "Ce", "Gz", "Ge"]
 # the eddy terms that have a zonal-wavenumber spectrum (LECResult.spectrum) and their per-level tables (LECResult.spectrum_levels;
 # Ce_1 = Rd / (p g) is a function of level alone, the same for every wavenumber: carried so that Ce's pieces stay together)
 SPECTRUM_TERMS = ["Ae", "Ke", "Ca", "Ce", "Ck"]

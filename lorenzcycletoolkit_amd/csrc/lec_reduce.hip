@@ -40,6 +40,7 @@ enum {
     V_COUNT = 34
 };
 static_assert(V_COUNT <= LEC_NLEVRAW, "levraw record too small");
+static_assert(V_SIG == LEC_LEVRAW_SIGMA, "lec_sections reads sigma from this slot");
 
 struct RedParams {
     const double* rows;

@@ -16,7 +16,7 @@ import numpy as np
 import torch
 
 from . import _lib, tables
-from .constants import (LEVEL_TERMS, SCALAR_TERMS, SPECTRUM_BUDGET_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_PLACES,
+from .constants import (LEVEL_TERMS, SCALAR_TERMS, SECTION_TERMS, SPECTRUM_BUDGET_TERMS, SPECTRUM_GENERATION_TERM, SPECTRUM_INTERACTION_PLACES,
                         SPECTRUM_LEVEL_TERMS, SPECTRUM_TERMS)
 
 
@@ -52,6 +52,13 @@ class LECResult:
     spectrum_tendency_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64
     spectrum_residual: Optional[torch.Tensor] = None         # [t_count, 2, N] fp64: RGe, RKe
     spectrum_residual_rest: Optional[torch.Tensor] = None    # [t_count, 2] fp64
+    # compute(..., sections=True) on ONE fixed box: the latitude x pressure sections of the ten terms (constants.SECTION_TERMS;
+    # ``lec_sections``).  Rows are the box's rows; sum_j cw_j X_f closes on ``levels``, sum_j cw_j C_f on ``scalars``
+    section_mean: Optional[torch.Tensor] = None      # [10, nl, nyb] fp64: the time mean of X_f(t, k, j) (NaN at any step: NaN)
+    section_lat: Optional[torch.Tensor] = None       # [t_count, 10, nyb] fp64: the column values C_f(t, j), in the units of ``scalars``
+    section_steps: Optional[torch.Tensor] = None     # [t_count, 10, nl, nyb] fp64: X_f itself (on request; a series that was one chunk)
+    section_spec_lat: Optional[torch.Tensor] = None  # [F, N + 1, nyb] fp64 (with wavenumbers=N): the time mean of the column value of
+                                                     # X_f^n, f = Ae Ke Ca Ce Ck (Ge), n = 1 .. N, then the rest (the total minus the N)
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -351,7 +358,8 @@ class LECEngine:
                 out: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
                 wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
-                spectrum_interactions: bool = False, spectrum_budget: bool = False) -> LECResult:
+                spectrum_interactions: bool = False, spectrum_budget: bool = False,
+                sections: bool = False, section_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -384,7 +392,16 @@ class LECEngine:
         ``rowspec_b``, whose four shares enter the same stage-2 batch in slots 16, 17, 20, 21), ``spectrum_tendency`` (dAe(n)/dt,
         dKe(n)/dt by ``tables.budgets_and_residuals``: np.gradient with dt = time_s[1] - time_s[0]) and ``spectrum_residual`` (RGe(n),
         RKe(n)), each with its ``_rest``.  It changes no bit of anything else; both ``spectrum_fused`` forms give the same bits.
+        ``sections`` (ONE fixed box, one process): also ``section_mean`` and ``section_lat`` -- and ``section_steps`` when asked for, and
+        ``section_spec_lat`` with ``wavenumbers`` --, the latitude x pressure sections of the ten terms (``section_stage``).  It
+        changes no bit of anything else; without it nothing new runs or allocates.
         """
+        if section_steps and not sections:
+            raise ValueError("section_steps: the per-step sections are part of sections=True")
+        if sections:
+            self._check_sections(boxes, per_step_boxes, steps, tm, tp)
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("sections run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
         if spectrum_budget:
             if wavenumbers is None:
                 raise ValueError("spectrum_budget: BAe(n), BKe(n) and the residuals are part of the zonal-wavenumber spectra: give wavenumbers=N")
@@ -417,13 +434,111 @@ class LECEngine:
             drop_any_time = False
         res = self.reduce(rows, boxes, phi_scale=phi_scale, drop_any_time=drop_any_time, merge_dropmask=merge_dropmask,
                           keep_rows=keep_rows, out=out)
+        sec = None
+        if sections:
+            # the level half of `reduce` left sigma in its levraw workspace; the next stage-2 call of this shape reuses it, so the
+            # sections keep a copy of their own
+            sec = self.section_begin(int(rows.shape[0]), int(rows.shape[2]), rows.device, n_wave=int(wavenumbers or 0),
+                                     generation=spectrum_generation, keep_steps=section_steps)
+            sec["levraw"] = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            if wavenumbers is None:
+                self.section_stage(rows, boxes, sec["levraw"], sec, 0)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
-                           interactions=spectrum_interactions, budget=spectrum_budget)
+                           interactions=spectrum_interactions, budget=spectrum_budget, sections=sec)
             if spectrum_budget:
                 self.spectrum_budget_terms(res, time_s)
+        if sec is not None:
+            self.section_finish(res, sec)
         return res
+
+    # -- latitude x pressure sections of one fixed box (lec_sections) -----------------------------------------------------------------
+    SECTION_SPEC_TERMS = ("Ae", "Ke", "Ca", "Ce", "Ck", "Ge")      # the order of lec_sections' spectral functions (Ge with qspec only)
+
+    @staticmethod
+    def _check_sections(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
+        n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
+        if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
+            raise ValueError("sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
+                             "no common rows to lay a section on")
+
+    def section_begin(self, t_total: int, nyb: int, device, *, n_wave: int = 0, generation: bool = False, keep_steps: bool = False) -> dict:
+        """The accumulators of the sections of a series of ``t_total`` steps (zeroed once, here): ``section_stage`` adds every chunk to
+        them, ``section_finish`` turns them into the result's fields."""
+        nl = int(self.level.size)
+        f64 = dict(dtype=torch.float64, device=device)
+        nf = 6 if generation else 5
+        return dict(t_total=int(t_total), nyb=int(nyb), n_wave=int(n_wave), nf=nf, generation=bool(generation),
+                    secsum=torch.zeros((nl, _lib.LEC_NSECTION, nyb), **f64), col=torch.empty((t_total, _lib.LEC_NSECTION, nyb), **f64),
+                    steps=torch.empty((t_total, nl, _lib.LEC_NSECTION, nyb), **f64) if keep_steps else None, work=None, specwork=None,
+                    speccolsum=torch.zeros((n_wave, nf, nyb), **f64) if n_wave else None)
+
+    def section_stage(self, rows: torch.Tensor, boxes, levraw: torch.Tensor, state: dict, t_offset: int, *,
+                      spec: Optional[torch.Tensor] = None, qspec: Optional[torch.Tensor] = None) -> None:
+        """``lec_sections`` on a chunk: rows [t_count, nl, nyb, 32] and ``levraw`` [t_count, nl, 40] as ``level_stage`` left it for the
+        same steps (sigma is read from it) -> the chunk's sections, their column values into ``state["col"][t_offset: t_offset + t_count]``
+        and their time sums added to ``state["secsum"]`` (``section_begin``).  ``spec`` [t_count, nl, nyb, N, 8] / ``qspec`` [t_count,
+        nl, nyb, N] (a ring's ``rowspec`` / ``rowspec_q``): also the sections of the wavenumbers' shares, their column values summed
+        over time into ``state["speccolsum"]``.  Chunks must come in time order; every number is independent of how the series is cut."""
+        t_count, nl = int(rows.shape[0]), int(rows.shape[1])
+        boxes, bt, dev = self._stage2_input(rows, boxes)
+        self._check_sections(boxes, False)
+        nyb = bt.nyb_max
+        if nyb != state["nyb"] or not (0 <= t_offset and t_offset + t_count <= state["t_total"]):
+            raise ValueError("section_stage: the chunk does not fit the series section_begin was given")
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        n = state["n_wave"]
+        if (spec is None) != (n == 0):
+            raise ValueError("section_stage: spec goes with section_begin(n_wave=N)")
+        if spec is not None and (spec.shape != (t_count, nl, nyb, n, 8) or spec.dtype != torch.float64 or spec.device != rows.device
+                                 or not spec.is_contiguous()):
+            raise ValueError("spec must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the rows' device")
+        if (qspec is not None) != (n > 0 and state["generation"]):
+            raise ValueError("section_stage: qspec goes with section_begin(generation=True)")
+        if qspec is not None and (qspec.shape != (t_count, nl, nyb, n) or qspec.dtype != torch.float64 or qspec.device != rows.device
+                                  or not qspec.is_contiguous()):
+            raise ValueError("qspec must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the rows' device")
+        f64 = dict(dtype=torch.float64, device=rows.device)
+        if state["steps"] is not None:
+            sec = state["steps"][t_offset: t_offset + t_count]
+        else:
+            if state["work"] is None or state["work"].shape[0] < t_count:
+                state["work"] = torch.empty((t_count, nl, _lib.LEC_NSECTION, nyb), **f64)
+            sec = state["work"][:t_count]
+        specsec = None
+        if n:
+            if state["specwork"] is None or state["specwork"].shape[0] < t_count:
+                state["specwork"] = torch.empty((t_count, nl, n, state["nf"], nyb), **f64)
+            specsec = state["specwork"][:t_count]
+        sa = _lib.SectionsArgs(
+            rows_d=_ptr(rows), t_count=t_count, nl=nl, n_box=1, nyb=nyb, box_d=_ptr(dev["box"]), lattab2_d=_ptr(dev["lattab2"]),
+            levtab2_d=_ptr(self._levtab2), levraw_d=_ptr(levraw), sec_d=_ptr(sec), col_d=_ptr(state["col"][t_offset: t_offset + t_count]),
+            secsum_d=_ptr(state["secsum"]), spec_d=_ptr(spec), qspec_d=_ptr(qspec), n_wave=n, reserved0=0, specsec_d=_ptr(specsec),
+            speccolsum_d=_ptr(state["speccolsum"]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+        with torch.cuda.device(rows.device):
+            _lib.check(self.lib.lec_sections(C.byref(sa)), "lec_sections")
+
+    def section_finish(self, res: LECResult, state: dict) -> None:
+        """``res.section_*`` from the accumulators of a finished series."""
+        t_total = state["t_total"]
+        res.section_mean = (state["secsum"] / float(t_total)).permute(1, 0, 2).contiguous()
+        res.section_lat = state["col"]
+        if state["steps"] is not None:
+            res.section_steps = state["steps"].permute(0, 2, 1, 3).contiguous()
+        if state["n_wave"]:
+            # the totals' column values summed over time in time order too, so that the rest does not depend on the chunks either
+            idx = torch.as_tensor([SECTION_TERMS.index(x) for x in self.SECTION_SPEC_TERMS[:state["nf"]]], device=state["col"].device)
+            tot = torch.zeros((state["nf"], state["nyb"]), dtype=torch.float64, device=state["col"].device)
+            for t in range(t_total):
+                tot += state["col"][t].index_select(0, idx)
+            shares = state["speccolsum"].permute(1, 0, 2)            # [F, N, nyb]
+            ssum = shares[:, 0].clone()
+            for k in range(1, state["n_wave"]):
+                ssum += shares[:, k]
+            res.section_spec_lat = (torch.cat([shares, (tot - ssum).unsqueeze(1)], dim=1) / float(t_total)).contiguous()
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
     # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records
@@ -709,7 +824,7 @@ class LECEngine:
 
     def _spectrum(self, res: LECResult, rows: torch.Tensor, tair, u, v, omega, boxes: PreparedBoxes, n: int, t_begin: int, phi_scale: float,
                   drop_any_time: Optional[bool], generation: Optional[dict] = None, fused: bool = False, interactions: bool = False,
-                  budget: bool = False) -> None:
+                  budget: bool = False, sections: Optional[dict] = None) -> None:
         """Fills ``res.spectrum*``.  X(n) is what stage 2 gives for X on row records whose slots 6 .. 13 hold the wavenumber-n shares and
         whose other entries are the ring pass's: the records are assembled for a chunk of time steps and all N wavenumbers at a time
         (at most ``SPECTRUM_CHUNK_BYTES``), the level x latitude half of ``lec_reduce`` turns each chunk into 40 numbers per (n, step,
@@ -720,7 +835,8 @@ class LECEngine:
         pass's records and the chunk's ``spec`` / ``qspec`` (the chunk is bounded by ``spec``), the same bits.  ``interactions``: S(n)
         and L(n) by ``spectrum_nl_stage`` in time chunks of its own records, a batch of its own.  ``budget``: slots 16, 17, 20, 21 of
         the same records hold ``rowspec_b``'s shares, which only the BAe and BKe columns read: BAe(n) and BKe(n) come out of the same
-        batch, and nothing else of it moves."""
+        batch, and nothing else of it moves.  ``sections`` (the state of ``section_begin``, with the totals' levraw under "levraw"):
+        every chunk's ``spec`` / ``qspec`` also go through ``section_stage``."""
         t_count, nl, nyb = (int(x) for x in rows.shape[:3])
         dev = rows.device
         f64 = dict(dtype=torch.float64, device=dev)
@@ -744,6 +860,8 @@ class LECEngine:
                 if budget:
                     bs = self.rowspec_b(tair, u, v, omega, rows[a:b], boxes, n, t_begin=t_begin + a, t_count=b - a, out=bspec[:b - a])
                 self.spectrum_level_stage(rows[a:b], sp, qs, boxes, levraw[:, a:b], phi_scale=phi_scale, bspec=bs)
+                if sections is not None:
+                    self.section_stage(rows[a:b], boxes, sections["levraw"][a:b], sections, a, spec=sp, qspec=qs)
             self._spectrum_shares(res, levraw, boxes, drop_any_time, generation is not None, budget)
             return
         tc = max(1, min(t_count, self.SPECTRUM_CHUNK_BYTES // (n * nl * nyb * _lib.LEC_NSTAT * 8)))
@@ -762,6 +880,8 @@ class LECEngine:
             if generation is not None:
                 qs = self.rowspec_q(tair, u, v, omega, boxes, n, t_begin=t_begin + a, t_count=c, out=qspec[:c], **generation)
                 rec[..., _LEC_S_QT] = qs.permute(3, 0, 1, 2)
+            if sections is not None:
+                self.section_stage(rows[a:b], boxes, sections["levraw"][a:b], sections, a, spec=sp, qspec=qs if generation is not None else None)
             if budget:
                 bs = self.rowspec_b(tair, u, v, omega, rows[a:b], boxes, n, t_begin=t_begin + a, t_count=c, out=bspec[:c]).permute(3, 0, 1, 2, 4)
                 rec.index_copy_(4, torch.as_tensor(_LEC_S_BUDGET, device=dev), bs)

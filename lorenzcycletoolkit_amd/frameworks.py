@@ -71,7 +71,8 @@ class BoxData:
                  southern_limit=None, northern_limit=None, args=None, results_subdirectory: str = ".",
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
-                 spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False):
+                 spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False,
+                 sections: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -81,6 +82,14 @@ class BoxData:
                 raise ValueError("periodic: one fixed box (the moving framework's ring is the 0..360 axis of --choose-periodic)")
             from .tables import box_indices
             self.xlength = ring_box_check(data.lon, box_indices(data.lat, data.lon, western_limit, eastern_limit, southern_limit, northern_limit))
+        self.sections = bool(sections)
+        self.section_mean = self.section_lat = self.section_spec_lat = None
+        if self.sections:               # (host work only, as above)
+            if boxes_limits is not None:
+                raise ValueError("sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes) has no common rows "
+                                 "to lay a section on")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("sections run on one GPU (no time shards)")
         self.wavenumbers = None if wavenumbers is None else int(wavenumbers)
         self.spectrum = self.spectrum_rest = self.spectrum_levels = None
         if wavenumbers is not None:     # (host work only, as above)
@@ -161,7 +170,8 @@ class BoxData:
                                                              **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
                                                              **({"spectrum_generation": True} if self.spectrum_generation else {}),
                                                              **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
-                                                             **({"spectrum_budget": True} if self.spectrum_budget else {}))
+                                                             **({"spectrum_budget": True} if self.spectrum_budget else {}),
+                                                             **({"sections": True} if self.sections else {}))
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)
@@ -196,6 +206,13 @@ class BoxData:
             for name in ("spectrum_b", "spectrum_tendency", "spectrum_residual"):
                 setattr(self, name, getattr(self.result, name).cpu().numpy())
                 setattr(self, name + "_rest", getattr(self.result, name + "_rest").cpu().numpy())
+        if self.result.section_mean is not None:
+            self.section_mean = self.result.section_mean.cpu().numpy()
+            self.section_lat = self.result.section_lat.cpu().numpy()
+            if self.result.section_spec_lat is not None:
+                self.section_spec_lat = self.result.section_spec_lat.cpu().numpy()
+            js, jn = self.boxes[0][2], self.boxes[0][3]
+            self.section_latitudes = np.asarray(data.lat[js: jn + 1], dtype=np.float64)
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -238,7 +255,8 @@ class BoxData:
                                    **({} if self.wavenumbers is None else {"wavenumbers": self.wavenumbers}),
                                    **({"spectrum_generation": True} if self.spectrum_generation else {}),
                                    **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
-                                   **({"spectrum_budget": True} if self.spectrum_budget else {}))
+                                   **({"spectrum_budget": True} if self.spectrum_budget else {}),
+                                   **({"sections": True} if self.sections else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -319,6 +337,51 @@ def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> N
                 f.write(format_level_table(table, labels))
         if labels[0] is None:            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
             pd.DataFrame(table, index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+
+
+def write_section_csvs(box_obj: "BoxData", directory: str, time_name: str, vert_name: str) -> None:
+    """results_sections/: for each of the ten terms ``<term>_lat_lv.csv`` -- the time mean of the term's latitude-pressure section, one row
+    per level (labelled as the columns of the per-level tables are: the level in Pa as a float), one column per latitude of the box in
+    degrees, in the units of the per-level table -- and ``<term>_lat.csv`` -- the section's vertical integral, one row per time step
+    (the time labels and number formatting of the per-level tables), in the units of the results CSV.  With spectra also
+    ``<term>_n_lat.csv`` for Ae, Ke, Ca, Ce, Ck (and Ge): the time mean of the vertical integral of every wavenumber's share, rows
+    1 .. N and ``rest``."""
+    from .constants import SECTION_TERMS
+    os.makedirs(directory, exist_ok=True)
+    lats = [repr(float(x)) for x in box_obj.section_latitudes]
+    labels = box_obj.row_labels("fixed")
+
+    def fixed_labels(names):
+        width = max(len(x) for x in names)
+        if any(len(x) != width for x in names):      # (labels of mixed widths: one call per row)
+            return None
+        return "".join(names).encode("ascii"), width
+
+    def write(path, first, names, table, lab=None):
+        with open(path, "wb") as f:
+            f.write((",".join([str(first)] + lats) + "\n").encode("utf-8"))
+            lab = fixed_labels(names) if lab is None else lab
+            if lab is not None:
+                f.write(format_level_table(table, lab))
+            else:
+                for name, row in zip(names, np.asarray(table, dtype=np.float64)):
+                    f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+
+    level_names = [repr(float(p)) for p in box_obj.PressureData]
+    for i, term in enumerate(SECTION_TERMS):
+        write(os.path.join(directory, f"{term}_lat_lv.csv"), vert_name, level_names, box_obj.section_mean[i])
+        path = os.path.join(directory, f"{term}_lat.csv")
+        if labels[0] is not None:
+            write(path, time_name, None, box_obj.section_lat[:, i, :], lab=labels)
+        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
+            with open(path, "wb") as f:
+                f.write((",".join([str(time_name)] + lats) + "\n").encode("utf-8"))
+            pd.DataFrame(box_obj.section_lat[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+    if box_obj.section_spec_lat is not None:
+        nf, n1 = box_obj.section_spec_lat.shape[:2]
+        names = [str(k) for k in range(1, n1)] + ["rest"]
+        for i, term in enumerate(LECEngine.SECTION_SPEC_TERMS[:nf]):
+            write(os.path.join(directory, f"{term}_n_lat.csv"), "n", names, box_obj.section_spec_lat[i])
 
 
 def ring_hint(lon, box):
@@ -523,13 +586,16 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         raise ValueError("--wavenumbers-budget goes with --wavenumbers N")
     if budget and len(data.time) < 2:
         raise ValueError("--wavenumbers-budget: the tendencies are finite differences in time: the series needs at least 2 time steps")
+    sections = bool(getattr(args, "sections", False))
+    if sections and shard is not None:
+        raise ValueError("--sections runs on one GPU")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
                           results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
                           spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}),
-                          **({"spectrum_budget": True} if budget else {}))
+                          **({"spectrum_budget": True} if budget else {}), **({"sections": True} if sections else {}))
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -563,6 +629,11 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
             app_logger.info(f"--wavenumbers-budget: BAe(n) and BKe(n) from the shares of the four triple products of the ring's rows, "
                             f"the tendencies dAe(n)/dt, dKe(n)/dt and the residuals RGe(n), RKe(n) (lec_rowspec_b_kernel: N = {int(wavenumbers)}, "
                             f"nx = {len(data.lon)}); written to {spectrum_directory}")
+    if sections:
+        section_directory = os.path.join(results_subdirectory, "results_sections")
+        write_section_csvs(box_obj, section_directory, time_name, vert_name)
+        app_logger.info(f"--sections: the latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge on the box's "
+                        f"{len(box_obj.section_latitudes)} rows (lec_sections); written to {section_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]

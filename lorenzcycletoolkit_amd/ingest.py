@@ -823,7 +823,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
                  slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
                  ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False,
-                 spectrum_interactions: bool = False, spectrum_budget: bool = False) -> LECResult:
+                 spectrum_interactions: bool = False, spectrum_budget: bool = False, sections: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -855,7 +855,16 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     ``spectrum_budget`` (with ``wavenumbers``; at least two time steps): also BAe(n), BKe(n), the tendencies and the residuals of
     ``LECEngine.compute(..., spectrum_budget=True)``, the same bits: every sub-chunk goes through ``rowspec_b`` beside ``rowspec`` (no
     time stencil: no halo) and ``lec_level_spec_b_ring``; tendencies and residuals are formed once the series' [T, N] shares exist.
+    ``sections`` (one fixed box, the whole series in one process): also ``section_mean``, ``section_lat`` and, with ``wavenumbers``,
+    ``section_spec_lat`` of ``LECEngine.compute(..., sections=True)``, the same bits: every sub-chunk's records go through
+    ``section_stage`` right after their level stage, and only the time sums and the column values outlive the sub-chunk.
     """
+    if sections:
+        if per_step_boxes:
+            raise ValueError("sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
+                             "no common rows to lay a section on")
+        if t_range is not None or merge_dropmask is not None or out is not None:
+            raise ValueError("sections run in one process on one GPU: a sharded run (t_range, merge_dropmask, out) has none")
     if spectrum_budget and wavenumbers is None:
         raise ValueError("spectrum_budget: BAe(n), BKe(n) and the residuals are part of the zonal-wavenumber spectra: give wavenumbers=N")
     if spectrum_interactions and wavenumbers is None:
@@ -1011,6 +1020,9 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             nl_buffers = (torch.empty((nl_steps, nl, bt.nyb_max, nw, 8), dtype=torch.float64, device=dev),
                           torch.empty((nl_steps, nl, bt.nyb_max, 8), dtype=torch.float64, device=dev))
             levraw_nl = torch.empty((nw + 1, t1 - t0, nl, _lib.LEC_NLEVRAW), dtype=torch.float64, device=dev)
+    sec_state = None
+    if sections:
+        sec_state = engine.section_begin(t1 - t0, bt.nyb_max, dev, n_wave=int(wavenumbers or 0), generation=spectrum_generation)
     time_s = plan.time_s
     phi_scale = ds.field_scale(variable_list_df, geo_role)
 
@@ -1079,6 +1091,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine.rowstats(f["tair"], f["u"], f["v"], f["omega"], f["geopt"], part, t_count=n, with_q=with_q, rows_out=rows[:n],
                             per_step_boxes=per_step_boxes, **kw)
             engine.level_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
+            if sec_state is not None and wavenumbers is None:
+                engine.section_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], sec_state, s0 - t0)
             if wavenumbers is not None:         # (never packed: the cubes hold T's halo, and rowspec_q reads T[t - 1], T[t + 1] from them)
                 fields = (f["tair"], f["u"], f["v"], f["omega"])
                 for a in range(0, n, spec_steps):
@@ -1092,6 +1106,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                         bs = engine.rowspec_b(*fields, rows[a:b], fixed_box, nw, t_begin=kw["t_begin"] + a, t_count=b - a, out=bspec[:b - a])
                     engine.spectrum_level_stage(rows[a:b], sp, qs, fixed_box, levraw_spec[:, s0 - t0 + a: s0 - t0 + b], phi_scale=phi_scale,
                                                 bspec=bs)
+                    if sec_state is not None:
+                        engine.section_stage(rows[a:b], fixed_box, levraw[s0 - t0 + a: s0 - t0 + b], sec_state, s0 - t0 + a, spec=sp, qspec=qs)
                 if spectrum_interactions:
                     engine.spectrum_nl_stage(*fields, rows[:n], fixed_box, nw, levraw_nl[:, s0 - t0: s1 - t0], t_begin=kw["t_begin"],
                                              phi_scale=phi_scale, buffers=nl_buffers)
@@ -1105,6 +1121,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine.spectrum_budget_terms(res, time_s)
         if spectrum_interactions:
             engine._spectrum_nl_shares(res, levraw_nl, fixed_box, True)
+    if sec_state is not None:
+        engine.section_finish(res, sec_state)
     on_device, reg_stats = pipe.finish()
     moved, host_s = pipe.moved, pipe.host_s
     if stats is not None:
