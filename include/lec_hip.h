@@ -970,6 +970,68 @@ typedef struct lec_sections_args {
 } lec_sections_args;
 int lec_sections(const lec_sections_args* args);
 
+/*
+ * -f [--periodic] --maps: the LONGITUDE-RESOLVED MAPS of the six eddy terms Ae Ke Ca Ce Ck Ge on one fixed box (an additive call: no
+ * struct, export or kernel result of ABI 11 changes; lec_maps.hip is a code object of its own).
+ *
+ * Every eddy term of stage 2 is the zonal average of a pointwise product times a factor of (time step t, level k, box row j) only; the
+ * map is the same expression with the zonal average left off, at box column i.  Primes are deviations from the row's zonal means, which
+ * are READ from the row record (slots LEC_S_MT / MU / MV / MW / MQ), never formed again; sigma is READ from slot LEC_LEVRAW_SIGMA of
+ * levraw_d; dphiTc, dphiUc, dphiV, dpT, dpU are the row factors of csrc/lec_level_row.inc (from the records of rows j +- 1 and levels
+ * k +- 1 and the area means), c1k = Rd / (p_k g), c / tn / mV the row's cos, tan and [v]:
+ *   f = 0 Ae  T'T' / (2 sigma)        1 Ke  u'u' + v'v'        2 Ca  -(v'T' dphiTc / (2 Re sigma) + w'T' dpT / sigma)        3 Ce  -c1k w'T'
+ *   4 Ck  c u'v' / Re dphiUc + v'v' / Re dphiV + tn u'u' mV / Re + w'u' dpU + w'v' dpU                      5 Ge  Q'T' / (cp sigma)
+ * (the factor of a product is formed ONCE per (t, k, j) and multiplied in: the zonal average of a map row equals the section's value to
+ * rounding, not bit for bit).  Q = cp (dT/dt + u dT/dx + v dT/dy - S w) at the point, the expression of lec_rowspec_q_ring and of
+ * lec_rowstats: tables and time axis as there; d/dlon centred with wrapped neighbours when ring = 1, and one-sided, 2 (T[i+1] - T[i]) /
+ * 2 (T[i] - T[i-1]), at the first / last column of an open box (ring = 0).  Nothing outside the box, the levels or the cube's steps is read.
+ *   col_d    [t_count][LEC_NMAP][nyb][nxb]  C_f(t, j, i) = s_f * trapezoid of the integrand over the levels' pressures, s_f = 1 / (2 g) for
+ *            Ke, 1 / g for Ck, else 1, with lec_sections' NaN rule per (t, j, i): interior NaN levels are bridged linearly in p, NaN levels
+ *            at either end are left out, a column without a finite level is NaN.  The caller's to keep, and the workspace of the sums.
+ *   mapsum_d [LEC_NMAP][nyb][nxb]           += sum over the call's steps of C_f, added step by step in time order; the caller zeroes it
+ *            once and divides by the number of steps: a NaN at any step makes the mean NaN.
+ *   hov_d    [t_count][LEC_NMAP][nxb]       H_f(t, i) = sum_j cw_j C_f(t, j, i), rows ascending, cw_j = lattab2_d[j][0]; NaN propagates.
+ *   coef_d   workspace [t_count][nl][nyb][LEC_MAPS_NCOEF]: the zonal means and factors of (t, k, j), written by the call's first kernel.
+ * nyb = jn - js + 1, nxb = ie - iw + 1; rows_d has exactly nyb rows per level.  On data without NaN the box's zonal average of
+ * C_f(t, j, .) (closed on a ring, the half-weight trapezoid on an open box) is lec_sections' col_d of that term, and that of H_f(t, .)
+ * the step's scalar.  Every output element has ONE writer and the sums run in a fixed order: no atomics, and the numbers depend neither
+ * on the launch nor on how a series is cut into calls, bit for bit.
+ * Validation.  Every refusal names the field and is made before any HIP call, never clamped.  LEC_ERR_ARG: null args or any null
+ * pointer; dtype; ring not 0 / 1, or ring = 1 with iw .. ie not 0 .. nx - 1; reserved0 != 0; nt < 2, nl < 2, ny < 2, nx < 3; t_begin /
+ * t_count outside the cube; iw / ie / js / jn outside 0 <= iw, iw + 2 <= ie < nx, 0 <= js < jn < ny; rows_d, lattab2_d, coef_d not
+ * 16-byte aligned, another table or output not 8-byte aligned, a cube not aligned to its element.  LEC_ERR_UNSUPPORTED: nl >
+ * LEC_MAX_LEVELS, t_count * nl >= 2^26, t_count * nyb * ceil(nxb / 64) >= 2^26, 6 * nyb * nxb or t_count * 6 * nxb >= 2^32 - 256 (HIP
+ * takes fewer than 2^32 threads per launch; the caller chunks).
+ */
+#define LEC_NMAP 6           /* Ae Ke Ca Ce Ck Ge */
+#define LEC_MAPS_NCOEF 16    /* doubles per (t, k, j) of coef_d */
+typedef struct lec_maps_args {
+    const void* tair_d;
+    const void* u_d;
+    const void* v_d;
+    const void* omega_d;
+    int32_t dtype;              /* enum lec_dtype (LEC_F64 or LEC_F32), common to the four cubes */
+    int32_t nt, nl, ny, nx;     /* cube dimensions */
+    int32_t t_begin, t_count;   /* process time steps [t_begin, t_begin + t_count) */
+    int32_t iw, ie, js, jn;     /* the box (inclusive grid columns and rows) */
+    int32_t ring;               /* 1: the box is the closed circle 0 .. nx - 1; 0: an open box */
+    int32_t reserved0;          /* must be 0 */
+    const double* rows_d;       /* [t_count][nl][nyb][LEC_NSTAT], the records of the same steps and box; 16-byte aligned */
+    const double* levraw_d;     /* [t_count][nl][LEC_NLEVRAW] as lec_reduce's level stage left it for these steps */
+    const double* lattab2_d;    /* [nyb][8], as lec_reduce takes it; 16-byte aligned */
+    const double* levtab2_d;    /* [nl][4] */
+    const double* lattab_d;     /* [nyb][4]: d/dlat a, b, c; 1 / dx_j (the box's lattab) */
+    const double* levtab_d;     /* [nl][3]: the static-stability coefficients of lec_rowstats */
+    const double* tcoef_d;      /* [nt][3]: np.gradient coefficients over the cube's time axis */
+    double inv_hdeg;            /* boxtab[2] of the box: 1 / (longitude step in degrees) */
+    double* coef_d;             /* workspace [t_count][nl][nyb][LEC_MAPS_NCOEF]; 16-byte aligned */
+    double* col_d;              /* out [t_count][LEC_NMAP][nyb][nxb] */
+    double* mapsum_d;           /* in/out [LEC_NMAP][nyb][nxb], accumulated */
+    double* hov_d;              /* out [t_count][LEC_NMAP][nxb] */
+    void* stream;
+} lec_maps_args;
+int lec_maps(const lec_maps_args* args);
+
 int lec_ingest(const lec_ingest_args* args);
 /*
  * lec_ingest for a series that continues across files (ABI 11, additive; lec_ingest_args unchanged): every file packs its values with

@@ -40,6 +40,10 @@ the GPU whole.
 (``lec_sections``: the row's own contribution to the per-level sums of stage 2), written to results_sections/<term>_lat_lv.csv (the time
 mean, levels x latitudes) and <term>_lat.csv (the vertical integral, time steps x latitudes); with --wavenumbers N also <term>_n_lat.csv.
 
+-f [--periodic] --maps: also the longitude-resolved maps of the eddy terms Ae, Ke, Ca, Ce, Ck, Ge on the box's points (``lec_maps``: the
+term's integrand with the zonal average left off, integrated over pressure), written to results_maps/<term>_lat_lon.csv (the time mean,
+latitudes x longitudes) and <term>_lon.csv (the area-weighted sum over latitude, time steps x longitudes: a Hovmoeller diagram).
+
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
 ``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
@@ -131,6 +135,14 @@ def create_arg_parser():
                         "every time step (rows: time steps, in the units of the results CSV).  With --wavenumbers N also <term>_n_lat.csv "
                         "for the spectral terms: the time mean of the vertical integral of every wavenumber's share (rows 1 .. N and "
                         "'rest').  Every other output file is unchanged.  One GPU; not for -t / -c")
+    parser.add_argument("--maps", action="store_true", default=argparse.SUPPRESS, help="with -f [--periodic]: also the longitude-resolved maps "
+                        "of the six eddy terms Ae, Ke, Ca, Ce, Ck and Ge (lec_maps: the term's integrand at every point of the box, the zonal "
+                        "average left off, integrated over pressure), written to results_maps/: <term>_lat_lon.csv, the time mean (rows: the "
+                        "box's latitudes, columns: its longitudes, in the units of the results CSV; the box's zonal average of a row is the "
+                        "term's --sections column) and <term>_lon.csv, the area-weighted sum over latitude at every time step (rows: time "
+                        "steps, columns: longitudes: a Hovmoeller diagram whose zonal average is the results CSV).  The zonal terms have no "
+                        "longitude structure and no map.  Every other output file is unchanged.  One GPU, data prepared on the host "
+                        "(--ingest auto resolves to host), evenly spaced longitudes; not for -t / -c")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -352,6 +364,18 @@ def refuse_periodic_options(args):
                              "move, and their sections would be system-relative composites")
         if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("--sections runs on one GPU: --gpus > 1 is not supported for the sections (run the totals sharded, the sections apart)")
+    if getattr(args, "maps", False):
+        if not args.fixed:
+            raise SystemExit("--maps goes with -f/--fixed: a map lies on the points of ONE fixed box; the boxes of a -t / -c run move, "
+                             "and their maps would be system-relative composites")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--maps runs on one GPU: --gpus > 1 is not supported for the maps (run the totals sharded, the maps apart)")
+        if getattr(args, "wavenumbers_chunk", None) is not None:
+            raise SystemExit("--maps prepares the data on the host: --wavenumbers-chunk streams the series and is not supported for the maps "
+                             "(the maps read the field cubes once more)")
+        if args.ingest == "device" or args.device_ingest:
+            raise SystemExit("--maps prepares the data on the host: --ingest device / --device-ingest is not supported for the maps "
+                             "(--ingest auto resolves to host)")
     n = getattr(args, "wavenumbers", None)
     chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:
@@ -473,6 +497,8 @@ def main(argv=None):
                                 "and the spectra are computed chunk by chunk (lec_level_spec_ring: no assembled row records)")
         elif args.ingest == "auto" and getattr(args, "wavenumbers", None) is not None:
             app_logger.info("--wavenumbers: --ingest auto resolves to host (the spectra run on host-prepared cubes)")
+        elif args.ingest == "auto" and getattr(args, "maps", False):
+            app_logger.info("--maps: --ingest auto resolves to host (the maps read host-prepared cubes once more)")
         elif args.ingest == "auto" and not args.device_ingest:
             from lorenzcycletoolkit_amd.ingest import prefers_device_ingest
             args.device_ingest, opened = prefers_device_ingest(args, "inputs/namelist", keep_open=True, app_logger=app_logger)

@@ -19,6 +19,8 @@ LEC_NLEVFUN = 28
 LEC_MAX_WAVENUMBERS = 64      # the largest n_wave of one lec_rowspec_ring call
 LEC_NSECTION = 10             # Az Ae Kz Ke Cz Ca Ck Ce Gz Ge: the terms that have a latitude-pressure section (lec_sections)
 LEC_LEVRAW_SIGMA = 33
+LEC_NMAP = 6                  # Ae Ke Ca Ce Ck Ge: the terms that have a longitude-resolved map (lec_maps)
+LEC_MAPS_NCOEF = 16           # doubles per (t, k, j) of lec_maps' coef_d workspace
 LEC_MAX_LEVELS = 160
 LEC_F64, LEC_F32, LEC_I16, LEC_I32, LEC_I8 = 0, 1, 2, 3, 4
 
@@ -50,7 +52,7 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_follow_seeds", "lec_follow_many", "lec_follow_seeds_series", "lec_follow_spans",
            "lec_follow_spans_chunk", "lec_follow_seeds_series_ring", "lec_follow_spans_chunk_ring", "lec_rowstats_ring",
            "lec_ingest_series", "lec_rowspec_ring", "lec_rowspec_q_ring", "lec_level_spec_ring",
-           "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring", "lec_sections"]
+           "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring", "lec_sections", "lec_maps"]
 
 
 class Tuning(C.Structure):
@@ -145,6 +147,19 @@ class SectionsArgs(C.Structure):
         ("sec_d", C.c_void_p), ("col_d", C.c_void_p), ("secsum_d", C.c_void_p),
         ("spec_d", C.c_void_p), ("qspec_d", C.c_void_p), ("n_wave", C.c_int32), ("reserved0", C.c_int32),
         ("specsec_d", C.c_void_p), ("speccolsum_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class MapsArgs(C.Structure):
+    """struct lec_maps_args (include/lec_hip.h)."""
+    _fields_ = [
+        ("tair_d", C.c_void_p), ("u_d", C.c_void_p), ("v_d", C.c_void_p), ("omega_d", C.c_void_p),
+        ("dtype", C.c_int32), ("nt", C.c_int32), ("nl", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+        ("t_begin", C.c_int32), ("t_count", C.c_int32), ("iw", C.c_int32), ("ie", C.c_int32), ("js", C.c_int32), ("jn", C.c_int32),
+        ("ring", C.c_int32), ("reserved0", C.c_int32),
+        ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p), ("lattab2_d", C.c_void_p), ("levtab2_d", C.c_void_p),
+        ("lattab_d", C.c_void_p), ("levtab_d", C.c_void_p), ("tcoef_d", C.c_void_p), ("inv_hdeg", C.c_double),
+        ("coef_d", C.c_void_p), ("col_d", C.c_void_p), ("mapsum_d", C.c_void_p), ("hov_d", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -323,6 +338,8 @@ def load():
     lib.lec_level_spec_b_ring.argtypes = [C.POINTER(LevelSpecBArgs)]
     lib.lec_sections.restype = C.c_int
     lib.lec_sections.argtypes = [C.POINTER(SectionsArgs)]
+    lib.lec_maps.restype = C.c_int
+    lib.lec_maps.argtypes = [C.POINTER(MapsArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

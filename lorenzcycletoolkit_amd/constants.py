@@ -16,6 +16,9 @@ LEVEL_TERMS = ["Az", "Ae", "Kz", "Ke", "Ge", "Gz", "Cz", "Cz_1", "Cz_2", "Ca", "
                "Ce", "Ce_1", "Ce_2", "Ck", "Ck_1", "Ck_2", "Ck_3", "Ck_4", "Ck_5"]
 # the terms that have a latitude-pressure section (LECResult.section_*; lec_sections), in the kernel's order
 SECTION_TERMS = ["Az", "Ae", "Kz", "Ke", "Cz", "Ca", "Ck", "Ce", "Gz", "Ge"]
+# the eddy terms that have a longitude-resolved map (LECResult.map_*; lec_maps), in the kernel's order; the zonal terms have no
+# longitude structure
+MAP_TERMS = ["Ae", "Ke", "Ca", "Ce", "Ck", "Ge"]
 # the eddy terms that have a zonal-wavenumber spectrum (LECResult.spectrum) and their per-level tables (LECResult.spectrum_levels;
 # Ce_1 = Rd / (p g) is a function of level alone, the same for every wavenumber: carried so that Ce's pieces stay together)
 SPECTRUM_TERMS = ["Ae", "Ke", "Ca", "Ce", "Ck"]

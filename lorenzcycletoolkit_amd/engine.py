@@ -59,6 +59,11 @@ class LECResult:
     section_steps: Optional[torch.Tensor] = None     # [t_count, 10, nl, nyb] fp64: X_f itself (on request; a series that was one chunk)
     section_spec_lat: Optional[torch.Tensor] = None  # [F, N + 1, nyb] fp64 (with wavenumbers=N): the time mean of the column value of
                                                      # X_f^n, f = Ae Ke Ca Ce Ck (Ge), n = 1 .. N, then the rest (the total minus the N)
+    # compute(..., maps=True) on ONE fixed box: the longitude-resolved maps of the six eddy terms (constants.MAP_TERMS; ``lec_maps``,
+    # DESIGN.md section 4.2d).  The box's zonal average of a map row closes on ``section_lat``, that of ``map_lon`` on ``scalars``
+    map_mean: Optional[torch.Tensor] = None          # [6, nyb, nxb] fp64: the time mean of the column values C_f(t, j, i) (NaN at any step: NaN)
+    map_lon: Optional[torch.Tensor] = None           # [t_count, 6, nxb] fp64: the Hovmoeller H_f(t, i) = sum_j cw_j C_f(t, j, i)
+    map_steps: Optional[torch.Tensor] = None         # [t_count, 6, nyb, nxb] fp64: C_f itself (on request; a series that was one chunk)
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -359,7 +364,7 @@ class LECEngine:
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
                 wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
                 spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                sections: bool = False, section_steps: bool = False) -> LECResult:
+                sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -395,7 +400,20 @@ class LECEngine:
         ``sections`` (ONE fixed box, one process): also ``section_mean`` and ``section_lat`` -- and ``section_steps`` when asked for, and
         ``section_spec_lat`` with ``wavenumbers`` --, the latitude x pressure sections of the ten terms (``section_stage``).  It
         changes no bit of anything else; without it nothing new runs or allocates.
+        ``maps`` (ONE fixed box with evenly spaced longitudes, one process, ``with_q`` and dT/dt from ``time_s`` / ``tcoef``): also
+        ``map_mean`` and ``map_lon`` -- and ``map_steps`` when asked for --, the longitude-resolved maps of the six eddy terms
+        (``map_stage``: the cubes are read once more).  It changes no bit of anything else; without it nothing new runs or allocates.
         """
+        if map_steps and not maps:
+            raise ValueError("map_steps: the per-step maps are part of maps=True")
+        if maps:
+            self._check_maps(boxes, per_step_boxes, steps, tm, tp)
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("maps run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
+            if dTdt is not None:
+                raise ValueError("maps: a dTdt cube is not supported (lec_maps forms dT/dt from the cube's time axis: give time_s or tcoef)")
+            if not with_q:
+                raise ValueError("maps need with_q: the map of Ge is Q'T' at every point, and its zonal mean [Q] comes from the row records")
         if section_steps and not sections:
             raise ValueError("section_steps: the per-step sections are part of sections=True")
         if sections:
@@ -443,6 +461,12 @@ class LECEngine:
             sec["levraw"] = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             if wavenumbers is None:
                 self.section_stage(rows, boxes, sec["levraw"], sec, 0)
+        if maps:
+            mp = self.map_begin(int(rows.shape[0]), boxes, rows.device, keep_steps=map_steps)
+            # (sigma is read from the level stage's levraw: the sections' copy, or one of the maps' own)
+            lr = sec["levraw"] if sec is not None else self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.map_stage(tair, u, v, omega, rows, boxes, lr, mp, 0, time_s=time_s, tcoef=tcoef, t_begin=t_begin)
+            self.map_finish(res, mp)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
@@ -540,6 +564,90 @@ class LECEngine:
                 ssum += shares[:, k]
             res.section_spec_lat = (torch.cat([shares, (tot - ssum).unsqueeze(1)], dim=1) / float(t_total)).contiguous()
 
+    # -- longitude-resolved maps of the eddy terms on one fixed box (lec_maps) ------------------------------------------------------------
+    # the column values C_f(t, j, i) and the row factors of the steps of ONE lec_maps call: a chunk that needs more is cut into sub-calls
+    MAP_CHUNK_BYTES = 256 << 20
+
+    @staticmethod
+    def _check_maps(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
+        n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
+        if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
+            raise ValueError("maps exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
+                             "no common points to lay a map on")
+
+    def map_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the maps of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once, here): ``map_stage``
+        adds every chunk to them, ``map_finish`` turns them into the result's fields."""
+        self._check_maps(boxes, False)
+        bx, bt, _ = self._resolve_boxes(boxes)
+        iw, ie, js, jn = bx[0]
+        nyb, nxb = jn - js + 1, ie - iw + 1
+        if bt.nyb_max != nyb:
+            raise ValueError("maps: the box's records must have the box's own row count (prepare_boxes without nyb_min)")
+        if not bt.lon_uniform:
+            raise ValueError("maps need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+        if nxb < 3:
+            raise ValueError("maps need at least 3 box columns")
+        f64 = dict(dtype=torch.float64, device=device)
+        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
+                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
+                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+
+    def map_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
+                  levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
+                  t_begin: int = 0) -> None:
+        """``lec_maps`` on a chunk: the cubes' steps [t_begin, t_begin + t_count), their row records ``rows`` [t_count, nl, nyb, 32] and
+        ``levraw`` [t_count, nl, 40] as ``level_stage`` left it for the same steps (sigma is read from it) -> the Hovmoeller rows
+        ``state["hov"][t_offset: t_offset + t_count]`` and the time sums added to ``state["mapsum"]`` (``map_begin``).  dT/dt over the
+        cube's time axis ``time_s`` (seconds, one entry per step of the cube) or ``tcoef``, as ``rowspec_q`` takes them.  A chunk whose
+        column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is
+        independent of how the series is cut, bit for bit."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        t_count = int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        self._check_maps(bx, False)
+        iw, ie, js, jn = bx[0]
+        nyb, nxb = jn - js + 1, ie - iw + 1
+        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
+                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
+            raise ValueError("map_stage: the chunk does not fit the series and box map_begin was given")
+        if not (0 <= t_begin and t_begin + t_count <= nt):
+            raise ValueError("map_stage: [t_begin, t_begin + t_count) lies outside the cubes")
+        if rows.device != tair.device:
+            raise ValueError("map_stage: rows and fields on one device")
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        tcoef = self._cube_tcoef("map_stage", time_s, tcoef, nt, tair.device)
+        f64 = dict(dtype=torch.float64, device=rows.device)
+        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+        if state["coef"] is None or state["coef"].shape[0] < sub:
+            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
+        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
+            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
+        for a in range(0, t_count, sub):
+            b = min(t_count, a + sub)
+            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+            ma = _lib.MapsArgs(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
+                t_begin=t_begin + a, t_count=b - a, iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, reserved0=0,
+                rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]), lattab2_d=_ptr(dev["lattab2"]), levtab2_d=_ptr(self._levtab2),
+                lattab_d=_ptr(dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]),
+                coef_d=_ptr(state["coef"]), col_d=_ptr(col), mapsum_d=_ptr(state["mapsum"]),
+                hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+            with torch.cuda.device(rows.device):
+                _lib.check(self.lib.lec_maps(C.byref(ma)), "lec_maps")
+
+    def map_finish(self, res: LECResult, state: dict) -> None:
+        """``res.map_*`` from the accumulators of a finished series."""
+        res.map_mean = state["mapsum"] / float(state["t_total"])
+        res.map_lon = state["hov"]
+        if state["steps"] is not None:
+            res.map_steps = state["steps"]
+
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
     # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records
     SPECTRUM_CHUNK_BYTES = 256 << 20
@@ -591,6 +699,24 @@ class LECEngine:
                 timing.append((ev0, ev1))
         return spec
 
+    def _cube_tcoef(self, who: str, time_s, tcoef: Optional[torch.Tensor], nt: int, device) -> torch.Tensor:
+        """The d/dt coefficients [nt, 3] of a cube's time axis on the device: ``tcoef`` checked, or built from ``time_s`` (seconds, one
+        entry per step of the cube) and kept for the next call on the same axis -- for the calls that form Q at every point."""
+        if tcoef is None:
+            if time_s is None:
+                raise ValueError(f"{who} needs time_s (seconds) or tcoef: Q holds dT/dt over the cube's time axis")
+            time_s = np.asarray(time_s, dtype=np.float64)
+            if time_s.size != nt:
+                raise ValueError("time_s must have one entry per time step of the cube")
+            if nt < 2:
+                raise ValueError("dT/dt by finite differences needs at least 2 time steps")
+            if self._tcoef is None or self._tcoef[0].shape != time_s.shape or not np.array_equal(self._tcoef[0], time_s):
+                self._tcoef = (time_s.copy(), self._up(tables.time_coefs(time_s)))
+            return self._tcoef[1]
+        if tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != device or not tcoef.is_contiguous():
+            raise ValueError("tcoef must be a contiguous fp64 [nt, 3] tensor on the fields' device")
+        return tcoef
+
     def rowspec_q(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, boxes: PreparedBoxes, wavenumbers: int, *,
                   time_s=None, tcoef: Optional[torch.Tensor] = None, t_begin: int = 0, t_count: Optional[int] = None,
                   out: Optional[torch.Tensor] = None, timing: Optional[list] = None) -> torch.Tensor:
@@ -605,19 +731,7 @@ class LECEngine:
         n = int(wavenumbers)
         if t_count is None:
             t_count = nt - t_begin
-        if tcoef is None:
-            if time_s is None:
-                raise ValueError("rowspec_q needs time_s (seconds) or tcoef: Q holds dT/dt over the cube's time axis")
-            time_s = np.asarray(time_s, dtype=np.float64)
-            if time_s.size != nt:
-                raise ValueError("time_s must have one entry per time step of the cube")
-            if nt < 2:
-                raise ValueError("dT/dt by finite differences needs at least 2 time steps")
-            if self._tcoef is None or self._tcoef[0].shape != time_s.shape or not np.array_equal(self._tcoef[0], time_s):
-                self._tcoef = (time_s.copy(), self._up(tables.time_coefs(time_s)))
-            tcoef = self._tcoef[1]
-        elif tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
-            raise ValueError("tcoef must be a contiguous fp64 [nt, 3] tensor on the fields' device")
+        tcoef = self._cube_tcoef("rowspec_q", time_s, tcoef, nt, tair.device)
         _, _, js, jn = boxes.boxes[0]
         shape = (t_count, nl, jn - js + 1, n)
         qspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out

@@ -72,7 +72,7 @@ class BoxData:
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
                  spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                 sections: bool = False):
+                 sections: bool = False, maps: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -90,6 +90,19 @@ class BoxData:
                                  "to lay a section on")
             if getattr(args, "shard", None) is not None:
                 raise ValueError("sections run on one GPU (no time shards)")
+        self.maps = bool(maps)
+        self.map_mean = self.map_lon = None
+        if self.maps:                   # (host work only, as above)
+            from .ingest import StreamedDataset as _StreamedData
+            if boxes_limits is not None:
+                raise ValueError("maps exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes) has no common points "
+                                 "to lay a map on")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("maps run on one GPU (no time shards)")
+            if dTdt is not None:
+                raise ValueError("maps: a dTdt cube is not supported (lec_maps forms dT/dt from the time axis)")
+            if isinstance(data, _StreamedData):
+                raise ValueError("maps prepare the data on the host: the streamed path (--ingest device / --device-ingest) is not supported")
         self.wavenumbers = None if wavenumbers is None else int(wavenumbers)
         self.spectrum = self.spectrum_rest = self.spectrum_levels = None
         if wavenumbers is not None:     # (host work only, as above)
@@ -213,6 +226,12 @@ class BoxData:
                 self.section_spec_lat = self.result.section_spec_lat.cpu().numpy()
             js, jn = self.boxes[0][2], self.boxes[0][3]
             self.section_latitudes = np.asarray(data.lat[js: jn + 1], dtype=np.float64)
+        if self.result.map_mean is not None:
+            self.map_mean = self.result.map_mean.cpu().numpy()
+            self.map_lon = self.result.map_lon.cpu().numpy()
+            iw, ie, js, jn = self.boxes[0]
+            self.map_latitudes = np.asarray(data.lat[js: jn + 1], dtype=np.float64)
+            self.map_longitudes = np.asarray(data.lon[iw: ie + 1], dtype=np.float64)
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -256,7 +275,7 @@ class BoxData:
                                    **({"spectrum_generation": True} if self.spectrum_generation else {}),
                                    **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
                                    **({"spectrum_budget": True} if self.spectrum_budget else {}),
-                                   **({"sections": True} if self.sections else {}))
+                                   **({"sections": True} if self.sections else {}), **({"maps": True} if self.maps else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -382,6 +401,36 @@ def write_section_csvs(box_obj: "BoxData", directory: str, time_name: str, vert_
         names = [str(k) for k in range(1, n1)] + ["rest"]
         for i, term in enumerate(LECEngine.SECTION_SPEC_TERMS[:nf]):
             write(os.path.join(directory, f"{term}_n_lat.csv"), "n", names, box_obj.section_spec_lat[i])
+
+
+def write_map_csvs(box_obj: "BoxData", directory: str, time_name: str, lat_name: str) -> None:
+    """results_maps/: for each of the six eddy terms ``<term>_lat_lon.csv`` -- the time mean of the term's map, one row per latitude of the
+    box (labelled in degrees, as a float), one column per longitude of the box in degrees, in the units of the results CSV -- and
+    ``<term>_lon.csv`` -- the map's area-weighted sum over latitude, one row per time step (the time labels and number formatting of the
+    per-level tables), one column per longitude: a Hovmoeller diagram whose zonal average is the results CSV."""
+    from .constants import MAP_TERMS
+    os.makedirs(directory, exist_ok=True)
+    lons = [repr(float(x)) for x in box_obj.map_longitudes]
+    lat_names = [repr(float(x)) for x in box_obj.map_latitudes]
+    labels = box_obj.row_labels("fixed")
+
+    def header(path, first):
+        with open(path, "wb") as f:
+            f.write((",".join([str(first)] + lons) + "\n").encode("utf-8"))
+
+    for i, term in enumerate(MAP_TERMS):
+        path = os.path.join(directory, f"{term}_lat_lon.csv")
+        header(path, lat_name)
+        with open(path, "ab") as f:      # (latitude labels of mixed widths: one call per row)
+            for name, row in zip(lat_names, np.asarray(box_obj.map_mean[i], dtype=np.float64)):
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+        path = os.path.join(directory, f"{term}_lon.csv")
+        header(path, time_name)
+        if labels[0] is not None:
+            with open(path, "ab") as f:
+                f.write(format_level_table(box_obj.map_lon[:, i, :], labels))
+        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
+            pd.DataFrame(box_obj.map_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
 
 
 def ring_hint(lon, box):
@@ -589,13 +638,27 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
     sections = bool(getattr(args, "sections", False))
     if sections and shard is not None:
         raise ValueError("--sections runs on one GPU")
+    maps = bool(getattr(args, "maps", False))
+    if maps:            # likewise refused before a file is written
+        from .ingest import StreamedDataset
+        from .tables import box_indices, is_uniform
+        if shard is not None:
+            raise ValueError("--maps runs on one GPU")
+        if isinstance(data, StreamedDataset):
+            raise ValueError("--maps prepares the data on the host: --ingest device / --device-ingest is not supported for the maps")
+        iw, ie, _, _ = box_indices(data.lat, data.lon, min_lon, max_lon, min_lat, max_lat)
+        if ie - iw + 1 < 3:
+            raise ValueError("--maps needs a box of at least 3 longitudes")
+        if not periodic and not is_uniform(np.asarray(data.lon, dtype=np.float64)):
+            raise ValueError("--maps needs evenly spaced longitudes")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
         box_obj = BoxData(data, variable_list_df, min_lon, max_lon, min_lat, max_lat, args, results_subdirectory,
                           results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
                           spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}),
-                          **({"spectrum_budget": True} if budget else {}), **({"sections": True} if sections else {}))
+                          **({"spectrum_budget": True} if budget else {}), **({"sections": True} if sections else {}),
+                          **({"maps": True} if maps else {}))
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -634,6 +697,11 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         write_section_csvs(box_obj, section_directory, time_name, vert_name)
         app_logger.info(f"--sections: the latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge on the box's "
                         f"{len(box_obj.section_latitudes)} rows (lec_sections); written to {section_directory}")
+    if maps:
+        map_directory = os.path.join(results_subdirectory, "results_maps")
+        write_map_csvs(box_obj, map_directory, time_name, variable_list_df.loc["Latitude"]["Variable"])
+        app_logger.info(f"--maps: the longitude-resolved maps of Ae, Ke, Ca, Ce, Ck, Ge on the box's {len(box_obj.map_latitudes)} x "
+                        f"{len(box_obj.map_longitudes)} points (lec_maps); written to {map_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]
