@@ -10,7 +10,8 @@ Bars.  1e-9 of the term's scale (its largest |value| in the case) for the per-st
 restatement, for the zonal average of a map row against the run's own ``section_lat`` and for that of the Hovmoeller against its scalars:
 the project's parity bar.  NaN patterns are the restatement's exactly; chunk independence and ``maps=False`` are bit for bit.
 Measured on MI355X: map_steps 5.2e-14, map_lon 4.6e-14, map_mean 2.6e-14, closure on section_lat 4.5e-15, on the scalars 9.9e-15 (each
-test prints its own figure)."""
+test prints its own figure).
+Uneven axes, inner bands (js > 0, NaN rows and columns around the box) and NaNs in the other fields: tests/test_gpu_ring_axes.py."""
 import dataclasses
 
 import numpy as np

@@ -9,7 +9,8 @@ Bars.  1e-9 of the term's scale (the largest |value| of the term in the case) fo
 restatement, for the closure of sum_j cw_j X_f on the engine's per-level tables, of sum_j cw_j C_f on its scalars, and for the Parseval
 closure of the spectral sections: the project's parity bar.  Chunk independence and ``sections=False`` are bit for bit.
 Measured on MI355X: sections 2.3e-13, columns 1.2e-13, means 1.5e-13, closure on levels 3.1e-15, on scalars 2.8e-15, Parseval 4.8e-15,
-spectral columns 2.9e-14 (each test prints its own figure)."""
+spectral columns 2.9e-14 (each test prints its own figure).
+Uneven axes, inner bands (js > 0, NaN rows and columns around the box) and NaNs in the other fields: tests/test_gpu_ring_axes.py."""
 import numpy as np
 import pytest
 
