@@ -44,6 +44,11 @@ mean, levels x latitudes) and <term>_lat.csv (the vertical integral, time steps 
 term's integrand with the zonal average left off, integrated over pressure), written to results_maps/<term>_lat_lon.csv (the time mean,
 latitudes x longitudes) and <term>_lon.csv (the area-weighted sum over latitude, time steps x longitudes: a Hovmoeller diagram).
 
+-t / -c --composites: also the system-relative composites of the same six eddy terms over the boxes that follow the system
+(``lec_composite``: ``lec_maps`` on box-relative points, every step with its own box), written to results_composites/<term>_dlat_dlon.csv
+(the time mean, box rows x box columns, labelled by the offset in degrees from the box's midpoint) and <term>_dlon.csv (the area-weighted
+sum over the box's rows, time steps x box columns).  One system whose boxes all have one shape.
+
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
 ``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
@@ -143,6 +148,14 @@ def create_arg_parser():
                         "steps, columns: longitudes: a Hovmoeller diagram whose zonal average is the results CSV).  The zonal terms have no "
                         "longitude structure and no map.  Every other output file is unchanged.  One GPU, data prepared on the host "
                         "(--ingest auto resolves to host), evenly spaced longitudes; not for -t / -c")
+    parser.add_argument("--composites", action="store_true", default=argparse.SUPPRESS, help="with -t --trackfile or -c (one system): also "
+                        "the system-relative composites of the six eddy terms Ae, Ke, Ca, Ce, Ck and Ge (lec_composite: the term's integrand at "
+                        "every point of every time step's box, integrated over pressure, laid on the box-relative points), written to "
+                        "results_composites/: <term>_dlat_dlon.csv, the time mean over the system's life (rows: the box's rows, columns: its "
+                        "columns, both labelled by the offset in degrees from the box's midpoint, in the units of the results CSV) and "
+                        "<term>_dlon.csv, the area-weighted sum over the box's rows at every time step (rows: time steps; the box's zonal "
+                        "average of a row is the results CSV).  Every other output file is unchanged.  One GPU, data prepared on the host "
+                        "(--ingest auto resolves to host), evenly spaced longitudes and latitudes, boxes of one shape; -f has --maps")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -376,6 +389,22 @@ def refuse_periodic_options(args):
         if args.ingest == "device" or args.device_ingest:
             raise SystemExit("--maps prepares the data on the host: --ingest device / --device-ingest is not supported for the maps "
                              "(--ingest auto resolves to host)")
+    if getattr(args, "composites", False):
+        if args.fixed:
+            raise SystemExit("--composites goes with -t / -c: ONE fixed box has --maps, the maps on the box's own points; a composite is "
+                             "laid on the box-relative points of the boxes that follow a system")
+        if args.trackfiles is not None:
+            raise SystemExit("--composites follows ONE system: --trackfiles analyses a batch of tracks and has no composites "
+                             "(run -t --trackfile FILE --composites for the track that matters)")
+        if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
+            raise SystemExit("--composites follows ONE system: -c --choose-systems / --choose-starts follows a batch and has no composites "
+                             "(run -t --trackfile on a track it wrote, with --composites)")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--composites runs on one GPU: --gpus > 1 is not supported for the composites (run the totals sharded, the "
+                             "composites apart)")
+        if args.ingest == "device" or args.device_ingest:
+            raise SystemExit("--composites prepares the data on the host: --ingest device / --device-ingest is not supported for the "
+                             "composites (--ingest auto resolves to host)")
     n = getattr(args, "wavenumbers", None)
     chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:
@@ -499,6 +528,8 @@ def main(argv=None):
             app_logger.info("--wavenumbers: --ingest auto resolves to host (the spectra run on host-prepared cubes)")
         elif args.ingest == "auto" and getattr(args, "maps", False):
             app_logger.info("--maps: --ingest auto resolves to host (the maps read host-prepared cubes once more)")
+        elif args.ingest == "auto" and getattr(args, "composites", False):
+            app_logger.info("--composites: --ingest auto resolves to host (the composites read the host-prepared series once more)")
         elif args.ingest == "auto" and not args.device_ingest:
             from lorenzcycletoolkit_amd.ingest import prefers_device_ingest
             args.device_ingest, opened = prefers_device_ingest(args, "inputs/namelist", keep_open=True, app_logger=app_logger)

@@ -64,6 +64,12 @@ class LECResult:
     map_mean: Optional[torch.Tensor] = None          # [6, nyb, nxb] fp64: the time mean of the column values C_f(t, j, i) (NaN at any step: NaN)
     map_lon: Optional[torch.Tensor] = None           # [t_count, 6, nxb] fp64: the Hovmoeller H_f(t, i) = sum_j cw_j C_f(t, j, i)
     map_steps: Optional[torch.Tensor] = None         # [t_count, 6, nyb, nxb] fp64: C_f itself (on request; a series that was one chunk)
+    # compute(..., per_step_boxes=True, composites=True) on per-step boxes of ONE shape: the system-relative composites of the same six
+    # terms on box-relative indices (``lec_composite``).  The zonal average over step t's box of
+    # ``composite_lon[t]`` closes on ``scalars[t]``
+    composite_mean: Optional[torch.Tensor] = None    # [6, nyb, nxb] fp64: the time mean of C_f(t, j, i), (j, i) relative to each step's box
+    composite_lon: Optional[torch.Tensor] = None     # [t_count, 6, nxb] fp64: H_f(t, i) = sum_j cw_j(t) C_f(t, j, i), cw of step t's box
+    composite_steps: Optional[torch.Tensor] = None   # [t_count, 6, nyb, nxb] fp64: C_f itself (on request)
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -364,7 +370,8 @@ class LECEngine:
                 tcoef: Optional[torch.Tensor] = None, steps: Optional[torch.Tensor] = None,
                 wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
                 spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False) -> LECResult:
+                sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False,
+                composites: bool = False, composite_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -403,7 +410,21 @@ class LECEngine:
         ``maps`` (ONE fixed box with evenly spaced longitudes, one process, ``with_q`` and dT/dt from ``time_s`` / ``tcoef``): also
         ``map_mean`` and ``map_lon`` -- and ``map_steps`` when asked for --, the longitude-resolved maps of the six eddy terms
         (``map_stage``: the cubes are read once more).  It changes no bit of anything else; without it nothing new runs or allocates.
+        ``composites`` (per-step boxes that all have ONE shape, evenly spaced longitudes, one process, ``with_q``; cubes, or a box-packed
+        series with its ``dTdt`` cube or ``tm`` / ``tp``): also ``composite_mean`` and ``composite_lon`` -- and ``composite_steps`` when
+        asked for --, the system-relative composites of the six eddy terms on box-relative indices (``composite_stage``: the cubes are
+        read once more).  It changes no bit of anything else; without it nothing new runs or allocates.
         """
+        if composite_steps and not composites:
+            raise ValueError("composite_steps: the per-step columns are part of composites=True")
+        if composites:
+            lon = getattr(self, "lon", None)
+            self._check_composites(boxes, per_step_boxes, steps, boxes.bt.lon_uniform if isinstance(boxes, PreparedBoxes)
+                                   else (None if lon is None else tables.is_uniform(lon)))
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("composites run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
+            if not with_q:
+                raise ValueError("composites need with_q: the composite of Ge is Q'T' at every point, and its zonal mean [Q] comes from the row records")
         if map_steps and not maps:
             raise ValueError("map_steps: the per-step maps are part of maps=True")
         if maps:
@@ -467,6 +488,12 @@ class LECEngine:
             lr = sec["levraw"] if sec is not None else self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             self.map_stage(tair, u, v, omega, rows, boxes, lr, mp, 0, time_s=time_s, tcoef=tcoef, t_begin=t_begin)
             self.map_finish(res, mp)
+        if composites:
+            pb = boxes if isinstance(boxes, PreparedBoxes) else PreparedBoxes(*self._resolve_boxes(boxes))
+            cp = self.composite_begin(int(rows.shape[0]), pb, rows.device, keep_steps=composite_steps)
+            lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.composite_stage(tair, u, v, omega, rows, pb, lr, cp, 0, time_s=time_s, dTdt=dTdt, tm=tm, tp=tp, tcoef=tcoef, t_begin=t_begin)
+            self.composite_finish(res, cp)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
@@ -647,6 +674,118 @@ class LECEngine:
         res.map_lon = state["hov"]
         if state["steps"] is not None:
             res.map_steps = state["steps"]
+
+    # -- system-relative composites of the eddy terms over per-step boxes of one shape (lec_composite) -----------------------------------
+    @staticmethod
+    def _check_composites(boxes, per_step_boxes, steps=None, lon_uniform: Optional[bool] = None) -> tuple:
+        """The refusals of the composites that need nothing but the boxes: returns (nyb, nxb), the one shape of every box."""
+        bx = boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes
+        if steps is not None:
+            raise ValueError("composites: a step table (steps=, the batch of lec_rowstats_steps) has none: composites exist for ONE track")
+        if per_step_boxes is False or (per_step_boxes is None and len(bx) == 1):
+            raise ValueError("composites exist for per-step boxes (per_step_boxes=True): a composite is laid on the box-relative points "
+                             "of a series of moving boxes; ONE fixed box has maps=True")
+        bx = [tuple(int(x) for x in b) for b in bx]
+        nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
+        for t, b in enumerate(bx):
+            h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
+            if (h, w) != (nyb, nxb):
+                raise ValueError(f"composites need boxes of ONE shape: the box of step {t} has {h} x {w} points (rows x columns), that of "
+                                 f"step 0 has {nyb} x {nxb}")
+        if nxb < 3:
+            raise ValueError("composites need at least 3 box columns")
+        if lon_uniform is False:
+            raise ValueError("composites need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+        return nyb, nxb
+
+    def composite_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the composites of a series of ``t_total`` steps whose boxes all have the shape of ``boxes``' (zeroed once,
+        here): ``composite_stage`` adds every chunk to them, ``composite_finish`` turns them into the result's fields."""
+        nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform)
+        if boxes.bt.nyb_max != nyb:
+            raise ValueError("composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
+        f64 = dict(dtype=torch.float64, device=device)
+        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
+                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
+                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+
+    def composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
+                        boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
+                        dTdt: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None, tp: Optional[torch.Tensor] = None,
+                        tcoef: Optional[torch.Tensor] = None, t_begin: int = 0) -> None:
+        """``lec_composite`` on a chunk: the cubes' steps [t_begin, t_begin + t_count), one box of ``boxes`` per step (prepared with
+        ``packed=True`` for a box-packed series, whose cubes are slabs), their row records ``rows`` [t_count, nl, nyb, 32] and ``levraw``
+        [t_count, nl, 40] as ``level_stage`` left it for the same steps -> the Hovmoeller rows ``state["hov"][t_offset: t_offset + t_count]``
+        and the time sums added to ``state["mapsum"]`` (``composite_begin``).  dT/dt as ``rowstats`` takes it: a ``dTdt`` cube (one in the
+        fields' fp32 is widened to fp64, the value stage 1 reads), or ``tm`` / ``tp`` with ``tcoef``, or -- an unpacked cube only -- the
+        cube's own time axis ``time_s`` / ``tcoef``.  A chunk whose column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into
+        sub-calls.  Chunks must come in time order; every number is independent of how the series is cut, bit for bit."""
+        if not isinstance(boxes, PreparedBoxes):
+            raise ValueError("composite_stage: boxes from prepare_boxes")
+        packed = "box_data" in boxes.dev
+        if (tm is None) != (tp is None):
+            raise ValueError("composite_stage: tm and tp come together")
+        if dTdt is not None and tm is not None:
+            raise ValueError("composite_stage: a dTdt cube or tm / tp, not both")
+        if packed and dTdt is None and tm is None:
+            raise ValueError("composite_stage: a box-packed series needs its dTdt cube or tm / tp (its time neighbours are other boxes)")
+        self._check_fields([tair, u, v, omega] + [c for c in (tm, tp) if c is not None], boxes if packed else None)
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        t_count = int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        if len(bx) != t_count:
+            raise ValueError("composite_stage: one box per step of the chunk")
+        nyb, nxb = self._check_composites(bx, True, None, bt.lon_uniform)
+        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
+                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
+            raise ValueError("composite_stage: the chunk does not fit the series and box shape composite_begin was given")
+        if not (0 <= t_begin and t_begin + t_count <= nt):
+            raise ValueError("composite_stage: [t_begin, t_begin + t_count) lies outside the cubes")
+        if rows.device != tair.device:
+            raise ValueError("composite_stage: rows and fields on one device")
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        if dTdt is not None:
+            if dTdt.shape != tair.shape or dTdt.device != tair.device or dTdt.dtype not in (torch.float64, torch.float32):
+                raise ValueError("dTdt must be a cube of the fields' shape on their device")
+            dTdt = dTdt.to(torch.float64).contiguous()
+            tcoef = None
+        elif tm is not None:
+            if tcoef is None or tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
+                raise ValueError("tm / tp need tcoef: a contiguous fp64 [nt, 3] tensor on the fields' device (the rows of the cubes' steps)")
+        else:
+            tcoef = self._cube_tcoef("composite_stage", time_s, tcoef, nt, tair.device)
+        box_host = np.ascontiguousarray([(0, b[1] - b[0], 0, b[3] - b[2]) for b in bx] if packed else bx, dtype=np.int32)
+        box_dev = dev["box_data" if packed else "box"]
+        f64 = dict(dtype=torch.float64, device=rows.device)
+        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+        if state["coef"] is None or state["coef"].shape[0] < sub:
+            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
+        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
+            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
+        for a in range(0, t_count, sub):
+            b = min(t_count, a + sub)
+            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+            ca = _lib.CompositeArgs(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp),
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
+                t_begin=t_begin + a, t_count=b - a, nyb=nyb, nxb=nxb, reserved0=0,
+                box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
+                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
+                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), tcoef_d=_ptr(tcoef),
+                coef_d=_ptr(state["coef"]), col_d=_ptr(col), mapsum_d=_ptr(state["mapsum"]),
+                hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+            with torch.cuda.device(rows.device):
+                _lib.check(self.lib.lec_composite(C.byref(ca)), "lec_composite")
+
+    def composite_finish(self, res: LECResult, state: dict) -> None:
+        """``res.composite_*`` from the accumulators of a finished series."""
+        res.composite_mean = state["mapsum"] / float(state["t_total"])
+        res.composite_lon = state["hov"]
+        if state["steps"] is not None:
+            res.composite_steps = state["steps"]
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
     # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records

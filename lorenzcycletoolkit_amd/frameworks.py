@@ -72,7 +72,7 @@ class BoxData:
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
                  spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                 sections: bool = False, maps: bool = False):
+                 sections: bool = False, maps: bool = False, composites: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -103,6 +103,18 @@ class BoxData:
                 raise ValueError("maps: a dTdt cube is not supported (lec_maps forms dT/dt from the time axis)")
             if isinstance(data, _StreamedData):
                 raise ValueError("maps prepare the data on the host: the streamed path (--ingest device / --device-ingest) is not supported")
+        self.composites = bool(composites)
+        self.composite_mean = self.composite_lon = None
+        if self.composites:             # (host work only, as above)
+            from .ingest import StreamedDataset as _StreamedData
+            if boxes_limits is None:
+                raise ValueError("composites exist for the per-step boxes of a track (boxes_limits): ONE fixed box has maps")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("composites run on one GPU (no time shards)")
+            if isinstance(data, _StreamedData):
+                raise ValueError("composites prepare the data on the host: the streamed path (--ingest device / --device-ingest) is not supported")
+            from .tables import box_indices
+            composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, *lim) for lim in boxes_limits], flag="composites", lat_too=False)
         self.wavenumbers = None if wavenumbers is None else int(wavenumbers)
         self.spectrum = self.spectrum_rest = self.spectrum_levels = None
         if wavenumbers is not None:     # (host work only, as above)
@@ -232,6 +244,10 @@ class BoxData:
             iw, ie, js, jn = self.boxes[0]
             self.map_latitudes = np.asarray(data.lat[js: jn + 1], dtype=np.float64)
             self.map_longitudes = np.asarray(data.lon[iw: ie + 1], dtype=np.float64)
+        if self.result.composite_mean is not None:
+            self.composite_mean = self.result.composite_mean.cpu().numpy()
+            self.composite_lon = self.result.composite_lon.cpu().numpy()
+            self.composite_dlat, self.composite_dlon = composite_offsets(data.lat, data.lon, self.boxes[0])
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -275,7 +291,8 @@ class BoxData:
                                    **({"spectrum_generation": True} if self.spectrum_generation else {}),
                                    **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
                                    **({"spectrum_budget": True} if self.spectrum_budget else {}),
-                                   **({"sections": True} if self.sections else {}), **({"maps": True} if self.maps else {}))
+                                   **({"sections": True} if self.sections else {}), **({"maps": True} if self.maps else {}),
+                                   **({"composites": True} if self.composites else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -297,7 +314,8 @@ class BoxData:
         pb = self.engine.prepare_boxes(boxes, nyb_min=nyb, packed=True)
         kw = self.engine.packed_dtdt(tm, f[0], tp, tcoef)
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
-                                   drop_any_time=False, merge_dropmask=merge, out=out, **kw)
+                                   drop_any_time=False, merge_dropmask=merge, out=out, **kw,
+                                   **({"composites": True} if self.composites else {}))
 
 
 def ring_box_check(lon, box) -> float:
@@ -431,6 +449,66 @@ def write_map_csvs(box_obj: "BoxData", directory: str, time_name: str, lat_name:
                 f.write(format_level_table(box_obj.map_lon[:, i, :], labels))
         else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
             pd.DataFrame(box_obj.map_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+
+
+def composites_check(lat, lon, boxes, flag: str = "--composites", lat_too: bool = True) -> tuple:
+    """The boxes of a track that is to be composited (index quadruples, one per time step) on the axes ``lat`` / ``lon``: all of ONE shape
+    (ValueError naming the first step that differs and both shapes), at least 3 columns wide, on evenly spaced longitudes -- and, for the
+    command line, latitudes (the offsets that label the files are those of the first step's box).  Host work only.  Returns (rows,
+    columns) of every box."""
+    from .tables import is_uniform
+    boxes = [tuple(int(x) for x in b) for b in boxes]
+    nyb, nxb = boxes[0][3] - boxes[0][2] + 1, boxes[0][1] - boxes[0][0] + 1
+    for t, b in enumerate(boxes):
+        h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
+        if (h, w) != (nyb, nxb):
+            raise ValueError(f"{flag} needs boxes of ONE shape: the box of step {t} has {h} x {w} points (rows x columns), that of step 0 "
+                             f"has {nyb} x {nxb} (a track near the data's edge, or one with width / length columns that change)")
+    if nxb < 3:
+        raise ValueError(f"{flag} needs boxes of at least 3 longitudes")
+    if not is_uniform(np.asarray(lon, dtype=np.float64)):
+        raise ValueError(f"{flag} needs evenly spaced longitudes")
+    if lat_too and not is_uniform(np.asarray(lat, dtype=np.float64)):
+        raise ValueError(f"{flag} needs evenly spaced latitudes: a box-relative row means the same offset at every step only there")
+    return nyb, nxb
+
+
+def composite_offsets(lat, lon, box):
+    """(dlat [nyb], dlon [nxb]): the offsets in degrees of the box's rows and columns from its midpoint, lat[js + j] - (lat[js] + lat[jn]) / 2
+    and likewise in longitude -- the labels of the composites' files, taken from the first step's box."""
+    iw, ie, js, jn = (int(x) for x in box)
+    la, lo = np.asarray(lat[js: jn + 1], dtype=np.float64), np.asarray(lon[iw: ie + 1], dtype=np.float64)
+    return la - (la[0] + la[-1]) / 2, lo - (lo[0] + lo[-1]) / 2
+
+
+def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
+    """results_composites/: for each of the six eddy terms ``<term>_dlat_dlon.csv`` -- the time-mean system-relative composite, one row per
+    box row, one column per box column, both labelled by the offset in degrees from the box's midpoint (``composite_offsets``), in the
+    units of the results CSV -- and ``<term>_dlon.csv`` -- the composite's area-weighted sum over the box's rows, one row per time step
+    (the time labels and number formatting of the per-level tables), one column per box column.  ``write_map_csvs``' format."""
+    from .constants import MAP_TERMS
+    os.makedirs(directory, exist_ok=True)
+    lons = [repr(float(x)) for x in box_obj.composite_dlon]
+    lat_names = [repr(float(x)) for x in box_obj.composite_dlat]
+    labels = box_obj.row_labels("fixed")
+
+    def header(path, first):
+        with open(path, "wb") as f:
+            f.write((",".join([str(first)] + lons) + "\n").encode("utf-8"))
+
+    for i, term in enumerate(MAP_TERMS):
+        path = os.path.join(directory, f"{term}_dlat_dlon.csv")
+        header(path, "dlat")
+        with open(path, "ab") as f:      # (labels of mixed widths: one call per row)
+            for name, row in zip(lat_names, np.asarray(box_obj.composite_mean[i], dtype=np.float64)):
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+        path = os.path.join(directory, f"{term}_dlon.csv")
+        header(path, time_name)
+        if labels[0] is not None:
+            with open(path, "ab") as f:
+                f.write(format_level_table(box_obj.composite_lon[:, i, :], labels))
+        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
+            pd.DataFrame(box_obj.composite_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
 
 
 def ring_hint(lon, box):
@@ -747,6 +825,17 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     vert_name = variable_list_df.loc["Vertical Level"]["Variable"]
     shard = getattr(args, "shard", None)
     root = shard is None or shard.root
+    composites = bool(getattr(args, "composites", False))
+    if composites:      # refused before a file is written
+        from .ingest import StreamedDataset
+        from .tables import box_indices
+        if shard is not None:
+            raise ValueError("--composites runs on one GPU")
+        if isinstance(data, StreamedDataset):
+            raise ValueError("--composites prepares the data on the host: --ingest device / --device-ingest is not supported for the composites")
+        track0 = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)
+        lims = [get_limits(track0, t) for t in pd.DatetimeIndex(data.time)]
+        composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in lims])
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     times = pd.DatetimeIndex(data.time)
@@ -766,8 +855,13 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     boxes = [(l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in limits]
     box_obj = BoxData(data, variable_list_df, args=args, results_subdirectory=results_subdirectory,
                       results_subdirectory_vertical_levels=results_subdirectory_vertical_levels, dTdt=dTdt,
-                      boxes_limits=boxes)
+                      boxes_limits=boxes, **({"composites": True} if composites else {}))
     phases.mark("ingest_compute_gather")
+    if composites:
+        composite_directory = os.path.join(results_subdirectory, "results_composites")
+        write_composite_csvs(box_obj, composite_directory, time_name)
+        app_logger.info(f"--composites: the system-relative composites of Ae, Ke, Ca, Ce, Ck, Ge on the boxes' {len(box_obj.composite_dlat)} x "
+                        f"{len(box_obj.composite_dlon)} box-relative points (lec_composite); written to {composite_directory}")
     # 850-hPa diagnostics of every box (lec_moving_framework.py:650-709); a time-sharded rank does its own steps, rank 0 gets them all
     from .diagnostics import track_diagnostics
     form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
