@@ -596,6 +596,44 @@ class LECEngine:
     MAP_CHUNK_BYTES = 256 << 20
 
     @staticmethod
+    def _mapcol_begin(t_total: int, nyb: int, nxb: int, device, keep_steps: bool) -> dict:
+        """The accumulators of the maps or composites of ``t_total`` steps on ``nyb`` x ``nxb`` points, zeroed."""
+        f64 = dict(dtype=torch.float64, device=device)
+        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
+                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
+                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+
+    def _mapcol_stage(self, cubes, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, t_begin: int, issue) -> None:
+        """What ``map_stage`` and ``composite_stage`` do alike once their own arguments are checked: ``levraw``'s check, the cut of the
+        chunk into sub-calls whose column values and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and
+        the sub-calls in time order: ``issue(a, b, shared)`` calls on the chunk's steps [a, b), ``shared`` the fields both args structs have."""
+        tair, u, v, omega = cubes
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        t_count, nyb, nxb = int(rows.shape[0]), state["nyb"], state["nxb"]
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        f64 = dict(dtype=torch.float64, device=rows.device)
+        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+        if state["coef"] is None or state["coef"].shape[0] < sub:
+            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
+        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
+            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
+        for a in range(0, t_count, sub):
+            b = min(t_count, a + sub)
+            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+            shared = dict(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
+                t_begin=t_begin + a, t_count=b - a, reserved0=0, rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
+                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), coef_d=_ptr(state["coef"]), col_d=_ptr(col),
+                mapsum_d=_ptr(state["mapsum"]), hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]),
+                stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+            with torch.cuda.device(rows.device):
+                issue(a, b, shared)
+
+    @staticmethod
     def _check_maps(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
         n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
         if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
@@ -615,10 +653,7 @@ class LECEngine:
             raise ValueError("maps need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
         if nxb < 3:
             raise ValueError("maps need at least 3 box columns")
-        f64 = dict(dtype=torch.float64, device=device)
-        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
-                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
-                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+        return self._mapcol_begin(t_total, nyb, nxb, device, keep_steps)
 
     def map_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
                   levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
@@ -630,8 +665,7 @@ class LECEngine:
         column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is
         independent of how the series is cut, bit for bit."""
         self._check_fields([tair, u, v, omega], None)
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        t_count = int(rows.shape[0])
+        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
         bx, bt, dev = self._stage2_input(rows, boxes)
         self._check_maps(bx, False)
         iw, ie, js, jn = bx[0]
@@ -643,30 +677,13 @@ class LECEngine:
             raise ValueError("map_stage: [t_begin, t_begin + t_count) lies outside the cubes")
         if rows.device != tair.device:
             raise ValueError("map_stage: rows and fields on one device")
-        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
-                or not levraw.is_contiguous()):
-            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
         tcoef = self._cube_tcoef("map_stage", time_s, tcoef, nt, tair.device)
-        f64 = dict(dtype=torch.float64, device=rows.device)
-        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
-        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
-        if state["coef"] is None or state["coef"].shape[0] < sub:
-            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
-        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
-            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
-        for a in range(0, t_count, sub):
-            b = min(t_count, a + sub)
-            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
-            ma = _lib.MapsArgs(
-                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
-                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
-                t_begin=t_begin + a, t_count=b - a, iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, reserved0=0,
-                rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]), lattab2_d=_ptr(dev["lattab2"]), levtab2_d=_ptr(self._levtab2),
-                lattab_d=_ptr(dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]),
-                coef_d=_ptr(state["coef"]), col_d=_ptr(col), mapsum_d=_ptr(state["mapsum"]),
-                hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-            with torch.cuda.device(rows.device):
-                _lib.check(self.lib.lec_maps(C.byref(ma)), "lec_maps")
+
+        def issue(a, b, shared):
+            ma = _lib.MapsArgs(iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, lattab2_d=_ptr(dev["lattab2"]),
+                               lattab_d=_ptr(dev["lattab"]), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]), **shared)
+            _lib.check(self.lib.lec_maps(C.byref(ma)), "lec_maps")
+        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
 
     def map_finish(self, res: LECResult, state: dict) -> None:
         """``res.map_*`` from the accumulators of a finished series."""
@@ -704,10 +721,7 @@ class LECEngine:
         nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform)
         if boxes.bt.nyb_max != nyb:
             raise ValueError("composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
-        f64 = dict(dtype=torch.float64, device=device)
-        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
-                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
-                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+        return self._mapcol_begin(t_total, nyb, nxb, device, keep_steps)
 
     def composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
                         boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
@@ -730,8 +744,7 @@ class LECEngine:
         if packed and dTdt is None and tm is None:
             raise ValueError("composite_stage: a box-packed series needs its dTdt cube or tm / tp (its time neighbours are other boxes)")
         self._check_fields([tair, u, v, omega] + [c for c in (tm, tp) if c is not None], boxes if packed else None)
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        t_count = int(rows.shape[0])
+        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
         bx, bt, dev = self._stage2_input(rows, boxes)
         if len(bx) != t_count:
             raise ValueError("composite_stage: one box per step of the chunk")
@@ -743,9 +756,6 @@ class LECEngine:
             raise ValueError("composite_stage: [t_begin, t_begin + t_count) lies outside the cubes")
         if rows.device != tair.device:
             raise ValueError("composite_stage: rows and fields on one device")
-        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
-                or not levraw.is_contiguous()):
-            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
         if dTdt is not None:
             if dTdt.shape != tair.shape or dTdt.device != tair.device or dTdt.dtype not in (torch.float64, torch.float32):
                 raise ValueError("dTdt must be a cube of the fields' shape on their device")
@@ -758,27 +768,14 @@ class LECEngine:
             tcoef = self._cube_tcoef("composite_stage", time_s, tcoef, nt, tair.device)
         box_host = np.ascontiguousarray([(0, b[1] - b[0], 0, b[3] - b[2]) for b in bx] if packed else bx, dtype=np.int32)
         box_dev = dev["box_data" if packed else "box"]
-        f64 = dict(dtype=torch.float64, device=rows.device)
-        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
-        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
-        if state["coef"] is None or state["coef"].shape[0] < sub:
-            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
-        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
-            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
-        for a in range(0, t_count, sub):
-            b = min(t_count, a + sub)
-            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+
+        def issue(a, b, shared):
             ca = _lib.CompositeArgs(
-                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp),
-                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
-                t_begin=t_begin + a, t_count=b - a, nyb=nyb, nxb=nxb, reserved0=0,
+                dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp), nyb=nyb, nxb=nxb, tcoef_d=_ptr(tcoef),
                 box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
-                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
-                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), tcoef_d=_ptr(tcoef),
-                coef_d=_ptr(state["coef"]), col_d=_ptr(col), mapsum_d=_ptr(state["mapsum"]),
-                hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-            with torch.cuda.device(rows.device):
-                _lib.check(self.lib.lec_composite(C.byref(ca)), "lec_composite")
+                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), **shared)
+            _lib.check(self.lib.lec_composite(C.byref(ca)), "lec_composite")
+        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
 
     def composite_finish(self, res: LECResult, state: dict) -> None:
         """``res.composite_*`` from the accumulators of a finished series."""

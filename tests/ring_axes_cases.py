@@ -16,7 +16,7 @@ levels, where the 0.03 clamp then binds:
   domain     cube (lat x lon)  band rows  levels  what it is for
   narrow     9 x 70            1 .. 7     9       the maps' 64-column wave seam (a ring of 70); the open box is columns 3 .. 67: 65 columns,
                                                   whose last lies alone in the second wave
-  tall       68 x 16           1 .. 66    9       the second 64-row trip of lec_section_rows_kernel and lec_maps_coef_kernel, the tall path
+  tall       68 x 16           1 .. 66    9       the second 64-row trip of lec_section_rows_kernel and lec_mapcol_coef_kernel, the tall path
                                                   of the level and level-spectrum kernels
   levels17   7 x 16            1 .. 5     17      kFoldBatch and the level march: two full batches of 8 levels plus one
 
@@ -35,7 +35,7 @@ process, never written to.
   tair[3, 0, 5, 63]           the top level, in the last lane of the first wave (its d/dlon neighbours are columns 62 and 64); it reaches
                               Q at step 2 through dT/dt.
 All column values stay finite, and every term changes at its own set of steps (``expectations["changed"]``): the six per-term states of
-lec_maps_col_kernel's level march differ from one another.
+lec_mapcol_col_kernel's level march differ from one another.
 
 The records cases (``records_build``) hold lec_rowstats_ring to tests/rowstats_restatement.py on ``narrow``, in the measure of
 tests/rowstats_cases.py.  They live here and not in that module's ``axes`` family: its CPU test asks every case of the family to see

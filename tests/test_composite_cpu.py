@@ -51,7 +51,7 @@ def test_composite_call_is_an_extension():
     assert set(re.findall(r"^int (lec_\w+)\(", ext, flags=re.M)) == set(_lib.EXT_EXPORTS)
     assert _lib.LEC_ABI_VERSION == 11 and lib.lec_version() == 11 and "#define LEC_ABI_VERSION 11" in hdr
     mk = open(os.path.join(ROOT, "lorenzcycletoolkit_amd", "csrc", "Makefile")).read()
-    assert "lec_composite.hip" in mk and "lec_hip_ext.h" in mk
+    assert "lec_composite.hip" in mk and "lec_hip_ext.h" in mk and "lec_mapcol.h" in mk
     A = _lib.CompositeArgs
     assert ctypes.sizeof(A) == 7 * 8 + 10 * 4 + 15 * 8 == 216
     offs = {n: getattr(A, n).offset for n, _ in A._fields_}
