@@ -3,10 +3,8 @@
 // --wavenumbers-interactions (include/lec_hip.h).  A translation unit of its own: its code object is loaded by
 // calls that ask for the interactions only.
 //
-// The workgroup, the lane mapping, the twiddle table and the fixed-order sum over the column classes are lec_rowspec_q_kernel's
-// (lec_rowspecq.hip): 256 threads per kRows (time, level, latitude) rows, thread tid on wavenumber n = 1 + tid % N and the
-// columns i = seg, seg + nseg, ... (seg = tid / N, nseg = 256 / N), the twiddle {cos, sin}(2 pi m / nx) read from the host-built table
-// with m = (n i) mod nx carried as an integer.  What differs is the staging phase.  Per trip of kChunk columns every thread forms, for
+// The workgroup, the lane mapping, the twiddle table and the fixed-order sum over the column classes are lec_rowspec_core.h's, with
+// kRows = 1 row per workgroup.  Per trip of kChunk columns every thread forms, for
 // its columns, the eddies T', u', v', w' against the zonal means of the row's record and the three tendencies
 //   A_x = u' D_lambda x + v' (D_phi x - D_phi [x]) + w' (D_p x - D_p [x])  (+ the metric terms of u and v)
 // from the row itself, its four neighbour rows in latitude and pressure (the row itself with coefficient 0 where a neighbour does not
@@ -25,24 +23,18 @@
 // at nx = 4096 with it 106 KiB, one workgroup.  Two rows per workgroup (one twiddle load for both, the siblings' form) cost 164 to 190
 // VGPRs and twice the LDS and were slower at every trip length tried; a trip of 2048 columns leaves one workgroup per CU and is twice
 // as slow.
-#include <hip/hip_runtime.h>
-#include <stdint.h>
-
-#include "../../include/lec_hip.h"
-#include "lec_internal.h"
+#include "lec_rowspec_core.h"
 #include "lec_sweep.h"
 
 namespace {
 
-constexpr int kThreads = 256;
+using namespace lec::spec;
+
 constexpr int kWaves = kThreads / 64;
 constexpr int kRows = 1;               // rows per workgroup (2 measured slower: registers and LDS cost more occupancy than the shared twiddle saves)
 constexpr int kChunk = 768;            // columns staged per trip: 36 KiB of LDS per row
 constexpr int kComp = 12;              // {T', u', v', A_T, A_u, A_v} x {cos, sin}
 constexpr int kTot = 9;                // physical-space sums of a row: A_x x' (3), A_x (3), x' (3)
-// the twiddle table in LDS: lec_rowspec_kernel's thresholds
-constexpr int kTwidLdsMinWave = 16;
-constexpr int kTwidLdsMaxRow = 4096;
 static_assert(kRows * kChunk * 6 >= kThreads * kComp, "the partial sums of one row reuse the staged columns");
 
 struct SpecNlParams {
@@ -64,15 +56,13 @@ __device__ __forceinline__ void stage_row(const SpecNlParams& p, const long long
                                           double2* __restrict__ fb, double2* __restrict__ fc, double (&tot)[kTot], const int tid) {
 #pragma clang fp contract(off)
     const int nx = p.nx;
-    const int jb = (int)(row % p.nyb);
-    const int k = (int)((row / p.nyb) % p.nl);
-    const int t = p.t_begin + (int)(row / ((long long)p.nyb * p.nl));
-    const size_t plane = (size_t)p.ny * nx, cube = plane * p.nl;
-    const size_t base = (size_t)t * cube + (size_t)k * plane + (size_t)(p.js + jb) * nx;
-    const E* __restrict__ rT = (const E*)p.T + base;
-    const E* __restrict__ rU = (const E*)p.U + base;
-    const E* __restrict__ rV = (const E*)p.V + base;
-    const E* __restrict__ rW = (const E*)p.W + base;
+    const Row<E> r = decode_row<E>(p, row);
+    const int jb = r.jb, k = r.k;
+    const size_t plane = r.plane;
+    const E* __restrict__ rT = r.T;
+    const E* __restrict__ rU = r.U;
+    const E* __restrict__ rV = r.V;
+    const E* __restrict__ rW = r.W;
     // a neighbour that does not exist: the row itself, whose coefficient in the tables is 0
     const long long oj0 = jb > 0 ? -(long long)nx : 0, oj1 = jb < p.nyb - 1 ? (long long)nx : 0;
     const long long ok0 = k > 0 ? -(long long)plane : 0, ok1 = k < p.nl - 1 ? (long long)plane : 0;
@@ -132,33 +122,15 @@ __global__ __launch_bounds__(kThreads) void lec_rowspec_nl_kernel(const SpecNlPa
     __shared__ __attribute__((aligned(16))) double2 fld[3][R][kChunk];
     __shared__ double red[R][LEC_MAX_WAVENUMBERS * kComp];
     __shared__ double wtot[R][kTot][kWaves];
-    extern __shared__ __attribute__((aligned(16))) double2 twl[];      // TWLDS: [nx]
     const int tid = threadIdx.x;
     const int N = p.n_wave, nx = p.nx;
     long long rows[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-        const long long row = (long long)blockIdx.x * R + r;
-        rows[r] = row < nrows ? row : nrows - 1;   // the last workgroup of a count R does not divide: the last row once more, written once
-    }
-    if (TWLDS)
-        for (int c = tid; c < nx; c += kThreads) twl[c] = p.twid[c];       // (the first trip's barrier publishes it)
+    wg_rows(nrows, rows);
+    stage_twiddles<TWLDS>(p.twid, nx, tid);
 
-    const int nseg = kThreads / N;
-    const bool active = tid < nseg * N;
-    const int n = 1 + tid % N, seg = tid / N;
-    int i = seg;                                   // this thread's next column
-    int m = (int)(((long long)n * seg) % nx);      // (n i) mod nx, an integer throughout
-    const int dm = (n * nseg) % nx;
-    double acc[R][kComp];
-    double tot[R][kTot];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-#pragma unroll
-        for (int q = 0; q < kComp; ++q) acc[r][q] = 0;
-#pragma unroll
-        for (int q = 0; q < kTot; ++q) tot[r][q] = 0;
-    }
+    Lane lane(tid, N, nx);
+    double acc[R][kComp] = {};
+    double tot[R][kTot] = {};
 
     for (int c0 = 0; c0 < nx; c0 += kChunk) {
         const int cn = min(kChunk, nx - c0);
@@ -166,25 +138,11 @@ __global__ __launch_bounds__(kThreads) void lec_rowspec_nl_kernel(const SpecNlPa
 #pragma unroll
         for (int r = 0; r < R; ++r) stage_row<E>(p, rows[r], c0, cn, fld[0][r], fld[1][r], fld[2][r], tot[r], tid);
         __syncthreads();
-        if (active) {
-            const int cend = c0 + cn;
-#pragma unroll 2
-            for (; i < cend; i += nseg) {
-                const double2 tw = TWLDS ? twl[m] : p.twid[m];
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    const double2 a = fld[0][r][i - c0], b = fld[1][r][i - c0], c = fld[2][r][i - c0];
-                    acc[r][0] = fma(a.x, tw.x, acc[r][0]); acc[r][1] = fma(a.x, tw.y, acc[r][1]);
-                    acc[r][2] = fma(a.y, tw.x, acc[r][2]); acc[r][3] = fma(a.y, tw.y, acc[r][3]);
-                    acc[r][4] = fma(b.x, tw.x, acc[r][4]); acc[r][5] = fma(b.x, tw.y, acc[r][5]);
-                    acc[r][6] = fma(b.y, tw.x, acc[r][6]); acc[r][7] = fma(b.y, tw.y, acc[r][7]);
-                    acc[r][8] = fma(c.x, tw.x, acc[r][8]); acc[r][9] = fma(c.x, tw.y, acc[r][9]);
-                    acc[r][10] = fma(c.y, tw.x, acc[r][10]); acc[r][11] = fma(c.y, tw.y, acc[r][11]);
-                }
-                m += dm;
-                if (m >= nx) m -= nx;
-            }
-        }
+        if (lane.active)
+            project<6, TWLDS>(lane, c0, c0 + cn, nx, p.twid, acc, [&](const int r, const int c, double (&x)[6]) {
+                const double2 a = fld[0][r][c], b = fld[1][r][c], d = fld[2][r][c];
+                x[0] = a.x; x[1] = a.y; x[2] = b.x; x[3] = b.y; x[4] = d.x; x[5] = d.y;
+            });
     }
     // the physical-space sums: over the wave, then over the waves in their order
 #pragma unroll
@@ -194,36 +152,25 @@ __global__ __launch_bounds__(kThreads) void lec_rowspec_nl_kernel(const SpecNlPa
             const double s = wave_sum(tot[r][q]);
             if ((tid & 63) == 0) wtot[r][q][tid >> 6] = s;
         }
-    double* const part = (double*)&fld[0][0][0];    // partial sums [seg][wavenumber][12] of ONE row: tid = seg N + (n - 1)
+    double* const part = (double*)&fld[0][0][0];    // the partial sums of ONE row
 #pragma unroll
     for (int r = 0; r < R; ++r) {
         __syncthreads();                            // the last trip, or the row before, has been read
-        if (active) {
-#pragma unroll
-            for (int q = 0; q < kComp; ++q) part[kComp * tid + q] = acc[r][q];
-        }
+        spill(lane, tid, part, acc[r]);
         __syncthreads();
-        for (int o = tid; o < kComp * N; o += kThreads) {  // one sum per (wavenumber, component), the column classes in their order
-            double s = 0;
-            for (int g = 0; g < nseg; ++g) s += part[kComp * g * N + o];
-            red[r][o] = s;
-        }
+        class_sum<kComp>(lane, tid, N, part, red[r]);
     }
     __syncthreads();
-    // slot s = 0, 1, 2: -2 C_n(A_x, x) = -2 w_n Re(A_x^_n conj(x^_n)), x = T, u, v; slots 3 .. 7: 0
+    // slot s = 0, 1, 2: -2 C_n(A_x, x) = -2 w_n Re(A_x^_n conj(x^_n)), x = T, u, v: fields {x, A_x} = {s, 3 + s}; slots 3 .. 7: 0
     const double inv = 1.0 / ((double)nx * (double)nx);
     const double inx = 1.0 / (double)nx;
 #pragma unroll
     for (int r = 0; r < R; ++r) {
-        if (r && rows[r] == rows[r - 1]) break;
+        if (row_repeated(rows, r)) break;
         for (int o = tid; o < 8 * N; o += kThreads) {
             const int nn = o >> 3, s = o & 7;
             double val = 0;
-            if (s < 3) {
-                const double* q = &red[r][kComp * nn];
-                const double wgt = (2 * (nn + 1) == nx) ? 1.0 : 2.0;      // the Nyquist wavenumber of an even ring counts once
-                val = -2.0 * (wgt * (q[6 + 2 * s] * q[2 * s] + q[7 + 2 * s] * q[2 * s + 1]) * inv);
-            }
+            if (s < 3) val = -2.0 * (wave_weight(nn, nx) * cov(&red[r][kComp * nn], 3 + s, s) * inv);
             p.nlspec[((size_t)rows[r] * N + nn) * 8 + s] = val;
         }
         if (tid < 8) {
@@ -239,70 +186,33 @@ __global__ __launch_bounds__(kThreads) void lec_rowspec_nl_kernel(const SpecNlPa
     }
 }
 
-template <typename E>
-int launch(const SpecNlParams& p, long long nrows, hipStream_t st) {
-    const unsigned nb = (unsigned)((nrows + kRows - 1) / kRows);
-    if (p.n_wave >= kTwidLdsMinWave && p.nx <= kTwidLdsMaxRow) {
-        const size_t lds = (size_t)p.nx * sizeof(double2);
-        // (more than 64 KiB of LDS per workgroup, static and dynamic together, has to be asked for)
-        if (hipFuncSetAttribute((const void*)lec_rowspec_nl_kernel<E, kRows, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess)
-            return LEC_ERR_LAUNCH;
-        hipLaunchKernelGGL((lec_rowspec_nl_kernel<E, kRows, true>), dim3(nb), dim3(kThreads), lds, st, p, nrows);
-    } else {
-        hipLaunchKernelGGL((lec_rowspec_nl_kernel<E, kRows, false>), dim3(nb), dim3(kThreads), 0, st, p, nrows);
-    }
-    return LEC_OK;
-}
-
 }  // namespace
 
 extern "C" int lec_rowspec_nl_ring(const lec_rowspec_nl_args* a) {
-    if (!a) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null args");
-    if (!a->tair_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null tair_d");
-    if (!a->u_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null u_d");
-    if (!a->v_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null v_d");
-    if (!a->omega_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null omega_d");
-    if (!a->rows_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null rows_d");
-    if (!a->twid_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null twid_d");
-    if (!a->lattab_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null lattab_d");
-    if (!a->ptab_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null ptab_d");
-    if (!a->nlspec_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null nlspec_d");
-    if (!a->nltot_d) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: null nltot_d");
-    if (a->dtype != LEC_F64 && a->dtype != LEC_F32) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: dtype must be LEC_F64 or LEC_F32");
-    if (a->nt < 1) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: nt must be >= 1");
-    if (a->nl < 1 || a->ny < 2) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: cube needs nl >= 1, ny >= 2");
-    if (a->nx < 3) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: nx must be >= 3 (a ring has at least 3 columns)");
-    if (a->t_begin < 0 || a->t_begin >= a->nt) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: t_begin outside the cube");
-    if (a->t_count < 1 || a->t_count > a->nt - a->t_begin) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: t_count: [t_begin, t_begin + t_count) outside the cube");
-    if (a->js < 0 || a->js >= a->ny) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: js outside the cube's latitudes");
-    if (a->jn < a->js || a->jn >= a->ny) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: jn must be js .. ny - 1");
-    if (a->jn == a->js) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: jn must be > js (a band needs two rows for d/dlat)");
-    if (a->n_wave < 1) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: n_wave must be >= 1");
-    if (a->n_wave > a->nx / 2) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: n_wave must be <= nx / 2 (a ring of nx columns holds the wavenumbers 1 .. nx / 2)");
-    if (a->n_wave > LEC_MAX_WAVENUMBERS) return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_rowspec_nl_ring: n_wave above LEC_MAX_WAVENUMBERS");
-    if ((uintptr_t)a->twid_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: twid_d must be 16-byte aligned");
-    if ((uintptr_t)a->rows_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: rows_d must be 16-byte aligned");
-    if ((uintptr_t)a->nlspec_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: nlspec_d must be 16-byte aligned");
-    if ((uintptr_t)a->nltot_d % 16) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: nltot_d must be 16-byte aligned");
-    if ((uintptr_t)a->lattab_d % 8) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: lattab_d must be 8-byte aligned");
-    if ((uintptr_t)a->ptab_d % 8) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: ptab_d must be 8-byte aligned");
-    const size_t esz = a->dtype == LEC_F32 ? 4 : 8;
-    const void* cubes[4] = {a->tair_d, a->u_d, a->v_d, a->omega_d};
-    for (const void* c : cubes)
-        if ((uintptr_t)c % esz) return lec_set_error(LEC_ERR_ARG, "lec_rowspec_nl_ring: cube pointer (tair_d, u_d, v_d, omega_d) not aligned to its element size");
-    const int nyb = a->jn - a->js + 1;
-    const long long nrows = (long long)a->t_count * a->nl * nyb;
-    if (nrows > 0x7fffffffLL) return lec_set_error(LEC_ERR_UNSUPPORTED, "lec_rowspec_nl_ring: more than 2^31-1 rows in one call");
+    const Refusals R{"lec_rowspec_nl_ring"};
+    int rc, nyb;
+    long long nrows;
+    if (!a) return R.refuse(LEC_ERR_ARG, "null args");
+    if ((rc = R.pointers(a, {{a->rows_d, "rows_d"}}, {{a->lattab_d, "lattab_d"}, {a->ptab_d, "ptab_d"}, {a->nlspec_d, "nlspec_d"},
+                                                     {a->nltot_d, "nltot_d"}})) != LEC_OK) return rc;
+    if ((rc = R.dtype(a)) != LEC_OK) return rc;
+    if (a->nt < 1) return R.refuse(LEC_ERR_ARG, "nt must be >= 1");
+    if (a->nl < 1 || a->ny < 2) return R.refuse(LEC_ERR_ARG, "cube needs nl >= 1, ny >= 2");
+    if ((rc = R.ring_steps_band(a)) != LEC_OK) return rc;
+    if (a->jn == a->js) return R.refuse(LEC_ERR_ARG, "jn must be > js (a band needs two rows for d/dlat)");
+    if ((rc = R.wavenumbers(a)) != LEC_OK) return rc;
+    if ((rc = R.aligned(a->rows_d, 16, "rows_d")) != LEC_OK) return rc;
+    if ((rc = R.aligned(a->nlspec_d, 16, "nlspec_d")) != LEC_OK) return rc;
+    if ((rc = R.aligned(a->nltot_d, 16, "nltot_d")) != LEC_OK) return rc;
+    if ((rc = R.aligned(a->lattab_d, 8, "lattab_d")) != LEC_OK) return rc;
+    if ((rc = R.aligned(a->ptab_d, 8, "ptab_d")) != LEC_OK) return rc;
+    if ((rc = R.cubes_rows(a, &nyb, &nrows)) != LEC_OK) return rc;
 
     SpecNlParams p;
-    p.T = a->tair_d; p.U = a->u_d; p.V = a->v_d; p.W = a->omega_d;
-    p.rows = a->rows_d; p.twid = (const double2*)a->twid_d; p.lattab = a->lattab_d; p.ptab = a->ptab_d;
+    common_params(p, a, nyb);
+    p.rows = a->rows_d; p.lattab = a->lattab_d; p.ptab = a->ptab_d;
     p.nlspec = a->nlspec_d; p.nltot = a->nltot_d; p.inv_hdeg = a->inv_hdeg;
-    p.nl = a->nl; p.ny = a->ny; p.nx = a->nx; p.t_begin = a->t_begin; p.js = a->js; p.nyb = nyb; p.n_wave = a->n_wave;
     hipStream_t st = (hipStream_t)a->stream;
-    const int rc = a->dtype == LEC_F64 ? launch<double>(p, nrows, st) : launch<float>(p, nrows, st);
-    if (rc != LEC_OK) return lec_set_error(rc, "lec_rowspec_nl_ring: the kernel's LDS could not be reserved");
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
-    return LEC_OK;
+    return R.launched(a->dtype == LEC_F64 ? launch(lec_rowspec_nl_kernel<double, kRows, true>, lec_rowspec_nl_kernel<double, kRows, false>, kRows, p, nrows, st)
+                                          : launch(lec_rowspec_nl_kernel<float, kRows, true>, lec_rowspec_nl_kernel<float, kRows, false>, kRows, p, nrows, st));
 }

@@ -808,32 +808,55 @@ class LECEngine:
         (slots 6 .. 13 of a row record, in that order) of every row of the ring's latitude band, for time steps
         [t_begin, t_begin + t_count) of the cubes.  ``boxes`` from ``prepare_boxes(..., ring=True)``; ``spec_out``: a caller-owned
         buffer; ``timing``: a list that receives one (start, end) pair of HIP events around the launch."""
-        self._check_fields([tair, u, v, omega], None)
+        return self._rowspec_call("lec_rowspec_ring", _lib.RowspecArgs, (tair, u, v, omega), boxes, wavenumbers, t_begin, t_count, (),
+                                  [("spec_d", "spec_out", spec_out, ("N", 8))], None, timing)[0]
+
+    def _rowspec_call(self, call: str, args_type, cubes, boxes: PreparedBoxes, wavenumbers, t_begin: int, t_count: Optional[int], rows: tuple,
+                      outs: list, own, timing: Optional[list]) -> list:
+        """What ``rowspec``, ``rowspec_q``, ``rowspec_nl`` and ``rowspec_b`` share, in the order their checks have always come: the
+        field and wavenumber checks, the ``t_count`` default, the band, ``own(nt, js, jn)`` -- the call's own checks and tables, returned
+        as its own fields of ``args_type`` --, the ``rows`` check (``rows``: ``()`` for a call that takes none, or ``(rows,)``), the
+        outputs ``outs`` -- (field, argument name, the caller's buffer or None, the shape after [t_count, nl, nyb] with "N" for the
+        wavenumbers) each --, the twiddle table and the call itself between a pair of events for ``timing``.  Returns the outputs."""
+        tair = cubes[0]
+        self._check_fields(list(cubes), None)
         nt, nl, ny, nx = (int(x) for x in tair.shape)
         self._check_wavenumbers(wavenumbers, boxes, nx)
         n = int(wavenumbers)
         if t_count is None:
             t_count = nt - t_begin
         _, _, js, jn = boxes.boxes[0]
-        shape = (t_count, nl, jn - js + 1, n, 8)
-        spec = torch.empty(shape, dtype=torch.float64, device=tair.device) if spec_out is None else spec_out
-        if spec.shape != shape or spec.dtype != torch.float64 or spec.device != tair.device or not spec.is_contiguous():
-            raise ValueError("spec_out must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the fields' device")
+        nyb = jn - js + 1
+        fields = own(nt, js, jn) if own is not None else {}
+        for r in rows:
+            if (r.shape != (t_count, nl, nyb, _lib.LEC_NSTAT) or r.dtype != torch.float64 or r.device != tair.device
+                    or not r.is_contiguous()):
+                raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb, 32] tensor on the fields' device: the ring pass's records of the same steps")
+            fields["rows_d"] = _ptr(r)
+        tensors = []
+        for field, name, given, tail in outs:
+            shape = (t_count, nl, nyb) + tuple(n if d == "N" else d for d in tail)
+            out = torch.empty(shape, dtype=torch.float64, device=tair.device) if given is None else given
+            if out.shape != shape or out.dtype != torch.float64 or out.device != tair.device or not out.is_contiguous():
+                raise ValueError(f"{name} must be a contiguous fp64 [t_count, nl, nyb, {', '.join(str(d) for d in tail)}] tensor on the fields' device")
+            fields[field] = _ptr(out)
+            tensors.append(out)
         if self._twid is None:
             self._twid = self._up(tables.twiddle_table(nx))
-        sa = _lib.RowspecArgs(
-            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
-            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, twid_d=_ptr(self._twid), spec_d=_ptr(spec),
-            stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
+        args = args_type(
+            tair_d=_ptr(cubes[0]), u_d=_ptr(cubes[1]), v_d=_ptr(cubes[2]), omega_d=_ptr(cubes[3]),
+            dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
+            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, twid_d=_ptr(self._twid),
+            stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream), **fields)
         with torch.cuda.device(tair.device):
             if timing is not None:
                 ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 ev0.record()
-            _lib.check(self.lib.lec_rowspec_ring(C.byref(sa)), "lec_rowspec_ring")
+            _lib.check(getattr(self.lib, call)(C.byref(args)), call)
             if timing is not None:
                 ev1.record()
                 timing.append((ev0, ev1))
-        return spec
+        return tensors
 
     def _cube_tcoef(self, who: str, time_s, tcoef: Optional[torch.Tensor], nt: int, device) -> torch.Tensor:
         """The d/dt coefficients [nt, 3] of a cube's time axis on the device: ``tcoef`` checked, or built from ``time_s`` (seconds, one
@@ -861,34 +884,11 @@ class LECEngine:
         pass's, with dT/dt over the cube's time axis ``time_s`` (seconds, one entry per step of the cube; or ``tcoef``, its d/dt
         coefficients already on the device); the tables are the prepared ring box's and the engine's own.  ``out``: a caller-owned
         buffer; ``timing``: a list that receives one (start, end) pair of HIP events around the launch."""
-        self._check_fields([tair, u, v, omega], None)
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        self._check_wavenumbers(wavenumbers, boxes, nx)
-        n = int(wavenumbers)
-        if t_count is None:
-            t_count = nt - t_begin
-        tcoef = self._cube_tcoef("rowspec_q", time_s, tcoef, nt, tair.device)
-        _, _, js, jn = boxes.boxes[0]
-        shape = (t_count, nl, jn - js + 1, n)
-        qspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
-        if qspec.shape != shape or qspec.dtype != torch.float64 or qspec.device != tair.device or not qspec.is_contiguous():
-            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the fields' device")
-        if self._twid is None:
-            self._twid = self._up(tables.twiddle_table(nx))
-        qa = _lib.RowspecQArgs(
-            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
-            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, twid_d=_ptr(self._twid),
-            lattab_d=_ptr(boxes.dev["lattab"]), levtab_d=_ptr(self._levtab), tcoef_d=_ptr(tcoef), inv_hdeg=float(boxes.bt.boxtab[0, 2]),
-            qspec_d=_ptr(qspec), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
-        with torch.cuda.device(tair.device):
-            if timing is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            _lib.check(self.lib.lec_rowspec_q_ring(C.byref(qa)), "lec_rowspec_q_ring")
-            if timing is not None:
-                ev1.record()
-                timing.append((ev0, ev1))
-        return qspec
+        def own(nt, js, jn):
+            return dict(lattab_d=_ptr(boxes.dev["lattab"]), levtab_d=_ptr(self._levtab), inv_hdeg=float(boxes.bt.boxtab[0, 2]),
+                        tcoef_d=_ptr(self._cube_tcoef("rowspec_q", time_s, tcoef, nt, tair.device)))
+        return self._rowspec_call("lec_rowspec_q_ring", _lib.RowspecQArgs, (tair, u, v, omega), boxes, wavenumbers, t_begin, t_count, (),
+                                  [("qspec_d", "out", out, ("N",))], own, timing)[0]
 
     def rowspec_nl(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes: PreparedBoxes,
                    n: int, *, t_begin: int = 0, t_count: Optional[int] = None, out: Optional[torch.Tensor] = None,
@@ -898,43 +898,14 @@ class LECEngine:
         for the wavenumbers 1 .. N and for the whole eddy covariance, slots 3 .. 7 are 0: ``spectrum_level_stage`` takes either as
         ``spec``.  ``rows`` [t_count, nl, nyb, 32]: the ring pass's records of the same steps [t_begin, t_begin + t_count) (their zonal
         means are the eddies' reference).  ``out`` / ``out_total``: caller-owned buffers; ``timing``: as ``rowspec``."""
-        self._check_fields([tair, u, v, omega], None)
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        self._check_wavenumbers(n, boxes, nx)
-        n = int(n)
-        if t_count is None:
-            t_count = nt - t_begin
-        _, _, js, jn = boxes.boxes[0]
-        nyb = jn - js + 1
-        if (rows.shape != (t_count, nl, nyb, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or rows.device != tair.device
-                or not rows.is_contiguous()):
-            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb, 32] tensor on the fields' device: the ring pass's records of the same steps")
-        shape = (t_count, nl, nyb, n, 8)
-        nlspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
-        if nlspec.shape != shape or nlspec.dtype != torch.float64 or nlspec.device != tair.device or not nlspec.is_contiguous():
-            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N, 8] tensor on the fields' device")
-        nltot = torch.empty((t_count, nl, nyb, 8), dtype=torch.float64, device=tair.device) if out_total is None else out_total
-        if nltot.shape != (t_count, nl, nyb, 8) or nltot.dtype != torch.float64 or nltot.device != tair.device or not nltot.is_contiguous():
-            raise ValueError("out_total must be a contiguous fp64 [t_count, nl, nyb, 8] tensor on the fields' device")
-        if self._twid is None:
-            self._twid = self._up(tables.twiddle_table(nx))
-        if self._ptab is None:
-            self._ptab = self._up(tables.pressure_coefs(self.level))
-        if "nl_lattab" not in boxes.dev:
-            boxes.dev["nl_lattab"] = self._up(tables.nl_lat_table(boxes.bt.lattab[0], self.lat[js:jn + 1]))
-        na = _lib.RowspecNlArgs(
-            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
-            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, rows_d=_ptr(rows), twid_d=_ptr(self._twid),
-            lattab_d=_ptr(boxes.dev["nl_lattab"]), ptab_d=_ptr(self._ptab), inv_hdeg=float(boxes.bt.boxtab[0, 2]),
-            nlspec_d=_ptr(nlspec), nltot_d=_ptr(nltot), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
-        with torch.cuda.device(tair.device):
-            if timing is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            _lib.check(self.lib.lec_rowspec_nl_ring(C.byref(na)), "lec_rowspec_nl_ring")
-            if timing is not None:
-                ev1.record()
-                timing.append((ev0, ev1))
+        def own(nt, js, jn):
+            if self._ptab is None:
+                self._ptab = self._up(tables.pressure_coefs(self.level))
+            if "nl_lattab" not in boxes.dev:
+                boxes.dev["nl_lattab"] = self._up(tables.nl_lat_table(boxes.bt.lattab[0], self.lat[js:jn + 1]))
+            return dict(lattab_d=_ptr(boxes.dev["nl_lattab"]), ptab_d=_ptr(self._ptab), inv_hdeg=float(boxes.bt.boxtab[0, 2]))
+        nlspec, nltot = self._rowspec_call("lec_rowspec_nl_ring", _lib.RowspecNlArgs, (tair, u, v, omega), boxes, n, t_begin, t_count, (rows,),
+                                           [("nlspec_d", "out", out, ("N", 8)), ("nltot_d", "out_total", out_total, (8,))], own, timing)
         return nlspec, nltot
 
     def rowspec_b(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes: PreparedBoxes,
@@ -945,36 +916,8 @@ class LECEngine:
         EV at the band's first and last row only, 0 elsewhere.  ``rows`` [t_count, nl, nyb, 32]: the ring pass's records of the same
         steps [t_begin, t_begin + t_count).  ``out``: a caller-owned buffer; ``timing``: as ``rowspec``.  One call per time chunk: the
         callers keep ``out`` within ``SPECTRUM_CHUNK_BYTES`` (``spectrum_chunk_steps``)."""
-        self._check_fields([tair, u, v, omega], None)
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        self._check_wavenumbers(n, boxes, nx)
-        n = int(n)
-        if t_count is None:
-            t_count = nt - t_begin
-        _, _, js, jn = boxes.boxes[0]
-        nyb = jn - js + 1
-        if (rows.shape != (t_count, nl, nyb, _lib.LEC_NSTAT) or rows.dtype != torch.float64 or rows.device != tair.device
-                or not rows.is_contiguous()):
-            raise ValueError("rows must be a contiguous fp64 [t_count, nl, nyb, 32] tensor on the fields' device: the ring pass's records of the same steps")
-        shape = (t_count, nl, nyb, n, 4)
-        bspec = torch.empty(shape, dtype=torch.float64, device=tair.device) if out is None else out
-        if bspec.shape != shape or bspec.dtype != torch.float64 or bspec.device != tair.device or not bspec.is_contiguous():
-            raise ValueError("out must be a contiguous fp64 [t_count, nl, nyb, N, 4] tensor on the fields' device")
-        if self._twid is None:
-            self._twid = self._up(tables.twiddle_table(nx))
-        ba = _lib.RowspecBArgs(
-            tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega), dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32,
-            nt=nt, nl=nl, ny=ny, nx=nx, t_begin=t_begin, t_count=t_count, js=js, jn=jn, n_wave=n, rows_d=_ptr(rows), twid_d=_ptr(self._twid),
-            bspec_d=_ptr(bspec), stream=C.c_void_p(torch.cuda.current_stream(tair.device).cuda_stream))
-        with torch.cuda.device(tair.device):
-            if timing is not None:
-                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                ev0.record()
-            _lib.check(self.lib.lec_rowspec_b_ring(C.byref(ba)), "lec_rowspec_b_ring")
-            if timing is not None:
-                ev1.record()
-                timing.append((ev0, ev1))
-        return bspec
+        return self._rowspec_call("lec_rowspec_b_ring", _lib.RowspecBArgs, (tair, u, v, omega), boxes, n, t_begin, t_count, (rows,),
+                                  [("bspec_d", "out", out, ("N", 4))], None, timing)[0]
 
     def spectrum_budget_terms(self, res: LECResult, time_s) -> None:
         """``res.spectrum_tendency*`` and ``res.spectrum_residual*`` from ``res.spectrum*`` and ``res.spectrum_b*`` of a whole series
