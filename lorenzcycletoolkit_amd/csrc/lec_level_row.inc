@@ -1,5 +1,6 @@
 // lec_level_row.inc -- the contributions of ONE latitude row to the 33 per-level sums of stage 2, included textually by the two
-// level kernels of lec_reduce.hip (identical source, identical arithmetic).  Expects in scope:
+// level kernels of lec_level_core.h, whichever record source they are instantiated on, and (LEC_ROW_COMMON + LEC_ROW_PART_A) by
+// lec_section_rows_kernel (identical source, identical arithmetic).  Expects in scope:
 //   r[LEC_NSTAT]               the row's record;  rjm[], rjp[]: the records of the rows j-1 / j+1 (only [T] [u] [v] are read)
 //   km2, kp2                   {[T], [u]} of the same row one level up / down
 //   cw wphi c tn gra grb grc   the row's latitude coefficients, cm / cp: cos(phi) of the rows j-1 / j+1

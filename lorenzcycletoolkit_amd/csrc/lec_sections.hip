@@ -10,27 +10,18 @@
 //   lec_section_fold_kernel  one thread per (function, row): per time step one scan of the levels with a running "last finite level"
 //                            (trapezoid and NaN rule in one pass), then the time sums, step by step in time order.  No atomics: every
 //                            output element has one writer, so the numbers do not depend on the launch or on how a series is cut.
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <stdint.h>
 #include <stdio.h>
 
-#include "../../include/lec_hip.h"
-#include "lec_internal.h"
-#include "lec_rowcommon.h"
-
-// as lec_reduce.hip: the row's source lines give the products stage 2 forms, none of them fused
-#pragma clang fp contract(off)
+// the levraw record (V_*), wave_sum and the physical constants of the level stage; contraction is off from here on: the row's source
+// lines give the products stage 2 forms, none of them fused
+#include "lec_level_core.h"
 
 namespace {
-using lec::dbl2_t;
+using namespace lec;
 
-constexpr double kG = LEC_G, kRe = LEC_RE, kRd = LEC_RD, kCp = LEC_CP_D;
 constexpr int kNSec = LEC_NSECTION;
 constexpr int kSpecSlots = 8;      // LEC_S_TT .. LEC_S_WV
-
-// the sums of lec_level_row.inc's part A (the levraw record of lec_reduce.hip)
-enum { V_AZ = 0, V_AE, V_KZ, V_KE, V_CZ2, V_CE2, V_CA1, V_CA2, V_CK1, V_CK2, V_CK3, V_CK4, V_CK5, V_GZ, V_GE, V_PART_A };
+constexpr int V_PART_A = V_GE + 1;      // the sums of lec_level_row.inc's part A: V_AZ .. V_GE
 // the sections, in the order of F_AZ .. F_GE of lec_reduce.hip
 enum { X_AZ = 0, X_AE, X_KZ, X_KE, X_CZ, X_CA, X_CK, X_CE, X_GZ, X_GE };
 static_assert(X_GE + 1 == kNSec, "ten sections");
@@ -47,12 +38,6 @@ struct SecParams {
     double* sec;             // [t_count][nl][10][nyb]
     double* specsec;         // [t_count][nl][n_wave][n_specfn][nyb]
 };
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 
 // grid ((1 + n_wave) * t_count * nl) -- level fastest, then time step, then wavenumber (0: the totals) --, block 64
 __global__ void __launch_bounds__(64) lec_section_rows_kernel(const SecParams p) {
