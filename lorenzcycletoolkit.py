@@ -49,6 +49,12 @@ latitudes x longitudes) and <term>_lon.csv (the area-weighted sum over latitude,
 (the time mean, box rows x box columns, labelled by the offset in degrees from the box's midpoint) and <term>_dlon.csv (the area-weighted
 sum over the box's rows, time steps x box columns).  One system whose boxes all have one shape.
 
+-t / -c --composite-sections: also the system-relative latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge over the boxes
+that follow the system (``lec_composite_sections``: ``lec_sections`` on box-relative rows, every step with its own box), written to
+results_composite_sections/<term>_dlat_lv.csv (the time mean, levels x box rows, labelled by the offset in degrees from the box's
+midpoint) and <term>_dlat.csv (the vertical integral, time steps x box rows).  One system whose boxes all have one row count; only the
+row records are read, so it runs on the streamed path (--ingest device / --device-ingest) too, and may be combined with --composites.
+
 --series FILE...: the time series that ``infile`` begins continues in these files (archives deliver a file per month or per day): same
 grid, levels and variables, time stamps that do not overlap; every file is decoded with its own scale_factor / add_offset (on the GPU:
 ``lec_ingest_series``, a table of packing constants per time step).  Every output is named after ``infile``.
@@ -156,6 +162,15 @@ def create_arg_parser():
                         "<term>_dlon.csv, the area-weighted sum over the box's rows at every time step (rows: time steps; the box's zonal "
                         "average of a row is the results CSV).  Every other output file is unchanged.  One GPU, data prepared on the host "
                         "(--ingest auto resolves to host), evenly spaced longitudes and latitudes, boxes of one shape; -f has --maps")
+    parser.add_argument("--composite-sections", dest="composite_sections", action="store_true", default=argparse.SUPPRESS,
+                        help="with -t --trackfile or -c (one system): also the system-relative latitude-pressure sections of the ten terms "
+                        "Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz and Ge (lec_composite_sections: the row's own contribution to the per-level sums "
+                        "of every time step's box, laid on the box-relative rows), written to results_composite_sections/: "
+                        "<term>_dlat_lv.csv, the time mean over the system's life (rows: levels, columns: the box's rows labelled by the "
+                        "offset in degrees from the box's midpoint, in the units of the per-level tables) and <term>_dlat.csv, the vertical "
+                        "integral at every time step (rows: time steps, in the units of the results CSV).  Every other output file is "
+                        "unchanged.  One GPU, host-prepared or streamed data, evenly spaced latitudes, boxes of one row count (their widths "
+                        "may differ); may be combined with --composites; -f has --sections")
     parser.add_argument("--device-ingest", action="store_true", help="stream the file's bytes to the GPU in chunks and decode / sort / crop them "
                         "there, instead of preparing the whole data set on the host (same results, bit for bit); the same as --ingest device")
     parser.add_argument("--ingest", choices=["auto", "host", "device"], default="auto", help="where the data are prepared: 'host' decodes, sorts "
@@ -405,6 +420,19 @@ def refuse_periodic_options(args):
         if args.ingest == "device" or args.device_ingest:
             raise SystemExit("--composites prepares the data on the host: --ingest device / --device-ingest is not supported for the "
                              "composites (--ingest auto resolves to host)")
+    if getattr(args, "composite_sections", False):
+        if args.fixed:
+            raise SystemExit("--composite-sections goes with -t / -c: ONE fixed box has --sections, the sections on the box's own rows; a "
+                             "system-relative section is laid on the box-relative rows of the boxes that follow a system")
+        if args.trackfiles is not None:
+            raise SystemExit("--composite-sections follows ONE system: --trackfiles analyses a batch of tracks and has no system-relative "
+                             "sections (run -t --trackfile FILE --composite-sections for the track that matters)")
+        if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
+            raise SystemExit("--composite-sections follows ONE system: -c --choose-systems / --choose-starts follows a batch and has no "
+                             "system-relative sections (run -t --trackfile on a track it wrote, with --composite-sections)")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--composite-sections runs on one GPU: --gpus > 1 is not supported for the system-relative sections (their "
+                             "time sums would have to merge in time order; run the totals sharded, the sections apart)")
     n = getattr(args, "wavenumbers", None)
     chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:

@@ -32,7 +32,7 @@ ORDER_AUTO, ORDER_MEMORY, ORDER_XCD_LAT, ORDER_XCD_TILED = 0, 1, 2, 7
 
 def source_digest() -> str:
     """sha256 (first 16 hex digits) over the kernel sources the library is built from (csrc/*.hip|.h|.inc + include/lec_hip.h,
-    include/lec_hip_ext.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
+    include/lec_hip_ext.h, include/lec_hip_ext2.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
     taken on the kernels it runs (the GPU box has the sources but no git history)."""
     import glob
     import hashlib
@@ -41,6 +41,7 @@ def source_digest() -> str:
                    + glob.glob(os.path.join(_HERE, "csrc", "*.inc")))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext2.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -56,6 +57,8 @@ EXPORTS = ["lec_version", "lec_last_error", "lec_max_row", "lec_rowstats", "lec_
            "lec_rowspec_nl_ring", "lec_rowspec_b_ring", "lec_level_spec_b_ring", "lec_sections", "lec_maps"]
 # calls added after ABI 11 was closed: declared in include/lec_hip_ext.h, exported from the same library, never part of EXPORTS
 EXT_EXPORTS = ["lec_composite"]
+# calls added after include/lec_hip_ext.h was closed: declared in include/lec_hip_ext2.h
+EXT2_EXPORTS = ["lec_composite_sections"]
 
 
 class Tuning(C.Structure):
@@ -176,6 +179,16 @@ class CompositeArgs(C.Structure):
         ("box_h", C.c_void_p), ("box_d", C.c_void_p), ("boxtab_d", C.c_void_p), ("lattab_d", C.c_void_p), ("lattab2_d", C.c_void_p),
         ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p), ("levtab_d", C.c_void_p), ("levtab2_d", C.c_void_p), ("tcoef_d", C.c_void_p),
         ("coef_d", C.c_void_p), ("col_d", C.c_void_p), ("mapsum_d", C.c_void_p), ("hov_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class CompositeSectionsArgs(C.Structure):
+    """struct lec_composite_sections_args (include/lec_hip_ext2.h)."""
+    _fields_ = [
+        ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p),
+        ("t_count", C.c_int32), ("nl", C.c_int32), ("nyb", C.c_int32), ("reserved0", C.c_int32),
+        ("box_h", C.c_void_p), ("box_d", C.c_void_p), ("lattab2_d", C.c_void_p), ("levtab2_d", C.c_void_p),
+        ("sec_d", C.c_void_p), ("col_d", C.c_void_p), ("secsum_d", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -358,6 +371,8 @@ def load():
     lib.lec_maps.argtypes = [C.POINTER(MapsArgs)]
     lib.lec_composite.restype = C.c_int
     lib.lec_composite.argtypes = [C.POINTER(CompositeArgs)]
+    lib.lec_composite_sections.restype = C.c_int
+    lib.lec_composite_sections.argtypes = [C.POINTER(CompositeSectionsArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

@@ -70,6 +70,12 @@ class LECResult:
     composite_mean: Optional[torch.Tensor] = None    # [6, nyb, nxb] fp64: the time mean of C_f(t, j, i), (j, i) relative to each step's box
     composite_lon: Optional[torch.Tensor] = None     # [t_count, 6, nxb] fp64: H_f(t, i) = sum_j cw_j(t) C_f(t, j, i), cw of step t's box
     composite_steps: Optional[torch.Tensor] = None   # [t_count, 6, nyb, nxb] fp64: C_f itself (on request)
+    # compute(..., per_step_boxes=True, composite_sections=True) on per-step boxes of ONE row count: the system-relative latitude x
+    # pressure sections of the ten terms on box-relative rows (``lec_composite_sections``).  With cw of step t's
+    # box, sum_j cw_j(t) X_f closes on ``levels[t]`` and sum_j cw_j(t) C_f on ``scalars[t]``
+    composite_section_mean: Optional[torch.Tensor] = None    # [10, nl, nyb] fp64: the time mean of X_f(t, k, j) (NaN at any step: NaN)
+    composite_section_lat: Optional[torch.Tensor] = None     # [t_count, 10, nyb] fp64: C_f(t, j), in the units of ``scalars``
+    composite_section_steps: Optional[torch.Tensor] = None   # [t_count, 10, nl, nyb] fp64: X_f itself (on request)
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -371,7 +377,8 @@ class LECEngine:
                 wavenumbers: Optional[int] = None, spectrum_generation: bool = False, spectrum_fused: bool = False,
                 spectrum_interactions: bool = False, spectrum_budget: bool = False,
                 sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False,
-                composites: bool = False, composite_steps: bool = False) -> LECResult:
+                composites: bool = False, composite_steps: bool = False,
+                composite_sections: bool = False, composite_section_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -414,7 +421,18 @@ class LECEngine:
         series with its ``dTdt`` cube or ``tm`` / ``tp``): also ``composite_mean`` and ``composite_lon`` -- and ``composite_steps`` when
         asked for --, the system-relative composites of the six eddy terms on box-relative indices (``composite_stage``: the cubes are
         read once more).  It changes no bit of anything else; without it nothing new runs or allocates.
+        ``composite_sections`` (per-step boxes that all have ONE row count -- widths may differ --, one process; any layout stage 1
+        takes, a ``steps`` table of one box per processed step included): also ``composite_section_mean`` and ``composite_section_lat``
+        -- and ``composite_section_steps`` when asked for --, the system-relative latitude x pressure sections of the ten terms on
+        box-relative rows (``composite_section_stage``: only the row records are read).  It changes no bit of anything else; without it
+        nothing new runs or allocates.
         """
+        if composite_section_steps and not composite_sections:
+            raise ValueError("composite_section_steps: the per-step sections are part of composite_sections=True")
+        if composite_sections:
+            self._check_composite_sections(boxes, True if steps is not None else per_step_boxes)
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("composite sections run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
         if composite_steps and not composites:
             raise ValueError("composite_steps: the per-step columns are part of composites=True")
         if composites:
@@ -494,6 +512,12 @@ class LECEngine:
             lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             self.composite_stage(tair, u, v, omega, rows, pb, lr, cp, 0, time_s=time_s, dTdt=dTdt, tm=tm, tp=tp, tcoef=tcoef, t_begin=t_begin)
             self.composite_finish(res, cp)
+        if composite_sections:
+            pb = boxes if isinstance(boxes, PreparedBoxes) else PreparedBoxes(*self._resolve_boxes(boxes))
+            cs = self.composite_section_begin(int(rows.shape[0]), pb, rows.device, keep_steps=composite_section_steps)
+            lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.composite_section_stage(rows, pb, lr, cs, 0)
+            self.composite_section_finish(res, cs)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
@@ -514,16 +538,38 @@ class LECEngine:
             raise ValueError("sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
                              "no common rows to lay a section on")
 
+    def _section_accumulators(self, t_total: int, nyb: int, device, keep_steps: bool) -> dict:
+        """The accumulators that ``section_*`` and ``composite_section_*`` have alike, zeroed: the time sums, the column values and --
+        on request -- the per-step sections of ``t_total`` steps on ``nyb`` rows."""
+        nl = int(self.level.size)
+        f64 = dict(dtype=torch.float64, device=device)
+        return dict(t_total=int(t_total), nyb=int(nyb), secsum=torch.zeros((nl, _lib.LEC_NSECTION, nyb), **f64),
+                    col=torch.empty((t_total, _lib.LEC_NSECTION, nyb), **f64),
+                    steps=torch.empty((t_total, nl, _lib.LEC_NSECTION, nyb), **f64) if keep_steps else None, work=None)
+
+    @staticmethod
+    def _section_chunk(who: str, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, nyb: int) -> torch.Tensor:
+        """What ``section_stage`` and ``composite_section_stage`` do alike once their boxes are checked: the chunk's fit into the series,
+        ``levraw``'s check, and where the chunk's sections go -- its steps of ``state["steps"]``, or the workspace grown to the chunk."""
+        t_count, nl = int(rows.shape[0]), int(rows.shape[1])
+        if nyb != state["nyb"] or not (0 <= t_offset and t_offset + t_count <= state["t_total"]):
+            raise ValueError(f"{who}_stage: the chunk does not fit the series {who}_begin was given")
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        if state["steps"] is not None:
+            return state["steps"][t_offset: t_offset + t_count]
+        if state["work"] is None or state["work"].shape[0] < t_count:
+            state["work"] = torch.empty((t_count, nl, _lib.LEC_NSECTION, nyb), dtype=torch.float64, device=rows.device)
+        return state["work"][:t_count]
+
     def section_begin(self, t_total: int, nyb: int, device, *, n_wave: int = 0, generation: bool = False, keep_steps: bool = False) -> dict:
         """The accumulators of the sections of a series of ``t_total`` steps (zeroed once, here): ``section_stage`` adds every chunk to
         them, ``section_finish`` turns them into the result's fields."""
-        nl = int(self.level.size)
-        f64 = dict(dtype=torch.float64, device=device)
         nf = 6 if generation else 5
-        return dict(t_total=int(t_total), nyb=int(nyb), n_wave=int(n_wave), nf=nf, generation=bool(generation),
-                    secsum=torch.zeros((nl, _lib.LEC_NSECTION, nyb), **f64), col=torch.empty((t_total, _lib.LEC_NSECTION, nyb), **f64),
-                    steps=torch.empty((t_total, nl, _lib.LEC_NSECTION, nyb), **f64) if keep_steps else None, work=None, specwork=None,
-                    speccolsum=torch.zeros((n_wave, nf, nyb), **f64) if n_wave else None)
+        return dict(self._section_accumulators(t_total, nyb, device, keep_steps), n_wave=int(n_wave), nf=nf, generation=bool(generation),
+                    specwork=None,
+                    speccolsum=torch.zeros((n_wave, nf, nyb), dtype=torch.float64, device=device) if n_wave else None)
 
     def section_stage(self, rows: torch.Tensor, boxes, levraw: torch.Tensor, state: dict, t_offset: int, *,
                       spec: Optional[torch.Tensor] = None, qspec: Optional[torch.Tensor] = None) -> None:
@@ -536,11 +582,7 @@ class LECEngine:
         boxes, bt, dev = self._stage2_input(rows, boxes)
         self._check_sections(boxes, False)
         nyb = bt.nyb_max
-        if nyb != state["nyb"] or not (0 <= t_offset and t_offset + t_count <= state["t_total"]):
-            raise ValueError("section_stage: the chunk does not fit the series section_begin was given")
-        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
-                or not levraw.is_contiguous()):
-            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        sec = self._section_chunk("section", rows, levraw, state, t_offset, nyb)
         n = state["n_wave"]
         if (spec is None) != (n == 0):
             raise ValueError("section_stage: spec goes with section_begin(n_wave=N)")
@@ -553,12 +595,6 @@ class LECEngine:
                                   or not qspec.is_contiguous()):
             raise ValueError("qspec must be a contiguous fp64 [t_count, nl, nyb, N] tensor on the rows' device")
         f64 = dict(dtype=torch.float64, device=rows.device)
-        if state["steps"] is not None:
-            sec = state["steps"][t_offset: t_offset + t_count]
-        else:
-            if state["work"] is None or state["work"].shape[0] < t_count:
-                state["work"] = torch.empty((t_count, nl, _lib.LEC_NSECTION, nyb), **f64)
-            sec = state["work"][:t_count]
         specsec = None
         if n:
             if state["specwork"] is None or state["specwork"].shape[0] < t_count:
@@ -590,6 +626,71 @@ class LECEngine:
             for k in range(1, state["n_wave"]):
                 ssum += shares[:, k]
             res.section_spec_lat = (torch.cat([shares, (tot - ssum).unsqueeze(1)], dim=1) / float(t_total)).contiguous()
+
+    # -- system-relative sections over per-step boxes of one row count (lec_composite_sections) ------------------------------------------
+    @staticmethod
+    def _check_composite_sections(boxes, per_step_boxes) -> int:
+        """The refusals of the system-relative sections that need nothing but the boxes: returns nyb, the one row count of every box."""
+        # (a series has thousands of boxes: no Python loop over them; PreparedBoxes hold them as an int32 [n, 4] table already)
+        bx = boxes.bt.box if isinstance(boxes, PreparedBoxes) else np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+        if per_step_boxes is False or (per_step_boxes is None and len(bx) == 1):
+            raise ValueError("composite sections exist for per-step boxes (per_step_boxes=True): a system-relative section is laid on the "
+                             "box-relative rows of a series of moving boxes; ONE fixed box has sections=True")
+        h = bx[:, 3].astype(np.int64) - bx[:, 2] + 1
+        nyb = int(h[0])
+        other = np.flatnonzero(h != nyb)
+        if other.size:
+            t = int(other[0])
+            raise ValueError(f"composite sections need boxes of ONE row count: the box of step {t} has {int(h[t])} rows, that of "
+                             f"step 0 has {nyb}")
+        if nyb < 2:
+            raise ValueError("composite sections need at least 2 box rows")
+        return nyb
+
+    def composite_section_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the system-relative sections of a series of ``t_total`` steps whose boxes all have the row count of
+        ``boxes``' (zeroed once, here): ``composite_section_stage`` adds every chunk to them, ``composite_section_finish`` turns them
+        into the result's fields."""
+        nyb = self._check_composite_sections(boxes, True)
+        if boxes.bt.nyb_max != nyb:
+            raise ValueError("composite sections: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
+        return self._section_accumulators(t_total, nyb, device, keep_steps)
+
+    def composite_section_stage(self, rows: torch.Tensor, boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int) -> None:
+        """``lec_composite_sections`` on a chunk: rows [t_count, nl, nyb, 32] of one box of ``boxes`` per step (packed or not: only the
+        records are read) and ``levraw`` [t_count, nl, 40] as ``level_stage`` left it for the same steps (sigma is read from it) -> the
+        chunk's sections on box-relative rows, their column values into ``state["col"][t_offset: t_offset + t_count]`` and their time sums
+        added to ``state["secsum"]`` (``composite_section_begin``).  Chunks must come in time order; every number is independent of how
+        the series is cut, bit for bit."""
+        if not isinstance(boxes, PreparedBoxes):
+            raise ValueError("composite_section_stage: boxes from prepare_boxes")
+        t_count, nl = int(rows.shape[0]), int(rows.shape[1])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        if len(bx) != t_count:
+            raise ValueError("composite_section_stage: one box per step of the chunk")
+        nyb = self._check_composite_sections(boxes, True)
+        if bt.nyb_max != nyb:
+            raise ValueError("composite sections: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
+        sec = self._section_chunk("composite_section", rows, levraw, state, t_offset, nyb)
+        packed = "box_data" in dev
+        box_host = np.ascontiguousarray(bt.box, dtype=np.int32)
+        if packed:          # as the cubes hold them: every box at the origin of its slab
+            zero = np.zeros(len(box_host), dtype=np.int32)
+            box_host = np.ascontiguousarray(np.stack([zero, box_host[:, 1] - box_host[:, 0], zero, box_host[:, 3] - box_host[:, 2]], axis=1))
+        ca = _lib.CompositeSectionsArgs(
+            rows_d=_ptr(rows), levraw_d=_ptr(levraw), t_count=t_count, nl=nl, nyb=nyb, reserved0=0,
+            box_h=C.c_void_p(box_host.ctypes.data), box_d=_ptr(dev["box_data" if packed else "box"]), lattab2_d=_ptr(dev["lattab2"]),
+            levtab2_d=_ptr(self._levtab2), sec_d=_ptr(sec), col_d=_ptr(state["col"][t_offset: t_offset + t_count]),
+            secsum_d=_ptr(state["secsum"]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+        with torch.cuda.device(rows.device):
+            _lib.check(self.lib.lec_composite_sections(C.byref(ca)), "lec_composite_sections")
+
+    def composite_section_finish(self, res: LECResult, state: dict) -> None:
+        """``res.composite_section_*`` from the accumulators of a finished series."""
+        res.composite_section_mean = (state["secsum"] / float(state["t_total"])).permute(1, 0, 2).contiguous()
+        res.composite_section_lat = state["col"]
+        if state["steps"] is not None:
+            res.composite_section_steps = state["steps"].permute(0, 2, 1, 3).contiguous()
 
     # -- longitude-resolved maps of the eddy terms on one fixed box (lec_maps) ------------------------------------------------------------
     # the column values C_f(t, j, i) and the row factors of the steps of ONE lec_maps call: a chunk that needs more is cut into sub-calls

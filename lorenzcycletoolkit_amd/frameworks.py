@@ -72,7 +72,7 @@ class BoxData:
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
                  spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                 sections: bool = False, maps: bool = False, composites: bool = False):
+                 sections: bool = False, maps: bool = False, composites: bool = False, composite_sections: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -115,6 +115,16 @@ class BoxData:
                 raise ValueError("composites prepare the data on the host: the streamed path (--ingest device / --device-ingest) is not supported")
             from .tables import box_indices
             composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, *lim) for lim in boxes_limits], flag="composites", lat_too=False)
+        self.composite_sections = bool(composite_sections)
+        self.composite_section_mean = self.composite_section_lat = None
+        if self.composite_sections:     # (host work only, as above; the streamed path is served: only row records are read)
+            if boxes_limits is None:
+                raise ValueError("composite sections exist for the per-step boxes of a track (boxes_limits): ONE fixed box has sections")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("composite sections run on one GPU (no time shards)")
+            from .tables import box_indices
+            composite_sections_check(data.lat, [box_indices(data.lat, data.lon, *lim) for lim in boxes_limits], flag="composite sections",
+                                     lat_too=False)
         self.wavenumbers = None if wavenumbers is None else int(wavenumbers)
         self.spectrum = self.spectrum_rest = self.spectrum_levels = None
         if wavenumbers is not None:     # (host work only, as above)
@@ -196,7 +206,8 @@ class BoxData:
                                                              **({"spectrum_generation": True} if self.spectrum_generation else {}),
                                                              **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
                                                              **({"spectrum_budget": True} if self.spectrum_budget else {}),
-                                                             **({"sections": True} if self.sections else {}))
+                                                             **({"sections": True} if self.sections else {}),
+                                                             **({"composite_sections": True} if self.composite_sections else {}))
             self.level_slices = self.ingest_stats.pop("level_slices", None)
         else:
             self.result = self._compute_resident(data, variable_list_df, dev, dTdt, merge, out)
@@ -248,6 +259,10 @@ class BoxData:
             self.composite_mean = self.result.composite_mean.cpu().numpy()
             self.composite_lon = self.result.composite_lon.cpu().numpy()
             self.composite_dlat, self.composite_dlon = composite_offsets(data.lat, data.lon, self.boxes[0])
+        if self.result.composite_section_mean is not None:
+            self.composite_section_mean = self.result.composite_section_mean.cpu().numpy()
+            self.composite_section_lat = self.result.composite_section_lat.cpu().numpy()
+            self.composite_section_dlat = composite_offsets(data.lat, data.lon, self.boxes[0])[0]
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -292,7 +307,8 @@ class BoxData:
                                    **({"spectrum_interactions": True} if self.spectrum_interactions else {}),
                                    **({"spectrum_budget": True} if self.spectrum_budget else {}),
                                    **({"sections": True} if self.sections else {}), **({"maps": True} if self.maps else {}),
-                                   **({"composites": True} if self.composites else {}))
+                                   **({"composites": True} if self.composites else {}),
+                                   **({"composite_sections": True} if self.composite_sections else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -315,7 +331,8 @@ class BoxData:
         kw = self.engine.packed_dtdt(tm, f[0], tp, tcoef)
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
                                    drop_any_time=False, merge_dropmask=merge, out=out, **kw,
-                                   **({"composites": True} if self.composites else {}))
+                                   **({"composites": True} if self.composites else {}),
+                                   **({"composite_sections": True} if self.composite_sections else {}))
 
 
 def ring_box_check(lon, box) -> float:
@@ -509,6 +526,56 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
                 f.write(format_level_table(box_obj.composite_lon[:, i, :], labels))
         else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
             pd.DataFrame(box_obj.composite_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+
+
+def composite_sections_check(lat, boxes, flag: str = "--composite-sections", lat_too: bool = True) -> int:
+    """The boxes of a track whose system-relative sections are wanted (index quadruples, one per time step) on the latitude axis ``lat``:
+    all of ONE row count (ValueError naming the first step that differs and both counts; widths may differ: a row record holds the zonal
+    means over its own box's width), at least 2 rows -- and, for the command line, evenly spaced latitudes (the offsets that label the
+    files are those of the first step's box).  Longitudes are not looked at.  Host work only.  Returns the row count of every box."""
+    from .tables import is_uniform
+    boxes = [tuple(int(x) for x in b) for b in boxes]
+    nyb = boxes[0][3] - boxes[0][2] + 1
+    for t, b in enumerate(boxes):
+        if b[3] - b[2] + 1 != nyb:
+            raise ValueError(f"{flag} needs boxes of ONE row count: the box of step {t} has {b[3] - b[2] + 1} rows, that of step 0 has {nyb} "
+                             "(a track near the data's edge, or one whose length column changes)")
+    if nyb < 2:
+        raise ValueError(f"{flag} needs boxes of at least 2 latitudes")
+    if lat_too and not is_uniform(np.asarray(lat, dtype=np.float64)):
+        raise ValueError(f"{flag} needs evenly spaced latitudes: a box-relative row means the same offset at every step only there")
+    return nyb
+
+
+def write_composite_section_csvs(box_obj: "BoxData", directory: str, time_name: str, vert_name: str) -> None:
+    """results_composite_sections/: for each of the ten terms ``<term>_dlat_lv.csv`` -- the time mean over the system's life of the term's
+    system-relative latitude-pressure section, one row per level (labelled as ``write_section_csvs`` labels them), one column per box row
+    labelled by its offset in degrees from the box's midpoint (``composite_offsets``, first step's box), in the units of the per-level
+    table -- and ``<term>_dlat.csv`` -- the section's vertical integral, one row per time step, in the units of the results CSV.
+    ``write_section_csvs``' number and time formatting."""
+    from .constants import SECTION_TERMS
+    os.makedirs(directory, exist_ok=True)
+    head = [repr(float(x)) for x in box_obj.composite_section_dlat]
+    labels = box_obj.row_labels("fixed")
+    level_names = [repr(float(p)) for p in box_obj.PressureData]
+
+    def header(path, first):
+        with open(path, "wb") as f:
+            f.write((",".join([str(first)] + head) + "\n").encode("utf-8"))
+
+    for i, term in enumerate(SECTION_TERMS):
+        path = os.path.join(directory, f"{term}_dlat_lv.csv")
+        header(path, vert_name)
+        with open(path, "ab") as f:      # (level labels may have mixed widths: one call per row)
+            for name, row in zip(level_names, np.asarray(box_obj.composite_section_mean[i], dtype=np.float64)):
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+        path = os.path.join(directory, f"{term}_dlat.csv")
+        header(path, time_name)
+        if labels[0] is not None:
+            with open(path, "ab") as f:
+                f.write(format_level_table(box_obj.composite_section_lat[:, i, :], labels))
+        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
+            pd.DataFrame(box_obj.composite_section_lat[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
 
 
 def ring_hint(lon, box):
@@ -836,6 +903,14 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
         track0 = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)
         lims = [get_limits(track0, t) for t in pd.DatetimeIndex(data.time)]
         composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in lims])
+    composite_sections = bool(getattr(args, "composite_sections", False))
+    if composite_sections:      # refused before a file is written
+        from .tables import box_indices
+        if shard is not None:
+            raise ValueError("--composite-sections runs on one GPU")
+        track0 = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)
+        lims = [get_limits(track0, t) for t in pd.DatetimeIndex(data.time)]
+        composite_sections_check(data.lat, [box_indices(data.lat, data.lon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in lims])
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     times = pd.DatetimeIndex(data.time)
@@ -855,8 +930,14 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     boxes = [(l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in limits]
     box_obj = BoxData(data, variable_list_df, args=args, results_subdirectory=results_subdirectory,
                       results_subdirectory_vertical_levels=results_subdirectory_vertical_levels, dTdt=dTdt,
-                      boxes_limits=boxes, **({"composites": True} if composites else {}))
+                      boxes_limits=boxes, **({"composites": True} if composites else {}),
+                      **({"composite_sections": True} if composite_sections else {}))
     phases.mark("ingest_compute_gather")
+    if composite_sections:
+        csec_directory = os.path.join(results_subdirectory, "results_composite_sections")
+        write_composite_section_csvs(box_obj, csec_directory, time_name, vert_name)
+        app_logger.info(f"--composite-sections: the system-relative latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge on "
+                        f"the boxes' {len(box_obj.composite_section_dlat)} box-relative rows (lec_composite_sections); written to {csec_directory}")
     if composites:
         composite_directory = os.path.join(results_subdirectory, "results_composites")
         write_composite_csvs(box_obj, composite_directory, time_name)

@@ -823,7 +823,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
                  t_range=None, merge_dropmask=None, out=None, staging: str = "auto", inflate: str = "auto",
                  slots: Optional[int] = None, keep_level: Optional[float] = None, packed: Optional[bool] = None,
                  ring: bool = False, wavenumbers: Optional[int] = None, spectrum_generation: bool = False,
-                 spectrum_interactions: bool = False, spectrum_budget: bool = False, sections: bool = False) -> LECResult:
+                 spectrum_interactions: bool = False, spectrum_budget: bool = False, sections: bool = False,
+                 composite_sections: bool = False) -> LECResult:
     """All LEC terms for the whole series, streamed from the memory-mapped file.
 
     ``boxes_limits``: one (west, east, south, north) in degrees (fixed framework, as inputs/box_limits) or one per time step
@@ -858,7 +859,16 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     ``sections`` (one fixed box, the whole series in one process): also ``section_mean``, ``section_lat`` and, with ``wavenumbers``,
     ``section_spec_lat`` of ``LECEngine.compute(..., sections=True)``, the same bits: every sub-chunk's records go through
     ``section_stage`` right after their level stage, and only the time sums and the column values outlive the sub-chunk.
+    ``composite_sections`` (``per_step_boxes`` of one row count, the whole series in one process; packed or not): also
+    ``composite_section_mean`` and ``composite_section_lat`` of ``LECEngine.compute(..., composite_sections=True)``, the same bits:
+    every sub-chunk's records go through ``composite_section_stage`` right after their level stage.
     """
+    if composite_sections:
+        if not per_step_boxes:
+            raise ValueError("composite sections exist for per-step boxes (per_step_boxes=True): a system-relative section is laid on the "
+                             "box-relative rows of a series of moving boxes; ONE fixed box has sections=True")
+        if t_range is not None or merge_dropmask is not None or out is not None:
+            raise ValueError("composite sections run in one process on one GPU: a sharded run (t_range, merge_dropmask, out) has none")
     if sections:
         if per_step_boxes:
             raise ValueError("sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
@@ -1023,6 +1033,7 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
     sec_state = None
     if sections:
         sec_state = engine.section_begin(t1 - t0, bt.nyb_max, dev, n_wave=int(wavenumbers or 0), generation=spectrum_generation)
+    csec_state = engine.composite_section_begin(t1 - t0, own_boxes, dev) if composite_sections else None
     time_s = plan.time_s
     phi_scale = ds.field_scale(variable_list_df, geo_role)
 
@@ -1093,6 +1104,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine.level_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], phi_scale=phi_scale)
             if sec_state is not None and wavenumbers is None:
                 engine.section_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], sec_state, s0 - t0)
+            if csec_state is not None:
+                engine.composite_section_stage(rows[:n], part, levraw[s0 - t0: s1 - t0], csec_state, s0 - t0)
             if wavenumbers is not None:         # (never packed: the cubes hold T's halo, and rowspec_q reads T[t - 1], T[t + 1] from them)
                 fields = (f["tair"], f["u"], f["v"], f["omega"])
                 for a in range(0, n, spec_steps):
@@ -1123,6 +1136,8 @@ def lec_streamed(raw: ds.RawDataset, plan: IngestPlan, variable_list_df, boxes_l
             engine._spectrum_nl_shares(res, levraw_nl, fixed_box, True)
     if sec_state is not None:
         engine.section_finish(res, sec_state)
+    if csec_state is not None:
+        engine.composite_section_finish(res, csec_state)
     on_device, reg_stats = pipe.finish()
     moved, host_s = pipe.moved, pipe.host_s
     if stats is not None:
