@@ -49,6 +49,12 @@ latitudes x longitudes) and <term>_lon.csv (the area-weighted sum over latitude,
 (the time mean, box rows x box columns, labelled by the offset in degrees from the box's midpoint) and <term>_dlon.csv (the area-weighted
 sum over the box's rows, time steps x box columns).  One system whose boxes all have one shape.
 
+-t --trackfiles / -c --choose-systems --batch-composites: the composites of EVERY track of a batch in the batch's one pass
+(``lec_composite_steps``: ``lec_composite`` on the union cube, every box with its step from the batch's step table, the time sums kept per
+track) and their ensemble mean (``lec_composite_ensemble``).  Every track's tree gets the results_composites/ of its own
+``-t --trackfile --composites`` run, byte for byte; the batch directory gets results_composites/<term>_dlat_dlon.csv, the mean over the
+tracks of their time-mean composites, and composites.csv -- one results_composites_<rows>x<columns>/ per box shape where shapes differ.
+
 -t / -c --composite-sections: also the system-relative latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge over the boxes
 that follow the system (``lec_composite_sections``: ``lec_sections`` on box-relative rows, every step with its own box), written to
 results_composite_sections/<term>_dlat_lv.csv (the time mean, levels x box rows, labelled by the offset in degrees from the box's
@@ -162,6 +168,15 @@ def create_arg_parser():
                         "<term>_dlon.csv, the area-weighted sum over the box's rows at every time step (rows: time steps; the box's zonal "
                         "average of a row is the results CSV).  Every other output file is unchanged.  One GPU, data prepared on the host "
                         "(--ingest auto resolves to host), evenly spaced longitudes and latitudes, boxes of one shape; -f has --maps")
+    parser.add_argument("--batch-composites", dest="batch_composites", action="store_true", default=argparse.SUPPRESS,
+                        help="with -t --trackfiles or -c --choose-systems / --choose-starts (a batch of tracks): the composites of EVERY track "
+                        "in the batch's one pass (lec_composite_steps) and their ensemble mean (lec_composite_ensemble).  Every track's tree "
+                        "gets results_composites/, byte for byte what -t --trackfile <it> --composites writes; the batch directory gets "
+                        "results_composites/<term>_dlat_dlon.csv, the mean over the tracks of their time-mean composites, and composites.csv "
+                        "(per track: its file, steps, box shape and the NaN points of its mean) -- one results_composites_<rows>x<columns>/ per "
+                        "box shape where the tracks' shapes differ.  Every other output file is unchanged.  Every track needs boxes of one "
+                        "shape along its life and evenly spaced longitudes and latitudes on its own crop.  One GPU, data prepared on the "
+                        "host (--ingest auto resolves to host); not with --batch-chunk; one system has --composites")
     parser.add_argument("--composite-sections", dest="composite_sections", action="store_true", default=argparse.SUPPRESS,
                         help="with -t --trackfile or -c (one system): also the system-relative latitude-pressure sections of the ten terms "
                         "Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz and Ge (lec_composite_sections: the row's own contribution to the per-level sums "
@@ -480,6 +495,27 @@ def refuse_batch_chunk_options(args):
         raise SystemExit("--batch-chunk streams the file to the GPU, --ingest host prepares it on the host: give one of the two")
 
 
+def refuse_batch_composites_options(args):
+    """--batch-composites is the composites of a batch of tracks held as union cubes on one GPU; said before anything is created."""
+    if not getattr(args, "batch_composites", False):
+        return
+    many = args.choose and (args.choose_systems is not None or args.choose_starts is not None)
+    if args.fixed:
+        raise SystemExit("--batch-composites goes with -t --trackfiles or -c --choose-systems / --choose-starts: ONE fixed box has --maps, "
+                         "the maps on the box's own points")
+    if args.trackfiles is None and not many:
+        raise SystemExit("--batch-composites composites a BATCH of tracks (-t --trackfiles, -c --choose-systems / --choose-starts): "
+                         "ONE system has --composites (-t --trackfile FILE --composites, -c --composites)")
+    if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise SystemExit("--batch-composites runs on one GPU: --gpus > 1 is not supported for a batch of tracks")
+    if args.batch_chunk is not None:
+        raise SystemExit("--batch-composites reads the union cubes once more: --batch-chunk streams the batch and never holds them "
+                         "(run the batch without --batch-chunk)")
+    if args.ingest == "device" or args.device_ingest:
+        raise SystemExit("--batch-composites prepares the data on the host: --ingest device / --device-ingest is not supported for the "
+                         "batch composites (--ingest auto resolves to host)")
+
+
 def _join_threshold(argv):
     """``--choose-threshold -5e-5`` as ``--choose-threshold=-5e-5`` (``--choose-end-threshold`` likewise): argparse takes a negative
     number in exponent form for an option."""
@@ -502,6 +538,7 @@ def main(argv=None):
     refuse_choose_options(args)
     refuse_periodic_options(args)
     refuse_batch_chunk_options(args)
+    refuse_batch_composites_options(args)
     refuse_series_options(args)
     if args.trackfiles is not None:
         return main_batch(args, argv)
@@ -675,6 +712,13 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
         if len(parts) > 1 or parts[0][0]:
             app_logger.info("Longitude axis per track: " + "; ".join(f"{'0..360 (across the +-180 meridian)' if origin else '-180..180'}: "
                             + ", ".join(trackfiles[n] for n in members) for origin, members in parts) + f" -- {len(parts)} pass(es) over the data")
+        batch_composites = bool(getattr(args, "batch_composites", False))
+        if batch_composites and len(parts) > 1:
+            raise ValueError("--batch-composites: the tracks take two longitude axes (" + "; ".join(
+                f"{'0..360' if origin else '-180..180'}: " + ", ".join(trackfiles[n] for n in members) for origin, members in parts)
+                + "), which are two passes over the data with no common ensemble: run the two sets apart")
+        if batch_composites and args.ingest == "auto":
+            app_logger.info("--batch-composites: --ingest auto resolves to host (the composites read the host-prepared union cubes once more)")
         rows = [None] * len(trackfiles)
         told = False
         for origin, members in parts:
@@ -701,6 +745,8 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
             else:
                 data, plan = batch.prepare_union(args, [trackfiles[n] for n in members], "inputs/namelist", app_logger, lon_origin=origin)
                 phases.mark("open_decode_and_prepare")
+            # --batch-composites: every track's shapes and axes, before a file is written; the box shapes are the ensembles
+            shapes = batch.composites_check(plan) if batch_composites else None
             directories = []
             for tr in plan.tracks:
                 tree = os.path.join("./LEC_Results/", f"{stem}_{tr.stem}_track")
@@ -719,7 +765,7 @@ def run_batch(args, argv, suffix, what, trackfiles_of):
                 finally:
                     raw.close()
             else:
-                lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args)
+                lec_moving_batch(data, variable_list_df, plan, directories, app_logger, args, batch_dir=batch_dir, composite_shapes=shapes)
                 del data
             for n, tr, d in zip(members, plan.tracks, directories):
                 rows[n] = (tr.path, d[0], tr.n)

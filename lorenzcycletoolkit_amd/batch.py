@@ -187,6 +187,22 @@ def plan_batch(lat, lon, lev, time, level_units, names, trackfiles: Sequence[str
     return plan
 
 
+def composites_check(plan: BatchPlan) -> Dict[Tuple[int, int], List[int]]:
+    """``--batch-composites``: ``frameworks.composites_check`` -- boxes of one shape along the track's life, at least 3 columns, evenly
+    spaced longitudes and latitudes -- applied to every track on its OWN crop, as its ``-t --trackfile --composites`` run applies it; a
+    violation refuses the batch naming the track file (the rule's message names the step).  Returns {(rows, columns): track indices in
+    batch order}: the tracks that enter one ensemble.  Host work only."""
+    from .frameworks import composites_check as check
+    shapes = {}
+    for k, tr in enumerate(plan.tracks):
+        wlat, wlon = tr.window(plan.lat, plan.lon)
+        try:
+            shapes.setdefault(check(wlat, wlon, tr.boxes, flag="--batch-composites"), []).append(k)
+        except ValueError as e:
+            _refuse(tr.path, e)
+    return shapes
+
+
 @dataclass
 class ChunkGroup:
     """One group's records of a chunk (``plan_chunks``), in (track, step) order."""

@@ -1,8 +1,8 @@
-// lec_mapcol.h -- what lec_maps (lec_maps.hip) and lec_composite (lec_composite.hip) share: the column integrals C_f(t, j, i) of the six
-// eddy terms Ae Ke Ca Ce Ck Ge at the points of a box, their time sums and their Hovmoeller rows (DESIGN.md sections 4.2d, 4.2e).  The
-// record layout, the Q expression, the integrands, the trapezoid rule and the refusals the two calls have in common are written once,
-// here.  The kernels have internal linkage and the column kernel is a template over the including file's launch struct, so each of the two
-// files instantiates kernels of its own and remains a code object of its own.
+// lec_mapcol.h -- what lec_maps (lec_maps.hip), lec_composite (lec_composite.hip) and lec_composite_steps (lec_composite_steps.hip) share:
+// the column integrals C_f(t, j, i) of the six eddy terms Ae Ke Ca Ce Ck Ge at the points of a box, their time sums and their Hovmoeller
+// rows (DESIGN.md sections 4.2d, 4.2e, 4.2g).  The record layout, the Q expression, the integrands, the trapezoid rule and the refusals the
+// calls have in common are written once, here.  The kernels have internal linkage and the column kernel is a template over the including
+// file's launch struct, so each of the files instantiates kernels of its own and remains a code object of its own.
 //   lec_mapcol_coef_kernel  one wave per (time step, level), lanes over rows in trips of 64: the area means in the order of the level stage
 //                  (lec_section_rows_kernel's), the row factors dphiTc dphiUc dphiV dpT dpU of lec_level_row.inc, and with sigma READ from
 //                  the levraw record everything a point multiplies by, as one record of LEC_MAPS_NCOEF doubles per (t, k, j).
@@ -144,13 +144,13 @@ __device__ __forceinline__ void trap_step(Trap& s, const double x, const double 
 //   int iw(tl), js(tl)                        the grid column and row of the box's first point
 //   const double* lattab_row(tl, jb)          the [4] entry of box row jb: the d/dlat triple and the d/dlon -> d/dx factor
 //   double inv_hdeg(tl)                       1 / h_deg of the box
-// and the members a DMODE reads: DT (0), TM and TP (1)
+// and the members a DMODE reads: DT (0), TM and TP (1), step (3)
 struct MapColGrid {
     const void *T, *U, *V, *W;
     const double* coef;      // [t_count][nl][nyb][kNC]
     const double* levtab;    // [nl][3]
     const double* levtab2;   // [nl][4]
-    const double* tcoef;     // [nt][3] (DMODE 1, 2)
+    const double* tcoef;     // [nt][3] (DMODE 1, 2); [t_count][3], by box (DMODE 3)
     double* col;             // [t_count][kNMap][nyb][nxb]
     int nt, nl, ny, nx, t_begin, t_count, nyb, nxb, nseg;
 };
@@ -159,7 +159,9 @@ struct MapColGrid {
 // (time step, row, 64 columns), lanes ALONG LONGITUDE (every cube load is a row segment), marching down the levels with T(k - 1) T(k)
 // T(k + 1) in registers; the box, its tables and the record of (t, k, j) are wave-uniform (scalar loads).
 // RING: lambda wraps; otherwise the box is open: one-sided d/dlon at its first and last column, nothing outside its columns is read.
-// DMODE: where dT/dt comes from -- 0 the fp64 cube DT, 1 tc[t] . (TM[t], T[t], TP[t]), 2 tc[t] . (T[t - 1], T[t], T[t + 1]) of the cube itself
+// DMODE: where dT/dt comes from -- 0 the fp64 cube DT, 1 tc[t] . (TM[t], T[t], TP[t]), 2 tc[t] . (T[t - 1], T[t], T[t + 1]) of the cube itself,
+// 3 a step table (lec_composite_steps): box tl reads cube step p.step[tl][0] and tc[tl] . (T[step[tl][1]], T[t], T[step[tl][2]]), DMODE 2's
+// expression; an entry outside [0, nt) reads nothing and the box's columns are NaN
 template <typename E, bool RING, int DMODE, typename P>
 __global__ void __launch_bounds__(64) lec_mapcol_col_kernel(const P p) {
 #pragma clang fp contract(off)
@@ -169,7 +171,17 @@ __global__ void __launch_bounds__(64) lec_mapcol_col_kernel(const P p) {
     const int jb = tj % nyb, tl = tj / nyb;
     const int e = seg * 64 + (int)threadIdx.x;          // box column
     if (e >= nxb) return;                               // (no barrier below)
-    const int t = p.t_begin + tl;
+    // (DMODE 3) the table's row of box tl: wave-uniform, scalar loads.  A row with an entry outside the cube marches over no level at all:
+    // nothing of the cubes is read, and a column without a finite level is NaN
+    int st = 0, stm = 0, stp = 0;
+    bool off_cube = false;
+    if constexpr (DMODE == 3) {
+        const int32_t* sr = p.step + 3 * (size_t)tl;
+        st = sr[0]; stm = sr[1]; stp = sr[2];
+        off_cube = (unsigned)st >= (unsigned)p.nt || (unsigned)stm >= (unsigned)p.nt || (unsigned)stp >= (unsigned)p.nt;
+        if (off_cube) st = stm = stp = 0;
+    }
+    const int t = DMODE == 3 ? st : p.t_begin + tl;
     const size_t plane = (size_t)p.ny * nx, cube = plane * nl;
     const int i = p.iw(tl) + e;
     const bool first = e == 0, last = e == nxb - 1;
@@ -188,20 +200,23 @@ __global__ void __launch_bounds__(64) lec_mapcol_col_kernel(const P p) {
     if constexpr (DMODE == 1) { pM = (const E*)p.TM + row0; pP = (const E*)p.TP + row0; }
     // a neighbour that does not exist: the row itself, whose coefficient in the tables is 0
     const ptrdiff_t ojm = jb > 0 ? -(ptrdiff_t)nx : 0, ojp = jb < nyb - 1 ? (ptrdiff_t)nx : 0;
-    const ptrdiff_t otm = t > 0 ? -(ptrdiff_t)cube : 0, otp = t < p.nt - 1 ? (ptrdiff_t)cube : 0;      // (DMODE 2)
+    // from T[t] to its time neighbours (DMODE 2; 3: those the table names)
+    const ptrdiff_t otm = DMODE == 3 ? (ptrdiff_t)(stm - st) * (ptrdiff_t)cube : (t > 0 ? -(ptrdiff_t)cube : 0);
+    const ptrdiff_t otp = DMODE == 3 ? (ptrdiff_t)(stp - st) * (ptrdiff_t)cube : (t < p.nt - 1 ? (ptrdiff_t)cube : 0);
     const double* lt = p.lattab_row(tl, jb);
     const double ga = lt[0], gb = lt[1], gc = lt[2];
     const double cx = 0.5 * p.inv_hdeg(tl) * lt[3];            // centred d/dlon -> d/dx
     double ta = 0.0, tb = 0.0, tc = 0.0;
-    if (DMODE != 0) { const double* tcf = p.tcoef + (size_t)t * 3; ta = tcf[0]; tb = tcf[1]; tc = tcf[2]; }
+    if (DMODE != 0) { const double* tcf = p.tcoef + (size_t)(DMODE == 3 ? tl : t) * 3; ta = tcf[0]; tb = tcf[1]; tc = tcf[2]; }
     const double* cf = p.coef + ((size_t)tl * nl * nyb + jb) * kNC;
 
     Trap s[kNMap];
 #pragma unroll
     for (int f = 0; f < kNMap; ++f) { s[f].r = 0.0; s[f].xl = 0.0; s[f].yl = 0.0; s[f].last = -1; }
 
-    double Tc = (double)pT[i], Tm = Tc;
-    for (int k = 0; k < nl; ++k) {
+    const bool skip = DMODE == 3 && off_cube;
+    double Tc = skip ? 0.0 : (double)pT[i], Tm = Tc;
+    for (int k = 0; k < (skip ? 0 : nl); ++k) {
         const E* __restrict__ rT = pT + (size_t)k * plane;
         const size_t ko = (size_t)k * plane + i;
         const double Tp = k < nl - 1 ? (double)rT[plane + i] : Tc;
@@ -318,9 +333,9 @@ void mapcol_col(const P& p, const int dtype, const dim3 grid, hipStream_t st) {
 
 // the four launches of a call on its stream.  A: lec_maps_args or lec_composite_args, whose common fields are read by name; p: the file's
 // column launch struct with its own members set; lt_stride: doubles from one step's lattab2 to the next; launch_col(p, grid, stream)
-// picks the file's RING and DMODE of mapcol_col
-template <typename A, typename P, typename L>
-int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_stride, L launch_col) {
+// picks the file's RING and DMODE of mapcol_col; launch_sum(f, stream) the file's time sums of the column values
+template <typename A, typename P, typename L, typename S>
+int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_stride, L launch_col, S launch_sum) {
     hipStream_t st = (hipStream_t)a->stream;
     const MapCoefParams c{a->rows_d, a->lattab2_d, a->levtab2_d, a->levraw_d, a->coef_d, a->t_count, a->nl, nyb, lt_stride};
     hipLaunchKernelGGL(lec_mapcol_coef_kernel, dim3((unsigned)(a->t_count * a->nl)), dim3(64), 0, st, c);
@@ -330,11 +345,19 @@ int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_st
     p.nyb = nyb; p.nxb = nxb; p.nseg = (nxb + 63) / 64;
     launch_col(p, dim3((unsigned)((long long)a->t_count * nyb * p.nseg)), st);
     const MapFoldParams f{a->col_d, a->lattab2_d, a->mapsum_d, a->hov_d, a->t_count, nyb, nxb, lt_stride};
-    hipLaunchKernelGGL(lec_mapcol_sum_kernel, dim3((unsigned)(((long long)kNMap * nyb * nxb + 255) / 256)), dim3(256), 0, st, f);
+    launch_sum(f, st);
     hipLaunchKernelGGL(lec_mapcol_hov_kernel, dim3((unsigned)(((long long)a->t_count * kNMap * nxb + 255) / 256)), dim3(256), 0, st, f);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
     return LEC_OK;
+}
+
+// lec_maps' and lec_composite's: ONE time sum over all the call's steps
+template <typename A, typename P, typename L>
+int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_stride, L launch_col) {
+    return mapcol_launch(a, p, nyb, nxb, lt_stride, launch_col, [nyb, nxb](const MapFoldParams& f, hipStream_t st) {
+        hipLaunchKernelGGL(lec_mapcol_sum_kernel, dim3((unsigned)(((long long)kNMap * nyb * nxb + 255) / 256)), dim3(256), 0, st, f);
+    });
 }
 
 }  // namespace

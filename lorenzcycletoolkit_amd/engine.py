@@ -70,6 +70,13 @@ class LECResult:
     composite_mean: Optional[torch.Tensor] = None    # [6, nyb, nxb] fp64: the time mean of C_f(t, j, i), (j, i) relative to each step's box
     composite_lon: Optional[torch.Tensor] = None     # [t_count, 6, nxb] fp64: H_f(t, i) = sum_j cw_j(t) C_f(t, j, i), cw of step t's box
     composite_steps: Optional[torch.Tensor] = None   # [t_count, 6, nyb, nxb] fp64: C_f itself (on request)
+    # compute(..., steps=tab, per_step_boxes=True, batch_composites=sizes): the composites of a BATCH of K tracks over one cube, track k
+    # owning sizes[k] consecutive boxes of the step table (``lec_composite_steps`` / ``lec_composite_ensemble``).
+    # Every track's share is, bit for bit, ``composite_*`` of the track's own run
+    batch_composite_mean: Optional[torch.Tensor] = None      # [K, 6, nyb, nxb] fp64: every track's time-mean composite
+    batch_composite_lon: Optional[torch.Tensor] = None       # [S, 6, nxb] fp64: H_f of every box, in table order
+    batch_composite_ensemble: Optional[torch.Tensor] = None  # [6, nyb, nxb] fp64: (mean[0] + mean[1] + ...) / K, tracks ascending
+    batch_composite_steps: Optional[torch.Tensor] = None     # [S, 6, nyb, nxb] fp64: C_f of every box (on request)
     # compute(..., per_step_boxes=True, composite_sections=True) on per-step boxes of ONE row count: the system-relative latitude x
     # pressure sections of the ten terms on box-relative rows (``lec_composite_sections``).  With cw of step t's
     # box, sum_j cw_j(t) X_f closes on ``levels[t]`` and sum_j cw_j(t) C_f on ``scalars[t]``
@@ -378,7 +385,8 @@ class LECEngine:
                 spectrum_interactions: bool = False, spectrum_budget: bool = False,
                 sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False,
                 composites: bool = False, composite_steps: bool = False,
-                composite_sections: bool = False, composite_section_steps: bool = False) -> LECResult:
+                composite_sections: bool = False, composite_section_steps: bool = False,
+                batch_composites: Optional[Sequence[int]] = None, batch_composite_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -426,7 +434,28 @@ class LECEngine:
         -- and ``composite_section_steps`` when asked for --, the system-relative latitude x pressure sections of the ten terms on
         box-relative rows (``composite_section_stage``: only the row records are read).  It changes no bit of anything else; without it
         nothing new runs or allocates.
+        ``batch_composites`` = sizes (with ``steps``: the boxes of K tracks over one cube, track k owning ``sizes[k]`` consecutive rows
+        of the table; every box of ONE shape, evenly spaced longitudes, one process, ``with_q``): also ``batch_composite_mean``,
+        ``batch_composite_lon`` and ``batch_composite_ensemble`` -- and ``batch_composite_steps`` when asked for --, every track's
+        composites and their ensemble mean (``batch_composite_stage``: the cubes are read once more).  A track's share has the bits of
+        ``composites=True`` on the track's own cube.  It changes no bit of anything else; without it nothing new runs or allocates.
         """
+        if batch_composite_steps and batch_composites is None:
+            raise ValueError("batch_composite_steps: the per-box columns are part of batch_composites=sizes")
+        if batch_composites is not None:
+            if steps is None:
+                raise ValueError("batch composites need a step table (steps=, the batch of lec_rowstats_steps): ONE track has composites=True")
+            lon = getattr(self, "lon", None)
+            nyb, _ = self._check_batch_composites(boxes, int(steps.shape[0]), batch_composites, boxes.bt.lon_uniform
+                                                  if isinstance(boxes, PreparedBoxes) else (None if lon is None else tables.is_uniform(lon)))
+            if isinstance(boxes, PreparedBoxes) and boxes.bt.nyb_max != nyb:
+                raise ValueError("batch composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min above it)")
+            # the table's host copy, taken before anything of this call is launched (later it would wait for stage 1 + stage 2)
+            steps_host = steps.cpu().numpy() if steps.device.type != "cpu" else steps.numpy()
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("batch composites run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
+            if not with_q:
+                raise ValueError("batch composites need with_q: the composite of Ge is Q'T' at every point, and its zonal mean [Q] comes from the row records")
         if composite_section_steps and not composite_sections:
             raise ValueError("composite_section_steps: the per-step sections are part of composite_sections=True")
         if composite_sections:
@@ -518,6 +547,12 @@ class LECEngine:
             lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             self.composite_section_stage(rows, pb, lr, cs, 0)
             self.composite_section_finish(res, cs)
+        if batch_composites is not None:
+            pb = boxes if isinstance(boxes, PreparedBoxes) else PreparedBoxes(*self._resolve_boxes(boxes))
+            bc = self.batch_composite_begin(batch_composites, pb, rows.device, keep_steps=batch_composite_steps)
+            lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.batch_composite_stage(tair, u, v, omega, rows, pb, lr, bc, 0, steps=steps, tcoef=tcoef, steps_host=steps_host)
+            self.batch_composite_finish(res, bc)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
@@ -704,6 +739,11 @@ class LECEngine:
                     hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
                     steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
 
+    def _mapcol_sub(self, nl: int, nyb: int, nxb: int, t_count: int) -> int:
+        """Steps per sub-call of a chunk of ``t_count`` steps: as many as keep the column values and row factors within ``MAP_CHUNK_BYTES``."""
+        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+        return max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+
     def _mapcol_stage(self, cubes, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, t_begin: int, issue) -> None:
         """What ``map_stage`` and ``composite_stage`` do alike once their own arguments are checked: ``levraw``'s check, the cut of the
         chunk into sub-calls whose column values and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and
@@ -715,8 +755,7 @@ class LECEngine:
                 or not levraw.is_contiguous()):
             raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
         f64 = dict(dtype=torch.float64, device=rows.device)
-        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
-        sub = max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+        sub = self._mapcol_sub(nl, nyb, nxb, t_count)
         if state["coef"] is None or state["coef"].shape[0] < sub:
             state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
         if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
@@ -884,6 +923,122 @@ class LECEngine:
         res.composite_lon = state["hov"]
         if state["steps"] is not None:
             res.composite_steps = state["steps"]
+
+    # -- composites of a batch of tracks over one cube and their ensemble (lec_composite_steps, lec_composite_ensemble) ------------------
+    @staticmethod
+    def _check_batch_composites(boxes, n_rows: int, sizes, lon_uniform: Optional[bool] = None) -> tuple:
+        """The refusals of the batch composites that need nothing but the boxes, the step table's row count and the tracks' sizes: returns
+        (nyb, nxb), the one shape of every box."""
+        bx = boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes
+        sizes = [int(n) for n in sizes]
+        if not sizes or min(sizes) < 1:
+            raise ValueError(f"batch_composites: every track needs at least one box, the sizes are {sizes}")
+        if sum(sizes) != len(bx) or sum(sizes) != n_rows:
+            raise ValueError(f"batch_composites: the sizes sum to {sum(sizes)}, the step table has {n_rows} rows and there are "
+                             f"{len(bx)} boxes: one box and one row per step of every track")
+        bx = [tuple(int(x) for x in b) for b in bx]
+        nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
+        for s, b in enumerate(bx):
+            h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
+            if (h, w) != (nyb, nxb):
+                raise ValueError(f"batch composites need boxes of ONE shape: box {s} has {h} x {w} points (rows x columns), box 0 has "
+                                 f"{nyb} x {nxb}")
+        if nxb < 3:
+            raise ValueError("batch composites need at least 3 box columns")
+        if lon_uniform is False:
+            raise ValueError("batch composites need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+        return nyb, nxb
+
+    def batch_composite_begin(self, sizes: Sequence[int], boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the composites of K tracks whose boxes are ``boxes``, track k owning ``sizes[k]`` consecutive ones (zeroed
+        once, here): ``batch_composite_stage`` adds every chunk to them, ``batch_composite_finish`` turns them into the result's fields."""
+        sizes = [int(n) for n in sizes]
+        nyb, nxb = self._check_batch_composites(boxes, len(boxes.boxes), sizes, boxes.bt.lon_uniform)
+        if boxes.bt.nyb_max != nyb:
+            raise ValueError("batch composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min above it)")
+        state = self._mapcol_begin(sum(sizes), nyb, nxb, device, keep_steps)
+        state["mapsum"] = torch.zeros((len(sizes), _lib.LEC_NMAP, nyb, nxb), dtype=torch.float64, device=device)
+        state["sizes"] = np.ascontiguousarray(sizes, dtype=np.int32)
+        state["sizes_dev"] = torch.as_tensor(state["sizes"]).to(device)      # (uploaded here: an upload after the launches would wait for them)
+        state["seg"] = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        return state
+
+    def batch_composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
+                              boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, steps: torch.Tensor,
+                              tcoef: torch.Tensor, steps_host: Optional[np.ndarray] = None) -> None:
+        """``lec_composite_steps`` on a chunk of the batch's boxes [t_offset, t_offset + s_count): one box of ``boxes``, one row of
+        ``steps`` / ``tcoef`` and one record of ``rows`` [s_count, nl, nyb, 32] / ``levraw`` [s_count, nl, 40] each -> the Hovmoeller rows
+        ``state["hov"][t_offset: t_offset + s_count]`` and every track's time sum added to its ``state["mapsum"][k]``.  A chunk whose
+        column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into sub-calls; a sub-call passes the tracks it intersects as
+        segments and the first of their accumulators.  Chunks must come in table order; a track cut by a sub-call or a chunk has the
+        bits of one that is not.  ``steps_host``: the caller's host copy of ``steps`` (int32 [s_count, 3]; the caller keeps the two
+        equal), which the call validates; without it the table is copied back from the device, which waits for the stream."""
+        if not isinstance(boxes, PreparedBoxes) or "box_data" in boxes.dev:
+            raise ValueError("batch_composite_stage: boxes from prepare_boxes, on the cubes' grid (a box-packed series has no step table)")
+        self._check_fields([tair, u, v, omega], None)
+        nt, s_count = int(tair.shape[0]), int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        if len(bx) != s_count:
+            raise ValueError("batch_composite_stage: one box per record of the chunk")
+        if steps_host is None:
+            if self.check_steps(steps, tcoef, nt, tair.device) != s_count:
+                raise ValueError("batch_composite_stage: one table row per record of the chunk")
+            steps_host = steps.cpu().numpy()
+        step_host = np.ascontiguousarray(steps_host, dtype=np.int32)
+        if (step_host.shape != (s_count, 3) or not isinstance(steps, torch.Tensor) or steps.dtype != torch.int32 or tuple(steps.shape) != (s_count, 3)
+                or steps.device != tair.device or not steps.is_contiguous()):
+            raise ValueError("batch_composite_stage: steps must be a contiguous int32 [s_count, 3] tensor on the fields' device, steps_host its host copy")
+        if (not isinstance(tcoef, torch.Tensor) or tuple(tcoef.shape) != (s_count, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device
+                or not tcoef.is_contiguous()):
+            raise ValueError(f"batch_composite_stage: tcoef must be a contiguous fp64 [{s_count}, 3] tensor (by box) on the fields' device")
+        bad = np.flatnonzero(np.any((step_host < 0) | (step_host >= nt), axis=1))
+        if bad.size:
+            raise ValueError(f"steps: box {int(bad[0])} names cube steps {step_host[bad[0]].tolist()} outside [0, {nt})")
+        seg = state["seg"]
+        if (bt.nyb_max != state["nyb"] or not (0 <= t_offset and t_offset + s_count <= state["t_total"])
+                or any((b[3] - b[2] + 1, b[1] - b[0] + 1) != (state["nyb"], state["nxb"]) for b in bx)):
+            raise ValueError("batch_composite_stage: the chunk does not fit the boxes and shape batch_composite_begin was given")
+        if rows.device != tair.device:
+            raise ValueError("batch_composite_stage: rows and fields on one device")
+        box_host = np.ascontiguousarray(bx, dtype=np.int32)
+        # every sub-call [a, b): the tracks it intersects, their offsets relative to a, and the first of their accumulators.  The tables
+        # of all sub-calls go to the device in ONE upload before the first launch (an upload between the sub-calls would wait for them)
+        sub, cuts, n_off = self._mapcol_sub(int(rows.shape[1]), state["nyb"], state["nxb"], s_count), {}, 0
+        for a in range(0, s_count, sub):
+            lo, hi = t_offset + a, t_offset + min(s_count, a + sub)
+            g0, g1 = int(np.searchsorted(seg, lo, side="right")) - 1, int(np.searchsorted(seg, hi, side="left"))
+            cuts[a] = (g0, g1, n_off, np.ascontiguousarray(np.clip(seg[g0: g1 + 1], lo, hi) - lo, dtype=np.int32))
+            n_off += g1 - g0 + 1
+        seg_dev = torch.as_tensor(np.concatenate([c[3] for c in cuts.values()])).to(rows.device)
+
+        def issue(a, b, shared):
+            g0, g1, off, seg_host = cuts[a]
+            shared = {k: x for k, x in shared.items() if k not in ("t_begin", "t_count", "mapsum_d")}
+            ca = _lib.CompositeStepsArgs(
+                s_count=b - a, nyb=state["nyb"], nxb=state["nxb"], n_seg=g1 - g0, step_h=C.c_void_p(step_host[a:b].ctypes.data),
+                step_d=_ptr(steps[a:b]), seg_h=C.c_void_p(seg_host.ctypes.data), seg_d=_ptr(seg_dev[off: off + g1 - g0 + 1]),
+                box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(dev["box"][a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
+                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), tcoef_d=_ptr(tcoef[a:b]),
+                mapsum_d=_ptr(state["mapsum"][g0:]), **shared)
+            _lib.check(self.lib.lec_composite_steps(C.byref(ca)), "lec_composite_steps")
+        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, 0, issue)
+
+    def batch_composite_finish(self, res: LECResult, state: dict) -> None:
+        """``res.batch_composite_*`` from the accumulators of a finished batch: ``lec_composite_ensemble`` turns the time sums into the
+        tracks' means (in place) and forms their ensemble mean."""
+        ms = state["mapsum"]
+        counts, counts_dev = state["sizes"], state["sizes_dev"]
+        ens = torch.empty(tuple(ms.shape[1:]), dtype=torch.float64, device=ms.device)
+        ea = _lib.CompositeEnsembleArgs(mapsum_d=_ptr(ms), count_h=C.c_void_p(counts.ctypes.data), count_d=_ptr(counts_dev),
+                                        n_track=int(ms.shape[0]), nyb=state["nyb"], nxb=state["nxb"], reserved0=0, mean_d=_ptr(ms),
+                                        ens_d=_ptr(ens), stream=C.c_void_p(torch.cuda.current_stream(ms.device).cuda_stream))
+        with torch.cuda.device(ms.device):
+            _lib.check(self.lib.lec_composite_ensemble(C.byref(ea)), "lec_composite_ensemble")
+        res.batch_composite_mean = ms
+        res.batch_composite_ensemble = ens
+        res.batch_composite_lon = state["hov"]
+        if state["steps"] is not None:
+            res.batch_composite_steps = state["steps"]
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
     # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records

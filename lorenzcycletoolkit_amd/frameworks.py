@@ -504,9 +504,8 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
     units of the results CSV -- and ``<term>_dlon.csv`` -- the composite's area-weighted sum over the box's rows, one row per time step
     (the time labels and number formatting of the per-level tables), one column per box column.  ``write_map_csvs``' format."""
     from .constants import MAP_TERMS
-    os.makedirs(directory, exist_ok=True)
+    write_composite_mean_csvs(box_obj.composite_mean, box_obj.composite_dlat, box_obj.composite_dlon, directory)
     lons = [repr(float(x)) for x in box_obj.composite_dlon]
-    lat_names = [repr(float(x)) for x in box_obj.composite_dlat]
     labels = box_obj.row_labels("fixed")
 
     def header(path, first):
@@ -514,11 +513,6 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
             f.write((",".join([str(first)] + lons) + "\n").encode("utf-8"))
 
     for i, term in enumerate(MAP_TERMS):
-        path = os.path.join(directory, f"{term}_dlat_dlon.csv")
-        header(path, "dlat")
-        with open(path, "ab") as f:      # (labels of mixed widths: one call per row)
-            for name, row in zip(lat_names, np.asarray(box_obj.composite_mean[i], dtype=np.float64)):
-                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
         path = os.path.join(directory, f"{term}_dlon.csv")
         header(path, time_name)
         if labels[0] is not None:
@@ -526,6 +520,21 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
                 f.write(format_level_table(box_obj.composite_lon[:, i, :], labels))
         else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
             pd.DataFrame(box_obj.composite_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+
+
+def write_composite_mean_csvs(mean, dlat, dlon, directory: str) -> None:
+    """``<term>_dlat_dlon.csv`` for each of the six eddy terms in ``directory``: ``mean`` [6, rows, columns], one row per box row, one
+    column per box column, labelled by the offsets ``dlat`` / ``dlon``.  The time-mean files of ``write_composite_csvs``, and the ensemble
+    mean of a batch of tracks (``lec_moving_batch``)."""
+    from .constants import MAP_TERMS
+    os.makedirs(directory, exist_ok=True)
+    head = (",".join(["dlat"] + [repr(float(x)) for x in dlon]) + "\n").encode("utf-8")
+    lat_names = [repr(float(x)) for x in dlat]
+    for i, term in enumerate(MAP_TERMS):
+        with open(os.path.join(directory, f"{term}_dlat_dlon.csv"), "wb") as f:
+            f.write(head)
+            for name, row in zip(lat_names, np.asarray(mean[i], dtype=np.float64)):      # (labels of mixed widths: one call per row)
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
 
 
 def composite_sections_check(lat, boxes, flag: str = "--composite-sections", lat_too: bool = True) -> int:
@@ -1005,11 +1014,16 @@ class _TrackResult:
     row_labels = BoxData.row_labels
 
 
-def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, directories, app_logger, args):
+def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, directories, app_logger, args, batch_dir=None,
+                     composite_shapes=None):
     """Many tracks over one data set (``batch.prepare_union``): ONE upload of the union cubes, one stage-1 + stage-2 call per group of
     tracks with equal record extents (``LECEngine.compute(steps=...)``), then every track's files written by the code ``lec_moving``
     writes them with.  ``directories``: per track (results, figures, vertical levels).  The files of every track are byte for byte
-    those of its own ``-t --trackfile`` run.  Returns [(results file, DataFrame)] in batch order."""
+    those of its own ``-t --trackfile`` run.  Returns [(results file, DataFrame)] in batch order.
+    ``composite_shapes`` (``--batch-composites``): what ``batch.composites_check(plan)`` returned, {(rows, columns): tracks}.  Every
+    group's call then also composites its tracks (``compute(batch_composites=...)``); every track's tree gets the ``results_composites/``
+    of its own ``--composites`` run, and ``batch_dir`` the ensemble mean of every box shape (``_write_batch_composites``).  The check
+    has left every track with one box shape on evenly spaced longitudes, so the plan's groups ARE those shapes."""
     from . import batch as bt
     from .diagnostics import track_diagnostics
     dev = _device(args)
@@ -1028,6 +1042,10 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
     app_logger.info(f"Batch of {len(plan.tracks)} tracks: union of {len(plan.tpos)} time steps on a {len(plan.lat)} x {len(plan.lon)} crop "
                     f"({need / 1e9:.2f} GB on the device), {len(plan.groups)} group(s) of equal box extents and longitude formulation")
     results = [None] * len(plan.tracks)
+    with_composites = composite_shapes is not None
+    if with_composites and {k[:2]: v for k, v in plan.groups.items()} != composite_shapes:
+        raise ValueError("composite_shapes: not batch.composites_check's result for this plan")
+    composites, ensembles = [None] * len(plan.tracks), []
     for (nyb, nxb, uniform), members in plan.groups.items():
         trs = [plan.tracks[k] for k in members]
         boxes = [b for tr in trs for b in tr.boxes]
@@ -1035,17 +1053,22 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
         tcoef = torch.as_tensor(np.concatenate([tr.tcoef for tr in trs])).to(dev)
         pb = engine.prepare_boxes(boxes, nyb_min=nyb, lon_uniform=uniform)      # (the formulation of the tracks' own crops)
         res = engine.compute(cubes[0], cubes[1], cubes[2], cubes[3], cubes[4], pb, phi_scale=phi_scale, per_step_boxes=True,
-                             drop_any_time=False, steps=steps, tcoef=tcoef)
+                             drop_any_time=False, steps=steps, tcoef=tcoef,
+                             **({"batch_composites": [tr.n for tr in trs]} if with_composites else {}))
         a = 0
-        for k, tr in zip(members, trs):
+        for n, (k, tr) in enumerate(zip(members, trs)):
             b = a + tr.n
             results[k] = LECResult(scalars=res.scalars[a:b], levels=res.levels[a:b], nanflag=res.nanflag[a:b], packed=res.packed[a:b])
+            if with_composites:
+                composites[k] = (res.batch_composite_mean[n].cpu().numpy(), res.batch_composite_lon[a:b].cpu().numpy())
             a = b
+        if with_composites:
+            ensembles.append(((nyb, nxb), members, res.batch_composite_ensemble.cpu().numpy()))
     torch.cuda.synchronize(dev)
     phases.mark("ingest_compute_gather")
     form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
     written = []
-    for tr, res, (results_subdirectory, figures_directory, vl_directory) in zip(plan.tracks, results, directories):
+    for k, (tr, res, (results_subdirectory, figures_directory, vl_directory)) in enumerate(zip(plan.tracks, results, directories)):
         view = bt.track_view(data, tr)
         _create_level_csvs(vl_directory, time_name, vert_name, view.level)
         holder = _TrackResult(view, variable_list_df, res, results_subdirectory, vl_directory)
@@ -1057,7 +1080,31 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
         app_logger.info(f"Track {tr.path}: {tr.n} time steps -> {results_subdirectory}")
         written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, positions, results_subdirectory,
                                              form, app_logger, args, lon_origin=ds.lon_origin_of_axis(view.lon)))
+        if with_composites:     # the files of the track's own --composites run (lec_moving), from the batch's numbers
+            holder.composite_mean, holder.composite_lon = composites[k]
+            holder.composite_dlat, holder.composite_dlon = composite_offsets(data.lat, data.lon, tr.boxes[0])
+            write_composite_csvs(holder, os.path.join(results_subdirectory, "results_composites"), time_name)
+    if with_composites:
+        _write_batch_composites(plan, data, ensembles, composites, directories, batch_dir, app_logger)
     return written
+
+
+def _write_batch_composites(plan, data, ensembles, composites, directories, batch_dir, app_logger):
+    """The ensemble means of a batch (``lec_moving_batch``): per box shape ``<term>_dlat_dlon.csv`` in ``write_composite_csvs``' layout
+    -- labelled by the offsets of the first track's first box -- and ``composites.csv``, one line per track that entered the mean.  One
+    shape: ``batch_dir/results_composites/``; several: ``batch_dir/results_composites_<rows>x<columns>/`` each."""
+    for (nyb, nxb), members, ens in ensembles:
+        name = "results_composites" if len(ensembles) == 1 else f"results_composites_{nyb}x{nxb}"
+        directory = os.path.join(batch_dir, name)
+        first = plan.tracks[members[0]]
+        dlat, dlon = composite_offsets(data.lat, data.lon, first.boxes[0])
+        write_composite_mean_csvs(ens, dlat, dlon, directory)
+        pd.DataFrame({"trackfile": [plan.tracks[k].path for k in members], "results_directory": [directories[k][0] for k in members],
+                      "steps": [plan.tracks[k].n for k in members], "rows": nyb, "columns": nxb,
+                      "nan_points": [int(np.isnan(composites[k][0]).sum()) for k in members]}).to_csv(os.path.join(directory, "composites.csv"), index=False)
+        app_logger.info(f"--batch-composites: {len(members)} track(s) of {nyb} x {nxb} box points (rows x columns) entered the ensemble mean of Ae, "
+                        f"Ke, Ca, Ce, Ck, Ge (lec_composite_steps, lec_composite_ensemble), written to {directory}: "
+                        + ", ".join(plan.tracks[k].path for k in members))
 
 
 def lec_moving_batch_streamed(raw: ds.RawDataset, variable_list_df: pd.DataFrame, plan, directories, app_logger, args):
