@@ -55,6 +55,11 @@ track) and their ensemble mean (``lec_composite_ensemble``).  Every track's tree
 ``-t --trackfile --composites`` run, byte for byte; the batch directory gets results_composites/<term>_dlat_dlon.csv, the mean over the
 tracks of their time-mean composites, and composites.csv -- one results_composites_<rows>x<columns>/ per box shape where shapes differ.
 
+-f [--periodic] --lon-sections: also the longitude-pressure sections of Ae, Ke, Ca, Ce, Ck, Ge (``lec_lonsections``: the maps' integrand
+summed over the box's rows with their area weights instead of over pressure), written to results_lon_sections/<term>_lon_lv.csv (the time
+mean, levels x longitudes).  -t / -c --composite-lon-sections: the same on the box-relative columns of the boxes that follow a system
+(``lec_composite_lonsections``), written to results_composite_lon_sections/<term>_dlon_lv.csv.  Not for batches, streamed or sharded runs.
+
 -t / -c --composite-sections: also the system-relative latitude-pressure sections of Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz, Ge over the boxes
 that follow the system (``lec_composite_sections``: ``lec_sections`` on box-relative rows, every step with its own box), written to
 results_composite_sections/<term>_dlat_lv.csv (the time mean, levels x box rows, labelled by the offset in degrees from the box's
@@ -168,6 +173,21 @@ def create_arg_parser():
                         "<term>_dlon.csv, the area-weighted sum over the box's rows at every time step (rows: time steps; the box's zonal "
                         "average of a row is the results CSV).  Every other output file is unchanged.  One GPU, data prepared on the host "
                         "(--ingest auto resolves to host), evenly spaced longitudes and latitudes, boxes of one shape; -f has --maps")
+    parser.add_argument("--lon-sections", dest="lon_sections", action="store_true", default=argparse.SUPPRESS,
+                        help="with -f [--periodic]: also the longitude-pressure sections of the six eddy terms Ae, Ke, Ca, Ce, Ck and Ge "
+                        "(lec_lonsections: the term's integrand at every point of the box, summed over the box's rows with their area "
+                        "weights), written to results_lon_sections/<term>_lon_lv.csv: the time mean (rows: the levels, columns: the box's "
+                        "longitudes in degrees) in the units of --sections' <term>_lat_lv.csv.  Its zonal average is the row-weighted sum "
+                        "of --sections, its vertical integral the Hovmoeller of --maps.  One GPU, data prepared on the host (--ingest auto "
+                        "resolves to host), evenly spaced longitudes, at least 3 of them; may be combined with --maps, --sections, "
+                        "--wavenumbers, --series and -r; -t / -c have --composite-lon-sections")
+    parser.add_argument("--composite-lon-sections", dest="composite_lon_sections", action="store_true", default=argparse.SUPPRESS,
+                        help="with -t --trackfile or -c (one system): also the system-relative longitude-pressure sections of the same six "
+                        "eddy terms over the boxes that follow the system (lec_composite_lonsections), written to "
+                        "results_composite_lon_sections/<term>_dlon_lv.csv: the time mean over the system's life (rows: the levels, "
+                        "columns: the box's columns, labelled by the offset in degrees from the box's midpoint).  What --composites needs: "
+                        "one GPU, data prepared on the host, evenly spaced longitudes and latitudes, boxes of one shape; may be combined "
+                        "with --composites and --composite-sections; -f has --lon-sections")
     parser.add_argument("--batch-composites", dest="batch_composites", action="store_true", default=argparse.SUPPRESS,
                         help="with -t --trackfiles or -c --choose-systems / --choose-starts (a batch of tracks): the composites of EVERY track "
                         "in the batch's one pass (lec_composite_steps) and their ensemble mean (lec_composite_ensemble).  Every track's tree "
@@ -448,6 +468,36 @@ def refuse_periodic_options(args):
         if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
             raise SystemExit("--composite-sections runs on one GPU: --gpus > 1 is not supported for the system-relative sections (their "
                              "time sums would have to merge in time order; run the totals sharded, the sections apart)")
+    if getattr(args, "lon_sections", False):
+        if not args.fixed:
+            raise SystemExit("--lon-sections goes with -f/--fixed: a longitude-pressure section lies on the columns of ONE fixed box; the "
+                             "boxes of a -t / -c run move, and have --composite-lon-sections on their box-relative columns")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--lon-sections runs on one GPU: --gpus > 1 is not supported for the longitude-pressure sections (run the "
+                             "totals sharded, the sections apart)")
+        if getattr(args, "wavenumbers_chunk", None) is not None:
+            raise SystemExit("--lon-sections prepares the data on the host: --wavenumbers-chunk streams the series and is not supported for "
+                             "the longitude-pressure sections (they read the field cubes once more)")
+        if args.ingest == "device" or args.device_ingest:
+            raise SystemExit("--lon-sections prepares the data on the host: --ingest device / --device-ingest is not supported for the "
+                             "longitude-pressure sections (--ingest auto resolves to host)")
+    if getattr(args, "composite_lon_sections", False):
+        if args.fixed:
+            raise SystemExit("--composite-lon-sections goes with -t / -c: ONE fixed box has --lon-sections, the sections on the box's own "
+                             "columns; a system-relative section is laid on the box-relative columns of the boxes that follow a system")
+        if args.trackfiles is not None:
+            raise SystemExit("--composite-lon-sections follows ONE system: --trackfiles analyses a batch of tracks and has no system-relative "
+                             "longitude-pressure sections (run -t --trackfile FILE --composite-lon-sections for the track that matters)")
+        if args.choose and (args.choose_systems is not None or args.choose_starts is not None):
+            raise SystemExit("--composite-lon-sections follows ONE system: -c --choose-systems / --choose-starts follows a batch and has no "
+                             "system-relative longitude-pressure sections (run -t --trackfile on a track it wrote, with "
+                             "--composite-lon-sections)")
+        if args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            raise SystemExit("--composite-lon-sections runs on one GPU: --gpus > 1 is not supported for the system-relative "
+                             "longitude-pressure sections (run the totals sharded, the sections apart)")
+        if args.ingest == "device" or args.device_ingest:
+            raise SystemExit("--composite-lon-sections prepares the data on the host: --ingest device / --device-ingest is not supported for "
+                             "the system-relative longitude-pressure sections (--ingest auto resolves to host)")
     n = getattr(args, "wavenumbers", None)
     chunk = getattr(args, "wavenumbers_chunk", None)
     if n is None:
@@ -595,6 +645,10 @@ def main(argv=None):
             app_logger.info("--maps: --ingest auto resolves to host (the maps read host-prepared cubes once more)")
         elif args.ingest == "auto" and getattr(args, "composites", False):
             app_logger.info("--composites: --ingest auto resolves to host (the composites read the host-prepared series once more)")
+        elif args.ingest == "auto" and getattr(args, "lon_sections", False):
+            app_logger.info("--lon-sections: --ingest auto resolves to host (the longitude-pressure sections read host-prepared cubes once more)")
+        elif args.ingest == "auto" and getattr(args, "composite_lon_sections", False):
+            app_logger.info("--composite-lon-sections: --ingest auto resolves to host (the sections read the host-prepared series once more)")
         elif args.ingest == "auto" and not args.device_ingest:
             from lorenzcycletoolkit_amd.ingest import prefers_device_ingest
             args.device_ingest, opened = prefers_device_ingest(args, "inputs/namelist", keep_open=True, app_logger=app_logger)

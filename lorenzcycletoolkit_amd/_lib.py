@@ -32,7 +32,7 @@ ORDER_AUTO, ORDER_MEMORY, ORDER_XCD_LAT, ORDER_XCD_TILED = 0, 1, 2, 7
 
 def source_digest() -> str:
     """sha256 (first 16 hex digits) over the kernel sources the library is built from (csrc/*.hip|.h|.inc + include/lec_hip.h,
-    include/lec_hip_ext.h, include/lec_hip_ext2.h, include/lec_hip_ext3.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
+    include/lec_hip_ext.h, include/lec_hip_ext2.h, include/lec_hip_ext3.h, include/lec_hip_ext4.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
     taken on the kernels it runs (the GPU box has the sources but no git history)."""
     import glob
     import hashlib
@@ -43,6 +43,7 @@ def source_digest() -> str:
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext2.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext3.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext4.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -62,6 +63,8 @@ EXT_EXPORTS = ["lec_composite"]
 EXT2_EXPORTS = ["lec_composite_sections"]
 # calls added after include/lec_hip_ext2.h was closed: declared in include/lec_hip_ext3.h
 EXT3_EXPORTS = ["lec_composite_steps", "lec_composite_ensemble"]
+# calls added after include/lec_hip_ext3.h was closed: declared in include/lec_hip_ext4.h
+EXT4_EXPORTS = ["lec_lonsections", "lec_composite_lonsections"]
 
 
 class Tuning(C.Structure):
@@ -214,6 +217,32 @@ class CompositeEnsembleArgs(C.Structure):
         ("mapsum_d", C.c_void_p), ("count_h", C.c_void_p), ("count_d", C.c_void_p),
         ("n_track", C.c_int32), ("nyb", C.c_int32), ("nxb", C.c_int32), ("reserved0", C.c_int32),
         ("mean_d", C.c_void_p), ("ens_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class LonSectionsArgs(C.Structure):
+    """struct lec_lonsections_args (include/lec_hip_ext4.h)."""
+    _fields_ = [
+        ("tair_d", C.c_void_p), ("u_d", C.c_void_p), ("v_d", C.c_void_p), ("omega_d", C.c_void_p),
+        ("dtype", C.c_int32), ("nt", C.c_int32), ("nl", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+        ("t_begin", C.c_int32), ("t_count", C.c_int32), ("iw", C.c_int32), ("ie", C.c_int32), ("js", C.c_int32), ("jn", C.c_int32),
+        ("ring", C.c_int32), ("reserved0", C.c_int32),
+        ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p), ("lattab2_d", C.c_void_p), ("levtab2_d", C.c_void_p),
+        ("lattab_d", C.c_void_p), ("levtab_d", C.c_void_p), ("tcoef_d", C.c_void_p), ("inv_hdeg", C.c_double),
+        ("coef_d", C.c_void_p), ("lonsec_d", C.c_void_p), ("lonsecsum_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class CompositeLonSectionsArgs(C.Structure):
+    """struct lec_composite_lonsections_args (include/lec_hip_ext4.h)."""
+    _fields_ = [
+        ("tair_d", C.c_void_p), ("u_d", C.c_void_p), ("v_d", C.c_void_p), ("omega_d", C.c_void_p),
+        ("dTdt_d", C.c_void_p), ("tm_d", C.c_void_p), ("tp_d", C.c_void_p),
+        ("dtype", C.c_int32), ("nt", C.c_int32), ("nl", C.c_int32), ("ny", C.c_int32), ("nx", C.c_int32),
+        ("t_begin", C.c_int32), ("t_count", C.c_int32), ("nyb", C.c_int32), ("nxb", C.c_int32), ("reserved0", C.c_int32),
+        ("box_h", C.c_void_p), ("box_d", C.c_void_p), ("boxtab_d", C.c_void_p), ("lattab_d", C.c_void_p), ("lattab2_d", C.c_void_p),
+        ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p), ("levtab_d", C.c_void_p), ("levtab2_d", C.c_void_p), ("tcoef_d", C.c_void_p),
+        ("coef_d", C.c_void_p), ("lonsec_d", C.c_void_p), ("lonsecsum_d", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -402,6 +431,10 @@ def load():
     lib.lec_composite_steps.argtypes = [C.POINTER(CompositeStepsArgs)]
     lib.lec_composite_ensemble.restype = C.c_int
     lib.lec_composite_ensemble.argtypes = [C.POINTER(CompositeEnsembleArgs)]
+    lib.lec_lonsections.restype = C.c_int
+    lib.lec_lonsections.argtypes = [C.POINTER(LonSectionsArgs)]
+    lib.lec_composite_lonsections.restype = C.c_int
+    lib.lec_composite_lonsections.argtypes = [C.POINTER(CompositeLonSectionsArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

@@ -83,6 +83,15 @@ class LECResult:
     composite_section_mean: Optional[torch.Tensor] = None    # [10, nl, nyb] fp64: the time mean of X_f(t, k, j) (NaN at any step: NaN)
     composite_section_lat: Optional[torch.Tensor] = None     # [t_count, 10, nyb] fp64: C_f(t, j), in the units of ``scalars``
     composite_section_steps: Optional[torch.Tensor] = None   # [t_count, 10, nl, nyb] fp64: X_f itself (on request)
+    # compute(..., lon_sections=True) on ONE fixed box: the longitude x pressure sections of the six eddy terms (constants.MAP_TERMS;
+    # ``lec_lonsections``), X_f(t, k, i) = sum_j cw_j Y_f(t, k, j, i) in the units of ``section_steps``.  The box's
+    # zonal average closes on sum_j cw_j ``section_steps``, s_f times the vertical trapezoid on ``map_lon``
+    lonsection_mean: Optional[torch.Tensor] = None   # [6, nl, nxb] fp64: the time mean of X_f(t, k, i) (NaN at any step: NaN)
+    lonsection_steps: Optional[torch.Tensor] = None  # [t_count, 6, nl, nxb] fp64: X_f itself (on request; a series that was one chunk)
+    # compute(..., per_step_boxes=True, composite_lon_sections=True) on per-step boxes of ONE shape: the same on the boxes' box-relative
+    # columns, cw of step t's box (``lec_composite_lonsections``).  The vertical trapezoid closes on ``composite_lon``
+    composite_lonsection_mean: Optional[torch.Tensor] = None    # [6, nl, nxb] fp64
+    composite_lonsection_steps: Optional[torch.Tensor] = None   # [t_count, 6, nl, nxb] fp64 (on request)
 
     def scalars_dict(self) -> Dict[str, np.ndarray]:
         s = self.scalars.cpu().numpy()
@@ -386,7 +395,9 @@ class LECEngine:
                 sections: bool = False, section_steps: bool = False, maps: bool = False, map_steps: bool = False,
                 composites: bool = False, composite_steps: bool = False,
                 composite_sections: bool = False, composite_section_steps: bool = False,
-                batch_composites: Optional[Sequence[int]] = None, batch_composite_steps: bool = False) -> LECResult:
+                batch_composites: Optional[Sequence[int]] = None, batch_composite_steps: bool = False,
+                lon_sections: bool = False, lon_section_steps: bool = False,
+                composite_lon_sections: bool = False, composite_lon_section_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
         (``tm`` / ``tp`` / ``tcoef``: a box-packed series; ``steps`` / ``tcoef``: the boxes of several tracks over one cube -- see
         ``rowstats``.)
@@ -439,7 +450,36 @@ class LECEngine:
         ``batch_composite_lon`` and ``batch_composite_ensemble`` -- and ``batch_composite_steps`` when asked for --, every track's
         composites and their ensemble mean (``batch_composite_stage``: the cubes are read once more).  A track's share has the bits of
         ``composites=True`` on the track's own cube.  It changes no bit of anything else; without it nothing new runs or allocates.
+        ``lon_sections`` (what ``maps`` needs: ONE fixed box with evenly spaced longitudes, one process, ``with_q`` and dT/dt from
+        ``time_s`` / ``tcoef``): also ``lonsection_mean`` -- and ``lonsection_steps`` when asked for --, the longitude x pressure sections
+        of the six eddy terms (``lonsection_stage``: the cubes are read once more; beside ``maps`` each call forms its own row factors).
+        ``composite_lon_sections`` (what ``composites`` needs): also ``composite_lonsection_mean`` -- and ``composite_lonsection_steps``
+        when asked for --, the same on the box-relative columns of per-step boxes of ONE shape (``composite_lonsection_stage``).  Neither
+        changes a bit of anything else; without them nothing new runs or allocates.
         """
+        if lon_section_steps and not lon_sections:
+            raise ValueError("lon_section_steps: the per-step sections are part of lon_sections=True")
+        if lon_sections:
+            self._check_lonsections(boxes, per_step_boxes, steps, tm, tp)
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("longitude-pressure sections run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
+            if dTdt is not None:
+                raise ValueError("longitude-pressure sections: a dTdt cube is not supported (lec_lonsections forms dT/dt from the cube's "
+                                 "time axis: give time_s or tcoef)")
+            if not with_q:
+                raise ValueError("longitude-pressure sections need with_q: the section of Ge is Q'T' at every point, and its zonal mean "
+                                 "[Q] comes from the row records")
+        if composite_lon_section_steps and not composite_lon_sections:
+            raise ValueError("composite_lon_section_steps: the per-step sections are part of composite_lon_sections=True")
+        if composite_lon_sections:
+            lon = getattr(self, "lon", None)
+            self._check_composites(boxes, per_step_boxes, steps, boxes.bt.lon_uniform if isinstance(boxes, PreparedBoxes)
+                                   else (None if lon is None else tables.is_uniform(lon)), what=self._COMPOSITE_LONSECTION_WORDS)
+            if merge_dropmask is not None or out is not None:
+                raise ValueError("composite longitude-pressure sections run in one process on one GPU: a sharded run (merge_dropmask, out) has none")
+            if not with_q:
+                raise ValueError("composite longitude-pressure sections need with_q: the section of Ge is Q'T' at every point, and its "
+                                 "zonal mean [Q] comes from the row records")
         if batch_composite_steps and batch_composites is None:
             raise ValueError("batch_composite_steps: the per-box columns are part of batch_composites=sizes")
         if batch_composites is not None:
@@ -553,6 +593,18 @@ class LECEngine:
             lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             self.batch_composite_stage(tair, u, v, omega, rows, pb, lr, bc, 0, steps=steps, tcoef=tcoef, steps_host=steps_host)
             self.batch_composite_finish(res, bc)
+        if lon_sections:
+            ls = self.lonsection_begin(int(rows.shape[0]), boxes, rows.device, keep_steps=lon_section_steps)
+            lr = sec["levraw"] if sec is not None else self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.lonsection_stage(tair, u, v, omega, rows, boxes, lr, ls, 0, time_s=time_s, tcoef=tcoef, t_begin=t_begin)
+            self.lonsection_finish(res, ls)
+        if composite_lon_sections:
+            pb = boxes if isinstance(boxes, PreparedBoxes) else PreparedBoxes(*self._resolve_boxes(boxes))
+            cl = self.composite_lonsection_begin(int(rows.shape[0]), pb, rows.device, keep_steps=composite_lon_section_steps)
+            lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
+            self.composite_lonsection_stage(tair, u, v, omega, rows, pb, lr, cl, 0, time_s=time_s, dTdt=dTdt, tm=tm, tp=tp, tcoef=tcoef,
+                                            t_begin=t_begin)
+            self.composite_lonsection_finish(res, cl)
         if wavenumbers is not None:
             self._spectrum(res, rows, tair, u, v, omega, boxes, int(wavenumbers), t_begin, phi_scale, drop_any_time,
                            generation=dict(time_s=time_s, tcoef=tcoef) if spectrum_generation else None, fused=spectrum_fused,
@@ -833,26 +885,33 @@ class LECEngine:
             res.map_steps = state["steps"]
 
     # -- system-relative composites of the eddy terms over per-step boxes of one shape (lec_composite) -----------------------------------
+    # (the output that asks, one of it, the fixed box's flag): the words of _check_composites' refusals
+    _COMPOSITE_WORDS = ("composites", "a composite", "maps=True")
+    _COMPOSITE_LONSECTION_WORDS = ("composite longitude-pressure sections", "a section", "lon_sections=True")
+
     @staticmethod
-    def _check_composites(boxes, per_step_boxes, steps=None, lon_uniform: Optional[bool] = None) -> tuple:
-        """The refusals of the composites that need nothing but the boxes: returns (nyb, nxb), the one shape of every box."""
+    def _check_composites(boxes, per_step_boxes, steps=None, lon_uniform: Optional[bool] = None,
+                          what: tuple = _COMPOSITE_WORDS) -> tuple:
+        """The refusals of the composites that need nothing but the boxes: returns (nyb, nxb), the one shape of every box.  ``what``: the
+        words of the output that asks (the composites', or those of the composite longitude-pressure sections, which need the same)."""
+        noun, one, fixed = what
         bx = boxes.boxes if isinstance(boxes, PreparedBoxes) else boxes
         if steps is not None:
-            raise ValueError("composites: a step table (steps=, the batch of lec_rowstats_steps) has none: composites exist for ONE track")
+            raise ValueError(f"{noun}: a step table (steps=, the batch of lec_rowstats_steps) has none: {noun} exist for ONE track")
         if per_step_boxes is False or (per_step_boxes is None and len(bx) == 1):
-            raise ValueError("composites exist for per-step boxes (per_step_boxes=True): a composite is laid on the box-relative points "
-                             "of a series of moving boxes; ONE fixed box has maps=True")
+            raise ValueError(f"{noun} exist for per-step boxes (per_step_boxes=True): {one} is laid on the box-relative points "
+                             f"of a series of moving boxes; ONE fixed box has {fixed}")
         bx = [tuple(int(x) for x in b) for b in bx]
         nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
         for t, b in enumerate(bx):
             h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
             if (h, w) != (nyb, nxb):
-                raise ValueError(f"composites need boxes of ONE shape: the box of step {t} has {h} x {w} points (rows x columns), that of "
+                raise ValueError(f"{noun} need boxes of ONE shape: the box of step {t} has {h} x {w} points (rows x columns), that of "
                                  f"step 0 has {nyb} x {nxb}")
         if nxb < 3:
-            raise ValueError("composites need at least 3 box columns")
+            raise ValueError(f"{noun} need at least 3 box columns")
         if lon_uniform is False:
-            raise ValueError("composites need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+            raise ValueError(f"{noun} need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
         return nyb, nxb
 
     def composite_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
@@ -862,6 +921,47 @@ class LECEngine:
         if boxes.bt.nyb_max != nyb:
             raise ValueError("composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
         return self._mapcol_begin(t_total, nyb, nxb, device, keep_steps)
+
+    def _composite_chunk(self, who: str, begin: str, what: tuple, tair, u, v, omega, rows, boxes, state: dict, t_offset: int, t_begin: int,
+                         time_s, dTdt, tm, tp, tcoef) -> tuple:
+        """What ``composite_stage`` and ``composite_lonsection_stage`` check and prepare alike: the layout and its source of dT/dt, the
+        boxes' one shape against ``state``, the chunk against the cubes.  Returns (nyb, nxb, dTdt as fp64, tcoef, the boxes as the cubes
+        hold them on the host and on the device, the boxes' device tables)."""
+        if not isinstance(boxes, PreparedBoxes):
+            raise ValueError(f"{who}: boxes from prepare_boxes")
+        packed = "box_data" in boxes.dev
+        if (tm is None) != (tp is None):
+            raise ValueError(f"{who}: tm and tp come together")
+        if dTdt is not None and tm is not None:
+            raise ValueError(f"{who}: a dTdt cube or tm / tp, not both")
+        if packed and dTdt is None and tm is None:
+            raise ValueError(f"{who}: a box-packed series needs its dTdt cube or tm / tp (its time neighbours are other boxes)")
+        self._check_fields([tair, u, v, omega] + [c for c in (tm, tp) if c is not None], boxes if packed else None)
+        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        if len(bx) != t_count:
+            raise ValueError(f"{who}: one box per step of the chunk")
+        nyb, nxb = self._check_composites(bx, True, None, bt.lon_uniform, what=what)
+        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
+                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
+            raise ValueError(f"{who}: the chunk does not fit the series and box shape {begin} was given")
+        if not (0 <= t_begin and t_begin + t_count <= nt):
+            raise ValueError(f"{who}: [t_begin, t_begin + t_count) lies outside the cubes")
+        if rows.device != tair.device:
+            raise ValueError(f"{who}: rows and fields on one device")
+        if dTdt is not None:
+            if dTdt.shape != tair.shape or dTdt.device != tair.device or dTdt.dtype not in (torch.float64, torch.float32):
+                raise ValueError("dTdt must be a cube of the fields' shape on their device")
+            dTdt = dTdt.to(torch.float64).contiguous()
+            tcoef = None
+        elif tm is not None:
+            if tcoef is None or tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
+                raise ValueError("tm / tp need tcoef: a contiguous fp64 [nt, 3] tensor on the fields' device (the rows of the cubes' steps)")
+        else:
+            tcoef = self._cube_tcoef(who, time_s, tcoef, nt, tair.device)
+        box_host = np.ascontiguousarray([(0, b[1] - b[0], 0, b[3] - b[2]) for b in bx] if packed else bx, dtype=np.int32)
+        box_dev = dev["box_data" if packed else "box"]
+        return nyb, nxb, dTdt, tcoef, box_host, box_dev, dev
 
     def composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
                         boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
@@ -874,40 +974,9 @@ class LECEngine:
         fields' fp32 is widened to fp64, the value stage 1 reads), or ``tm`` / ``tp`` with ``tcoef``, or -- an unpacked cube only -- the
         cube's own time axis ``time_s`` / ``tcoef``.  A chunk whose column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into
         sub-calls.  Chunks must come in time order; every number is independent of how the series is cut, bit for bit."""
-        if not isinstance(boxes, PreparedBoxes):
-            raise ValueError("composite_stage: boxes from prepare_boxes")
-        packed = "box_data" in boxes.dev
-        if (tm is None) != (tp is None):
-            raise ValueError("composite_stage: tm and tp come together")
-        if dTdt is not None and tm is not None:
-            raise ValueError("composite_stage: a dTdt cube or tm / tp, not both")
-        if packed and dTdt is None and tm is None:
-            raise ValueError("composite_stage: a box-packed series needs its dTdt cube or tm / tp (its time neighbours are other boxes)")
-        self._check_fields([tair, u, v, omega] + [c for c in (tm, tp) if c is not None], boxes if packed else None)
-        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
-        bx, bt, dev = self._stage2_input(rows, boxes)
-        if len(bx) != t_count:
-            raise ValueError("composite_stage: one box per step of the chunk")
-        nyb, nxb = self._check_composites(bx, True, None, bt.lon_uniform)
-        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
-                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
-            raise ValueError("composite_stage: the chunk does not fit the series and box shape composite_begin was given")
-        if not (0 <= t_begin and t_begin + t_count <= nt):
-            raise ValueError("composite_stage: [t_begin, t_begin + t_count) lies outside the cubes")
-        if rows.device != tair.device:
-            raise ValueError("composite_stage: rows and fields on one device")
-        if dTdt is not None:
-            if dTdt.shape != tair.shape or dTdt.device != tair.device or dTdt.dtype not in (torch.float64, torch.float32):
-                raise ValueError("dTdt must be a cube of the fields' shape on their device")
-            dTdt = dTdt.to(torch.float64).contiguous()
-            tcoef = None
-        elif tm is not None:
-            if tcoef is None or tcoef.shape != (nt, 3) or tcoef.dtype != torch.float64 or tcoef.device != tair.device or not tcoef.is_contiguous():
-                raise ValueError("tm / tp need tcoef: a contiguous fp64 [nt, 3] tensor on the fields' device (the rows of the cubes' steps)")
-        else:
-            tcoef = self._cube_tcoef("composite_stage", time_s, tcoef, nt, tair.device)
-        box_host = np.ascontiguousarray([(0, b[1] - b[0], 0, b[3] - b[2]) for b in bx] if packed else bx, dtype=np.int32)
-        box_dev = dev["box_data" if packed else "box"]
+        nyb, nxb, dTdt, tcoef, box_host, box_dev, dev = self._composite_chunk(
+            "composite_stage", "composite_begin", self._COMPOSITE_WORDS, tair, u, v, omega, rows, boxes, state, t_offset, t_begin, time_s,
+            dTdt, tm, tp, tcoef)
 
         def issue(a, b, shared):
             ca = _lib.CompositeArgs(
@@ -923,6 +992,139 @@ class LECEngine:
         res.composite_lon = state["hov"]
         if state["steps"] is not None:
             res.composite_steps = state["steps"]
+
+    # -- longitude x pressure sections of the eddy terms: one fixed box (lec_lonsections), per-step boxes (lec_composite_lonsections) -----
+    @staticmethod
+    def _check_lonsections(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
+        n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
+        if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
+            raise ValueError("longitude-pressure sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a "
+                             "packed layout) has no common columns to lay a section on; it has composite_lon_sections=True")
+
+    def _lonsec_begin(self, t_total: int, nyb: int, nxb: int, device, keep_steps: bool) -> dict:
+        """The accumulators of the longitude x pressure sections of ``t_total`` steps on ``nl`` levels x ``nxb`` columns, zeroed."""
+        f64 = dict(dtype=torch.float64, device=device)
+        nl = int(self.level.size)
+        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, lonsecsum=torch.zeros((_lib.LEC_NMAP, nl, nxb), **f64),
+                    steps=torch.empty((t_total, _lib.LEC_NMAP, nl, nxb), **f64) if keep_steps else None, work=None, coef=None)
+
+    def _lonsec_sub(self, nl: int, nyb: int, nxb: int, t_count: int) -> int:
+        """Steps per sub-call of a chunk of ``t_count`` steps: as many as keep the sections and row factors within ``MAP_CHUNK_BYTES``."""
+        per_step = 8 * (_lib.LEC_NMAP * nl * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+        return max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
+
+    def _lonsec_stage(self, cubes, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, t_begin: int, issue) -> None:
+        """``_mapcol_stage`` for the two longitude x pressure calls: ``levraw``'s check, the cut of the chunk into sub-calls whose sections
+        and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and the sub-calls in time order:
+        ``issue(a, b, shared)`` calls on the chunk's steps [a, b), ``shared`` the fields both args structs have."""
+        tair, u, v, omega = cubes
+        nt, nl, ny, nx = (int(x) for x in tair.shape)
+        t_count, nyb, nxb = int(rows.shape[0]), state["nyb"], state["nxb"]
+        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
+                or not levraw.is_contiguous()):
+            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        if state["lonsecsum"].shape[1] != nl:
+            raise ValueError("the cubes' levels are not the engine's")
+        f64 = dict(dtype=torch.float64, device=rows.device)
+        sub = self._lonsec_sub(nl, nyb, nxb, t_count)
+        if state["coef"] is None or state["coef"].shape[0] < sub:
+            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
+        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
+            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nl, nxb), **f64)
+        for a in range(0, t_count, sub):
+            b = min(t_count, a + sub)
+            sec = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+            shared = dict(
+                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
+                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
+                t_begin=t_begin + a, t_count=b - a, reserved0=0, rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
+                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), coef_d=_ptr(state["coef"]), lonsec_d=_ptr(sec),
+                lonsecsum_d=_ptr(state["lonsecsum"]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+            with torch.cuda.device(rows.device):
+                issue(a, b, shared)
+
+    def lonsection_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the longitude x pressure sections of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once,
+        here): ``lonsection_stage`` adds every chunk to them, ``lonsection_finish`` turns them into the result's fields."""
+        self._check_lonsections(boxes, False)
+        bx, bt, _ = self._resolve_boxes(boxes)
+        iw, ie, js, jn = bx[0]
+        nyb, nxb = jn - js + 1, ie - iw + 1
+        if bt.nyb_max != nyb:
+            raise ValueError("longitude-pressure sections: the box's records must have the box's own row count (prepare_boxes without nyb_min)")
+        if not bt.lon_uniform:
+            raise ValueError("longitude-pressure sections need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+        if nxb < 3:
+            raise ValueError("longitude-pressure sections need at least 3 box columns")
+        return self._lonsec_begin(t_total, nyb, nxb, device, keep_steps)
+
+    def lonsection_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
+                         levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
+                         t_begin: int = 0) -> None:
+        """``lec_lonsections`` on a chunk, with ``map_stage``'s arguments: the time sums are added to ``state["lonsecsum"]`` and, when
+        kept, the steps written to ``state["steps"][t_offset: t_offset + t_count]``.  A chunk whose sections and row factors exceed
+        ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is independent of how the series is cut,
+        bit for bit."""
+        self._check_fields([tair, u, v, omega], None)
+        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        self._check_lonsections(bx, False)
+        iw, ie, js, jn = bx[0]
+        nyb, nxb = jn - js + 1, ie - iw + 1
+        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
+                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
+            raise ValueError("lonsection_stage: the chunk does not fit the series and box lonsection_begin was given")
+        if not (0 <= t_begin and t_begin + t_count <= nt):
+            raise ValueError("lonsection_stage: [t_begin, t_begin + t_count) lies outside the cubes")
+        if rows.device != tair.device:
+            raise ValueError("lonsection_stage: rows and fields on one device")
+        tcoef = self._cube_tcoef("lonsection_stage", time_s, tcoef, nt, tair.device)
+
+        def issue(a, b, shared):
+            la = _lib.LonSectionsArgs(iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, lattab2_d=_ptr(dev["lattab2"]),
+                                      lattab_d=_ptr(dev["lattab"]), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]), **shared)
+            _lib.check(self.lib.lec_lonsections(C.byref(la)), "lec_lonsections")
+        self._lonsec_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+
+    def lonsection_finish(self, res: LECResult, state: dict) -> None:
+        """``res.lonsection_*`` from the accumulators of a finished series."""
+        res.lonsection_mean = state["lonsecsum"] / float(state["t_total"])
+        if state["steps"] is not None:
+            res.lonsection_steps = state["steps"]
+
+    def composite_lonsection_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the composite longitude x pressure sections of a series of ``t_total`` steps whose boxes all have the shape
+        of ``boxes``' (zeroed once, here)."""
+        nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform, what=self._COMPOSITE_LONSECTION_WORDS)
+        if boxes.bt.nyb_max != nyb:
+            raise ValueError("composite longitude-pressure sections: the boxes' records must have the boxes' own row count (prepare_boxes "
+                             "without nyb_min)")
+        return self._lonsec_begin(t_total, nyb, nxb, device, keep_steps)
+
+    def composite_lonsection_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
+                                   boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
+                                   dTdt: Optional[torch.Tensor] = None, tm: Optional[torch.Tensor] = None,
+                                   tp: Optional[torch.Tensor] = None, tcoef: Optional[torch.Tensor] = None, t_begin: int = 0) -> None:
+        """``lec_composite_lonsections`` on a chunk, with ``composite_stage``'s arguments (layouts and the three sources of dT/dt): the
+        time sums are added to ``state["lonsecsum"]`` and, when kept, the steps written to ``state["steps"]``.  Chunks must come in time
+        order; every number is independent of how the series is cut, bit for bit."""
+        nyb, nxb, dTdt, tcoef, box_host, box_dev, dev = self._composite_chunk(
+            "composite_lonsection_stage", "composite_lonsection_begin", self._COMPOSITE_LONSECTION_WORDS, tair, u, v, omega, rows, boxes,
+            state, t_offset, t_begin, time_s, dTdt, tm, tp, tcoef)
+
+        def issue(a, b, shared):
+            ca = _lib.CompositeLonSectionsArgs(
+                dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp), nyb=nyb, nxb=nxb, tcoef_d=_ptr(tcoef),
+                box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
+                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), **shared)
+            _lib.check(self.lib.lec_composite_lonsections(C.byref(ca)), "lec_composite_lonsections")
+        self._lonsec_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+
+    def composite_lonsection_finish(self, res: LECResult, state: dict) -> None:
+        """``res.composite_lonsection_*`` from the accumulators of a finished series."""
+        res.composite_lonsection_mean = state["lonsecsum"] / float(state["t_total"])
+        if state["steps"] is not None:
+            res.composite_lonsection_steps = state["steps"]
 
     # -- composites of a batch of tracks over one cube and their ensemble (lec_composite_steps, lec_composite_ensemble) ------------------
     @staticmethod

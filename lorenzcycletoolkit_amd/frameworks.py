@@ -72,7 +72,8 @@ class BoxData:
                  results_subdirectory_vertical_levels: str = ".", dTdt: Optional[np.ndarray] = None,
                  boxes_limits=None, periodic: bool = False, wavenumbers: Optional[int] = None,
                  spectrum_generation: bool = False, spectrum_interactions: bool = False, spectrum_budget: bool = False,
-                 sections: bool = False, maps: bool = False, composites: bool = False, composite_sections: bool = False):
+                 sections: bool = False, maps: bool = False, composites: bool = False, composite_sections: bool = False,
+                 lon_sections: bool = False, composite_lon_sections: bool = False):
         if args is not None and not getattr(args, "residuals", True):
             # the reference looks up "Friction Velocity" here and fails (box_data.py:190-195; SURVEY B-8)
             raise KeyError("Friction Velocity")
@@ -103,6 +104,35 @@ class BoxData:
                 raise ValueError("maps: a dTdt cube is not supported (lec_maps forms dT/dt from the time axis)")
             if isinstance(data, _StreamedData):
                 raise ValueError("maps prepare the data on the host: the streamed path (--ingest device / --device-ingest) is not supported")
+        self.lon_sections = bool(lon_sections)
+        self.lonsection_mean = None
+        if self.lon_sections:           # (host work only, as above)
+            from .ingest import StreamedDataset as _StreamedData
+            if boxes_limits is not None:
+                raise ValueError("longitude-pressure sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes) "
+                                 "has no common columns to lay a section on; it has composite_lon_sections")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("longitude-pressure sections run on one GPU (no time shards)")
+            if dTdt is not None:
+                raise ValueError("longitude-pressure sections: a dTdt cube is not supported (lec_lonsections forms dT/dt from the time axis)")
+            if isinstance(data, _StreamedData):
+                raise ValueError("longitude-pressure sections prepare the data on the host: the streamed path (--ingest device / "
+                                 "--device-ingest) is not supported")
+        self.composite_lon_sections = bool(composite_lon_sections)
+        self.composite_lonsection_mean = None
+        if self.composite_lon_sections:     # (host work only, as above)
+            from .ingest import StreamedDataset as _StreamedData
+            if boxes_limits is None:
+                raise ValueError("composite longitude-pressure sections exist for the per-step boxes of a track (boxes_limits): ONE fixed "
+                                 "box has lon_sections")
+            if getattr(args, "shard", None) is not None:
+                raise ValueError("composite longitude-pressure sections run on one GPU (no time shards)")
+            if isinstance(data, _StreamedData):
+                raise ValueError("composite longitude-pressure sections prepare the data on the host: the streamed path (--ingest device / "
+                                 "--device-ingest) is not supported")
+            from .tables import box_indices
+            composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, *lim) for lim in boxes_limits],
+                             flag="composite longitude-pressure sections", lat_too=False)
         self.composites = bool(composites)
         self.composite_mean = self.composite_lon = None
         if self.composites:             # (host work only, as above)
@@ -263,6 +293,13 @@ class BoxData:
             self.composite_section_mean = self.result.composite_section_mean.cpu().numpy()
             self.composite_section_lat = self.result.composite_section_lat.cpu().numpy()
             self.composite_section_dlat = composite_offsets(data.lat, data.lon, self.boxes[0])[0]
+        if self.result.lonsection_mean is not None:
+            self.lonsection_mean = self.result.lonsection_mean.cpu().numpy()
+            iw, ie = self.boxes[0][0], self.boxes[0][1]
+            self.lonsection_longitudes = np.asarray(data.lon[iw: ie + 1], dtype=np.float64)
+        if self.result.composite_lonsection_mean is not None:
+            self.composite_lonsection_mean = self.result.composite_lonsection_mean.cpu().numpy()
+            self.composite_lonsection_dlon = composite_offsets(data.lat, data.lon, self.boxes[0])[1]
 
     def row_labels(self, method: str):
         """The time-stamp column of the per-level tables (formatted once per series, not once per table)."""
@@ -308,7 +345,9 @@ class BoxData:
                                    **({"spectrum_budget": True} if self.spectrum_budget else {}),
                                    **({"sections": True} if self.sections else {}), **({"maps": True} if self.maps else {}),
                                    **({"composites": True} if self.composites else {}),
-                                   **({"composite_sections": True} if self.composite_sections else {}))
+                                   **({"composite_sections": True} if self.composite_sections else {}),
+                                   **({"lon_sections": True} if self.lon_sections else {}),
+                                   **({"composite_lon_sections": True} if self.composite_lon_sections else {}))
 
     def _compute_resident_packed(self, arrays, common, data, dev, phi_scale, merge, out) -> LECResult:
         """The moving framework on host-prepared data: the reference slices every step's box out of the crop (box_data.py:297-310);
@@ -332,7 +371,8 @@ class BoxData:
         return self.engine.compute(f[0], f[1], f[2], f[3], f[4], pb, phi_scale=phi_scale, t_begin=0, t_count=t1 - t0, per_step_boxes=True,
                                    drop_any_time=False, merge_dropmask=merge, out=out, **kw,
                                    **({"composites": True} if self.composites else {}),
-                                   **({"composite_sections": True} if self.composite_sections else {}))
+                                   **({"composite_sections": True} if self.composite_sections else {}),
+                                   **({"composite_lon_sections": True} if self.composite_lon_sections else {}))
 
 
 def ring_box_check(lon, box) -> float:
@@ -587,6 +627,35 @@ def write_composite_section_csvs(box_obj: "BoxData", directory: str, time_name: 
             pd.DataFrame(box_obj.composite_section_lat[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
 
 
+def _write_lon_lv_csvs(mean, columns, level_names, directory: str, suffix: str, vert_name: str) -> None:
+    """``<term><suffix>`` for each of the six eddy terms in ``directory``: ``mean`` [6, levels, columns], one row per level labelled as
+    ``write_section_csvs`` labels them, one column per entry of ``columns`` (degrees).  The number format of the ``--sections`` files."""
+    from .constants import MAP_TERMS
+    os.makedirs(directory, exist_ok=True)
+    head = (",".join([str(vert_name)] + [repr(float(x)) for x in columns]) + "\n").encode("utf-8")
+    for i, term in enumerate(MAP_TERMS):
+        with open(os.path.join(directory, f"{term}{suffix}"), "wb") as f:
+            f.write(head)
+            for name, row in zip(level_names, np.asarray(mean[i], dtype=np.float64)):      # (labels of mixed widths: one call per row)
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+
+
+def write_lon_section_csvs(box_obj: "BoxData", directory: str, vert_name: str) -> None:
+    """results_lon_sections/: for each of the six eddy terms ``<term>_lon_lv.csv`` -- the time mean of the term's longitude-pressure
+    section, one row per level (labelled as ``write_section_csvs`` labels them), one column per longitude of the box in degrees, in the
+    units of ``<term>_lat_lv.csv``.  ``write_section_csvs``' number formatting."""
+    _write_lon_lv_csvs(box_obj.lonsection_mean, box_obj.lonsection_longitudes, [repr(float(p)) for p in box_obj.PressureData], directory,
+                       "_lon_lv.csv", vert_name)
+
+
+def write_composite_lon_section_csvs(box_obj: "BoxData", directory: str, vert_name: str) -> None:
+    """results_composite_lon_sections/: for each of the six eddy terms ``<term>_dlon_lv.csv`` -- the time mean over the system's life of
+    the term's system-relative longitude-pressure section, one row per level, one column per box column labelled by its offset in degrees
+    from the box's midpoint (``composite_offsets``, first step's box)."""
+    _write_lon_lv_csvs(box_obj.composite_lonsection_mean, box_obj.composite_lonsection_dlon, [repr(float(p)) for p in box_obj.PressureData],
+                       directory, "_dlon_lv.csv", vert_name)
+
+
 def ring_hint(lon, box):
     """The line a plain -f run logs when its box spans the whole longitude axis of a ring (None otherwise): the run treats the circle
     as a limited area, --periodic closes it."""
@@ -805,6 +874,20 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
             raise ValueError("--maps needs a box of at least 3 longitudes")
         if not periodic and not is_uniform(np.asarray(data.lon, dtype=np.float64)):
             raise ValueError("--maps needs evenly spaced longitudes")
+    lon_sections = bool(getattr(args, "lon_sections", False))
+    if lon_sections:    # likewise refused before a file is written
+        from .ingest import StreamedDataset
+        from .tables import box_indices, is_uniform
+        if shard is not None:
+            raise ValueError("--lon-sections runs on one GPU")
+        if isinstance(data, StreamedDataset):
+            raise ValueError("--lon-sections prepares the data on the host: --ingest device / --device-ingest is not supported for the "
+                             "longitude-pressure sections")
+        iw, ie, _, _ = box_indices(data.lat, data.lon, min_lon, max_lon, min_lat, max_lat)
+        if ie - iw + 1 < 3:
+            raise ValueError("--lon-sections needs a box of at least 3 longitudes")
+        if not periodic and not is_uniform(np.asarray(data.lon, dtype=np.float64)):
+            raise ValueError("--lon-sections needs evenly spaced longitudes")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     try:
@@ -812,7 +895,7 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
                           results_subdirectory_vertical_levels, periodic=periodic, wavenumbers=wavenumbers,
                           spectrum_generation=generation, **({"spectrum_interactions": True} if interactions else {}),
                           **({"spectrum_budget": True} if budget else {}), **({"sections": True} if sections else {}),
-                          **({"maps": True} if maps else {}))
+                          **({"maps": True} if maps else {}), **({"lon_sections": True} if lon_sections else {}))
     except Exception:
         app_logger.exception("An exception occurred while creating BoxData object")
         raise
@@ -856,6 +939,11 @@ def lec_fixed(data: ds.LECDataset, variable_list_df: pd.DataFrame, results_subdi
         write_map_csvs(box_obj, map_directory, time_name, variable_list_df.loc["Latitude"]["Variable"])
         app_logger.info(f"--maps: the longitude-resolved maps of Ae, Ke, Ca, Ce, Ck, Ge on the box's {len(box_obj.map_latitudes)} x "
                         f"{len(box_obj.map_longitudes)} points (lec_maps); written to {map_directory}")
+    if lon_sections:
+        lonsec_directory = os.path.join(results_subdirectory, "results_lon_sections")
+        write_lon_section_csvs(box_obj, lonsec_directory, vert_name)
+        app_logger.info(f"--lon-sections: the longitude-pressure sections of Ae, Ke, Ca, Ce, Ck, Ge on the box's {len(data.level)} levels x "
+                        f"{len(box_obj.lonsection_longitudes)} longitudes (lec_lonsections); written to {lonsec_directory}")
     df = pd.DataFrame(index=pd.DatetimeIndex(data.time))
     for col in FIXED_COLUMNS:                       # BΦZ / BΦE are computed, then dropped (:252-253,:287-290)
         df[col] = terms[col]
@@ -920,6 +1008,19 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
         track0 = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)
         lims = [get_limits(track0, t) for t in pd.DatetimeIndex(data.time)]
         composite_sections_check(data.lat, [box_indices(data.lat, data.lon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in lims])
+    composite_lon_sections = bool(getattr(args, "composite_lon_sections", False))
+    if composite_lon_sections:      # refused before a file is written
+        from .ingest import StreamedDataset
+        from .tables import box_indices
+        if shard is not None:
+            raise ValueError("--composite-lon-sections runs on one GPU")
+        if isinstance(data, StreamedDataset):
+            raise ValueError("--composite-lon-sections prepares the data on the host: --ingest device / --device-ingest is not supported "
+                             "for the composite longitude-pressure sections")
+        track0 = ds.track_on_axis(ds.read_track(trackfile, app_logger), data.lon)
+        lims = [get_limits(track0, t) for t in pd.DatetimeIndex(data.time)]
+        composites_check(data.lat, data.lon, [box_indices(data.lat, data.lon, l["min_lon"], l["max_lon"], l["min_lat"], l["max_lat"]) for l in lims],
+                         flag="--composite-lon-sections")
     if root:
         _create_level_csvs(results_subdirectory_vertical_levels, time_name, vert_name, data.level)
     times = pd.DatetimeIndex(data.time)
@@ -940,8 +1041,15 @@ def lec_moving(data: ds.LECDataset, variable_list_df: pd.DataFrame, dTdt, result
     box_obj = BoxData(data, variable_list_df, args=args, results_subdirectory=results_subdirectory,
                       results_subdirectory_vertical_levels=results_subdirectory_vertical_levels, dTdt=dTdt,
                       boxes_limits=boxes, **({"composites": True} if composites else {}),
-                      **({"composite_sections": True} if composite_sections else {}))
+                      **({"composite_sections": True} if composite_sections else {}),
+                      **({"composite_lon_sections": True} if composite_lon_sections else {}))
     phases.mark("ingest_compute_gather")
+    if composite_lon_sections:
+        clon_directory = os.path.join(results_subdirectory, "results_composite_lon_sections")
+        write_composite_lon_section_csvs(box_obj, clon_directory, vert_name)
+        app_logger.info(f"--composite-lon-sections: the system-relative longitude-pressure sections of Ae, Ke, Ca, Ce, Ck, Ge on the boxes' "
+                        f"{len(data.level)} levels x {len(box_obj.composite_lonsection_dlon)} box-relative columns "
+                        f"(lec_composite_lonsections); written to {clon_directory}")
     if composite_sections:
         csec_directory = os.path.join(results_subdirectory, "results_composite_sections")
         write_composite_section_csvs(box_obj, csec_directory, time_name, vert_name)
