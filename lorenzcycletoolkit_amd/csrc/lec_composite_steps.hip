@@ -76,15 +76,6 @@ __global__ void __launch_bounds__(256) lec_composite_ensemble_kernel(const EnsPa
     p.ens[id] = s / (double)p.n_track;
 }
 
-// what mapcol_launch reads by name, for a call whose steps are its boxes
-struct LaunchView {
-    const void *tair_d, *u_d, *v_d, *omega_d;
-    const double *rows_d, *lattab2_d, *levtab_d, *levtab2_d, *levraw_d, *tcoef_d;
-    double *coef_d, *col_d, *mapsum_d, *hov_d;
-    int nt, nl, ny, nx, t_begin, t_count;
-    void* stream;
-};
-
 }  // namespace
 
 extern "C" int lec_composite_steps(const lec_composite_steps_args* a) {
@@ -150,37 +141,23 @@ extern "C" int lec_composite_steps(const lec_composite_steps_args* a) {
         snprintf(m, sizeof(m), "seg_h[n_seg] = %d must be s_count = %d", a->seg_h[a->n_seg], a->s_count);
         return chk.refuse(LEC_ERR_ARG, m);
     }
-    for (int s = 0; s < a->s_count; ++s) {
-        const int32_t* b = a->box_h + 4 * (size_t)s;
-        const long long w = (long long)b[1] - b[0] + 1, h = (long long)b[3] - b[2] + 1;
-        if (w != a->nxb || h != a->nyb) {
-            snprintf(m, sizeof(m), "box_h: box %d is %lld x %lld (rows x columns), the call's nyb x nxb is %d x %d: every box of a "
-                     "composite has one shape", s, h, w, a->nyb, a->nxb);
-            return chk.refuse(LEC_ERR_ARG, m);
-        }
-        if (b[0] < 0 || b[1] >= a->nx || b[2] < 0 || b[3] >= a->ny) {
-            snprintf(m, sizeof(m), "box_h: box %d {iw, ie, js, jn} = {%d, %d, %d, %d} lies outside the %d x %d cube", s, b[0], b[1], b[2], b[3],
-                     a->ny, a->nx);
-            return chk.refuse(LEC_ERR_ARG, m);
-        }
-    }
+    if (int r = chk.boxes(a, a->s_count, "box")) return r;
     if (int r = chk.align16(a->rows_d, a->lattab2_d, a->coef_d)) return r;
     const void* tabs[] = {a->levraw_d, a->levtab2_d, a->lattab_d, a->levtab_d, a->tcoef_d, a->boxtab_d, a->col_d, a->hov_d, a->mapsum_d};
     const char* tabn[] = {"levraw_d", "levtab2_d", "lattab_d", "levtab_d", "tcoef_d", "boxtab_d", "col_d", "hov_d", "mapsum_d"};
     const void* cubes[] = {a->tair_d, a->u_d, a->v_d, a->omega_d};
     const int nyb = a->nyb, nxb = a->nxb, n_seg = a->n_seg;
-    if (int r = chk.tables_cubes_limits(tabs, tabn, 9, cubes, 4, "tair_d, u_d, v_d, omega_d", a->dtype, a->s_count, a->nl, nyb, nxb, "nyb, nxb"))
+    if (int r = chk.tables_cubes_limits({tabs, tabn, 9, cubes, 4, "tair_d, u_d, v_d, omega_d", a->dtype}, a->s_count, a->nl, nyb, nxb, "nyb, nxb"))
         return r;
     if ((long long)n_seg * kNMap * nyb * nxb >= (1LL << 32) - 256)
         return chk.refuse(LEC_ERR_UNSUPPORTED, "n_seg * 6 * nyb * nxb must stay below 2^32 threads in one call");
 
-    const LaunchView v{a->tair_d, a->u_d, a->v_d, a->omega_d, a->rows_d, a->lattab2_d, a->levtab_d, a->levtab2_d, a->levraw_d, a->tcoef_d,
-                       a->coef_d, a->col_d, a->mapsum_d, a->hov_d, a->nt, a->nl, a->ny, a->nx, 0, a->s_count, a->stream};
     ColParams p;
     p.step = a->step_d; p.box = a->box_d; p.boxtab = a->boxtab_d; p.lattab = a->lattab_d;
     const int32_t* seg_d = a->seg_d;
     const int dtype = a->dtype;
-    return mapcol_launch(&v, p, nyb, nxb, nyb * 8,
+    const MapcolRun run{a->col_d, a->mapsum_d, a->hov_d, nyb, 0, a->s_count};      // the call's steps are its boxes
+    return mapcol_launch(a, p, run, nyb, nxb, nyb * 8,
                          [dtype](const ColParams& q, dim3 grid, hipStream_t st) { mapcol_col<false, 3>(q, dtype, grid, st); },
                          [seg_d, n_seg, nyb, nxb](const MapFoldParams& f, hipStream_t st) {
                              const SegSumParams sp{f, seg_d, n_seg};

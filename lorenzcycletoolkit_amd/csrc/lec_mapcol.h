@@ -1,8 +1,10 @@
-// lec_mapcol.h -- what lec_maps (lec_maps.hip), lec_composite (lec_composite.hip) and lec_composite_steps (lec_composite_steps.hip) share:
-// the column integrals C_f(t, j, i) of the six eddy terms Ae Ke Ca Ce Ck Ge at the points of a box, their time sums and their Hovmoeller
-// rows (DESIGN.md sections 4.2d, 4.2e, 4.2g).  The record layout, the Q expression, the integrands, the trapezoid rule and the refusals the
-// calls have in common are written once, here.  The kernels have internal linkage and the column kernel is a template over the including
-// file's launch struct, so each of the files instantiates kernels of its own and remains a code object of its own.
+// lec_mapcol.h -- what lec_maps (lec_maps.hip), lec_composite (lec_composite.hip), lec_composite_steps (lec_composite_steps.hip) and the two
+// calls of lec_lonsections.hip share: the column integrals C_f(t, j, i) of the six eddy terms Ae Ke Ca Ce Ck Ge at the points of a box, their
+// time sums and their Hovmoeller rows (DESIGN.md sections 4.2d, 4.2e, 4.2g, 4.2h).  The record layout, the trapezoid rule, the launches of a
+// call (mapcol_launch) and the refusals the calls have in common (MapcolRefusals) are written once, here; the Q expression and the
+// integrands of a point once in lec_mapcol_point.inc, which the column kernel here and lec_lonsections.hip's row-march kernel include.  The
+// kernels have internal linkage and the column kernel is a template over the including file's launch struct, so each of the files
+// instantiates kernels of its own and remains a code object of its own.
 //   lec_mapcol_coef_kernel  one wave per (time step, level), lanes over rows in trips of 64: the area means in the order of the level stage
 //                  (lec_section_rows_kernel's), the row factors dphiTc dphiUc dphiV dpT dpU of lec_level_row.inc, and with sigma READ from
 //                  the levraw record everything a point multiplies by, as one record of LEC_MAPS_NCOEF doubles per (t, k, j).
@@ -218,38 +220,17 @@ __global__ void __launch_bounds__(64) lec_mapcol_col_kernel(const P p) {
     double Tc = skip ? 0.0 : (double)pT[i], Tm = Tc;
     for (int k = 0; k < (skip ? 0 : nl); ++k) {
         const E* __restrict__ rT = pT + (size_t)k * plane;
-        const size_t ko = (size_t)k * plane + i;
+        const size_t po = (size_t)k * plane + i;
         const double Tp = k < nl - 1 ? (double)rT[plane + i] : Tc;
         const double Tl = (double)rT[il], Tr = (double)rT[ir];
         const double Tjm = (double)rT[ojm + i], Tjp = (double)rT[ojp + i];
-        const double Uv = (double)pU[ko], Vv = (double)pV[ko], Wv = (double)pW[ko];
+        const double Uv = (double)pU[po], Vv = (double)pV[po], Wv = (double)pW[po];
         const double* lv = p.levtab + (size_t)k * 3;
         const double al = lv[0], be = lv[1], gm = lv[2];
         const double x = p.levtab2[4 * k];
         const double* c = cf + (size_t)k * nyb * kNC;      // wave-uniform: scalar loads
 
-        // Q / cp = dT/dt + u dT/dx + v dT/dy - S w: stage_row's expression (lec_rowspecq.hip), fma form kept
-        // centred on a ring; one-sided at an open box's first and last column
-        const double d = RING ? Tr - Tl : (first ? 2.0 * (Tr - Tc) : (last ? 2.0 * (Tc - Tl) : Tr - Tl));
-        const double adv = (Uv * cx) * d;
-        const double sP = stencil3(ga, Tjm, gc, Tjp, gb, Tc);
-        const double sS = stencil3(al, Tm, gm, Tp, be, Tc);
-        double dTdt;
-        if (DMODE == 0) dTdt = pD[ko];
-        else if (DMODE == 1) dTdt = stencil3(ta, (double)pM[ko], tc, (double)pP[ko], tb, Tc);
-        else dTdt = stencil3(ta, (double)rT[otm + i], tc, (double)rT[otp + i], tb, Tc);
-        const double rest = dTdt + adv;
-        const double fq = fma(-Wv, sS, fma(Vv, sP, rest));
-
-        const double a = Tc - c[C_MT], b = Uv - c[C_MU], v = Vv - c[C_MV], w = Wv - c[C_MW];
-        const double q = kCp * fq - c[C_MQ];
-        const double wT = w * a, vv = v * v, uu = b * b;
-        const double yAe = (a * a) * c[C_AE];
-        const double yKe = uu + vv;
-        const double yCa = -((v * a) * c[C_CA1] + wT * c[C_CA2]);
-        const double yCe = -(c[C_CE] * wT);
-        const double yCk = (b * v) * c[C_CK1] + vv * c[C_CK2] + uu * c[C_CK3] + (w * b) * c[C_DPU] + (w * v) * c[C_DPU];
-        const double yGe = (q * a) * c[C_GE];
+#include "lec_mapcol_point.inc"
         trap_step(s[M_AE], x, yAe, k);
         trap_step(s[M_KE], x, yKe, k);
         trap_step(s[M_CA], x, yCa, k);
@@ -331,41 +312,52 @@ void mapcol_col(const P& p, const int dtype, const dim3 grid, hipStream_t st) {
     else hipLaunchKernelGGL((lec_mapcol_col_kernel<float, RING, DMODE, P>), grid, dim3(64), 0, st, p);
 }
 
-// the four launches of a call on its stream.  A: lec_maps_args or lec_composite_args, whose common fields are read by name; p: the file's
-// column launch struct with its own members set; lt_stride: doubles from one step's lattab2 to the next; launch_col(p, grid, stream)
-// picks the file's RING and DMODE of mapcol_col; launch_sum(f, stream) the file's time sums of the column values
+// what differs between the calls of the family at launch: the per-step output [t_count][kNMap][ext][nxb] and the target of its time sums,
+// the extent the column grid and the sum kernel run over (the box's rows nyb for maps and composites, the levels nl for the longitude x
+// pressure sections), the Hovmoeller rows (null: no such launch), and the call's steps
+struct MapcolRun {
+    double *step, *sum, *hov;
+    int ext, t_begin, t_count;
+};
+
+// the launches of a call on its stream: the factors, the file's column kernel, the time sums and (r.hov) the Hovmoeller rows.  A: the
+// call's args struct, whose common fields are read by name; p: the file's column launch struct with its own members set; lt_stride:
+// doubles from one step's lattab2 to the next; launch_col(p, grid, stream) picks the file's kernel, RING and DMODE; launch_sum(f, stream)
+// the file's time sums of the per-step output
 template <typename A, typename P, typename L, typename S>
-int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_stride, L launch_col, S launch_sum) {
+int mapcol_launch(const A* a, P p, const MapcolRun r, const int nyb, const int nxb, const int lt_stride, L launch_col, S launch_sum) {
     hipStream_t st = (hipStream_t)a->stream;
-    const MapCoefParams c{a->rows_d, a->lattab2_d, a->levtab2_d, a->levraw_d, a->coef_d, a->t_count, a->nl, nyb, lt_stride};
-    hipLaunchKernelGGL(lec_mapcol_coef_kernel, dim3((unsigned)(a->t_count * a->nl)), dim3(64), 0, st, c);
+    const MapCoefParams c{a->rows_d, a->lattab2_d, a->levtab2_d, a->levraw_d, a->coef_d, r.t_count, a->nl, nyb, lt_stride};
+    hipLaunchKernelGGL(lec_mapcol_coef_kernel, dim3((unsigned)(r.t_count * a->nl)), dim3(64), 0, st, c);
     p.T = a->tair_d; p.U = a->u_d; p.V = a->v_d; p.W = a->omega_d;
-    p.coef = a->coef_d; p.levtab = a->levtab_d; p.levtab2 = a->levtab2_d; p.tcoef = a->tcoef_d; p.col = a->col_d;
-    p.nt = a->nt; p.nl = a->nl; p.ny = a->ny; p.nx = a->nx; p.t_begin = a->t_begin; p.t_count = a->t_count;
+    p.coef = a->coef_d; p.levtab = a->levtab_d; p.levtab2 = a->levtab2_d; p.tcoef = a->tcoef_d; p.col = r.step;
+    p.nt = a->nt; p.nl = a->nl; p.ny = a->ny; p.nx = a->nx; p.t_begin = r.t_begin; p.t_count = r.t_count;
     p.nyb = nyb; p.nxb = nxb; p.nseg = (nxb + 63) / 64;
-    launch_col(p, dim3((unsigned)((long long)a->t_count * nyb * p.nseg)), st);
-    const MapFoldParams f{a->col_d, a->lattab2_d, a->mapsum_d, a->hov_d, a->t_count, nyb, nxb, lt_stride};
+    launch_col(p, dim3((unsigned)((long long)r.t_count * r.ext * p.nseg)), st);
+    // lec_mapcol_sum_kernel is generic over its element count: for the sections nl stands where the maps have nyb (lattab2, hov not read)
+    const MapFoldParams f{r.step, a->lattab2_d, r.sum, r.hov, r.t_count, r.ext, nxb, lt_stride};
     launch_sum(f, st);
-    hipLaunchKernelGGL(lec_mapcol_hov_kernel, dim3((unsigned)(((long long)a->t_count * kNMap * nxb + 255) / 256)), dim3(256), 0, st, f);
+    if (r.hov)
+        hipLaunchKernelGGL(lec_mapcol_hov_kernel, dim3((unsigned)(((long long)r.t_count * kNMap * nxb + 255) / 256)), dim3(256), 0, st, f);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return lec_set_error(LEC_ERR_LAUNCH, hipGetErrorString(e));
     return LEC_OK;
 }
 
-// lec_maps' and lec_composite's: ONE time sum over all the call's steps
+// every call but lec_composite_steps: ONE time sum over all the call's steps
 template <typename A, typename P, typename L>
-int mapcol_launch(const A* a, P p, const int nyb, const int nxb, const int lt_stride, L launch_col) {
-    return mapcol_launch(a, p, nyb, nxb, lt_stride, launch_col, [nyb, nxb](const MapFoldParams& f, hipStream_t st) {
-        hipLaunchKernelGGL(lec_mapcol_sum_kernel, dim3((unsigned)(((long long)kNMap * nyb * nxb + 255) / 256)), dim3(256), 0, st, f);
+int mapcol_launch(const A* a, P p, const MapcolRun r, const int nyb, const int nxb, const int lt_stride, L launch_col) {
+    return mapcol_launch(a, p, r, nyb, nxb, lt_stride, launch_col, [r, nxb](const MapFoldParams& f, hipStream_t st) {
+        hipLaunchKernelGGL(lec_mapcol_sum_kernel, dim3((unsigned)(((long long)kNMap * r.ext * nxb + 255) / 256)), dim3(256), 0, st, f);
     });
 }
 
 }  // namespace
 
-// the refusals lec_maps and lec_composite have in common, under the call's name.  Each returns LEC_OK or the refusal's code; the two calls
-// run them between their own, in the order their messages have always come
+// the refusals the calls of the family have in common, under the call's name.  Each returns LEC_OK or the refusal's code; the calls run
+// them between their own, in the order their messages have always come.  Members templated on A read the args struct's fields by name
 struct MapcolRefusals {
-    const char* call;      // "lec_maps" / "lec_composite"
+    const char* call;      // "lec_maps", "lec_composite", ...
 
     int refuse(int code, const char* what) const {
         char msg[320];
@@ -392,23 +384,128 @@ struct MapcolRefusals {
         if ((uintptr_t)coef_d % 16) return refuse(LEC_ERR_ARG, "coef_d must be 16-byte aligned");
         return LEC_OK;
     }
-    // the 8-byte tables tabs[ntab] by their names, the cubes (cube_names: as the message lists them), and the launch limits (dims: the
-    // fields that set rows and columns).  HIP takes fewer than 2^32 threads per launch: one 64-lane workgroup per (time step, level) and
-    // per (time step, row, 64 columns), one thread per element of mapsum_d and of hov_d
-    int tables_cubes_limits(const void* const* tabs, const char* const* tabn, int ntab, const void* const* cubes, int ncube,
-                            const char* cube_names, int dtype, int t_count, int nl, int nyb, int nxb, const char* dims) const {
+    // the first null of ptrs[n] under its message
+    int nulls(const void* const* ptrs, const char* const* what, int n) const {
+        for (int i = 0; i < n; ++i)
+            if (!ptrs[i]) return refuse(LEC_ERR_ARG, what[i]);
+        return LEC_OK;
+    }
+    // a FIXED box (lec_maps, lec_lonsections), a non-null: the inputs, the call's outputs outs[nout] under their messages, then the cube,
+    // the steps and the box.  few_cols, few_rows: the call's words for a box of fewer than three columns and of fewer than two rows
+    template <typename A>
+    int fixed_box(const A* a, const void* const* outs, const char* const* out_null, int nout, const char* few_cols, const char* few_rows) const {
+        const void* in[] = {a->tair_d, a->u_d, a->v_d, a->omega_d, a->rows_d, a->levraw_d, a->lattab2_d, a->levtab2_d, a->lattab_d, a->levtab_d,
+                            a->tcoef_d, a->coef_d};
+        const char* in_null[] = {"null tair_d", "null u_d", "null v_d", "null omega_d", "null rows_d", "null levraw_d", "null lattab2_d",
+                                 "null levtab2_d", "null lattab_d", "null levtab_d",
+                                 "null tcoef_d (a dT/dt cube is not supported: dT/dt comes from the cube's time axis)",
+                                 "null coef_d (the workspace of the row factors)"};
+        if (int r = nulls(in, in_null, 12)) return r;
+        if (int r = nulls(outs, out_null, nout)) return r;
+        if (int r = dtype(a->dtype)) return r;
+        if (a->ring != 0 && a->ring != 1) return refuse(LEC_ERR_ARG, "ring must be 0 or 1");
+        if (a->reserved0 != 0) return refuse(LEC_ERR_ARG, "reserved0 must be 0");
+        if (a->nt < 2) return refuse(LEC_ERR_ARG, "nt must be >= 2 (dT/dt by finite differences over the cube's time axis)");
+        if (int r = levels(a->nl)) return r;
+        if (a->ny < 2) return refuse(LEC_ERR_ARG, "ny must be >= 2");
+        if (a->nx < 3) return refuse(LEC_ERR_ARG, "nx must be >= 3");
+        if (int r = steps(a->nt, a->t_begin, a->t_count)) return r;
+        if (a->iw < 0 || a->iw >= a->nx) return refuse(LEC_ERR_ARG, "iw outside the cube's longitudes");
+        if (a->ie < a->iw || a->ie >= a->nx) return refuse(LEC_ERR_ARG, "ie must be iw .. nx - 1");
+        if (a->ie - a->iw + 1 < 3) return refuse(LEC_ERR_ARG, few_cols);
+        if (a->ring && (a->iw != 0 || a->ie != a->nx - 1)) return refuse(LEC_ERR_ARG, "ring: iw .. ie must be 0 .. nx - 1 (a ring is the whole circle)");
+        if (a->js < 0 || a->js >= a->ny) return refuse(LEC_ERR_ARG, "js outside the cube's latitudes");
+        if (a->jn <= a->js || a->jn >= a->ny) return refuse(LEC_ERR_ARG, few_rows);
+        return align16(a->rows_d, a->lattab2_d, a->coef_d);
+    }
+    // dT/dt by lec_rowstats' rule (lec_composite, lec_composite_lonsections): one source, and a cube long enough for it.  *dmode: the
+    // column kernel's DMODE
+    template <typename A>
+    int dTdt_source(const A* a, int* dmode) const {
+        if ((a->tm_d != nullptr) != (a->tp_d != nullptr))
+            return refuse(LEC_ERR_ARG, a->tm_d ? "tm_d without tp_d (a box-packed series needs both time neighbours)"
+                                               : "tp_d without tm_d (a box-packed series needs both time neighbours)");
+        if (a->dTdt_d && a->tm_d) return refuse(LEC_ERR_ARG, "dTdt_d together with tm_d / tp_d: give one source of dT/dt");
+        if (!a->dTdt_d && !a->tcoef_d) return refuse(LEC_ERR_ARG, "null tcoef_d without dTdt_d: no source of dT/dt");
+        *dmode = a->dTdt_d ? 0 : (a->tm_d ? 1 : 2);
+        if (a->nt < 1) return refuse(LEC_ERR_ARG, "nt must be >= 1");
+        if (*dmode == 2 && a->nt < 2)
+            return refuse(LEC_ERR_ARG, "nt must be >= 2 when dT/dt comes from the cube's own time neighbours (no dTdt_d, tm_d / tp_d)");
+        return LEC_OK;
+    }
+    // a series of MOVING boxes (lec_composite, lec_composite_lonsections), a non-null: fixed_box's counterpart.  few_cols: the call's words
+    // for boxes of fewer than three columns; *dmode: dTdt_source's
+    template <typename A>
+    int moving_boxes(const A* a, const void* const* outs, const char* const* out_null, int nout, const char* few_cols, int* dmode) const {
+        const void* in[] = {a->tair_d, a->u_d, a->v_d, a->omega_d, a->box_h, a->box_d, a->boxtab_d, a->lattab_d, a->lattab2_d, a->rows_d,
+                            a->levraw_d, a->levtab_d, a->levtab2_d, a->coef_d};
+        const char* in_null[] = {"null tair_d", "null u_d", "null v_d", "null omega_d",
+                                 "null box_h (the host copy of the boxes: their shapes are checked before anything is launched)", "null box_d",
+                                 "null boxtab_d", "null lattab_d", "null lattab2_d", "null rows_d", "null levraw_d", "null levtab_d",
+                                 "null levtab2_d", "null coef_d (the workspace of the row factors)"};
+        if (int r = nulls(in, in_null, 14)) return r;
+        if (int r = nulls(outs, out_null, nout)) return r;
+        if (int r = dtype(a->dtype)) return r;
+        if (a->reserved0 != 0) return refuse(LEC_ERR_ARG, "reserved0 must be 0");
+        if (int r = dTdt_source(a, dmode)) return r;
+        if (int r = levels(a->nl)) return r;
+        if (a->nyb < 2) return refuse(LEC_ERR_ARG, "nyb must be >= 2 (a box needs two rows for d/dlat)");
+        if (a->nxb < 3) return refuse(LEC_ERR_ARG, few_cols);
+        if (a->ny < a->nyb) return refuse(LEC_ERR_ARG, "ny must be >= nyb");
+        if (a->nx < a->nxb) return refuse(LEC_ERR_ARG, "nx must be >= nxb");
+        if (int r = steps(a->nt, a->t_begin, a->t_count)) return r;
+        if (int r = boxes(a, a->t_count, "the box of step")) return r;
+        if (int r = align16(a->rows_d, a->lattab2_d, a->coef_d)) return r;
+        if ((uintptr_t)a->box_d % 4) return refuse(LEC_ERR_ARG, "box_d must be 4-byte aligned");
+        if ((uintptr_t)a->box_h % 4) return refuse(LEC_ERR_ARG, "box_h must be 4-byte aligned");
+        return LEC_OK;
+    }
+    // every box of box_h[n] nyb x nxb and inside the cube: on the HOST copy, before any HIP call.  which: "the box of step" / "box"
+    template <typename A>
+    int boxes(const A* a, int n, const char* which) const {
+        for (int t = 0; t < n; ++t) {
+            const int32_t* b = a->box_h + 4 * (size_t)t;
+            const long long w = (long long)b[1] - b[0] + 1, h = (long long)b[3] - b[2] + 1;
+            char m[256];
+            if (w != a->nxb || h != a->nyb) {
+                snprintf(m, sizeof(m), "box_h: %s %d is %lld x %lld (rows x columns), the call's nyb x nxb is %d x %d: every box of a "
+                         "composite has one shape", which, t, h, w, a->nyb, a->nxb);
+                return refuse(LEC_ERR_ARG, m);
+            }
+            if (b[0] < 0 || b[1] >= a->nx || b[2] < 0 || b[3] >= a->ny) {
+                snprintf(m, sizeof(m), "box_h: %s %d {iw, ie, js, jn} = {%d, %d, %d, %d} lies outside the %d x %d cube", which, t, b[0], b[1],
+                         b[2], b[3], a->ny, a->nx);
+                return refuse(LEC_ERR_ARG, m);
+            }
+        }
+        return LEC_OK;
+    }
+    // the 8-byte tables tabs[ntab] by their names and the cubes (cube_names: as the message lists them)
+    struct Aligned {
+        const void* const* tabs; const char* const* tabn; int ntab;
+        const void* const* cubes; int ncube; const char* cube_names; int dtype;
+    };
+    int tables_cubes(const Aligned& p) const {
         char m[128];
-        for (int i = 0; i < ntab; ++i)
-            if ((uintptr_t)tabs[i] % 8) {
-                snprintf(m, sizeof(m), "%s must be 8-byte aligned", tabn[i]);
+        for (int i = 0; i < p.ntab; ++i)
+            if ((uintptr_t)p.tabs[i] % 8) {
+                snprintf(m, sizeof(m), "%s must be 8-byte aligned", p.tabn[i]);
                 return refuse(LEC_ERR_ARG, m);
             }
-        const size_t esz = dtype == LEC_F32 ? 4 : 8;
-        for (int i = 0; i < ncube; ++i)
-            if ((uintptr_t)cubes[i] % esz) {
-                snprintf(m, sizeof(m), "cube pointer (%s) not aligned to its element size", cube_names);
+        const size_t esz = p.dtype == LEC_F32 ? 4 : 8;
+        for (int i = 0; i < p.ncube; ++i)
+            if ((uintptr_t)p.cubes[i] % esz) {
+                snprintf(m, sizeof(m), "cube pointer (%s) not aligned to its element size", p.cube_names);
                 return refuse(LEC_ERR_ARG, m);
             }
+        return LEC_OK;
+    }
+    // those alignments, then the launch limits of maps and composites (dims: the fields that set rows and columns).  HIP takes fewer than
+    // 2^32 threads per launch: one 64-lane workgroup per (time step, level) and per (time step, row, 64 columns), one thread per element of
+    // mapsum_d and of hov_d
+    int tables_cubes_limits(const Aligned& p, int t_count, int nl, int nyb, int nxb, const char* dims) const {
+        if (int r = tables_cubes(p)) return r;
+        char m[128];
         if ((long long)t_count * nl >= (1LL << 26))
             return refuse(LEC_ERR_UNSUPPORTED, "t_count * nl must stay below 2^26 in one call (cut the series into several calls)");
         if ((long long)t_count * nyb * ((nxb + 63) / 64) >= (1LL << 26))
@@ -419,6 +516,21 @@ struct MapcolRefusals {
         }
         if ((long long)t_count * kNMap * nxb >= (1LL << 32) - 256)
             return refuse(LEC_ERR_UNSUPPORTED, "t_count * 6 * columns must stay below 2^32 threads in one call");
+        return LEC_OK;
+    }
+    // those alignments, then the launch limits of the longitude x pressure sections: one 64-lane workgroup per (time step, level, 64
+    // columns) -- which bounds the factors' (time step, level) too -- and one thread per element of lonsecsum_d
+    int tables_cubes_lonsec_limits(const Aligned& p, int t_count, int nl, int nxb, const char* cols) const {
+        if (int r = tables_cubes(p)) return r;
+        char m[160];
+        if ((long long)t_count * nl * ((nxb + 63) / 64) >= (1LL << 26)) {
+            snprintf(m, sizeof(m), "t_count * nl * ceil(columns / 64) (%s) must stay below 2^26 in one call (cut the series into several calls)", cols);
+            return refuse(LEC_ERR_UNSUPPORTED, m);
+        }
+        if ((long long)kNMap * nl * nxb >= (1LL << 32) - 256) {
+            snprintf(m, sizeof(m), "6 * nl * columns (%s) must stay below 2^32 threads", cols);
+            return refuse(LEC_ERR_UNSUPPORTED, m);
+        }
         return LEC_OK;
     }
 };

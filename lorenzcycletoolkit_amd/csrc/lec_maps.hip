@@ -28,48 +28,24 @@ struct ColParams : MapColGrid {
 extern "C" int lec_maps(const lec_maps_args* a) {
     const MapcolRefusals chk{"lec_maps"};
     if (!a) return chk.refuse(LEC_ERR_ARG, "null args");
-    if (!a->tair_d) return chk.refuse(LEC_ERR_ARG, "null tair_d");
-    if (!a->u_d) return chk.refuse(LEC_ERR_ARG, "null u_d");
-    if (!a->v_d) return chk.refuse(LEC_ERR_ARG, "null v_d");
-    if (!a->omega_d) return chk.refuse(LEC_ERR_ARG, "null omega_d");
-    if (!a->rows_d) return chk.refuse(LEC_ERR_ARG, "null rows_d");
-    if (!a->levraw_d) return chk.refuse(LEC_ERR_ARG, "null levraw_d");
-    if (!a->lattab2_d) return chk.refuse(LEC_ERR_ARG, "null lattab2_d");
-    if (!a->levtab2_d) return chk.refuse(LEC_ERR_ARG, "null levtab2_d");
-    if (!a->lattab_d) return chk.refuse(LEC_ERR_ARG, "null lattab_d");
-    if (!a->levtab_d) return chk.refuse(LEC_ERR_ARG, "null levtab_d");
-    if (!a->tcoef_d) return chk.refuse(LEC_ERR_ARG, "null tcoef_d (a dT/dt cube is not supported: dT/dt comes from the cube's time axis)");
-    if (!a->coef_d) return chk.refuse(LEC_ERR_ARG, "null coef_d (the workspace of the row factors)");
-    if (!a->col_d) return chk.refuse(LEC_ERR_ARG, "null col_d (the column values, which are the workspace of the sums too)");
-    if (!a->hov_d) return chk.refuse(LEC_ERR_ARG, "null hov_d");
-    if (!a->mapsum_d) return chk.refuse(LEC_ERR_ARG, "null mapsum_d");
-    if (int r = chk.dtype(a->dtype)) return r;
-    if (a->ring != 0 && a->ring != 1) return chk.refuse(LEC_ERR_ARG, "ring must be 0 or 1");
-    if (a->reserved0 != 0) return chk.refuse(LEC_ERR_ARG, "reserved0 must be 0");
-    if (a->nt < 2) return chk.refuse(LEC_ERR_ARG, "nt must be >= 2 (dT/dt by finite differences over the cube's time axis)");
-    if (int r = chk.levels(a->nl)) return r;
-    if (a->ny < 2) return chk.refuse(LEC_ERR_ARG, "ny must be >= 2");
-    if (a->nx < 3) return chk.refuse(LEC_ERR_ARG, "nx must be >= 3");
-    if (int r = chk.steps(a->nt, a->t_begin, a->t_count)) return r;
-    if (a->iw < 0 || a->iw >= a->nx) return chk.refuse(LEC_ERR_ARG, "iw outside the cube's longitudes");
-    if (a->ie < a->iw || a->ie >= a->nx) return chk.refuse(LEC_ERR_ARG, "ie must be iw .. nx - 1");
-    if (a->ie - a->iw + 1 < 3) return chk.refuse(LEC_ERR_ARG, "ie - iw + 1 must be >= 3 (a map needs three box columns)");
-    if (a->ring && (a->iw != 0 || a->ie != a->nx - 1)) return chk.refuse(LEC_ERR_ARG, "ring: iw .. ie must be 0 .. nx - 1 (a ring is the whole circle)");
-    if (a->js < 0 || a->js >= a->ny) return chk.refuse(LEC_ERR_ARG, "js outside the cube's latitudes");
-    if (a->jn <= a->js || a->jn >= a->ny) return chk.refuse(LEC_ERR_ARG, "jn must be js + 1 .. ny - 1 (a box needs two rows for d/dlat)");
-    if (int r = chk.align16(a->rows_d, a->lattab2_d, a->coef_d)) return r;
+    const void* outs[] = {a->col_d, a->hov_d, a->mapsum_d};
+    const char* out_null[] = {"null col_d (the column values, which are the workspace of the sums too)", "null hov_d", "null mapsum_d"};
+    if (int r = chk.fixed_box(a, outs, out_null, 3, "ie - iw + 1 must be >= 3 (a map needs three box columns)",
+                              "jn must be js + 1 .. ny - 1 (a box needs two rows for d/dlat)"))
+        return r;
     const void* tabs[] = {a->levraw_d, a->levtab2_d, a->lattab_d, a->levtab_d, a->tcoef_d, a->col_d, a->hov_d, a->mapsum_d};
     const char* tabn[] = {"levraw_d", "levtab2_d", "lattab_d", "levtab_d", "tcoef_d", "col_d", "hov_d", "mapsum_d"};
     const void* cubes[] = {a->tair_d, a->u_d, a->v_d, a->omega_d};
     const int nyb = a->jn - a->js + 1, nxb = a->ie - a->iw + 1;
-    if (int r = chk.tables_cubes_limits(tabs, tabn, 8, cubes, 4, "tair_d, u_d, v_d, omega_d", a->dtype, a->t_count, a->nl, nyb, nxb,
+    if (int r = chk.tables_cubes_limits({tabs, tabn, 8, cubes, 4, "tair_d, u_d, v_d, omega_d", a->dtype}, a->t_count, a->nl, nyb, nxb,
                                         "js, jn, iw, ie"))
         return r;
 
     ColParams p;
     p.lattab = a->lattab_d; p.inv_hdeg_ = a->inv_hdeg; p.iw_ = a->iw; p.js_ = a->js;
     // dT/dt over the cube's own time axis: DMODE 2
-    return mapcol_launch(a, p, nyb, nxb, 0, [a](const ColParams& q, dim3 grid, hipStream_t st) {
+    const MapcolRun run{a->col_d, a->mapsum_d, a->hov_d, nyb, a->t_begin, a->t_count};
+    return mapcol_launch(a, p, run, nyb, nxb, 0, [a](const ColParams& q, dim3 grid, hipStream_t st) {
         if (a->ring) mapcol_col<true, 2>(q, a->dtype, grid, st);
         else mapcol_col<false, 2>(q, a->dtype, grid, st);
     });

@@ -779,49 +779,66 @@ class LECEngine:
         if state["steps"] is not None:
             res.composite_section_steps = state["steps"].permute(0, 2, 1, 3).contiguous()
 
-    # -- longitude-resolved maps of the eddy terms on one fixed box (lec_maps) ------------------------------------------------------------
-    # the column values C_f(t, j, i) and the row factors of the steps of ONE lec_maps call: a chunk that needs more is cut into sub-calls
+    # -- the family of csrc/lec_mapcol.h: maps and longitude x pressure sections of the eddy terms on one fixed box (lec_maps,
+    # lec_lonsections), composites and composite sections over per-step boxes of one shape (lec_composite, lec_composite_lonsections) ------
+    # the per-step output and the row factors of the steps of ONE call: a chunk that needs more is cut into sub-calls
     MAP_CHUNK_BYTES = 256 << 20
+    # the two outputs of the family: (``state``'s key of the time sums, the args structs' field of the per-step output, that of its time
+    # sums, whether the output is laid on the box's rows).  A step's output is [LEC_NMAP, ext, nxb]: ext is nyb where it is, and Hovmoeller
+    # rows ``state["hov"]`` go with it; for the sections ext is nl
+    _MAPS_OUT = ("mapsum", "col_d", "mapsum_d", True)
+    _LONSEC_OUT = ("lonsecsum", "lonsec_d", "lonsecsum_d", False)
 
-    @staticmethod
-    def _mapcol_begin(t_total: int, nyb: int, nxb: int, device, keep_steps: bool) -> dict:
-        """The accumulators of the maps or composites of ``t_total`` steps on ``nyb`` x ``nxb`` points, zeroed."""
+    def _mapcol_begin(self, out: tuple, t_total: int, nyb: int, nxb: int, device, keep_steps: bool) -> dict:
+        """The accumulators of the output ``out`` over ``t_total`` steps on boxes of ``nyb`` x ``nxb`` points, zeroed."""
         f64 = dict(dtype=torch.float64, device=device)
-        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, mapsum=torch.zeros((_lib.LEC_NMAP, nyb, nxb), **f64),
-                    hov=torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64),
-                    steps=torch.empty((t_total, _lib.LEC_NMAP, nyb, nxb), **f64) if keep_steps else None, work=None, coef=None)
+        total, _, _, on_rows = out
+        ext = nyb if on_rows else int(self.level.size)
+        state = dict(t_total=int(t_total), nyb=nyb, nxb=nxb, ext=ext, out=out, work=None, coef=None)
+        state[total] = torch.zeros((_lib.LEC_NMAP, ext, nxb), **f64)
+        if on_rows:
+            state["hov"] = torch.empty((t_total, _lib.LEC_NMAP, nxb), **f64)
+        state["steps"] = torch.empty((t_total, _lib.LEC_NMAP, ext, nxb), **f64) if keep_steps else None
+        return state
 
-    def _mapcol_sub(self, nl: int, nyb: int, nxb: int, t_count: int) -> int:
-        """Steps per sub-call of a chunk of ``t_count`` steps: as many as keep the column values and row factors within ``MAP_CHUNK_BYTES``."""
-        per_step = 8 * (_lib.LEC_NMAP * nyb * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
+    def _mapcol_sub(self, nl: int, state: dict, t_count: int) -> int:
+        """Steps per sub-call of a chunk of ``t_count`` steps: as many as keep the per-step output and the row factors within
+        ``MAP_CHUNK_BYTES``."""
+        per_step = 8 * (_lib.LEC_NMAP * state["ext"] * state["nxb"] + nl * state["nyb"] * _lib.LEC_MAPS_NCOEF)
         return max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
 
     def _mapcol_stage(self, cubes, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, t_begin: int, issue) -> None:
-        """What ``map_stage`` and ``composite_stage`` do alike once their own arguments are checked: ``levraw``'s check, the cut of the
-        chunk into sub-calls whose column values and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and
-        the sub-calls in time order: ``issue(a, b, shared)`` calls on the chunk's steps [a, b), ``shared`` the fields both args structs have."""
+        """What the stages of the family do alike once their own arguments are checked: ``levraw``'s check, the cut of the chunk into
+        sub-calls whose per-step output and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and the
+        sub-calls in time order: ``issue(a, b, shared)`` calls on the chunk's steps [a, b), ``shared`` the fields the args structs of
+        ``state``'s output have in common."""
         tair, u, v, omega = cubes
         nt, nl, ny, nx = (int(x) for x in tair.shape)
-        t_count, nyb, nxb = int(rows.shape[0]), state["nyb"], state["nxb"]
+        t_count, nyb, nxb, ext = int(rows.shape[0]), state["nyb"], state["nxb"], state["ext"]
+        total, step_field, sum_field, on_rows = state["out"]
         if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
                 or not levraw.is_contiguous()):
             raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
+        if not on_rows and ext != nl:
+            raise ValueError("the cubes' levels are not the engine's")
         f64 = dict(dtype=torch.float64, device=rows.device)
-        sub = self._mapcol_sub(nl, nyb, nxb, t_count)
+        sub = self._mapcol_sub(nl, state, t_count)
         if state["coef"] is None or state["coef"].shape[0] < sub:
             state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
         if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
-            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nyb, nxb), **f64)
+            state["work"] = torch.empty((sub, _lib.LEC_NMAP, ext, nxb), **f64)
         for a in range(0, t_count, sub):
             b = min(t_count, a + sub)
-            col = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
+            step = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
             shared = dict(
                 tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
                 dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
                 t_begin=t_begin + a, t_count=b - a, reserved0=0, rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
-                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), coef_d=_ptr(state["coef"]), col_d=_ptr(col),
-                mapsum_d=_ptr(state["mapsum"]), hov_d=_ptr(state["hov"][t_offset + a: t_offset + b]),
+                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), coef_d=_ptr(state["coef"]),
                 stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+            shared[step_field], shared[sum_field] = _ptr(step), _ptr(state[total])
+            if on_rows:
+                shared["hov_d"] = _ptr(state["hov"][t_offset + a: t_offset + b])
             with torch.cuda.device(rows.device):
                 issue(a, b, shared)
 
@@ -832,20 +849,57 @@ class LECEngine:
             raise ValueError("maps exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a packed layout) has "
                              "no common points to lay a map on")
 
-    def map_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
-        """The accumulators of the maps of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once, here): ``map_stage``
-        adds every chunk to them, ``map_finish`` turns them into the result's fields."""
-        self._check_maps(boxes, False)
+    @staticmethod
+    def _check_lonsections(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
+        n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
+        if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
+            raise ValueError("longitude-pressure sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a "
+                             "packed layout) has no common columns to lay a section on; it has composite_lon_sections=True")
+
+    def _fixed_begin(self, out: tuple, noun: str, check, t_total: int, boxes, device, keep_steps: bool) -> dict:
+        """``map_begin`` and ``lonsection_begin``: the fixed box's refusals in the words of the output ``noun``, then its accumulators."""
+        check(boxes, False)
         bx, bt, _ = self._resolve_boxes(boxes)
         iw, ie, js, jn = bx[0]
         nyb, nxb = jn - js + 1, ie - iw + 1
         if bt.nyb_max != nyb:
-            raise ValueError("maps: the box's records must have the box's own row count (prepare_boxes without nyb_min)")
+            raise ValueError(f"{noun}: the box's records must have the box's own row count (prepare_boxes without nyb_min)")
         if not bt.lon_uniform:
-            raise ValueError("maps need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+            raise ValueError(f"{noun} need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
         if nxb < 3:
-            raise ValueError("maps need at least 3 box columns")
-        return self._mapcol_begin(t_total, nyb, nxb, device, keep_steps)
+            raise ValueError(f"{noun} need at least 3 box columns")
+        return self._mapcol_begin(out, t_total, nyb, nxb, device, keep_steps)
+
+    def _fixed_chunk(self, who: str, begin: str, check, struct, call: str, *, cubes, rows, boxes, levraw, state: dict, t_offset: int,
+                     t_begin: int, time_s, tcoef) -> None:
+        """``map_stage`` and ``lonsection_stage``: the chunk against the cubes and against ``state``, then the C call ``call`` on the args
+        struct ``struct`` per sub-call.  The stage's own arguments come by keyword, ``cubes`` = (tair, u, v, omega)."""
+        tair, u, v, omega = cubes
+        self._check_fields([tair, u, v, omega], None)
+        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
+        bx, bt, dev = self._stage2_input(rows, boxes)
+        check(bx, False)
+        iw, ie, js, jn = bx[0]
+        nyb, nxb = jn - js + 1, ie - iw + 1
+        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
+                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
+            raise ValueError(f"{who}: the chunk does not fit the series and box {begin} was given")
+        if not (0 <= t_begin and t_begin + t_count <= nt):
+            raise ValueError(f"{who}: [t_begin, t_begin + t_count) lies outside the cubes")
+        if rows.device != tair.device:
+            raise ValueError(f"{who}: rows and fields on one device")
+        tcoef = self._cube_tcoef(who, time_s, tcoef, nt, tair.device)
+
+        def issue(a, b, shared):
+            fa = struct(iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, lattab2_d=_ptr(dev["lattab2"]), lattab_d=_ptr(dev["lattab"]),
+                        tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]), **shared)
+            _lib.check(getattr(self.lib, call)(C.byref(fa)), call)
+        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+
+    def map_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the maps of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once, here): ``map_stage``
+        adds every chunk to them, ``map_finish`` turns them into the result's fields."""
+        return self._fixed_begin(self._MAPS_OUT, "maps", self._check_maps, t_total, boxes, device, keep_steps)
 
     def map_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
                   levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
@@ -856,26 +910,8 @@ class LECEngine:
         cube's time axis ``time_s`` (seconds, one entry per step of the cube) or ``tcoef``, as ``rowspec_q`` takes them.  A chunk whose
         column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is
         independent of how the series is cut, bit for bit."""
-        self._check_fields([tair, u, v, omega], None)
-        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
-        bx, bt, dev = self._stage2_input(rows, boxes)
-        self._check_maps(bx, False)
-        iw, ie, js, jn = bx[0]
-        nyb, nxb = jn - js + 1, ie - iw + 1
-        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
-                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
-            raise ValueError("map_stage: the chunk does not fit the series and box map_begin was given")
-        if not (0 <= t_begin and t_begin + t_count <= nt):
-            raise ValueError("map_stage: [t_begin, t_begin + t_count) lies outside the cubes")
-        if rows.device != tair.device:
-            raise ValueError("map_stage: rows and fields on one device")
-        tcoef = self._cube_tcoef("map_stage", time_s, tcoef, nt, tair.device)
-
-        def issue(a, b, shared):
-            ma = _lib.MapsArgs(iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, lattab2_d=_ptr(dev["lattab2"]),
-                               lattab_d=_ptr(dev["lattab"]), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]), **shared)
-            _lib.check(self.lib.lec_maps(C.byref(ma)), "lec_maps")
-        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+        self._fixed_chunk("map_stage", "map_begin", self._check_maps, _lib.MapsArgs, "lec_maps", cubes=(tair, u, v, omega), rows=rows,
+                          boxes=boxes, levraw=levraw, state=state, t_offset=t_offset, t_begin=t_begin, time_s=time_s, tcoef=tcoef)
 
     def map_finish(self, res: LECResult, state: dict) -> None:
         """``res.map_*`` from the accumulators of a finished series."""
@@ -884,10 +920,47 @@ class LECEngine:
         if state["steps"] is not None:
             res.map_steps = state["steps"]
 
-    # -- system-relative composites of the eddy terms over per-step boxes of one shape (lec_composite) -----------------------------------
+    def lonsection_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the longitude x pressure sections of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once,
+        here): ``lonsection_stage`` adds every chunk to them, ``lonsection_finish`` turns them into the result's fields."""
+        return self._fixed_begin(self._LONSEC_OUT, "longitude-pressure sections", self._check_lonsections, t_total, boxes, device, keep_steps)
+
+    def lonsection_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
+                         levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
+                         t_begin: int = 0) -> None:
+        """``lec_lonsections`` on a chunk, with ``map_stage``'s arguments: the time sums are added to ``state["lonsecsum"]`` and, when
+        kept, the steps written to ``state["steps"][t_offset: t_offset + t_count]``.  A chunk whose sections and row factors exceed
+        ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is independent of how the series is cut,
+        bit for bit."""
+        self._fixed_chunk("lonsection_stage", "lonsection_begin", self._check_lonsections, _lib.LonSectionsArgs, "lec_lonsections",
+                          cubes=(tair, u, v, omega), rows=rows, boxes=boxes, levraw=levraw, state=state, t_offset=t_offset, t_begin=t_begin,
+                          time_s=time_s, tcoef=tcoef)
+
+    def lonsection_finish(self, res: LECResult, state: dict) -> None:
+        """``res.lonsection_*`` from the accumulators of a finished series."""
+        res.lonsection_mean = state["lonsecsum"] / float(state["t_total"])
+        if state["steps"] is not None:
+            res.lonsection_steps = state["steps"]
+
     # (the output that asks, one of it, the fixed box's flag): the words of _check_composites' refusals
     _COMPOSITE_WORDS = ("composites", "a composite", "maps=True")
     _COMPOSITE_LONSECTION_WORDS = ("composite longitude-pressure sections", "a section", "lon_sections=True")
+
+    @staticmethod
+    def _one_shape(bx, lon_uniform: Optional[bool], noun: str, box: str, first: str) -> tuple:
+        """(nyb, nxb) of boxes of ONE shape with three columns or more on evenly spaced longitudes, or the refusal in the words of the
+        output ``noun``; ``box``, ``first``: how it names box t and box 0."""
+        bx = [tuple(int(x) for x in b) for b in bx]
+        nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
+        for t, b in enumerate(bx):
+            h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
+            if (h, w) != (nyb, nxb):
+                raise ValueError(f"{noun} need boxes of ONE shape: {box} {t} has {h} x {w} points (rows x columns), {first} has {nyb} x {nxb}")
+        if nxb < 3:
+            raise ValueError(f"{noun} need at least 3 box columns")
+        if lon_uniform is False:
+            raise ValueError(f"{noun} need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
+        return nyb, nxb
 
     @staticmethod
     def _check_composites(boxes, per_step_boxes, steps=None, lon_uniform: Optional[bool] = None,
@@ -901,32 +974,21 @@ class LECEngine:
         if per_step_boxes is False or (per_step_boxes is None and len(bx) == 1):
             raise ValueError(f"{noun} exist for per-step boxes (per_step_boxes=True): {one} is laid on the box-relative points "
                              f"of a series of moving boxes; ONE fixed box has {fixed}")
-        bx = [tuple(int(x) for x in b) for b in bx]
-        nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
-        for t, b in enumerate(bx):
-            h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
-            if (h, w) != (nyb, nxb):
-                raise ValueError(f"{noun} need boxes of ONE shape: the box of step {t} has {h} x {w} points (rows x columns), that of "
-                                 f"step 0 has {nyb} x {nxb}")
-        if nxb < 3:
-            raise ValueError(f"{noun} need at least 3 box columns")
-        if lon_uniform is False:
-            raise ValueError(f"{noun} need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
-        return nyb, nxb
+        return LECEngine._one_shape(bx, lon_uniform, noun, "the box of step", "that of step 0")
 
-    def composite_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
-        """The accumulators of the composites of a series of ``t_total`` steps whose boxes all have the shape of ``boxes``' (zeroed once,
-        here): ``composite_stage`` adds every chunk to them, ``composite_finish`` turns them into the result's fields."""
-        nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform)
+    def _composite_begin(self, out: tuple, what: tuple, t_total: int, boxes: PreparedBoxes, device, keep_steps: bool) -> dict:
+        """``composite_begin`` and ``composite_lonsection_begin``: the boxes' refusals in the words ``what``, then the accumulators."""
+        nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform, what=what)
         if boxes.bt.nyb_max != nyb:
-            raise ValueError("composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
-        return self._mapcol_begin(t_total, nyb, nxb, device, keep_steps)
+            raise ValueError(f"{what[0]}: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min)")
+        return self._mapcol_begin(out, t_total, nyb, nxb, device, keep_steps)
 
-    def _composite_chunk(self, who: str, begin: str, what: tuple, tair, u, v, omega, rows, boxes, state: dict, t_offset: int, t_begin: int,
-                         time_s, dTdt, tm, tp, tcoef) -> tuple:
-        """What ``composite_stage`` and ``composite_lonsection_stage`` check and prepare alike: the layout and its source of dT/dt, the
-        boxes' one shape against ``state``, the chunk against the cubes.  Returns (nyb, nxb, dTdt as fp64, tcoef, the boxes as the cubes
-        hold them on the host and on the device, the boxes' device tables)."""
+    def _composite_chunk(self, who: str, begin: str, what: tuple, struct, call: str, *, cubes, rows, boxes, levraw, state: dict,
+                         t_offset: int, t_begin: int, time_s, dTdt, tm, tp, tcoef) -> None:
+        """``composite_stage`` and ``composite_lonsection_stage``: the layout and its source of dT/dt, the boxes' one shape against
+        ``state``, the chunk against the cubes, then the C call ``call`` on the args struct ``struct`` per sub-call, with the boxes as
+        the cubes hold them.  The stage's own arguments come by keyword, ``cubes`` = (tair, u, v, omega)."""
+        tair, u, v, omega = cubes
         if not isinstance(boxes, PreparedBoxes):
             raise ValueError(f"{who}: boxes from prepare_boxes")
         packed = "box_data" in boxes.dev
@@ -961,7 +1023,18 @@ class LECEngine:
             tcoef = self._cube_tcoef(who, time_s, tcoef, nt, tair.device)
         box_host = np.ascontiguousarray([(0, b[1] - b[0], 0, b[3] - b[2]) for b in bx] if packed else bx, dtype=np.int32)
         box_dev = dev["box_data" if packed else "box"]
-        return nyb, nxb, dTdt, tcoef, box_host, box_dev, dev
+
+        def issue(a, b, shared):
+            ca = struct(dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp), nyb=nyb, nxb=nxb, tcoef_d=_ptr(tcoef),
+                        box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
+                        lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), **shared)
+            _lib.check(getattr(self.lib, call)(C.byref(ca)), call)
+        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+
+    def composite_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
+        """The accumulators of the composites of a series of ``t_total`` steps whose boxes all have the shape of ``boxes``' (zeroed once,
+        here): ``composite_stage`` adds every chunk to them, ``composite_finish`` turns them into the result's fields."""
+        return self._composite_begin(self._MAPS_OUT, self._COMPOSITE_WORDS, t_total, boxes, device, keep_steps)
 
     def composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
                         boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
@@ -974,17 +1047,9 @@ class LECEngine:
         fields' fp32 is widened to fp64, the value stage 1 reads), or ``tm`` / ``tp`` with ``tcoef``, or -- an unpacked cube only -- the
         cube's own time axis ``time_s`` / ``tcoef``.  A chunk whose column values and row factors exceed ``MAP_CHUNK_BYTES`` is cut into
         sub-calls.  Chunks must come in time order; every number is independent of how the series is cut, bit for bit."""
-        nyb, nxb, dTdt, tcoef, box_host, box_dev, dev = self._composite_chunk(
-            "composite_stage", "composite_begin", self._COMPOSITE_WORDS, tair, u, v, omega, rows, boxes, state, t_offset, t_begin, time_s,
-            dTdt, tm, tp, tcoef)
-
-        def issue(a, b, shared):
-            ca = _lib.CompositeArgs(
-                dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp), nyb=nyb, nxb=nxb, tcoef_d=_ptr(tcoef),
-                box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
-                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), **shared)
-            _lib.check(self.lib.lec_composite(C.byref(ca)), "lec_composite")
-        self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+        self._composite_chunk("composite_stage", "composite_begin", self._COMPOSITE_WORDS, _lib.CompositeArgs, "lec_composite",
+                              cubes=(tair, u, v, omega), rows=rows, boxes=boxes, levraw=levraw, state=state, t_offset=t_offset,
+                              t_begin=t_begin, time_s=time_s, dTdt=dTdt, tm=tm, tp=tp, tcoef=tcoef)
 
     def composite_finish(self, res: LECResult, state: dict) -> None:
         """``res.composite_*`` from the accumulators of a finished series."""
@@ -993,113 +1058,10 @@ class LECEngine:
         if state["steps"] is not None:
             res.composite_steps = state["steps"]
 
-    # -- longitude x pressure sections of the eddy terms: one fixed box (lec_lonsections), per-step boxes (lec_composite_lonsections) -----
-    @staticmethod
-    def _check_lonsections(boxes, per_step_boxes, steps=None, tm=None, tp=None) -> None:
-        n = len(boxes.boxes) if isinstance(boxes, PreparedBoxes) else len(boxes)
-        if per_step_boxes or n != 1 or steps is not None or tm is not None or tp is not None:
-            raise ValueError("longitude-pressure sections exist for ONE fixed box: a series of per-step boxes (a track, chosen boxes, a "
-                             "packed layout) has no common columns to lay a section on; it has composite_lon_sections=True")
-
-    def _lonsec_begin(self, t_total: int, nyb: int, nxb: int, device, keep_steps: bool) -> dict:
-        """The accumulators of the longitude x pressure sections of ``t_total`` steps on ``nl`` levels x ``nxb`` columns, zeroed."""
-        f64 = dict(dtype=torch.float64, device=device)
-        nl = int(self.level.size)
-        return dict(t_total=int(t_total), nyb=nyb, nxb=nxb, lonsecsum=torch.zeros((_lib.LEC_NMAP, nl, nxb), **f64),
-                    steps=torch.empty((t_total, _lib.LEC_NMAP, nl, nxb), **f64) if keep_steps else None, work=None, coef=None)
-
-    def _lonsec_sub(self, nl: int, nyb: int, nxb: int, t_count: int) -> int:
-        """Steps per sub-call of a chunk of ``t_count`` steps: as many as keep the sections and row factors within ``MAP_CHUNK_BYTES``."""
-        per_step = 8 * (_lib.LEC_NMAP * nl * nxb + nl * nyb * _lib.LEC_MAPS_NCOEF)
-        return max(1, min(t_count, int(self.MAP_CHUNK_BYTES) // per_step))
-
-    def _lonsec_stage(self, cubes, rows: torch.Tensor, levraw: torch.Tensor, state: dict, t_offset: int, t_begin: int, issue) -> None:
-        """``_mapcol_stage`` for the two longitude x pressure calls: ``levraw``'s check, the cut of the chunk into sub-calls whose sections
-        and row factors stay within ``MAP_CHUNK_BYTES``, the workspaces grown to a sub-call, and the sub-calls in time order:
-        ``issue(a, b, shared)`` calls on the chunk's steps [a, b), ``shared`` the fields both args structs have."""
-        tair, u, v, omega = cubes
-        nt, nl, ny, nx = (int(x) for x in tair.shape)
-        t_count, nyb, nxb = int(rows.shape[0]), state["nyb"], state["nxb"]
-        if (levraw.shape != (t_count, nl, _lib.LEC_NLEVRAW) or levraw.dtype != torch.float64 or levraw.device != rows.device
-                or not levraw.is_contiguous()):
-            raise ValueError("levraw must be a contiguous fp64 [t_count, nl, 40] tensor on the rows' device")
-        if state["lonsecsum"].shape[1] != nl:
-            raise ValueError("the cubes' levels are not the engine's")
-        f64 = dict(dtype=torch.float64, device=rows.device)
-        sub = self._lonsec_sub(nl, nyb, nxb, t_count)
-        if state["coef"] is None or state["coef"].shape[0] < sub:
-            state["coef"] = torch.empty((sub, nl, nyb, _lib.LEC_MAPS_NCOEF), **f64)
-        if state["steps"] is None and (state["work"] is None or state["work"].shape[0] < sub):
-            state["work"] = torch.empty((sub, _lib.LEC_NMAP, nl, nxb), **f64)
-        for a in range(0, t_count, sub):
-            b = min(t_count, a + sub)
-            sec = state["steps"][t_offset + a: t_offset + b] if state["steps"] is not None else state["work"][: b - a]
-            shared = dict(
-                tair_d=_ptr(tair), u_d=_ptr(u), v_d=_ptr(v), omega_d=_ptr(omega),
-                dtype=_lib.LEC_F64 if tair.dtype == torch.float64 else _lib.LEC_F32, nt=nt, nl=nl, ny=ny, nx=nx,
-                t_begin=t_begin + a, t_count=b - a, reserved0=0, rows_d=_ptr(rows[a:b]), levraw_d=_ptr(levraw[a:b]),
-                levtab_d=_ptr(self._levtab), levtab2_d=_ptr(self._levtab2), coef_d=_ptr(state["coef"]), lonsec_d=_ptr(sec),
-                lonsecsum_d=_ptr(state["lonsecsum"]), stream=C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-            with torch.cuda.device(rows.device):
-                issue(a, b, shared)
-
-    def lonsection_begin(self, t_total: int, boxes, device, *, keep_steps: bool = False) -> dict:
-        """The accumulators of the longitude x pressure sections of a series of ``t_total`` steps on the fixed box ``boxes`` (zeroed once,
-        here): ``lonsection_stage`` adds every chunk to them, ``lonsection_finish`` turns them into the result's fields."""
-        self._check_lonsections(boxes, False)
-        bx, bt, _ = self._resolve_boxes(boxes)
-        iw, ie, js, jn = bx[0]
-        nyb, nxb = jn - js + 1, ie - iw + 1
-        if bt.nyb_max != nyb:
-            raise ValueError("longitude-pressure sections: the box's records must have the box's own row count (prepare_boxes without nyb_min)")
-        if not bt.lon_uniform:
-            raise ValueError("longitude-pressure sections need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
-        if nxb < 3:
-            raise ValueError("longitude-pressure sections need at least 3 box columns")
-        return self._lonsec_begin(t_total, nyb, nxb, device, keep_steps)
-
-    def lonsection_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor, boxes,
-                         levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None, tcoef: Optional[torch.Tensor] = None,
-                         t_begin: int = 0) -> None:
-        """``lec_lonsections`` on a chunk, with ``map_stage``'s arguments: the time sums are added to ``state["lonsecsum"]`` and, when
-        kept, the steps written to ``state["steps"][t_offset: t_offset + t_count]``.  A chunk whose sections and row factors exceed
-        ``MAP_CHUNK_BYTES`` is cut into sub-calls.  Chunks must come in time order; every number is independent of how the series is cut,
-        bit for bit."""
-        self._check_fields([tair, u, v, omega], None)
-        nt, t_count = int(tair.shape[0]), int(rows.shape[0])
-        bx, bt, dev = self._stage2_input(rows, boxes)
-        self._check_lonsections(bx, False)
-        iw, ie, js, jn = bx[0]
-        nyb, nxb = jn - js + 1, ie - iw + 1
-        if (nyb != state["nyb"] or nxb != state["nxb"] or bt.nyb_max != nyb
-                or not (0 <= t_offset and t_offset + t_count <= state["t_total"])):
-            raise ValueError("lonsection_stage: the chunk does not fit the series and box lonsection_begin was given")
-        if not (0 <= t_begin and t_begin + t_count <= nt):
-            raise ValueError("lonsection_stage: [t_begin, t_begin + t_count) lies outside the cubes")
-        if rows.device != tair.device:
-            raise ValueError("lonsection_stage: rows and fields on one device")
-        tcoef = self._cube_tcoef("lonsection_stage", time_s, tcoef, nt, tair.device)
-
-        def issue(a, b, shared):
-            la = _lib.LonSectionsArgs(iw=iw, ie=ie, js=js, jn=jn, ring=1 if bt.ring else 0, lattab2_d=_ptr(dev["lattab2"]),
-                                      lattab_d=_ptr(dev["lattab"]), tcoef_d=_ptr(tcoef), inv_hdeg=float(bt.boxtab[0, 2]), **shared)
-            _lib.check(self.lib.lec_lonsections(C.byref(la)), "lec_lonsections")
-        self._lonsec_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
-
-    def lonsection_finish(self, res: LECResult, state: dict) -> None:
-        """``res.lonsection_*`` from the accumulators of a finished series."""
-        res.lonsection_mean = state["lonsecsum"] / float(state["t_total"])
-        if state["steps"] is not None:
-            res.lonsection_steps = state["steps"]
-
     def composite_lonsection_begin(self, t_total: int, boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
         """The accumulators of the composite longitude x pressure sections of a series of ``t_total`` steps whose boxes all have the shape
         of ``boxes``' (zeroed once, here)."""
-        nyb, nxb = self._check_composites(boxes, True, None, boxes.bt.lon_uniform, what=self._COMPOSITE_LONSECTION_WORDS)
-        if boxes.bt.nyb_max != nyb:
-            raise ValueError("composite longitude-pressure sections: the boxes' records must have the boxes' own row count (prepare_boxes "
-                             "without nyb_min)")
-        return self._lonsec_begin(t_total, nyb, nxb, device, keep_steps)
+        return self._composite_begin(self._LONSEC_OUT, self._COMPOSITE_LONSECTION_WORDS, t_total, boxes, device, keep_steps)
 
     def composite_lonsection_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
                                    boxes: PreparedBoxes, levraw: torch.Tensor, state: dict, t_offset: int, *, time_s=None,
@@ -1108,17 +1070,10 @@ class LECEngine:
         """``lec_composite_lonsections`` on a chunk, with ``composite_stage``'s arguments (layouts and the three sources of dT/dt): the
         time sums are added to ``state["lonsecsum"]`` and, when kept, the steps written to ``state["steps"]``.  Chunks must come in time
         order; every number is independent of how the series is cut, bit for bit."""
-        nyb, nxb, dTdt, tcoef, box_host, box_dev, dev = self._composite_chunk(
-            "composite_lonsection_stage", "composite_lonsection_begin", self._COMPOSITE_LONSECTION_WORDS, tair, u, v, omega, rows, boxes,
-            state, t_offset, t_begin, time_s, dTdt, tm, tp, tcoef)
-
-        def issue(a, b, shared):
-            ca = _lib.CompositeLonSectionsArgs(
-                dTdt_d=_ptr(dTdt), tm_d=_ptr(tm), tp_d=_ptr(tp), nyb=nyb, nxb=nxb, tcoef_d=_ptr(tcoef),
-                box_h=C.c_void_p(box_host[a:b].ctypes.data), box_d=_ptr(box_dev[a:b]), boxtab_d=_ptr(dev["boxtab"][a:b]),
-                lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), **shared)
-            _lib.check(self.lib.lec_composite_lonsections(C.byref(ca)), "lec_composite_lonsections")
-        self._lonsec_stage((tair, u, v, omega), rows, levraw, state, t_offset, t_begin, issue)
+        self._composite_chunk("composite_lonsection_stage", "composite_lonsection_begin", self._COMPOSITE_LONSECTION_WORDS,
+                              _lib.CompositeLonSectionsArgs, "lec_composite_lonsections", cubes=(tair, u, v, omega), rows=rows, boxes=boxes,
+                              levraw=levraw, state=state, t_offset=t_offset, t_begin=t_begin, time_s=time_s, dTdt=dTdt, tm=tm, tp=tp,
+                              tcoef=tcoef)
 
     def composite_lonsection_finish(self, res: LECResult, state: dict) -> None:
         """``res.composite_lonsection_*`` from the accumulators of a finished series."""
@@ -1138,18 +1093,7 @@ class LECEngine:
         if sum(sizes) != len(bx) or sum(sizes) != n_rows:
             raise ValueError(f"batch_composites: the sizes sum to {sum(sizes)}, the step table has {n_rows} rows and there are "
                              f"{len(bx)} boxes: one box and one row per step of every track")
-        bx = [tuple(int(x) for x in b) for b in bx]
-        nyb, nxb = bx[0][3] - bx[0][2] + 1, bx[0][1] - bx[0][0] + 1
-        for s, b in enumerate(bx):
-            h, w = b[3] - b[2] + 1, b[1] - b[0] + 1
-            if (h, w) != (nyb, nxb):
-                raise ValueError(f"batch composites need boxes of ONE shape: box {s} has {h} x {w} points (rows x columns), box 0 has "
-                                 f"{nyb} x {nxb}")
-        if nxb < 3:
-            raise ValueError("batch composites need at least 3 box columns")
-        if lon_uniform is False:
-            raise ValueError("batch composites need evenly spaced longitudes: the d/dlon of Q at a point is the uniform axis' difference")
-        return nyb, nxb
+        return LECEngine._one_shape(bx, lon_uniform, "batch composites", "box", "box 0")
 
     def batch_composite_begin(self, sizes: Sequence[int], boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
         """The accumulators of the composites of K tracks whose boxes are ``boxes``, track k owning ``sizes[k]`` consecutive ones (zeroed
@@ -1158,7 +1102,7 @@ class LECEngine:
         nyb, nxb = self._check_batch_composites(boxes, len(boxes.boxes), sizes, boxes.bt.lon_uniform)
         if boxes.bt.nyb_max != nyb:
             raise ValueError("batch composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min above it)")
-        state = self._mapcol_begin(sum(sizes), nyb, nxb, device, keep_steps)
+        state = self._mapcol_begin(self._MAPS_OUT, sum(sizes), nyb, nxb, device, keep_steps)
         state["mapsum"] = torch.zeros((len(sizes), _lib.LEC_NMAP, nyb, nxb), dtype=torch.float64, device=device)
         state["sizes"] = np.ascontiguousarray(sizes, dtype=np.int32)
         state["sizes_dev"] = torch.as_tensor(state["sizes"]).to(device)      # (uploaded here: an upload after the launches would wait for them)
@@ -1205,7 +1149,7 @@ class LECEngine:
         box_host = np.ascontiguousarray(bx, dtype=np.int32)
         # every sub-call [a, b): the tracks it intersects, their offsets relative to a, and the first of their accumulators.  The tables
         # of all sub-calls go to the device in ONE upload before the first launch (an upload between the sub-calls would wait for them)
-        sub, cuts, n_off = self._mapcol_sub(int(rows.shape[1]), state["nyb"], state["nxb"], s_count), {}, 0
+        sub, cuts, n_off = self._mapcol_sub(int(rows.shape[1]), state, s_count), {}, 0
         for a in range(0, s_count, sub):
             lo, hi = t_offset + a, t_offset + min(s_count, a + sub)
             g0, g1 = int(np.searchsorted(seg, lo, side="right")) - 1, int(np.searchsorted(seg, hi, side="left"))

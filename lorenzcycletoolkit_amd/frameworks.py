@@ -402,6 +402,31 @@ def wavenumbers_check(n: int, nx: int) -> None:
         raise ValueError(f"--wavenumbers {n}: at most {LEC_MAX_WAVENUMBERS} (LEC_MAX_WAVENUMBERS)")
 
 
+def _write_labelled_rows(path: str, first: str, columns, names, table) -> None:
+    """``path``: the header line ``first`` and ``columns`` (strings), then one row of ``table`` per entry of ``names``, its label: in one
+    ``format_level_table`` call where the labels have one width, else in one call per row (the same bytes)."""
+    width = len(names[0])
+    with open(path, "wb") as f:
+        f.write((",".join([str(first)] + list(columns)) + "\n").encode("utf-8"))
+        if all(len(x) == width for x in names):
+            f.write(format_level_table(table, ("".join(names).encode("ascii"), width)))
+        else:
+            for name, row in zip(names, np.asarray(table, dtype=np.float64)):
+                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+
+
+def _write_time_table(path: str, first: str, columns, labels, times, table) -> None:
+    """``path``: the header line ``first`` and ``columns`` (strings), then one row of ``table`` per time step under the fixed-width
+    ``labels`` of ``time_labels`` -- or, for time stamps pandas prints at mixed widths, written by pandas itself, as for the per-level
+    tables."""
+    with open(path, "wb") as f:
+        f.write((",".join([str(first)] + list(columns)) + "\n").encode("utf-8"))
+        if labels[0] is not None:
+            f.write(format_level_table(table, labels))
+    if labels[0] is None:
+        pd.DataFrame(table, index=pd.DatetimeIndex(times)).to_csv(path, mode="a", header=None)
+
+
 def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> None:
     """results_wavenumbers/<term>_n.csv for Ae, Ke, Ca, Ce, Ck -- and Ge, and the non-linear transfers S and L (W m-2, positive: wavenumber
     n gains), and the budget's BAe, BKe, dAedt, dKedt, RGe, RKe, when their spectra were asked for --: one row per time step -- the time labels and number formatting of the per-level
@@ -410,7 +435,7 @@ def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> N
                             SPECTRUM_TENDENCY_FILES, SPECTRUM_TERMS)
     os.makedirs(directory, exist_ok=True)
     n = box_obj.spectrum.shape[2]
-    header = ",".join([str(time_name)] + [str(k) for k in range(1, n + 1)] + ["rest"]) + "\n"
+    columns = [str(k) for k in range(1, n + 1)] + ["rest"]
     labels = box_obj.row_labels("fixed")
     files = [(term, box_obj.spectrum[:, i, :], box_obj.spectrum_rest[:, i: i + 1]) for i, term in enumerate(SPECTRUM_TERMS)]
     if box_obj.spectrum_ge is not None:
@@ -423,14 +448,7 @@ def write_spectrum_csvs(box_obj: "BoxData", directory: str, time_name: str) -> N
             shares_, rest_ = getattr(box_obj, field), getattr(box_obj, field + "_rest")
             files += [(term, shares_[:, i, :], rest_[:, i: i + 1]) for i, term in enumerate(names)]
     for term, shares, rest in files:
-        table = np.concatenate([shares, rest], axis=1)
-        path = os.path.join(directory, f"{term}_n.csv")
-        with open(path, "wb") as f:
-            f.write(header.encode("utf-8"))
-            if labels[0] is not None:
-                f.write(format_level_table(table, labels))
-        if labels[0] is None:            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
-            pd.DataFrame(table, index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+        _write_time_table(os.path.join(directory, f"{term}_n.csv"), time_name, columns, labels, box_obj.time, np.concatenate([shares, rest], axis=1))
 
 
 def write_section_csvs(box_obj: "BoxData", directory: str, time_name: str, vert_name: str) -> None:
@@ -444,38 +462,15 @@ def write_section_csvs(box_obj: "BoxData", directory: str, time_name: str, vert_
     os.makedirs(directory, exist_ok=True)
     lats = [repr(float(x)) for x in box_obj.section_latitudes]
     labels = box_obj.row_labels("fixed")
-
-    def fixed_labels(names):
-        width = max(len(x) for x in names)
-        if any(len(x) != width for x in names):      # (labels of mixed widths: one call per row)
-            return None
-        return "".join(names).encode("ascii"), width
-
-    def write(path, first, names, table, lab=None):
-        with open(path, "wb") as f:
-            f.write((",".join([str(first)] + lats) + "\n").encode("utf-8"))
-            lab = fixed_labels(names) if lab is None else lab
-            if lab is not None:
-                f.write(format_level_table(table, lab))
-            else:
-                for name, row in zip(names, np.asarray(table, dtype=np.float64)):
-                    f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
-
     level_names = [repr(float(p)) for p in box_obj.PressureData]
     for i, term in enumerate(SECTION_TERMS):
-        write(os.path.join(directory, f"{term}_lat_lv.csv"), vert_name, level_names, box_obj.section_mean[i])
-        path = os.path.join(directory, f"{term}_lat.csv")
-        if labels[0] is not None:
-            write(path, time_name, None, box_obj.section_lat[:, i, :], lab=labels)
-        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
-            with open(path, "wb") as f:
-                f.write((",".join([str(time_name)] + lats) + "\n").encode("utf-8"))
-            pd.DataFrame(box_obj.section_lat[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+        _write_labelled_rows(os.path.join(directory, f"{term}_lat_lv.csv"), vert_name, lats, level_names, box_obj.section_mean[i])
+        _write_time_table(os.path.join(directory, f"{term}_lat.csv"), time_name, lats, labels, box_obj.time, box_obj.section_lat[:, i, :])
     if box_obj.section_spec_lat is not None:
         nf, n1 = box_obj.section_spec_lat.shape[:2]
         names = [str(k) for k in range(1, n1)] + ["rest"]
         for i, term in enumerate(LECEngine.SECTION_SPEC_TERMS[:nf]):
-            write(os.path.join(directory, f"{term}_n_lat.csv"), "n", names, box_obj.section_spec_lat[i])
+            _write_labelled_rows(os.path.join(directory, f"{term}_n_lat.csv"), "n", lats, names, box_obj.section_spec_lat[i])
 
 
 def write_map_csvs(box_obj: "BoxData", directory: str, time_name: str, lat_name: str) -> None:
@@ -488,24 +483,9 @@ def write_map_csvs(box_obj: "BoxData", directory: str, time_name: str, lat_name:
     lons = [repr(float(x)) for x in box_obj.map_longitudes]
     lat_names = [repr(float(x)) for x in box_obj.map_latitudes]
     labels = box_obj.row_labels("fixed")
-
-    def header(path, first):
-        with open(path, "wb") as f:
-            f.write((",".join([str(first)] + lons) + "\n").encode("utf-8"))
-
     for i, term in enumerate(MAP_TERMS):
-        path = os.path.join(directory, f"{term}_lat_lon.csv")
-        header(path, lat_name)
-        with open(path, "ab") as f:      # (latitude labels of mixed widths: one call per row)
-            for name, row in zip(lat_names, np.asarray(box_obj.map_mean[i], dtype=np.float64)):
-                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
-        path = os.path.join(directory, f"{term}_lon.csv")
-        header(path, time_name)
-        if labels[0] is not None:
-            with open(path, "ab") as f:
-                f.write(format_level_table(box_obj.map_lon[:, i, :], labels))
-        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
-            pd.DataFrame(box_obj.map_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+        _write_labelled_rows(os.path.join(directory, f"{term}_lat_lon.csv"), lat_name, lons, lat_names, box_obj.map_mean[i])
+        _write_time_table(os.path.join(directory, f"{term}_lon.csv"), time_name, lons, labels, box_obj.time, box_obj.map_lon[:, i, :])
 
 
 def composites_check(lat, lon, boxes, flag: str = "--composites", lat_too: bool = True) -> tuple:
@@ -547,19 +527,8 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
     write_composite_mean_csvs(box_obj.composite_mean, box_obj.composite_dlat, box_obj.composite_dlon, directory)
     lons = [repr(float(x)) for x in box_obj.composite_dlon]
     labels = box_obj.row_labels("fixed")
-
-    def header(path, first):
-        with open(path, "wb") as f:
-            f.write((",".join([str(first)] + lons) + "\n").encode("utf-8"))
-
     for i, term in enumerate(MAP_TERMS):
-        path = os.path.join(directory, f"{term}_dlon.csv")
-        header(path, time_name)
-        if labels[0] is not None:
-            with open(path, "ab") as f:
-                f.write(format_level_table(box_obj.composite_lon[:, i, :], labels))
-        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
-            pd.DataFrame(box_obj.composite_lon[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+        _write_time_table(os.path.join(directory, f"{term}_dlon.csv"), time_name, lons, labels, box_obj.time, box_obj.composite_lon[:, i, :])
 
 
 def write_composite_mean_csvs(mean, dlat, dlon, directory: str) -> None:
@@ -568,13 +537,9 @@ def write_composite_mean_csvs(mean, dlat, dlon, directory: str) -> None:
     mean of a batch of tracks (``lec_moving_batch``)."""
     from .constants import MAP_TERMS
     os.makedirs(directory, exist_ok=True)
-    head = (",".join(["dlat"] + [repr(float(x)) for x in dlon]) + "\n").encode("utf-8")
-    lat_names = [repr(float(x)) for x in dlat]
+    columns, lat_names = [repr(float(x)) for x in dlon], [repr(float(x)) for x in dlat]
     for i, term in enumerate(MAP_TERMS):
-        with open(os.path.join(directory, f"{term}_dlat_dlon.csv"), "wb") as f:
-            f.write(head)
-            for name, row in zip(lat_names, np.asarray(mean[i], dtype=np.float64)):      # (labels of mixed widths: one call per row)
-                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+        _write_labelled_rows(os.path.join(directory, f"{term}_dlat_dlon.csv"), "dlat", columns, lat_names, mean[i])
 
 
 def composite_sections_check(lat, boxes, flag: str = "--composite-sections", lat_too: bool = True) -> int:
@@ -607,24 +572,10 @@ def write_composite_section_csvs(box_obj: "BoxData", directory: str, time_name: 
     head = [repr(float(x)) for x in box_obj.composite_section_dlat]
     labels = box_obj.row_labels("fixed")
     level_names = [repr(float(p)) for p in box_obj.PressureData]
-
-    def header(path, first):
-        with open(path, "wb") as f:
-            f.write((",".join([str(first)] + head) + "\n").encode("utf-8"))
-
     for i, term in enumerate(SECTION_TERMS):
-        path = os.path.join(directory, f"{term}_dlat_lv.csv")
-        header(path, vert_name)
-        with open(path, "ab") as f:      # (level labels may have mixed widths: one call per row)
-            for name, row in zip(level_names, np.asarray(box_obj.composite_section_mean[i], dtype=np.float64)):
-                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
-        path = os.path.join(directory, f"{term}_dlat.csv")
-        header(path, time_name)
-        if labels[0] is not None:
-            with open(path, "ab") as f:
-                f.write(format_level_table(box_obj.composite_section_lat[:, i, :], labels))
-        else:                            # time stamps pandas prints at mixed widths: pandas writes the rows, as for the per-level tables
-            pd.DataFrame(box_obj.composite_section_lat[:, i, :], index=pd.DatetimeIndex(box_obj.time)).to_csv(path, mode="a", header=None)
+        _write_labelled_rows(os.path.join(directory, f"{term}_dlat_lv.csv"), vert_name, head, level_names, box_obj.composite_section_mean[i])
+        _write_time_table(os.path.join(directory, f"{term}_dlat.csv"), time_name, head, labels, box_obj.time,
+                          box_obj.composite_section_lat[:, i, :])
 
 
 def _write_lon_lv_csvs(mean, columns, level_names, directory: str, suffix: str, vert_name: str) -> None:
@@ -632,12 +583,9 @@ def _write_lon_lv_csvs(mean, columns, level_names, directory: str, suffix: str, 
     ``write_section_csvs`` labels them, one column per entry of ``columns`` (degrees).  The number format of the ``--sections`` files."""
     from .constants import MAP_TERMS
     os.makedirs(directory, exist_ok=True)
-    head = (",".join([str(vert_name)] + [repr(float(x)) for x in columns]) + "\n").encode("utf-8")
+    columns = [repr(float(x)) for x in columns]
     for i, term in enumerate(MAP_TERMS):
-        with open(os.path.join(directory, f"{term}{suffix}"), "wb") as f:
-            f.write(head)
-            for name, row in zip(level_names, np.asarray(mean[i], dtype=np.float64)):      # (labels of mixed widths: one call per row)
-                f.write(format_level_table(row[None, :], (name.encode("ascii"), len(name))))
+        _write_labelled_rows(os.path.join(directory, f"{term}{suffix}"), vert_name, columns, level_names, mean[i])
 
 
 def write_lon_section_csvs(box_obj: "BoxData", directory: str, vert_name: str) -> None:

@@ -87,6 +87,10 @@ def test_ext4_surface():
     src = read("lorenzcycletoolkit_amd", "csrc", "lec_lonsections.hip")
     assert '#include "lec_mapcol.h"' in src and "lec_mapcol_coef_kernel" in src and "lec_mapcol_sum_kernel" in src
     assert "__shared__" not in src and "atomic" not in src
+    # one text of the point integrand: the file both kernels include
+    csrc = os.path.join(ROOT, "lorenzcycletoolkit_amd", "csrc")
+    assert [n for n in sorted(os.listdir(csrc)) if re.search(r"\bdouble yGe\b", read(csrc, n))] == ["lec_mapcol_point.inc"]
+    assert '#include "lec_mapcol_point.inc"' in src and '#include "lec_mapcol_point.inc"' in read(csrc, "lec_mapcol.h")
 
 
 def test_struct_layouts():
