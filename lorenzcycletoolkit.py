@@ -54,6 +54,10 @@ sum over the box's rows, time steps x box columns).  One system whose boxes all 
 track) and their ensemble mean (``lec_composite_ensemble``).  Every track's tree gets the results_composites/ of its own
 ``-t --trackfile --composites`` run, byte for byte; the batch directory gets results_composites/<term>_dlat_dlon.csv, the mean over the
 tracks of their time-mean composites, and composites.csv -- one results_composites_<rows>x<columns>/ per box shape where shapes differ.
+--batch-composites-phase lifetime:B | peak:L: also phase-aligned ensembles (``lec_composite_phase_sum``, ``lec_composite_phase_ensemble``):
+every track's life cut into B bins, or the tracks aligned on their step of peak |min_max_zeta_850| with L lags on either side; a track
+enters a bin's ensemble where it has a step in it.  The ensemble directory gets phases/ (per bin <term>_dlat_dlon_phase<bb>.csv and
+<term>_sd_dlat_dlon_phase<bb>.csv, phases.csv, phase_members.csv, phase_terms.csv); nothing else changes.
 
 -f [--periodic] --lon-sections: also the longitude-pressure sections of Ae, Ke, Ca, Ce, Ck, Ge (``lec_lonsections``: the maps' integrand
 summed over the box's rows with their area weights instead of over pressure), written to results_lon_sections/<term>_lon_lv.csv (the time
@@ -197,6 +201,15 @@ def create_arg_parser():
                         "box shape where the tracks' shapes differ.  Every other output file is unchanged.  Every track needs boxes of one "
                         "shape along its life and evenly spaced longitudes and latitudes on its own crop.  One GPU, data prepared on the "
                         "host (--ingest auto resolves to host); not with --batch-chunk; one system has --composites")
+    parser.add_argument("--batch-composites-phase", dest="batch_composites_phase", metavar="lifetime:B|peak:L", default=argparse.SUPPRESS,
+                        help="with --batch-composites: also PHASE-ALIGNED ensembles of the composites (lec_composite_phase_sum, "
+                        "lec_composite_phase_ensemble).  A clock gives every track B ranges of its own steps.  lifetime:B cuts every track's "
+                        "life into B bins, step s of n in bin (s * B) // n; peak:L aligns the tracks on their step of peak intensity -- the "
+                        "first step at which |min_max_zeta_850| of the track's *_trackfile is largest -- and takes the 2 L + 1 lags -L .. +L in "
+                        "steps (the tracks need one common, even time spacing).  A track enters a bin's ensemble where it has a step in it.  "
+                        "The ensemble directory gets phases/: <term>_dlat_dlon_phase<bb>.csv (the mean over the bin's tracks of their means "
+                        "over the bin) and <term>_sd_dlat_dlon_phase<bb>.csv (their n - 1 standard deviation) per bin, phases.csv, "
+                        "phase_members.csv and phase_terms.csv (the results CSVs' columns averaged the same way).  No other file changes")
     parser.add_argument("--composite-sections", dest="composite_sections", action="store_true", default=argparse.SUPPRESS,
                         help="with -t --trackfile or -c (one system): also the system-relative latitude-pressure sections of the ten terms "
                         "Az, Ae, Kz, Ke, Cz, Ca, Ck, Ce, Gz and Ge (lec_composite_sections: the row's own contribution to the per-level sums "
@@ -547,6 +560,15 @@ def refuse_batch_chunk_options(args):
 
 def refuse_batch_composites_options(args):
     """--batch-composites is the composites of a batch of tracks held as union cubes on one GPU; said before anything is created."""
+    clock = getattr(args, "batch_composites_phase", None)
+    if clock is not None:
+        if not getattr(args, "batch_composites", False):
+            raise SystemExit("--batch-composites-phase bins the composites of a batch of tracks: it goes with --batch-composites")
+        from lorenzcycletoolkit_amd.batch import parse_phase_clock
+        try:
+            parse_phase_clock(clock)
+        except ValueError as e:
+            raise SystemExit(str(e))
     if not getattr(args, "batch_composites", False):
         return
     many = args.choose and (args.choose_systems is not None or args.choose_starts is not None)

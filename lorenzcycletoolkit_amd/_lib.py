@@ -32,7 +32,7 @@ ORDER_AUTO, ORDER_MEMORY, ORDER_XCD_LAT, ORDER_XCD_TILED = 0, 1, 2, 7
 
 def source_digest() -> str:
     """sha256 (first 16 hex digits) over the kernel sources the library is built from (csrc/*.hip|.h|.inc + include/lec_hip.h,
-    include/lec_hip_ext.h, include/lec_hip_ext2.h, include/lec_hip_ext3.h, include/lec_hip_ext4.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
+    include/lec_hip_ext.h, include/lec_hip_ext2.h, include/lec_hip_ext3.h, include/lec_hip_ext4.h, include/lec_hip_ext5.h, names and contents, sorted): stored with a profile so that a later run can tell whether a stored counter measurement was
     taken on the kernels it runs (the GPU box has the sources but no git history)."""
     import glob
     import hashlib
@@ -44,6 +44,7 @@ def source_digest() -> str:
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext2.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext3.h"))
     files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext4.h"))
+    files.append(os.path.join(os.path.dirname(_HERE), "include", "lec_hip_ext5.h"))
     for f in files:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
@@ -65,6 +66,8 @@ EXT2_EXPORTS = ["lec_composite_sections"]
 EXT3_EXPORTS = ["lec_composite_steps", "lec_composite_ensemble"]
 # calls added after include/lec_hip_ext3.h was closed: declared in include/lec_hip_ext4.h
 EXT4_EXPORTS = ["lec_lonsections", "lec_composite_lonsections"]
+# calls added after include/lec_hip_ext4.h was closed: declared in include/lec_hip_ext5.h
+EXT5_EXPORTS = ["lec_composite_phase_sum", "lec_composite_phase_ensemble"]
 
 
 class Tuning(C.Structure):
@@ -243,6 +246,24 @@ class CompositeLonSectionsArgs(C.Structure):
         ("box_h", C.c_void_p), ("box_d", C.c_void_p), ("boxtab_d", C.c_void_p), ("lattab_d", C.c_void_p), ("lattab2_d", C.c_void_p),
         ("rows_d", C.c_void_p), ("levraw_d", C.c_void_p), ("levtab_d", C.c_void_p), ("levtab2_d", C.c_void_p), ("tcoef_d", C.c_void_p),
         ("coef_d", C.c_void_p), ("lonsec_d", C.c_void_p), ("lonsecsum_d", C.c_void_p), ("stream", C.c_void_p),
+    ]
+
+
+class CompositePhaseSumArgs(C.Structure):
+    """struct lec_composite_phase_sum_args (include/lec_hip_ext5.h)."""
+    _fields_ = [
+        ("col_d", C.c_void_p), ("range_h", C.c_void_p), ("range_d", C.c_void_p), ("phasesum_d", C.c_void_p),
+        ("s_count", C.c_int32), ("nyb", C.c_int32), ("nxb", C.c_int32), ("n_cell", C.c_int32), ("reserved0", C.c_int32),
+        ("stream", C.c_void_p),
+    ]
+
+
+class CompositePhaseEnsembleArgs(C.Structure):
+    """struct lec_composite_phase_ensemble_args (include/lec_hip_ext5.h)."""
+    _fields_ = [
+        ("phasesum_d", C.c_void_p), ("count_h", C.c_void_p), ("count_d", C.c_void_p),
+        ("n_track", C.c_int32), ("n_bin", C.c_int32), ("nyb", C.c_int32), ("nxb", C.c_int32), ("reserved0", C.c_int32),
+        ("mean_d", C.c_void_p), ("ens_d", C.c_void_p), ("spread_d", C.c_void_p), ("stream", C.c_void_p),
     ]
 
 
@@ -435,6 +456,10 @@ def load():
     lib.lec_lonsections.argtypes = [C.POINTER(LonSectionsArgs)]
     lib.lec_composite_lonsections.restype = C.c_int
     lib.lec_composite_lonsections.argtypes = [C.POINTER(CompositeLonSectionsArgs)]
+    lib.lec_composite_phase_sum.restype = C.c_int
+    lib.lec_composite_phase_sum.argtypes = [C.POINTER(CompositePhaseSumArgs)]
+    lib.lec_composite_phase_ensemble.restype = C.c_int
+    lib.lec_composite_phase_ensemble.argtypes = [C.POINTER(CompositePhaseEnsembleArgs)]
     lib.lec_rowstats_steps.restype = C.c_int
     lib.lec_rowstats_steps.argtypes = [C.POINTER(RowstatsArgs), C.c_void_p]
     lib.lec_reduce.restype = C.c_int

@@ -18,6 +18,9 @@ With ``--batch-chunk N`` the union is never decoded or uploaded whole: ``plan_ch
 file steps to stage (T also for the time neighbours its records name in other chunks) and, per group, the records and their
 ``lec_ingest`` step rows; ``ingest.lec_streamed_batch`` streams the file chunk by chunk.
 
+``--batch-composites-phase``: ``phase_ranges`` is the clock that gives every track B ranges of its own steps (``lifetime:B``, ``peak:L``),
+``phase_terms`` the per-bin ensemble mean of the tracks' results.
+
 This module is host-only (NumPy / pandas); ``frameworks.lec_moving_batch`` / ``lec_moving_batch_streamed`` run the plan on the GPU.
 """
 from __future__ import annotations
@@ -203,6 +206,100 @@ def composites_check(plan: BatchPlan) -> Dict[Tuple[int, int], List[int]]:
     return shapes
 
 
+def parse_phase_clock(text) -> Tuple[str, int]:
+    """``--batch-composites-phase``'s value ``lifetime:B`` (B >= 1) or ``peak:L`` (L >= 0) as (kind, number); a ValueError in words
+    otherwise."""
+    if isinstance(text, tuple) and len(text) == 2:
+        kind, num = text
+    else:
+        kind, sep, num = str(text).partition(":")
+        if not sep or not (num[1:] if num[:1] in "+-" else num).isdigit():
+            raise ValueError(f"--batch-composites-phase: '{text}' is not a clock: lifetime:B (B >= 1 bins of the normalised lifetime) or "
+                             f"peak:L (L >= 0 steps on either side of the step of peak intensity)")
+        num = int(num)
+    if kind not in ("lifetime", "peak"):
+        raise ValueError(f"--batch-composites-phase: '{text}' names the clock '{kind}': the clocks are lifetime:B and peak:L")
+    if kind == "lifetime" and num < 1:
+        raise ValueError(f"--batch-composites-phase: lifetime:{num}: a lifetime needs B >= 1 bins")
+    if kind == "peak" and num < 0:
+        raise ValueError(f"--batch-composites-phase: peak:{num}: L >= 0 steps on either side of the peak")
+    return kind, int(num)
+
+
+def lifetime_ranges(n: int, n_bin: int) -> np.ndarray:
+    """int32 [B, 2]: step s of a track of ``n`` steps lies in bin (s * B) // n, so bin b is [ceil(b n / B), ceil((b + 1) n / B)) -- integer
+    arithmetic only.  Every step lies in exactly one bin; a track with n < B has empty bins."""
+    edges = [(b * int(n) + n_bin - 1) // n_bin for b in range(n_bin + 1)]
+    return np.array([[edges[b], edges[b + 1]] for b in range(n_bin)], dtype=np.int32)
+
+
+def peak_step(values) -> int:
+    """The first step at which |value| is largest among the finite values; -1 when there is none."""
+    v = np.abs(np.asarray(values, dtype=np.float64))
+    v = np.where(np.isfinite(v), v, -1.0)
+    return int(np.argmax(v)) if v.size and v.max() >= 0.0 else -1
+
+
+def _spacing(tr) -> np.timedelta64:
+    """The one spacing of the track's time axis; a BatchRefusal naming the track file when it has none."""
+    d = np.diff(np.asarray(tr.time, dtype="datetime64[ns]"))
+    if d.size == 0 or not np.all(d == d[0]):
+        raise BatchRefusal(f"track file {tr.path}: --batch-composites-phase peak:L needs an evenly spaced time axis (a lag in steps must be a "
+                           f"lag in hours), this track's steps are " + ", ".join(sorted({f"{x / np.timedelta64(1, 'h'):g} h" for x in d})) + " apart")
+    return d[0]
+
+
+def phase_ranges(plan, clock, intensities=None) -> np.ndarray:
+    """int32 [K, B, 2]: the clock's B ranges [begin, end) of every track's own step indices (``LECEngine.compute``'s
+    ``batch_composite_phases``).  ``clock``: ``lifetime:B`` / ``peak:L`` or ``parse_phase_clock``'s pair.  ``peak:L``: B = 2 L + 1, bin b
+    holds the single step s_peak + (b - L) where the track has it, s_peak = ``peak_step(intensities[k])`` -- ``intensities``: per track
+    its ``min_max_zeta_850`` series, the column of its ``*_trackfile``.  A track without a finite value, with an uneven time axis or with
+    another spacing than the first track's refuses the batch by name."""
+    kind, num = parse_phase_clock(clock)
+    if kind == "lifetime":
+        return np.stack([lifetime_ranges(tr.n, num) for tr in plan.tracks])
+    if intensities is None or len(intensities) != len(plan.tracks):
+        raise ValueError("phase_ranges: peak:L needs every track's intensities (min_max_zeta_850 per step)")
+    spacing = [_spacing(tr) for tr in plan.tracks]
+    for tr, d in zip(plan.tracks, spacing):
+        if d != spacing[0]:
+            raise BatchRefusal(f"track file {tr.path}: its steps are {d / np.timedelta64(1, 'h'):g} h apart, those of {plan.tracks[0].path} "
+                               f"{spacing[0] / np.timedelta64(1, 'h'):g} h: with --batch-composites-phase peak:L a lag in steps would not be a lag in hours")
+    out = np.zeros((len(plan.tracks), 2 * num + 1, 2), dtype=np.int32)
+    for k, (tr, val) in enumerate(zip(plan.tracks, intensities)):
+        if len(val) != tr.n:
+            raise ValueError(f"phase_ranges: track {k} has {tr.n} steps and {len(val)} intensities")
+        sp = peak_step(val)
+        if sp < 0:
+            raise BatchRefusal(f"track file {tr.path}: no finite min_max_zeta_850 at any step: --batch-composites-phase peak:L has no peak to align it on")
+        for b in range(2 * num + 1):
+            s = sp + b - num
+            out[k, b] = (s, s + 1) if 0 <= s < tr.n else (0, 0)
+    return out
+
+
+def phase_labels(clock, spacing_hours=None) -> List[str]:
+    """The bins' labels in ``phases.csv``: ``lifetime [b/B, (b+1)/B)`` or ``lag -2 steps (-12 h)``."""
+    kind, num = parse_phase_clock(clock)
+    if kind == "lifetime":
+        return [f"lifetime [{b}/{num}, {b + 1}/{num})" for b in range(num)]
+    return [f"lag {l:+d} steps" + ("" if spacing_hours is None else f" ({l * spacing_hours:+g} h)") for l in range(-num, num + 1)]
+
+
+def phase_terms(frames: Sequence[pd.DataFrame], ranges) -> pd.DataFrame:
+    """Per bin the ensemble mean of every column of the tracks' results: each track's mean over its steps in the bin, then the mean over
+    the tracks that have a step there (NaN where none has).  ``frames``: the tracks' results DataFrames, ``ranges`` [K, B, 2].  The
+    per-period cycle the reference's plot scripts form from ``periods.csv``, on host NumPy."""
+    ranges = np.asarray(ranges)
+    columns = list(frames[0].columns)
+    out = np.full((ranges.shape[1], len(columns)), np.nan)
+    for b in range(ranges.shape[1]):
+        per = [np.mean(f[columns].to_numpy(dtype=float)[lo:hi], axis=0) for f, (lo, hi) in zip(frames, ranges[:, b]) if hi > lo]
+        if per:
+            out[b] = np.mean(np.stack(per), axis=0)
+    return pd.DataFrame(out, columns=columns, index=pd.RangeIndex(ranges.shape[1], name="bin"))
+
+
 @dataclass
 class ChunkGroup:
     """One group's records of a chunk (``plan_chunks``), in (track, step) order."""
@@ -258,10 +355,11 @@ def union_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> int:
     return n_fields * itemsize * len(plan.tpos) * len(plan.px.level) * len(plan.lat) * len(plan.lon)
 
 
-def device_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> dict:
+def device_bytes(plan: BatchPlan, n_fields: int, itemsize: int, phase_bins: int = 0) -> dict:
     """Device memory of a batch run (``frameworks.lec_moving_batch``): the union cubes (held throughout), the row records of the
     largest group (one group's stage-1 output at a time: fp64 [boxes, nl, nyb_max, 32]) with stage 2's workspaces, and the packed
-    per-step results of all tracks (kept until the files are written)."""
+    per-step results of all tracks (kept until the files are written).  ``phase_bins`` = B (``--batch-composites-phase``): the results
+    also hold every group's accumulator of the (track, bin) cells [K, B, 6, nyb, nxb] and the bins' ensemble and spread."""
     from . import _lib
     nl = len(plan.px.level)
     cubes = union_bytes(plan, n_fields, itemsize)
@@ -270,6 +368,8 @@ def device_bytes(plan: BatchPlan, n_fields: int, itemsize: int) -> dict:
         n = sum(plan.tracks[k].n for k in members)
         rows = max(rows, 8 * n * nl * (key[0] * _lib.LEC_NSTAT + 8 + _lib.LEC_NLEVRAW))
     results = 8 * sum(tr.n for tr in plan.tracks) * (_lib.LEC_NSCALAR + _lib.LEC_NLEVTAB * nl + 1)
+    if phase_bins:
+        results += 8 * sum((len(members) + 2) * int(phase_bins) * _lib.LEC_NMAP * key[0] * key[1] for key, members in plan.groups.items())
     return {"cubes": cubes, "records": rows, "results": results, "total": cubes + rows + results}
 
 

@@ -77,6 +77,14 @@ class LECResult:
     batch_composite_lon: Optional[torch.Tensor] = None       # [S, 6, nxb] fp64: H_f of every box, in table order
     batch_composite_ensemble: Optional[torch.Tensor] = None  # [6, nyb, nxb] fp64: (mean[0] + mean[1] + ...) / K, tracks ascending
     batch_composite_steps: Optional[torch.Tensor] = None     # [S, 6, nyb, nxb] fp64: C_f of every box (on request)
+    # ... batch_composite_phases=ranges [K, B, 2]: B ranges [begin, end) of every track's own steps, a CELL per (track, bin); a range may be
+    # empty (``lec_composite_phase_sum`` / ``lec_composite_phase_ensemble``).  A track is a MEMBER of the bins in
+    # which it has a step; the ensemble and its spread run over a bin's members
+    batch_phase_mean: Optional[torch.Tensor] = None          # [K, B, 6, nyb, nxb] fp64: the mean over the cell's steps; NaN for an empty cell
+    batch_phase_ensemble: Optional[torch.Tensor] = None      # [B, 6, nyb, nxb] fp64: the members' means, added in track order, / members
+    batch_phase_spread: Optional[torch.Tensor] = None        # [B, 6, nyb, nxb] fp64: the members' n - 1 standard deviation; NaN below 2 members
+    batch_phase_count: Optional[np.ndarray] = None           # host int32 [K, B]: the steps of every cell
+    batch_phase_members: Optional[np.ndarray] = None         # host int32 [B]: the tracks with at least one step in the bin
     # compute(..., per_step_boxes=True, composite_sections=True) on per-step boxes of ONE row count: the system-relative latitude x
     # pressure sections of the ten terms on box-relative rows (``lec_composite_sections``).  With cw of step t's
     # box, sum_j cw_j(t) X_f closes on ``levels[t]`` and sum_j cw_j(t) C_f on ``scalars[t]``
@@ -396,6 +404,7 @@ class LECEngine:
                 composites: bool = False, composite_steps: bool = False,
                 composite_sections: bool = False, composite_section_steps: bool = False,
                 batch_composites: Optional[Sequence[int]] = None, batch_composite_steps: bool = False,
+                batch_composite_phases=None,
                 lon_sections: bool = False, lon_section_steps: bool = False,
                 composite_lon_sections: bool = False, composite_lon_section_steps: bool = False) -> LECResult:
         """All LEC terms for time steps [t_begin, t_begin + t_count) of the cubes: ``rowstats`` then ``reduce``.
@@ -450,6 +459,11 @@ class LECEngine:
         ``batch_composite_lon`` and ``batch_composite_ensemble`` -- and ``batch_composite_steps`` when asked for --, every track's
         composites and their ensemble mean (``batch_composite_stage``: the cubes are read once more).  A track's share has the bits of
         ``composites=True`` on the track's own cube.  It changes no bit of anything else; without it nothing new runs or allocates.
+        ``batch_composite_phases`` = ranges (with ``batch_composites``: an int array [K, B, 2], B ranges [begin, end) of every track's
+        own step indices, 0 <= begin <= end <= sizes[k]; a range may be empty and ranges may overlap): also ``batch_phase_mean``,
+        ``batch_phase_ensemble``, ``batch_phase_spread``, ``batch_phase_count`` and ``batch_phase_members``, every (track, bin) cell's
+        mean composite and per bin the ensemble and spread of the tracks that have a step in it (``lec_composite_phase_sum`` after
+        every ``lec_composite_steps``, then ``lec_composite_phase_ensemble``).  It changes no bit of anything else.
         ``lon_sections`` (what ``maps`` needs: ONE fixed box with evenly spaced longitudes, one process, ``with_q`` and dT/dt from
         ``time_s`` / ``tcoef``): also ``lonsection_mean`` -- and ``lonsection_steps`` when asked for --, the longitude x pressure sections
         of the six eddy terms (``lonsection_stage``: the cubes are read once more; beside ``maps`` each call forms its own row factors).
@@ -457,6 +471,10 @@ class LECEngine:
         when asked for --, the same on the box-relative columns of per-step boxes of ONE shape (``composite_lonsection_stage``).  Neither
         changes a bit of anything else; without them nothing new runs or allocates.
         """
+        if batch_composite_phases is not None:      # in words, before the library or a device is touched
+            if batch_composites is None:
+                raise ValueError("batch_composite_phases: the phases are ranges of the steps of batch_composites=sizes: give the sizes")
+            batch_composite_phases = self._check_batch_phases(batch_composites, batch_composite_phases)
         if lon_section_steps and not lon_sections:
             raise ValueError("lon_section_steps: the per-step sections are part of lon_sections=True")
         if lon_sections:
@@ -589,7 +607,8 @@ class LECEngine:
             self.composite_section_finish(res, cs)
         if batch_composites is not None:
             pb = boxes if isinstance(boxes, PreparedBoxes) else PreparedBoxes(*self._resolve_boxes(boxes))
-            bc = self.batch_composite_begin(batch_composites, pb, rows.device, keep_steps=batch_composite_steps)
+            bc = self.batch_composite_begin(batch_composites, pb, rows.device, keep_steps=batch_composite_steps,
+                                            phases=batch_composite_phases)
             lr = self._workspace(int(rows.shape[0]), int(rows.shape[1]), rows.device)[1].clone()
             self.batch_composite_stage(tair, u, v, omega, rows, pb, lr, bc, 0, steps=steps, tcoef=tcoef, steps_host=steps_host)
             self.batch_composite_finish(res, bc)
@@ -1095,10 +1114,37 @@ class LECEngine:
                              f"{len(bx)} boxes: one box and one row per step of every track")
         return LECEngine._one_shape(bx, lon_uniform, "batch composites", "box", "box 0")
 
-    def batch_composite_begin(self, sizes: Sequence[int], boxes: PreparedBoxes, device, *, keep_steps: bool = False) -> dict:
-        """The accumulators of the composites of K tracks whose boxes are ``boxes``, track k owning ``sizes[k]`` consecutive ones (zeroed
-        once, here): ``batch_composite_stage`` adds every chunk to them, ``batch_composite_finish`` turns them into the result's fields."""
+    @staticmethod
+    def _check_batch_phases(sizes, ranges) -> np.ndarray:
+        """The refusals of ``batch_composite_phases`` that need nothing but the tracks' sizes: returns the ranges as int32 [K, B, 2]."""
         sizes = [int(n) for n in sizes]
+        try:
+            r = np.asarray(ranges)
+        except (ValueError, TypeError):
+            r = np.empty(0, dtype=object)
+        if r.ndim != 3 or r.shape[0] != len(sizes) or r.shape[1] < 1 or r.shape[2] != 2 or r.dtype.kind not in "iu":
+            raise ValueError(f"batch_composite_phases: an integer array [K, B, 2] of B >= 1 ranges [begin, end) for each of the K = {len(sizes)} "
+                             f"tracks, not {getattr(r, 'dtype', None)} {tuple(r.shape)}")
+        r = r.astype(np.int64)
+        for k, n in enumerate(sizes):
+            for b in range(r.shape[1]):
+                lo, hi = int(r[k, b, 0]), int(r[k, b, 1])
+                if lo < 0:
+                    raise ValueError(f"batch_composite_phases: track {k}, bin {b}: the range [{lo}, {hi}) begins before the track's first step")
+                if lo > hi:
+                    raise ValueError(f"batch_composite_phases: track {k}, bin {b}: the range [{lo}, {hi}) has begin > end (an empty range has begin = end)")
+                if hi > n:
+                    raise ValueError(f"batch_composite_phases: track {k}, bin {b}: the range [{lo}, {hi}) ends after the track's {n} steps")
+        return np.ascontiguousarray(r, dtype=np.int32)
+
+    def batch_composite_begin(self, sizes: Sequence[int], boxes: PreparedBoxes, device, *, keep_steps: bool = False, phases=None) -> dict:
+        """The accumulators of the composites of K tracks whose boxes are ``boxes``, track k owning ``sizes[k]`` consecutive ones (zeroed
+        once, here): ``batch_composite_stage`` adds every chunk to them, ``batch_composite_finish`` turns them into the result's fields.
+        ``phases``: ranges [K, B, 2] of the tracks' own steps (``compute``'s ``batch_composite_phases``): also the zeroed accumulator
+        [K, B, 6, nyb, nxb] of the cells' sums."""
+        sizes = [int(n) for n in sizes]
+        if phases is not None:
+            phases = self._check_batch_phases(sizes, phases)
         nyb, nxb = self._check_batch_composites(boxes, len(boxes.boxes), sizes, boxes.bt.lon_uniform)
         if boxes.bt.nyb_max != nyb:
             raise ValueError("batch composites: the boxes' records must have the boxes' own row count (prepare_boxes without nyb_min above it)")
@@ -1107,6 +1153,13 @@ class LECEngine:
         state["sizes"] = np.ascontiguousarray(sizes, dtype=np.int32)
         state["sizes_dev"] = torch.as_tensor(state["sizes"]).to(device)      # (uploaded here: an upload after the launches would wait for them)
         state["seg"] = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int64)
+        if phases is not None:
+            n_bin = int(phases.shape[1])
+            state["phasesum"] = torch.zeros((len(sizes), n_bin, _lib.LEC_NMAP, nyb, nxb), dtype=torch.float64, device=device)
+            # the cells' ranges in the batch's boxes, cell = k * B + b
+            state["phase_abs"] = (phases.astype(np.int64) + state["seg"][:-1, None, None]).reshape(-1, 2)
+            state["phase_count"] = np.ascontiguousarray(phases[:, :, 1] - phases[:, :, 0], dtype=np.int32)
+            state["phase_count_dev"] = torch.as_tensor(state["phase_count"]).to(device)
         return state
 
     def batch_composite_stage(self, tair: torch.Tensor, u: torch.Tensor, v: torch.Tensor, omega: torch.Tensor, rows: torch.Tensor,
@@ -1155,7 +1208,19 @@ class LECEngine:
             g0, g1 = int(np.searchsorted(seg, lo, side="right")) - 1, int(np.searchsorted(seg, hi, side="left"))
             cuts[a] = (g0, g1, n_off, np.ascontiguousarray(np.clip(seg[g0: g1 + 1], lo, hi) - lo, dtype=np.int32))
             n_off += g1 - g0 + 1
-        seg_dev = torch.as_tensor(np.concatenate([c[3] for c in cuts.values()])).to(rows.device)
+        # the phases' cells likewise: the contiguous run from the first to the last cell whose range holds a box of the sub-call, the
+        # ranges clipped to it and relative to it (a cell of the run that holds none is empty there and is not written)
+        pabs, pcuts, n_cell = state.get("phase_abs"), {}, 0
+        if pabs is not None:
+            for a in range(0, s_count, sub):
+                lo, hi = t_offset + a, t_offset + min(s_count, a + sub)
+                hit = np.flatnonzero((np.minimum(pabs[:, 1], hi) > np.maximum(pabs[:, 0], lo)))
+                if hit.size:
+                    c0, c1 = int(hit[0]), int(hit[-1]) + 1
+                    pcuts[a] = (c0, c1, n_cell, np.ascontiguousarray(np.clip(pabs[c0:c1], lo, hi) - lo, dtype=np.int32))
+                    n_cell += c1 - c0
+        tabs = torch.as_tensor(np.concatenate([c[3] for c in cuts.values()] + [c[3].ravel() for c in pcuts.values()])).to(rows.device)
+        seg_dev, range_dev = tabs[:n_off], tabs[n_off:].view(-1, 2)
 
         def issue(a, b, shared):
             g0, g1, off, seg_host = cuts[a]
@@ -1167,6 +1232,13 @@ class LECEngine:
                 lattab_d=_ptr(dev["lattab"][a:b]), lattab2_d=_ptr(dev["lattab2"][a:b]), tcoef_d=_ptr(tcoef[a:b]),
                 mapsum_d=_ptr(state["mapsum"][g0:]), **shared)
             _lib.check(self.lib.lec_composite_steps(C.byref(ca)), "lec_composite_steps")
+            if a in pcuts:      # the cells' sums from the columns this sub-call wrote, on its stream
+                c0, c1, off, range_host = pcuts[a]
+                pa = _lib.CompositePhaseSumArgs(
+                    col_d=shared["col_d"], range_h=C.c_void_p(range_host.ctypes.data), range_d=_ptr(range_dev[off: off + c1 - c0]),
+                    phasesum_d=_ptr(state["phasesum"].view(-1, _lib.LEC_NMAP, state["nyb"], state["nxb"])[c0:]), s_count=b - a,
+                    nyb=state["nyb"], nxb=state["nxb"], n_cell=c1 - c0, reserved0=0, stream=shared["stream"])
+                _lib.check(self.lib.lec_composite_phase_sum(C.byref(pa)), "lec_composite_phase_sum")
         self._mapcol_stage((tair, u, v, omega), rows, levraw, state, t_offset, 0, issue)
 
     def batch_composite_finish(self, res: LECResult, state: dict) -> None:
@@ -1185,6 +1257,19 @@ class LECEngine:
         res.batch_composite_lon = state["hov"]
         if state["steps"] is not None:
             res.batch_composite_steps = state["steps"]
+        if "phasesum" in state:
+            ps, cnt = state["phasesum"], state["phase_count"]
+            f64 = dict(dtype=torch.float64, device=ps.device)
+            pens, spread = torch.empty(tuple(ps.shape[1:]), **f64), torch.empty(tuple(ps.shape[1:]), **f64)
+            pe = _lib.CompositePhaseEnsembleArgs(
+                phasesum_d=_ptr(ps), count_h=C.c_void_p(cnt.ctypes.data), count_d=_ptr(state["phase_count_dev"]), n_track=int(ps.shape[0]),
+                n_bin=int(ps.shape[1]), nyb=state["nyb"], nxb=state["nxb"], reserved0=0, mean_d=_ptr(ps), ens_d=_ptr(pens),
+                spread_d=_ptr(spread), stream=C.c_void_p(torch.cuda.current_stream(ps.device).cuda_stream))
+            with torch.cuda.device(ps.device):
+                _lib.check(self.lib.lec_composite_phase_ensemble(C.byref(pe)), "lec_composite_phase_ensemble")
+            res.batch_phase_mean, res.batch_phase_ensemble, res.batch_phase_spread = ps, pens, spread
+            res.batch_phase_count = cnt.copy()
+            res.batch_phase_members = (cnt >= 1).sum(axis=0).astype(np.int32)
 
     # -- zonal-wavenumber spectra on a ring ----------------------------------------------------------------------------------------
     # assembled row records (N wavenumbers x a chunk of time steps) resident at once; the fused form: the chunk's spectral records

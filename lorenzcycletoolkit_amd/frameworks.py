@@ -531,15 +531,15 @@ def write_composite_csvs(box_obj: "BoxData", directory: str, time_name: str) -> 
         _write_time_table(os.path.join(directory, f"{term}_dlon.csv"), time_name, lons, labels, box_obj.time, box_obj.composite_lon[:, i, :])
 
 
-def write_composite_mean_csvs(mean, dlat, dlon, directory: str) -> None:
+def write_composite_mean_csvs(mean, dlat, dlon, directory: str, name: str = "{term}_dlat_dlon.csv") -> None:
     """``<term>_dlat_dlon.csv`` for each of the six eddy terms in ``directory``: ``mean`` [6, rows, columns], one row per box row, one
     column per box column, labelled by the offsets ``dlat`` / ``dlon``.  The time-mean files of ``write_composite_csvs``, and the ensemble
-    mean of a batch of tracks (``lec_moving_batch``)."""
+    mean of a batch of tracks (``lec_moving_batch``); ``name``: the files' name where it is another (the phases of a batch)."""
     from .constants import MAP_TERMS
     os.makedirs(directory, exist_ok=True)
     columns, lat_names = [repr(float(x)) for x in dlon], [repr(float(x)) for x in dlat]
     for i, term in enumerate(MAP_TERMS):
-        _write_labelled_rows(os.path.join(directory, f"{term}_dlat_dlon.csv"), "dlat", columns, lat_names, mean[i])
+        _write_labelled_rows(os.path.join(directory, name.format(term=term)), "dlat", columns, lat_names, mean[i])
 
 
 def composite_sections_check(lat, boxes, flag: str = "--composite-sections", lat_too: bool = True) -> int:
@@ -1079,14 +1079,21 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
     ``composite_shapes`` (``--batch-composites``): what ``batch.composites_check(plan)`` returned, {(rows, columns): tracks}.  Every
     group's call then also composites its tracks (``compute(batch_composites=...)``); every track's tree gets the ``results_composites/``
     of its own ``--composites`` run, and ``batch_dir`` the ensemble mean of every box shape (``_write_batch_composites``).  The check
-    has left every track with one box shape on evenly spaced longitudes, so the plan's groups ARE those shapes."""
+    has left every track with one box shape on evenly spaced longitudes, so the plan's groups ARE those shapes.
+    ``args.batch_composites_phase`` (``--batch-composites-phase``, with ``composite_shapes``): a clock ``lifetime:B`` / ``peak:L``; the
+    groups' calls also fold the composites over the clock's ranges (``batch.phase_ranges``, ``compute(batch_composite_phases=...)``) and
+    every ensemble directory gets ``phases/`` (``_write_batch_phases``).  The peak clock needs every track's ``min_max_zeta_850``: the
+    tracks' 850-hPa diagnostics are then evaluated before the groups' calls, and the write loop reuses them."""
     from . import batch as bt
     from .diagnostics import track_diagnostics
     dev = _device(args)
     time_name = variable_list_df.loc["Time"]["Variable"]
     vert_name = variable_list_df.loc["Vertical Level"]["Variable"]
     arrays, common, phi_scale = host_fields(data, variable_list_df)
-    mem = bt.device_bytes(plan, len(arrays), np.dtype(common).itemsize)
+    with_composites = composite_shapes is not None
+    clock = bt.parse_phase_clock(args.batch_composites_phase) if with_composites and getattr(args, "batch_composites_phase", None) else None
+    mem = bt.device_bytes(plan, len(arrays), np.dtype(common).itemsize,
+                          **({"phase_bins": clock[1] if clock[0] == "lifetime" else 2 * clock[1] + 1} if clock else {}))
     need = mem["total"]
     free = torch.cuda.mem_get_info(dev)[0]
     if need > free // 2:
@@ -1098,7 +1105,17 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
     app_logger.info(f"Batch of {len(plan.tracks)} tracks: union of {len(plan.tpos)} time steps on a {len(plan.lat)} x {len(plan.lon)} crop "
                     f"({need / 1e9:.2f} GB on the device), {len(plan.groups)} group(s) of equal box extents and longitude formulation")
     results = [None] * len(plan.tracks)
-    with_composites = composite_shapes is not None
+    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
+
+    def diagnostics_of(tr):
+        # the 850-hPa diagnostics on the track's own crop: the stencil's end coefficients depend on the crop's edges
+        return track_diagnostics(bt.track_view(data, tr), variable_list_df, tr.limits, tr.track, use_track_zeta=bool(getattr(args, "zeta", False)),
+                                 device=dev, formulation=form)
+    found, ranges, phase_out = None, None, []
+    if clock is not None:
+        if clock[0] == "peak":
+            found = [diagnostics_of(tr) for tr in plan.tracks]
+        ranges = bt.phase_ranges(plan, clock, None if found is None else [[p["min_max_zeta_850"] for p in f] for f in found])
     if with_composites and {k[:2]: v for k, v in plan.groups.items()} != composite_shapes:
         raise ValueError("composite_shapes: not batch.composites_check's result for this plan")
     composites, ensembles = [None] * len(plan.tracks), []
@@ -1110,7 +1127,8 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
         pb = engine.prepare_boxes(boxes, nyb_min=nyb, lon_uniform=uniform)      # (the formulation of the tracks' own crops)
         res = engine.compute(cubes[0], cubes[1], cubes[2], cubes[3], cubes[4], pb, phi_scale=phi_scale, per_step_boxes=True,
                              drop_any_time=False, steps=steps, tcoef=tcoef,
-                             **({"batch_composites": [tr.n for tr in trs]} if with_composites else {}))
+                             **({"batch_composites": [tr.n for tr in trs]} if with_composites else {}),
+                             **({"batch_composite_phases": ranges[members]} if ranges is not None else {}))
         a = 0
         for n, (k, tr) in enumerate(zip(members, trs)):
             b = a + tr.n
@@ -1120,9 +1138,11 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
             a = b
         if with_composites:
             ensembles.append(((nyb, nxb), members, res.batch_composite_ensemble.cpu().numpy()))
+        if ranges is not None:
+            phase_out.append((res.batch_phase_ensemble.cpu().numpy(), res.batch_phase_spread.cpu().numpy(), res.batch_phase_count,
+                              res.batch_phase_members))
     torch.cuda.synchronize(dev)
     phases.mark("ingest_compute_gather")
-    form = getattr(args, "vorticity_form", None) or "metpy_no_crs"
     written = []
     for k, (tr, res, (results_subdirectory, figures_directory, vl_directory)) in enumerate(zip(plan.tracks, results, directories)):
         view = bt.track_view(data, tr)
@@ -1130,9 +1150,7 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
         holder = _TrackResult(view, variable_list_df, res, results_subdirectory, vl_directory)
         if int(holder.nanflag.sum()):
             app_logger.warning(f"{tr.path}: NaN level values were interpolated/dropped per time step (_handle_nans semantics)")
-        # the 850-hPa diagnostics on the track's own crop: the stencil's end coefficients depend on the crop's edges
-        positions = track_diagnostics(view, variable_list_df, tr.limits, tr.track, use_track_zeta=bool(getattr(args, "zeta", False)),
-                                      device=dev, formulation=form)
+        positions = diagnostics_of(tr) if found is None else found[k]
         app_logger.info(f"Track {tr.path}: {tr.n} time steps -> {results_subdirectory}")
         written.append(_write_moving_results(holder, pd.DatetimeIndex(view.time), view.time_s, tr.limits, positions, results_subdirectory,
                                              form, app_logger, args, lon_origin=ds.lon_origin_of_axis(view.lon)))
@@ -1142,7 +1160,50 @@ def lec_moving_batch(data: ds.LECDataset, variable_list_df: pd.DataFrame, plan, 
             write_composite_csvs(holder, os.path.join(results_subdirectory, "results_composites"), time_name)
     if with_composites:
         _write_batch_composites(plan, data, ensembles, composites, directories, batch_dir, app_logger)
+    if ranges is not None:
+        _write_batch_phases(plan, data, ensembles, phase_out, clock, ranges, found, [df for _, df in written], batch_dir, app_logger)
     return written
+
+
+def _write_batch_phases(plan, data, ensembles, phase_out, clock, ranges, found, frames, batch_dir, app_logger):
+    """``phases/`` in every ensemble directory of a batch (``_write_batch_composites``' directories): per bin ``<term>_dlat_dlon_phase<bb>.csv``
+    (the ensemble over the bin's members) and ``<term>_sd_dlat_dlon_phase<bb>.csv`` (their n - 1 standard deviation) in
+    ``write_composite_mean_csvs``' layout and labels; ``phases.csv`` (per bin: label, members, total steps), ``phase_members.csv`` (per
+    track its steps in every bin; with the peak clock also its peak's step, time and value) and ``phase_terms.csv``
+    (``batch.phase_terms`` of the tracks' results)."""
+    from . import batch as bt
+    n_bin = int(ranges.shape[1])
+    width = max(2, len(str(n_bin - 1)))
+    hours = None
+    if clock[0] == "peak":
+        t = plan.tracks[0].time
+        hours = float((t[1] - t[0]) / np.timedelta64(1, "h"))
+    labels = bt.phase_labels(clock, hours)
+    for ((nyb, nxb), members, _), (ens, spread, count, n_members) in zip(ensembles, phase_out):
+        name = "results_composites" if len(ensembles) == 1 else f"results_composites_{nyb}x{nxb}"
+        directory = os.path.join(batch_dir, name, "phases")
+        dlat, dlon = composite_offsets(data.lat, data.lon, plan.tracks[members[0]].boxes[0])
+        for b in range(n_bin):
+            bb = f"{b:0{width}d}"
+            write_composite_mean_csvs(ens[b], dlat, dlon, directory, name="{term}_dlat_dlon_phase" + bb + ".csv")
+            write_composite_mean_csvs(spread[b], dlat, dlon, directory, name="{term}_sd_dlat_dlon_phase" + bb + ".csv")
+        pd.DataFrame({"bin": np.arange(n_bin), "label": labels, "members": np.asarray(n_members, dtype=int),
+                      "steps": np.asarray(count, dtype=int).sum(axis=0)}).to_csv(os.path.join(directory, "phases.csv"), index=False)
+        table = {"trackfile": [plan.tracks[k].path for k in members], "steps": [plan.tracks[k].n for k in members]}
+        if found is not None:
+            peaks = [bt.peak_step([p["min_max_zeta_850"] for p in found[k]]) for k in members]
+            table["s_peak"] = peaks
+            table["peak_time"] = [str(pd.Timestamp(plan.tracks[k].time[s])) for k, s in zip(members, peaks)]
+            table["peak_min_max_zeta_850"] = [repr(float(found[k][s]["min_max_zeta_850"])) for k, s in zip(members, peaks)]
+        for b in range(n_bin):
+            table[f"phase{b:0{width}d}"] = np.asarray(count, dtype=int)[:, b]
+        pd.DataFrame(table).to_csv(os.path.join(directory, "phase_members.csv"), index=False)
+        terms = bt.phase_terms([frames[k] for k in members], ranges[members])
+        terms.insert(0, "label", labels)
+        terms.to_csv(os.path.join(directory, "phase_terms.csv"))
+        app_logger.info(f"--batch-composites-phase {clock[0]}:{clock[1]}: {n_bin} bin(s) over {len(members)} track(s) of {nyb} x {nxb} box points "
+                        f"(lec_composite_phase_sum, lec_composite_phase_ensemble), members per bin {np.asarray(n_members).tolist()}, written to {directory}")
+    return None
 
 
 def _write_batch_composites(plan, data, ensembles, composites, directories, batch_dir, app_logger):

@@ -17,8 +17,13 @@ the streamed one (``--batch-chunk N``), ``--reps`` runs of each in turn after on
 streamed run's own phase seconds from its log, and whether every file of every track's tree is the same bytes.  ``--host-cli PATH``: the
 host-prepared leg runs another checkout's lorenzcycletoolkit.py (the parent commit's, for a comparison that does not rest on this tree).
 
-Reads nothing outside the tree.  Usage: python tools/bench_batch.py [--tracks K] [--steps 40] [--reps 5] | --cli [--tracks K]
-       [--batch-chunk N [--reps 5] [--host-cli PATH]]
+``--batch-composites``: the batch's ``compute`` calls also composite their tracks (``batch_composites=sizes``; the loop leg and the bits
+check are as without it).  ``--batch-composites-phase lifetime:B`` (with it): also the phase-aligned ensembles
+(``batch_composite_phases=``), and the JSON line carries the two phase kernels' own times, HIP events around ``lec_composite_phase_sum``
+over all of the batch's boxes in one call and around ``lec_composite_phase_ensemble``, on buffers of the batch's shapes.
+
+Reads nothing outside the tree.  Usage: python tools/bench_batch.py [--tracks K] [--steps 40] [--reps 5] [--batch-composites
+       [--batch-composites-phase lifetime:B]] | --cli [--tracks K] [--batch-chunk N [--reps 5] [--host-cli PATH]]
 """
 import argparse
 import json
@@ -54,6 +59,43 @@ def _tracks(k, n, nt, lat, lon, rng):
 def _events():
     a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     return a, b
+
+
+def _phase_kernel_times(eng, group, dev, reps):
+    """The two phase kernels alone on buffers of the group's shapes: lec_composite_phase_sum over all the group's boxes in ONE call (the
+    engine issues it per sub-call) and lec_composite_phase_ensemble; HIP events around each call, medians and quartiles over ``reps``."""
+    import ctypes as C
+
+    from lorenzcycletoolkit_amd import _lib
+    members, pb, st, tc, extra = group
+    sizes, ranges = extra["batch_composites"], extra["batch_composite_phases"]
+    state = eng.batch_composite_begin(sizes, pb, dev, phases=ranges)
+    nyb, nxb, S = state["nyb"], state["nxb"], int(sum(sizes))
+    col = torch.randn((S, _lib.LEC_NMAP, nyb, nxb), dtype=torch.float64, device=dev)
+    rng_h = np.ascontiguousarray(state["phase_abs"], dtype=np.int32)
+    rng_d = torch.as_tensor(rng_h).to(dev)
+    ps, cnt = state["phasesum"], state["phase_count"]
+    ens, spread = torch.empty_like(ps[0]), torch.empty_like(ps[0])
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    sa = _lib.CompositePhaseSumArgs(col_d=p(col), range_h=C.c_void_p(rng_h.ctypes.data), range_d=p(rng_d), phasesum_d=p(ps), s_count=S, nyb=nyb,
+                                    nxb=nxb, n_cell=int(rng_h.shape[0]), reserved0=0, stream=stream)
+    mean = torch.empty_like(ps)
+    ea = _lib.CompositePhaseEnsembleArgs(phasesum_d=p(ps), count_h=C.c_void_p(cnt.ctypes.data), count_d=p(state["phase_count_dev"]),
+                                         n_track=int(ps.shape[0]), n_bin=int(ps.shape[1]), nyb=nyb, nxb=nxb, reserved0=0, mean_d=p(mean),
+                                         ens_d=p(ens), spread_d=p(spread), stream=stream)
+    ts, te = [], []
+    for r in range(reps + 2):                   # (two warm-up rounds)
+        e = [_events(), _events()]
+        e[0][0].record(); _lib.check(eng.lib.lec_composite_phase_sum(C.byref(sa)), "lec_composite_phase_sum"); e[0][1].record()
+        e[1][0].record(); _lib.check(eng.lib.lec_composite_phase_ensemble(C.byref(ea)), "lec_composite_phase_ensemble"); e[1][1].record()
+        torch.cuda.synchronize()
+        if r >= 2:
+            ts.append(e[0][0].elapsed_time(e[0][1]))
+            te.append(e[1][0].elapsed_time(e[1][1]))
+    q = lambda v: {"median": float(np.median(v)), "iqr": [float(np.percentile(v, 25)), float(np.percentile(v, 75))]}
+    return {"boxes": S, "cells": int(rng_h.shape[0]), "box_points": [nyb, nxb], "lec_composite_phase_sum": q(ts), "lec_composite_phase_ensemble": q(te),
+            "bytes_read_by_phase_sum": int(8 * S * _lib.LEC_NMAP * nyb * nxb)}
 
 
 CLI_FILE = "synthetic.write_classic_nc: float32 classic NetCDF, 7 levels, 1 degree, 40 three-hourly steps"
@@ -168,6 +210,8 @@ def main():
     ap.add_argument("--dtype", choices=["float32", "float64"], default="float32")
     ap.add_argument("--seed", type=int, default=2024)
     ap.add_argument("--only-steps-kernel", action="store_true", help="run the batch's stage-1 launches alone (profiler runs)")
+    ap.add_argument("--batch-composites", action="store_true", help="the batch leg also composites its tracks (compute(batch_composites=sizes))")
+    ap.add_argument("--batch-composites-phase", metavar="lifetime:B", help="with --batch-composites: also the phase-aligned ensembles")
     ap.add_argument("--cli", action="store_true", help="the command line: K single-track processes against one --trackfiles process")
     ap.add_argument("--batch-chunk", type=int, metavar="N", help="with --cli: the --trackfiles run prepared on the host against the streamed one "
                     "(--batch-chunk N), --reps runs of each")
@@ -175,6 +219,8 @@ def main():
     a = ap.parse_args()
     if a.batch_chunk is not None and not a.cli:
         ap.error("--batch-chunk goes with --cli")
+    if a.batch_composites_phase and not a.batch_composites:
+        ap.error("--batch-composites-phase goes with --batch-composites")
     if a.cli:
         print(json.dumps(cli_wall_clock(a.tracks, a.seed) if a.batch_chunk is None else
                          cli_streamed_batch(a.tracks, a.seed, a.batch_chunk, a.reps, a.host_cli)))
@@ -205,16 +251,25 @@ def main():
         st = np.concatenate([np.stack([tracks[k][0], np.r_[tracks[k][0][0], tracks[k][0][:-1]], np.r_[tracks[k][0][1:], tracks[k][0][-1]]], 1)
                              for k in members]).astype(np.int32)
         tc = np.concatenate([tables.time_coefs(time_s[tracks[k][0]] - time_s[tracks[k][0][0]]) for k in members])
-        prepared.append((members, eng.prepare_boxes(boxes, nyb_min=nyb), torch.as_tensor(st).to(dev), torch.as_tensor(tc).to(dev)))
+        extra = {}
+        if a.batch_composites:
+            extra["batch_composites"] = [len(tracks[k][0]) for k in members]
+        if a.batch_composites_phase:
+            from lorenzcycletoolkit_amd import batch
+            kind, n_bin = batch.parse_phase_clock(a.batch_composites_phase)
+            if kind != "lifetime":
+                ap.error("--batch-composites-phase: lifetime:B here (a peak needs the tracks' 850-hPa diagnostics)")
+            extra["batch_composite_phases"] = np.stack([batch.lifetime_ranges(len(tracks[k][0]), n_bin) for k in members])
+        prepared.append((members, eng.prepare_boxes(boxes, nyb_min=nyb), torch.as_tensor(st).to(dev), torch.as_tensor(tc).to(dev), extra))
 
     def batch_pass(timing=None):
         cubes = [torch.as_tensor(h).to(dev) for h in host]
         outs = {}
-        for members, pb, st, tc in prepared:
+        for members, pb, st, tc, extra in prepared:
             if a.only_steps_kernel:
                 eng.rowstats(*cubes, pb, steps=st, tcoef=tc, timing=timing)
                 continue
-            res = eng.compute(*cubes, pb, steps=st, tcoef=tc, per_step_boxes=True, drop_any_time=False, timing=timing)
+            res = eng.compute(*cubes, pb, steps=st, tcoef=tc, per_step_boxes=True, drop_any_time=False, timing=timing, **extra)
             o = 0
             for k in members:
                 outs[k] = res.packed[o: o + len(tracks[k][0])]
@@ -268,6 +323,9 @@ def main():
     out["loop_ms"] = {"median": float(np.median(lw)), "min": float(np.min(lw)), "all": [round(x, 2) for x in lw],
                       "what": "wall clock: per track host slice of every box + upload of the box-packed series + dT/dt + stage 1 + stage 2"}
     out["speedup_median"] = out["loop_ms"]["median"] / out["batch_ms"]["median"]
+    out["batch_composites"], out["batch_composites_phase"] = bool(a.batch_composites), a.batch_composites_phase
+    if a.batch_composites_phase:
+        out["phase_kernels_ms"] = _phase_kernel_times(eng, prepared[0], dev, max(a.reps, 5) * 4)
     out["bits_equal_batch_vs_loop"] = bool(same_ab)
     # share of the roofline of the step-table stage-1 launches, counted as bench.py counts the cube layout (the box is read: 5 fields)
     kbytes = 5 * nl * 61 * 61 * esz * out["boxes"]
